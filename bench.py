@@ -11,18 +11,24 @@ the GPU it runs the torch.distributed.run command above as a child process, forw
 A "step" is one factorisation (mtk::qr::qr; C ABI tsqr_mi_qr_f32, or the row-partitioned driver for N > 1) of a synthetic matrix
 already resident in HBM.  `value` / `ms_per_step` are the REFERENCE'S PROTOCOL: K BLOCKING calls one after the other on the same
 (q, r, a) -- src/test.cu:289-309 -- issued by one C loop (tsqr_mi_qr_f32_loop at loop depth 1: no interpreter time between calls),
-W untimed calls in front.  Beside it, each with its own roofline object (apply-pass duration from HIP events over a leg of the same
-schedule):
+W untimed calls in front, taken in steady state.  A plain run does only that: set-up, SETTLE_STEPS untimed blocking calls that carry
+the GPU past its start-up clock / power transient, the W + K window, and the JSON line.
+--dump-outputs DIR: after the timed window, what its last call handed the caller -- R whole and a fixed sample of Q's rows -- as
+DIR/r.npy and DIR/q.npy (float32, row-major; see dump_outputs).  The input is a fixed function of the arguments.
+--full adds, in this order before the `value` window: one checked blocking call (accuracy in fp64), then, each with its own roofline
+object (apply-pass duration from HIP events over a leg of the same schedule):
   first_window     the same blocking window taken at process start (inside the GPU's clock / power transient after idle)
   stream_same_a    the K calls as a stream on the same A (tsqr_mi_qr_f32_loop, depth 3: chained schedule where it applies)
   stream_rotating  K calls over R >= 3 rotating (A, Q, R) triples through the batch entry (tsqr_mi_qr_f32_batch): no call finds its A
                    in the 256 MiB Infinity Cache left there by an earlier call -- the cache-cold number
   blocking_rotating  the same rotation as blocking calls
+and K blocking calls under HIP events (`roofline`); after it, the accuracy of what the `value` window left in Q and R, the device
+probe and the CPU baseline.
 Weak scaling (default): every rank owns 2^20 rows (N = 8 is BASELINE's C4, 2^23 x 64).  --scaling strong: the GLOBAL matrix is fixed
 (2^23 x 64 unless --m says otherwise) and split over the ranks.
 --workload selects the BASELINE.json configuration: c2 (default, the headline: 2^20 x 64 fp32_tc_cor U(-1,1)), c3 (2^20 x 128,
 --mode fp32_tc_cor | fp32_notc), c5 (latms cond 1e8, 2^20 x 64, Reorthogonalize = true); c4 is `--gpus 8` of c2's per-GPU shape.
-Prints ONE JSON line on rank 0 (contract in the task prompt) including `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0; with --full it also holds the accuracy figures and the `roofline` and `cpu_baseline` objects.
 """
 import argparse
 import json
@@ -61,6 +67,10 @@ import torch.distributed as dist  # noqa: E402
 
 PEAK_F32_MATRIX_TFLOPS = 157.3     # MI355X fp32 MFMA/vector peak (MI355X_MICROARCH.md, chip-level parameters)
 PEAK_HBM_TBS = 8.0                 # HBM3E spec
+# calls 10-30 of a process run 5-8 % slow (GPU clock / power settling, profiles/r02_experiment_log.md; about 20 ms of streaming
+# removes it): a plain run issues these untimed blocking calls before its W + K window so that `value` stays a steady-state figure
+SETTLE_STEPS = 128
+DUMP_Q_BYTES = 32 << 20            # --dump-outputs: Q is sampled by rows down to this size (float32)
 
 
 def f_qr(m, n):
@@ -177,6 +187,20 @@ def pmc_traffic(kernel_class, m, n, mode):
     return None, None
 
 
+def dump_outputs(dirname, q_t, r_t, m, n):
+    """What the last timed call handed its caller, for comparing two builds output for output: DIR/r.npy = R (n x n) whole and
+    DIR/q.npy = Q (m x n) -- all rows when they fit in DUMP_Q_BYTES, otherwise the rows numpy.random.default_rng(0).choice(m, k,
+    replace=False) picks, ascending, k = DUMP_Q_BYTES / (4 n).  Both float32, row-major.  q_t / r_t are the engine's column-major
+    (n, ld) / (n, n) tensors; with several ranks, rank 0's row block."""
+    os.makedirs(dirname, exist_ok=True)
+    k = DUMP_Q_BYTES // (4 * n)
+    if k < m:
+        idx = np.sort(np.random.default_rng(0).choice(m, k, replace=False))
+        q_t = q_t[:, torch.from_numpy(idx).to(q_t.device)]
+    np.save(os.path.join(dirname, "q.npy"), np.ascontiguousarray(q_t.float().cpu().numpy().T))
+    np.save(os.path.join(dirname, "r.npy"), np.ascontiguousarray(r_t.float().cpu().numpy().T))
+
+
 WORKLOADS = {
     # BASELINE.json configs[1], [2], [4] ([3] = `--gpus 8` of c2's per-GPU shape; [0] is the CPU-runnable LAPACK case, tests/test_gpu_configs.py)
     "c2": dict(m=1 << 20, n=64, mode="fp32_tc_cor", reorth=0, input="uniform", cpu_rows=1 << 20),
@@ -197,6 +221,11 @@ def parse_args(argv=None):
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--mode", default=None, choices=["fp32_tc_cor", "fp32_notc", "fp32_tc_nocor", "fp16_notc", "fp16_tc_nocor"])
     ap.add_argument("--reorth", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside `value`: the checked call and the accuracy figures, the extra windows and their roofline legs, the "
+                         "device probe and the CPU baseline (the options below that shape those are --full options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write R and a fixed row sample of Q from the last timed call as DIR/r.npy, DIR/q.npy (float32)")
     ap.add_argument("--cpu-sample-rows", type=int, default=None)   # c2: the whole headline matrix, ~15 s of CPU work on 16 host threads
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-first-window", action="store_true", help="skip the extra timing window at process start (profiling runs)")
@@ -337,7 +366,7 @@ def main():
         return a, torch.empty(n, ld, dtype=io_dt, device=dev)[:, :m], torch.zeros(n, n, dtype=io_dt, device=dev)
 
     d_a, d_q, d_r = new_triple(0)
-    a_keep = d_a.clone() if n > 64 else None                 # n > 64: the engine may overwrite A (it does not on the one-panel path)
+    a_keep = d_a.clone() if n > 64 and args.full else None   # n > 64: the engine may overwrite A (it does not on the one-panel path)
     eng = None
     if args.rehearse:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -370,7 +399,7 @@ def main():
     # rotating buffers (one GPU, fp32 I/O): R triples more than an Infinity Cache apart, K calls = one call of the batch entry over the
     # cyclic sequence of triples -- every call runs on an A the cache has not seen since R - 1 other matrices went through it
     rot = None
-    if single and not io_half and args.rotate >= 3 and not args.only_value:
+    if args.full and single and not io_half and args.rotate >= 3 and not args.only_value:
         triples = [(d_a, d_q, d_r)] + [new_triple(s) for s in range(1, args.rotate)]
         binds = {}
 
@@ -445,18 +474,25 @@ def main():
             o["roofline"] = rf
         return o
 
-    # 1. one blocking step, checked: accuracy of the factorisation evaluated in fp64, A untouched
-    set_depth(1)
-    run_steps(1)
-    set_depth(3)
-    barrier()
-    orth_first, res_first = accuracy(d_q, d_r, a_keep if a_keep is not None else d_a)
-    a_untouched = True if a_keep is None else bool(torch.equal(a_keep, d_a))
-    if not a_untouched:                                      # panel path for n > 64 (ill-conditioned input): every step needs a fresh A
-        raise SystemExit("bench.py: the engine overwrote A on this workload; timing repeated calls on it would not measure the workload")
+    if args.full:
+        # 1. one blocking step, checked: accuracy of the factorisation evaluated in fp64, A untouched
+        set_depth(1)
+        run_steps(1)
+        set_depth(3)
+        barrier()
+        orth_first, res_first = accuracy(d_q, d_r, a_keep if a_keep is not None else d_a)
+        a_untouched = True if a_keep is None else bool(torch.equal(a_keep, d_a))
+        if not a_untouched:                                  # panel path for n > 64 (ill-conditioned input): every step needs a fresh A
+            raise SystemExit("bench.py: the engine overwrote A on this workload; timing repeated calls on it would not measure the workload")
+    elif gpu:
+        # a plain run: carry the GPU past its start-up transient, where --full runs the windows below
+        set_depth(1)
+        run_steps(SETTLE_STEPS)
+        set_depth(3)
+        barrier()
 
     extras = {}
-    if not args.only_value and not args.rehearse:
+    if args.full and not args.only_value and not args.rehearse:
         # 2. the blocking window at process start: the first ~30 calls of a process run 5-8 % slower than all later ones (GPU clock /
         #    power settling after idle: profiles/r02_experiment_log.md) -- the position round 2's `value` was taken at
         if not args.no_first_window:
@@ -483,12 +519,15 @@ def main():
             extras["stream_rotating"]["residual_last_triple"] = r2
 
     # 5. the roofline leg of `value`: K blocking calls under HIP events
-    prof = profiled_leg(run_steps, 1)
+    prof = profiled_leg(run_steps, 1) if args.full else None
     # 6. the contract's window: W + K BLOCKING calls (the reference's protocol, src/test.cu:289-309)
     ms_per_step = timed_window(run_steps, 1)
     gflops = flops / (ms_per_step * 1e-3) / 1e9
-    # accuracy of what the timed schedule left in Q and R (the last call of the window)
-    orth_fro, residual = accuracy(d_q, d_r, a_keep if a_keep is not None else d_a)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_q, d_r, m, n)
+    if args.full:
+        # accuracy of what the timed schedule left in Q and R (the last call of the window)
+        orth_fro, residual = accuracy(d_q, d_r, a_keep if a_keep is not None else d_a)
 
     if rank == 0:
         engine_name = "numpy-double (rehearsal)" if args.rehearse else bq.ENGINE_NAMES.get(eng.last_engine if eng is not None else bq.last_engine(), "?")
@@ -520,20 +559,26 @@ def main():
                    "parallelism": "row-partitioned x%d" % world,
                    "dist_transport": (eng.transport if eng is not None else None), "dist_exchange": exchange},
                "call_protocol": "value / ms_per_step: K BLOCKING calls on the same (q, r, a), one after the other (reference src/test.cu:289-309), issued by one C loop "
-                                "(loop depth 1), W untimed calls in front; taken in steady state (window_order) -- first_window is the same window at process start",
-               "orth_fro": orth_fro, "orth_ref_metric": orth_fro / np.sqrt(n), "residual": residual,
-               "orth_fro_checked_step": orth_first, "residual_checked_step": res_first,
-               "window_order": "1 checked blocking step; first_window (W + K blocking); stream_same_a (W + K, then K under HIP events); stream_rotating, "
-                               "two_in_flight_rotating, blocking_rotating (W + K each; K under events for the first and the last); K blocking calls under HIP events "
-                               "(`roofline`); then the W + K blocking window `value` is taken from; orth_fro / residual are evaluated on the Q and R that window left",
-               "roofline": roofline}
-        out.update(extras)
+                                "(loop depth 1), W untimed calls in front; taken in steady state (window_order) -- with --full, first_window is the same window at process start",
+               "full": args.full}
+        if args.full:
+            out.update({"orth_fro": orth_fro, "orth_ref_metric": orth_fro / np.sqrt(n), "residual": residual,
+                        "orth_fro_checked_step": orth_first, "residual_checked_step": res_first,
+                        "window_order": "1 checked blocking step; first_window (W + K blocking); stream_same_a (W + K, then K under HIP events); stream_rotating, "
+                                        "two_in_flight_rotating, blocking_rotating (W + K each; K under events for the first and the last); K blocking calls under HIP "
+                                        "events (`roofline`); then the W + K blocking window `value` is taken from; orth_fro / residual are evaluated on the Q and R "
+                                        "that window left",
+                        "roofline": roofline})
+            out.update(extras)
+        else:
+            out["window_order"] = ("%d untimed blocking calls (past the start-up transient); then the W + K blocking window `value` is taken from" % SETTLE_STEPS
+                                   if gpu else "the W + K window `value` is taken from")
         if args.rehearse:
             out["rehearsal"] = True
             out["data"] = "synthetic (CPU rehearsal with the numpy test double: NOT a measurement of the product)"
-        if not args.rehearse:
+        if args.full and not args.rehearse:
             out["device"] = device_probe()
-        if world == 1 and not args.no_cpu_baseline and not args.rehearse and not io_half:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.rehearse and not io_half:
             out["cpu_baseline"] = cpu_baseline(n, args.mode, args.cpu_sample_rows)
         print(json.dumps(out))
     if dist.is_initialized():

@@ -33,7 +33,7 @@ def _bench(*argv, env_extra=None):
 
 
 def test_bare_multi_gpu_invocation_starts_its_own_ranks():
-    d = _bench("--gpus", "2", "--backend", "gloo", "--rehearse", "--m", "4096", "--steps", "3", "--warmup", "1")
+    d = _bench("--gpus", "2", "--backend", "gloo", "--rehearse", "--m", "4096", "--steps", "3", "--warmup", "1", "--full")
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["rehearsal"] is True
     assert d["metric"] == "tsqr_gflops" and d["unit"] == "GFLOP/s" and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert d["config"]["parallelism"] == "row-partitioned x2" and d["config"]["m_per_gpu"] == 4096 and d["config"]["n"] == 64
@@ -55,14 +55,34 @@ def test_single_rank_rehearsal_and_workload_names():
     assert (a.workload, a.m, a.n, a.mode, a.reorth, a.gpus) == ("c2", 1 << 20, 64, "fp32_tc_cor", 0, 1)
 
 
+def test_plain_run_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline fields only; --dump-outputs writes R and Q of the last timed call (float32), the same
+    for the same arguments in every run, and Q's row sample is orthonormal columns scaled by sqrt(sample / m)."""
+    d = _bench("--gpus", "1", "--backend", "gloo", "--rehearse", "--m", "2048", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "a"))
+    assert d["full"] is False and d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert not {"orth_fro", "roofline", "cpu_baseline", "device", "first_window"} & set(d)
+    _bench("--gpus", "1", "--backend", "gloo", "--rehearse", "--m", "2048", "--steps", "3", "--warmup", "2", "--full", "--dump-outputs", str(tmp_path / "b"))
+    for name, shape in (("q", (2048, 64)), ("r", (64, 64))):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.array_equal(a, b)
+    q, r = np.load(tmp_path / "a" / "q.npy"), np.load(tmp_path / "a" / "r.npy")
+    assert np.abs(np.tril(r, -1)).max() == 0 and np.abs(q.T @ q - np.eye(64)).max() < 1e-5
+    sys.path.insert(0, ROOT)
+    import bench
+    big = tmp_path / "c"
+    m = 2 * bench.DUMP_Q_BYTES // (4 * 64)
+    bench.dump_outputs(str(big), torch.zeros(64, m), torch.zeros(64, 64), m, 64)
+    assert np.load(big / "q.npy").shape == (m // 2, 64)
+
+
 def test_world_size_8_rehearsal_weak_and_strong():
     """the N = 8 launch (BASELINE's C4 shape of ranks) rehearsed on CPU -- eight gloo ranks, the numpy double as the
     per-rank executor -- in both scaling modes.  weak: --m rows per rank; strong: --m is the GLOBAL row count, split over the ranks."""
-    d = _bench("--gpus", "8", "--backend", "gloo", "--rehearse", "--m", "1024", "--steps", "2", "--warmup", "1")
+    d = _bench("--gpus", "8", "--backend", "gloo", "--rehearse", "--m", "1024", "--steps", "2", "--warmup", "1", "--full")
     assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["config"]["m_per_gpu"] == 1024 and "8192 x 64" in d["config"]["workload"]
     assert d["config"]["parallelism"] == "row-partitioned x8" and d["config"]["dist_exchange"].startswith("gram_allreduce")
     assert d["orth_fro"] < 1e-5 and d["residual"] < 1e-6
-    d = _bench("--gpus", "8", "--backend", "gloo", "--rehearse", "--scaling", "strong", "--m", "8192", "--steps", "2", "--warmup", "1")
+    d = _bench("--gpus", "8", "--backend", "gloo", "--rehearse", "--scaling", "strong", "--m", "8192", "--steps", "2", "--warmup", "1", "--full")
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["m_per_gpu"] == 1024 and "8192 x 64" in d["config"]["workload"]
     assert d["orth_fro"] < 1e-5 and d["residual"] < 1e-6
     sys.path.insert(0, ROOT)

@@ -1,14 +1,15 @@
 #!/bin/bash
 # GPU box: headline bench A/B over environment switches (each run = a fresh process), then the GPU test suite.
-# usage: tools/gpu_ab.sh "<env assignments A>" "<env assignments B>" ...   ("-" = no switch); output -> gpurun_out/ab_*.json
+# usage: tools/gpu_ab.sh "<env assignments A>" "<env assignments B>" ...   ("-" = no switch); output -> $OUT_DIR/ab_*.json (default runs/)
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out
+O=${OUT_DIR:-runs}
+mkdir -p $O
 i=0
 for v in "$@"; do
 	[ "$v" = "-" ] && v=""
 	for rep in $(seq 1 ${REPS:-2}); do
-		env $v timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/ab_${i}_${rep}.json 2> gpurun_out/ab_${i}_${rep}.err || { echo "bench failed for [$v]"; tail -5 gpurun_out/ab_${i}_${rep}.err; exit 1; }
-		python - "$v" gpurun_out/ab_${i}_${rep}.json <<'PY'
+		env $v timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_${i}_${rep}.json 2> $O/ab_${i}_${rep}.err || { echo "bench failed for [$v]"; tail -5 $O/ab_${i}_${rep}.err; exit 1; }
+		python - "$v" $O/ab_${i}_${rep}.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 k = d["roofline"]["kernel_ms_per_step"]

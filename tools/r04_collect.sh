@@ -9,10 +9,10 @@ O=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $O
 step() { echo "== $*"; }
 
-step "kernel stats of: python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline"
+step "kernel stats of: python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline"
 rm -rf $O/r04_kb
-rocprofv3 --output-format csv --kernel-trace --stats -d $O/r04_kb -o b -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/r04_bench_under_rocprof.json 2> $O/r04_kb.err || { tail -5 $O/r04_kb.err; exit 1; }
-python3 tools/kstats.py $O/r04_kb/b_kernel_stats.csv $O/r04_rocprofv3_kernel_stats_bench.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline (2^20 x 64 fp32_tc_cor; windows: 1 checked call, first_window, stream_same_a (+ its event leg), stream_rotating / two_in_flight_rotating / blocking_rotating over 4 triples, K blocking calls under events, value = W + K blocking calls)" > /dev/null
+rocprofv3 --output-format csv --kernel-trace --stats -d $O/r04_kb -o b -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/r04_bench_under_rocprof.json 2> $O/r04_kb.err || { tail -5 $O/r04_kb.err; exit 1; }
+python3 tools/kstats.py $O/r04_kb/b_kernel_stats.csv $O/r04_rocprofv3_kernel_stats_bench.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline (2^20 x 64 fp32_tc_cor; windows: 1 checked call, first_window, stream_same_a (+ its event leg), stream_rotating / two_in_flight_rotating / blocking_rotating over 4 triples, K blocking calls under events, value = W + K blocking calls)" > /dev/null
 rm -rf $O/r04_kb
 
 step "per-call timelines (tools/loop_run.py; depth 1 = blocking calls, 2 = two in flight, 3 = chained where it applies; rot4 = four different matrices through the batch entry)"
