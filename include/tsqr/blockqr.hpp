@@ -260,7 +260,8 @@ inline state_t qr_finish(ticket& t) {
 //     for (i = 0; i < count; i++) mtk::qr::qr<mode, Reorth>(q[i], ldq, r[i], ldr, a[i], lda, m, n, buffer, handle);
 // computes -- bit for bit, including the fallback ladder of a matrix the conditioning check rejects -- issued as a stream: the 22 us
 // in which one workgroup factors the Gram matrix of matrix i are hidden in the Gram pass of matrix i + 1 (tsqr_mi.h for the rules:
-// q[i] and r[i] must be clear of a[i + 1] for that; in place, q[i] == a[i], is fine).  q, r, a: host arrays of device pointers.
+// calls i and i + 1 must not conflict -- Q(i) or R(i) overlapping Q(i + 1), R(i + 1) or A(i + 1), or Q(i + 1) or R(i + 1) overlapping
+// A(i) -- or they run one after the other; in place, q[i] == a[i], is fine).  q, r, a: host arrays of device pointers.
 // states (optional): the state_t of every call.  Returns the first non-zero state_t.  All implemented modes (half-typed pointers for the fp16 I/O modes).
 template <mtk::qr::compute_mode mode, bool Reorthogonalize>
 inline state_t qr_batch(

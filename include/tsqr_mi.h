@@ -90,7 +90,10 @@ int tsqr_mi_qr_f32(int mode, int reorth,
  * profiling on, h_wl not pinned) are executed inside submit, blocking; finish then just returns their state.
  * Rules: a ticket lives until it is finished, by the thread that submitted it, tickets are finished in submission order; the
  * arguments (A, Q, R, work buffers) stay valid and unmodified by the host until then.  Two calls in flight may share the work
- * buffers (everything runs in stream order) -- but not Q, R or (n > 64) A if the results of both are wanted.
+ * buffers (everything runs in stream order).  A call that CONFLICTS with a ticket of the thread not finished yet -- Q or R of the
+ * earlier call overlaps Q, R or A of the new one, or Q or R of the new call overlaps A of the earlier one (byte ranges of
+ * ((n - 1) ld + rows) elements) -- is not enqueued before it: submit finishes the open tickets up to that one first (their finish then
+ * returns the state), so the pair gives what two blocking calls give.
  * Any other entry point of this library called by the thread meanwhile first waits for the verdicts of its tickets in flight.
  */
 typedef struct tsqr_mi_ticket {
@@ -129,7 +132,8 @@ int tsqr_mi_qr_f32_finish(tsqr_mi_ticket* ticket);
  * are bit for bit those of the blocking call (tests/test_gpu_async.py).  Returns the first non-zero state.
  * The chained schedules launch the Gram pass of call i + 1 before the apply pass of call i; they are taken only when that is the
  * blocking order, i.e. when Q and R do not overlap A (a loop that factors in place, q == a, runs at depth 2: call i + 1 of the
- * blocking loop factors the Q that call i left in A, and so does the stream). */
+ * blocking loop factors the Q that call i left in A, and so does the stream -- after a rejected call, call i + 1 is redone as a
+ * blocking call). */
 int tsqr_mi_qr_f32_loop(int count, int mode, int reorth,
                         float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
                         size_t m, size_t n,
@@ -142,8 +146,11 @@ void tsqr_mi_set_loop_depth(int depth);   /* 1, 2 or 3 (default); applies to eve
  * lda) into q[i] (ldq) and r[i] (ldr); the leading dimensions, the shape, the mode and the work buffers are shared.  The calls are
  * issued as the stream tsqr_mi_qr_f32_loop issues (tsqr_mi_set_loop_depth): at depth 3 full 64-column matrices of 128 k <= 2^20 rows
  * (and 128-column matrices of 64 k >= 32640 rows) take the chained schedule -- the R-factor chain of matrix i inside the Gram launch of
- * matrix i + 1 -- as long as no output of call i is an input of call i + 1 (q[i], r[i] clear of a[i + 1]; q[i] == a[i], in place, is
- * fine); everything else, and everything at depth 2, runs two calls in flight in stream order; depth 1 is a loop of blocking calls.
+ * matrix i + 1 -- as long as no two neighbouring calls conflict; everything else, and everything at depth 2, runs two calls in flight
+ * in stream order; depth 1 is a loop of blocking calls.  Calls i and i + 1 CONFLICT when Q(i) or R(i) overlaps Q(i + 1), R(i + 1) or
+ * A(i + 1), or Q(i + 1) or R(i + 1) overlaps A(i) (byte ranges of ((n - 1) ld + rows) elements; a call's own q[i] == a[i], in place,
+ * and two A's that are only read are no conflict): a conflicting pair is issued one call after the other (call i finished before
+ * call i + 1 is enqueued), so that a rejected call i runs its ladder before call i + 1 reads or writes anything of it.
  * Whatever the schedule, every matrix gets the blocking call's result bit for bit: a matrix the conditioning check rejects mid-batch
  * gets its whole ladder (the chained schedule ends at it and a fresh one starts behind it), the accepted ones around it stand.
  * states (optional, `count` ints): the state of every call.  Returns the first non-zero state (0: all factored); a negative value
@@ -185,8 +192,8 @@ int tsqr_mi_qr_f16_loop(int count, int mode, int reorth,
 
 /* `count` DIFFERENT half-typed matrices of one shape: tsqr_mi_qr_f32_batch for the fp16 I/O modes (q, r, a: host arrays of device pointers to halves).
  * Calls the native path takes (16 < n <= 64, no reorth, aligned halves, accepted by the bf16-split level) are issued as a stream -- two in flight, for
- * n = 64 the chained schedule while q[i], r[i] are clear of a[i + 1] and a matrix is small enough for two to share the Infinity Cache --, everything else
- * as blocking calls; a matrix rejected mid-stream gets its whole ladder (conversion path), the accepted ones around it stand.  The same halves as
+ * n = 64 the chained schedule while a matrix is small enough for two to share the Infinity Cache --, everything else, and a batch in which two neighbouring
+ * calls conflict (as tsqr_mi_qr_f32_batch), as blocking calls; a matrix rejected mid-stream gets its whole ladder (conversion path), the accepted ones around it stand.  The same halves as
  * `count` calls of tsqr_mi_qr_f16.  states (optional): the state of every call.  Returns the first non-zero state. */
 int tsqr_mi_qr_f16_batch(int count, int mode, int reorth,
                          void* const* q, size_t ldq, void* const* r, size_t ldr, const void* const* a, size_t lda,
@@ -267,7 +274,9 @@ int tsqr_mi_qr_f32_dist_fn_loop(int count, int mode, int reorth,
                                 void* wq, void* wr, float* gather_buf,
                                 void* nccl_comm, void* nccl_allreduce_fn, void* nccl_allgather_fn, int nranks, void* stream);
 /* *_batch: `count` DIFFERENT row-partitioned matrices of one shape (host arrays of device pointers; one block height per rank for all of them), issued as
- * the stream of calls of the *_loop entries; every rank passes the same count and operands of the same eligibility.  states (optional): per call. */
+ * the stream of calls of the *_loop entries; every rank passes the same count and operands of the same eligibility.  When two neighbouring calls conflict
+ * (tsqr_mi_qr_f32_batch) on ANY rank -- the ranks agree on that with one all-reduce of one flag per batch call -- the batch runs as blocking calls on every
+ * rank.  states (optional): per call. */
 int tsqr_mi_qr_f32_dist_fn_batch(int count, int mode, int reorth,
                                  float* const* q, size_t ldq, float* const* r, size_t ldr, float* const* a, size_t lda,
                                  size_t m_local, size_t n,

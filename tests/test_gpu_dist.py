@@ -258,3 +258,70 @@ def test_batch_of_row_partitioned_matrices(heights, cond, k):
     rejected matrix in the stream (all ranks take its ladder alike): bit for bit the K single calls, on every rank."""
     res = _run(heights, 64, cond=cond, loop=k, worker=_batch_worker)
     assert res["ok"] == 1 and res["r_same"]
+
+
+def _overlap_worker(rank, world, port, heights, n, mode, reorth, policy, cond, loop, out):
+    """A feed-forward batch (a[i + 1] is q[i]) whose matrix 0 is rejected by the bf16-split level, carved out of one pre-filled pool per
+    rank: (a) the overlap exists on rank 0 only, rank 1 has disjoint operands; (b) on every rank.  Every rank compares qr_batch at depths
+    2 and 3 with its own blocking sequence on a copy of its pool.  The ranks must choose the same schedule, or their collectives pair up
+    wrongly."""
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tsqr_gpu_amd import blockqr as bq, dist as tdist
+    rng = np.random.Generator(np.random.MT19937(23))
+    m_glob = sum(heights)
+    row0 = sum(heights[:rank]); m_local = heights[rank]
+    u, _ = np.linalg.qr(rng.standard_normal((m_glob, n)))
+    v, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    a0 = ((u * np.geomspace(1.0, 1.0 / cond, n)) @ v.T).astype(np.float32)[row0:row0 + m_local]
+    drv = tdist.RowPartitionedQR(bq.compute_mode[mode], m_local, n, comm="callbacks")
+    k = loop
+    res = {}
+    for case in ("a", "b"):
+        overlap = case == "b" or rank == 0
+        prng = np.random.Generator(np.random.MT19937(31 + rank))
+        host = prng.uniform(-1, 1, size=(2 * k * n, m_local)).astype(np.float32)
+        host[:n] = a0.T
+        init = torch.from_numpy(host).cuda()
+        ops = [((i + 1) * n if overlap else (k + i) * n, i * n) for i in range(k)]      # (q column, a column)
+
+        def views(pool):
+            return [pool[qc:qc + n] for qc, _ in ops], [pool[ac:ac + n] for _, ac in ops]
+        want = init.clone()
+        r_want = [torch.zeros(n, n, device="cuda") for _ in range(k)]
+        qs, as_ = views(want)
+        st1, engines = [], []
+        for i in range(k):
+            st1.append(drv.qr(qs[i], m_local, r_want[i], as_[i], m_local))
+            engines.append(drv.last_engine)
+        ok = st1 == [0] * k and engines[0] not in (3, 5)
+        for depth in (2, 3):
+            pool = init.clone()
+            rs = [torch.zeros(n, n, device="cuda") for _ in range(k)]
+            qs, as_ = views(pool)
+            bq.set_loop_depth(depth)
+            try:
+                st2, states = drv.qr_batch(qs, m_local, rs, as_, m_local)
+            finally:
+                bq.set_loop_depth(3)
+            torch.cuda.synchronize()
+            ok = ok and st2 == 0 and states == [0] * k and torch.equal(pool.view(torch.int32), want.view(torch.int32))
+            ok = ok and all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(rs, r_want))
+        flag = torch.tensor([1 if ok else 0])
+        flags = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+        dist.all_gather(flags, flag)
+        res[case] = [int(f.item()) for f in flags]
+    if rank == 0:
+        out.put(res)
+    dist.destroy_process_group()
+
+
+def test_batch_of_row_partitioned_matrices_on_overlapping_operands():
+    """tsqr_mi_qr_f32_dist_cb_batch with q[i] == a[i + 1] and a rejected matrix 0, the overlap on one rank only and on both: every rank
+    leaves its operands bit for bit as its blocking calls do (both cases in one pair of processes: their start-up dominates)."""
+    res = _run((32768, 16384), 64, cond=1e6, loop=4, worker=_overlap_worker)
+    assert res == {"a": [1, 1], "b": [1, 1]}, res

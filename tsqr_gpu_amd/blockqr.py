@@ -66,7 +66,7 @@ class Ticket(ctypes.Structure):
         # The library holds the address of a ticket in flight, so one must not go away unfinished -- but finish belongs to the thread
         # that submitted it (include/tsqr_mi.h), and a finaliser runs wherever the collector happens to be, possibly at interpreter
         # shutdown: finish here only on the submitting thread of a live interpreter; otherwise say what went wrong.
-        if self.pending != 1:
+        if self.pending == 0:                          # (1: in flight; 2: verdict read -- the library still lists it until finish)
             return
         import sys
         import threading
@@ -359,6 +359,32 @@ def bind_loop(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, mode=None, reorthog
     return call
 
 
+def check_batch_operands(qs, ldq, rs, ldr, as_, lda, m, n, half=False):
+    """Every tensor of a batch before anything touches the GPU (the C side reads raw pointers): float32 (float16 for the fp16 I/O modes),
+    on the GPU, a leading dimension of at least its rows, and room for the whole column-major operand, (n - 1) ld + rows elements.
+    Raises TypeError or ValueError."""
+    import torch
+    want = torch.float16 if half else torch.float32
+    if not (len(qs) == len(rs) == len(as_)):
+        raise ValueError("qr_batch: q, r and a must name the same number of matrices")
+    ops = (("q", qs, ldq, m), ("r", rs, ldr, n), ("a", as_, lda, m))
+    for name, ts, ld, rows in ops:
+        for i, t in enumerate(ts):
+            if t.dtype != want:
+                raise TypeError("qr_batch: %s[%d] is %s, this mode takes %s" % (name, i, t.dtype, want))
+    for name, ts, ld, rows in ops:
+        if ld < rows:
+            raise ValueError("qr_batch: ld%s = %d is smaller than the %d rows of %s" % (name, ld, rows, name))
+        need = (n - 1) * ld + rows if n > 0 else 0
+        for i, t in enumerate(ts):
+            if t.numel() < need:
+                raise ValueError("qr_batch: %s[%d] holds %d elements, an operand of %d x %d with ld %d needs %d" % (name, i, t.numel(), rows, n, ld, need))
+    for name, ts, ld, rows in ops:
+        for i, t in enumerate(ts):
+            if not t.is_cuda:
+                raise TypeError("qr_batch: %s[%d] is not a GPU tensor" % (name, i))
+
+
 def bind_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream=None, mode=None, reorthogonalize=None):
     """mtk::qr::qr_batch (tsqr_mi_qr_f32_batch / tsqr_mi_qr_f16_batch): qs, rs, as_ are equally long sequences of float32 tensors
     (float16 for the two fp16 I/O modes), one (q, r, a) triple per matrix, all of the shape m x n with the shared leading dimensions.  Returns a callable: call() factors every matrix (blocking) and
@@ -366,14 +392,9 @@ def bind_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream=None, mode=None, reo
     import torch
     mode = bf.mode if mode is None else compute_mode(mode)
     reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    if mode in FP16_MODES:
-        if bf.mode not in FP16_MODES:
-            raise RuntimeError("the buffer was allocated for %s: an fp16 mode needs the larger work space of its own allocate()" % bf.mode.name)
-        for t in list(qs) + list(rs) + list(as_):
-            if t.dtype != torch.float16:
-                raise TypeError("%s takes float16 tensors (io type half, reference src/tsqr.hpp:38-39)" % mode.name)
-    if not (len(qs) == len(rs) == len(as_)):
-        raise ValueError("qr_batch: q, r and a must name the same number of matrices")
+    if mode in FP16_MODES and bf.mode not in FP16_MODES:
+        raise RuntimeError("the buffer was allocated for %s: an fp16 mode needs the larger work space of its own allocate()" % bf.mode.name)
+    check_batch_operands(qs, ldq, rs, ldr, as_, lda, m, n, half=mode in FP16_MODES)   # (float16 for the fp16 modes: io type half, reference src/tsqr.hpp:38-39)
     if stream is None:
         stream = torch.cuda.current_stream()
     count = len(as_)

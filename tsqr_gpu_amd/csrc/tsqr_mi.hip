@@ -27,8 +27,10 @@
 #include <cstring>
 #include <dlfcn.h>
 #include <string>
+#include <vector>
 
 #include "../../include/tsqr_mi.h"
+#include "stream_order.h"
 #include "tsqr_kernels.hip"
 #include "tsqr_wide.hip"
 #include "validate.hip"
@@ -1543,11 +1545,32 @@ static int submit_impl(const CallEnv& env, int mode, int reorth, float* q, size_
 	t_pending[slot] = t;
 	return TSQR_MI_SUCCESS;
 }
+// the tickets of the public entry this thread has not finished yet, in submission order
+thread_local std::vector<tsqr_mi_ticket*> t_open;
+static tsqr_order::Operands ticket_ops(const tsqr_mi_ticket* t) {
+	return tsqr_order::operands(t->q, t->ldq, t->r, t->ldr, t->a, t->lda, t->m, t->n, sizeof(float));
+}
+static int finish_impl(const CallEnv& env, tsqr_mi_ticket* t);
 int tsqr_mi_qr_f32_submit(int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
                           size_t m, size_t n, void* wq_v, void* wr_v, float* reorth_w, unsigned* d_wl, unsigned* h_wl,
                           void* stream, tsqr_mi_ticket* t) {
 	(void)reorth_w; (void)d_wl;
-	return submit_impl(CallEnv{}, mode, reorth, q, ldq, r, ldr, a, lda, m, n, wq_v, wr_v, h_wl, stream, t, nullptr, /*own_flag=*/true);
+	if (!t) return TSQR_MI_ERROR_INVALID_SIZE;
+	// a call that conflicts with a ticket still open (stream_order.h) must not be enqueued before that ticket is finished: finish the open
+	// tickets up to the last conflicting one here (the same thread, in submission order); their own finish then returns the state
+	const tsqr_order::Operands me = tsqr_order::operands(q, ldq, r, ldr, a, lda, m, n, sizeof(float));
+	size_t upto = 0;
+	for (size_t k = 0; k < t_open.size(); k++)
+		if (tsqr_order::conflict(ticket_ops(t_open[k]), me)) upto = k + 1;
+	for (size_t k = 0; k < upto; k++) {
+		tsqr_mi_ticket* o = t_open.front();
+		t_open.erase(t_open.begin());
+		const int rc = finish_impl(CallEnv{}, o);
+		if (rc < 0) { *t = tsqr_mi_ticket{}; return t->state = rc; }
+	}
+	const int rc = submit_impl(CallEnv{}, mode, reorth, q, ldq, r, ldr, a, lda, m, n, wq_v, wr_v, h_wl, stream, t, nullptr, /*own_flag=*/true);
+	if (!rc && t->pending) t_open.push_back(t);
+	return rc;
 }
 
 static int finish_impl(const CallEnv& env, tsqr_mi_ticket* t) {
@@ -1569,7 +1592,11 @@ static int finish_impl(const CallEnv& env, tsqr_mi_ticket* t) {
 	else c.start_level = 1;                              // the bf16-split level was rejected: the ladder resumes at the fp64 Gram level
 	return t->state = qr_core(c, engine_of(t->mode), t->reorth, t->q, t->ldq, t->r, t->ldr, t->a, t->lda, t->m, t->n);
 }
-int tsqr_mi_qr_f32_finish(tsqr_mi_ticket* t) { return finish_impl(CallEnv{}, t); }
+int tsqr_mi_qr_f32_finish(tsqr_mi_ticket* t) {
+	for (size_t k = 0; k < t_open.size(); k++)
+		if (t_open[k] == t) { t_open.erase(t_open.begin() + k); break; }
+	return finish_impl(CallEnv{}, t);
+}
 
 // ---- a stream of calls: `count` factorisations of ONE shape on one stream with one set of work buffers.  The loop entries pass the same
 // (q, r, a) every time (the reference's speed protocol, src/test.cu:299-309), the batch entry one triple per call (a caller with many
@@ -1593,20 +1620,22 @@ struct Mats {
 };
 struct Call { int mode, reorth; size_t ldq, ldr, lda, m, n; void* wq; void* wr; unsigned* h_wl; void* stream; };
 
-// The chained schedules launch the Gram pass of call i + 1 BEFORE the apply pass of call i, in the launch that writes R of call i.  That
-// is the blocking order only if no output of call i is an input of call i + 1: Q(i) and R(i) must not overlap A(i + 1).  (A loop over one
-// triple factored in place, q == a, fails this test: call i + 1 of the blocking loop factors the Q that call i left there.)
-static bool chain_order_safe(const Mats& mt, int count, const Call& cl, size_t esz = sizeof(float)) {
-	auto overlap = [](const void* p, size_t pb, const void* s, size_t sb) {
-		const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), b0 = reinterpret_cast<uintptr_t>(s);
-		return a0 < b0 + sb && b0 < a0 + pb;
-	};
-	const size_t qb = ((cl.n - 1) * cl.ldq + cl.m) * esz, ab = ((cl.n - 1) * cl.lda + cl.m) * esz, rb = ((cl.n - 1) * cl.ldr + cl.n) * esz;
-	const int pairs = mt.same() ? 1 : count - 1;
-	for (int i = 0; i < pairs; i++) {
-		const int j = mt.same() ? i : i + 1;
-		if (overlap(mt.q(i), qb, mt.a(j), ab) || overlap(mt.r(i), rb, mt.a(j), ab)) return false;
-	}
+// Every schedule that enqueues call i + 1 before call i is finished follows one rule (stream_order.h): calls i and i + 1 must not conflict.
+static tsqr_order::Operands ops_of(const Mats& mt, int i, const Call& cl, size_t esz) {
+	return tsqr_order::operands(mt.q(i), cl.ldq, mt.r(i), cl.ldr, mt.a(i), cl.lda, cl.m, cl.n, esz);
+}
+// calls i and i + 1 of a batch conflict (a loop over one triple: never -- see out_of_order below)
+static bool pair_conflicts(const Mats& mt, int count, int i, const Call& cl, size_t esz = sizeof(float)) {
+	return !mt.same() && i + 1 < count && tsqr_order::conflict(ops_of(mt, i, cl, esz), ops_of(mt, i + 1, cl, esz));
+}
+// The chained schedules launch the Gram pass of call i + 1 BEFORE the apply pass of call i: a batch takes them only when no pair of its calls
+// conflicts.  A loop over one triple takes them only when the triple does not feed itself (Q or R overlaps A, e.g. q == a: call i + 1 of
+// the blocking loop factors the Q that call i left there); it keeps two calls in flight even then, because a rejected call leaves A untouched
+// and the next attempt, rejected alike, is redone (two_in_flight).
+static bool out_of_order(const Mats& mt, int count, const Call& cl, size_t esz = sizeof(float)) {
+	if (mt.same()) { const tsqr_order::Operands o = ops_of(mt, 0, cl, esz); return !tsqr_order::feeds(o, o); }
+	for (int i = 0; i + 1 < count; i++)
+		if (pair_conflicts(mt, count, i, cl, esz)) return false;
 	return true;
 }
 
@@ -1688,7 +1717,7 @@ static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 		return NOT_MINE;
 	for (int i = 0; i < (mt.same() ? 1 : count); i++)
 		if ((reinterpret_cast<uintptr_t>(mt.a(i)) & 15) != 0) return NOT_MINE;
-	if (!chain_order_safe(mt, count, cl) || !chain_fits_cache(mt, cl)) return NOT_MINE;
+	if (!out_of_order(mt, count, cl) || !chain_fits_cache(mt, cl)) return NOT_MINE;
 	Ctx c;
 	init_ctx(c, cl.wq, cl.wr, m, n, cl.stream);
 	c.rows_global = (double)m;
@@ -1791,7 +1820,7 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 		return NOT_MINE;
 	for (int i = 0; i < (mt.same() ? 1 : count); i++)
 		if ((reinterpret_cast<uintptr_t>(mt.a(i)) & 15) != 0) return NOT_MINE;
-	if (!chain_order_safe(mt, count, cl) || !chain_fits_cache(mt, cl)) return NOT_MINE;
+	if (!out_of_order(mt, count, cl) || !chain_fits_cache(mt, cl)) return NOT_MINE;
 	Ctx c;
 	init_ctx(c, cl.wq, cl.wr, m, n, cl.stream);
 	c.rows_global = (double)m;
@@ -1901,7 +1930,7 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 	Ctx c;
 	env_ctx(c, env, cl.wq, cl.wr, m, n, nullptr, cl.stream, /*keep_in_flight=*/false);
 	bool mine = c.hsig.dev && !cl.reorth && n == PW && m % 128 == 0 && m <= ((size_t)1 << 20) && lda % 4 == 0 && lda <= ((size_t)1 << 24) && lda >= m && ldq >= m &&
-	            ldr >= n && c.policy == 0 && c.gram_level == 2 && !g_set.debug && chain_order_safe(mt, count, cl);
+	            ldr >= n && c.policy == 0 && c.gram_level == 2 && !g_set.debug && out_of_order(mt, count, cl);
 	for (int i = 0; mine && i < (mt.same() ? 1 : count); i++) mine = (reinterpret_cast<uintptr_t>(mt.a(i)) & 15) == 0;
 	c.fold_cor = (engine == 1);
 	static DevOnce attr;
@@ -2028,30 +2057,68 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 }
 
 // Two calls in flight: call i + 1 is submitted before call i is finished; the completion word of call i is raised by the first kernel of
-// call i + 1 (stream order: it starts when call i has finished), only the last call carries a completion kernel of its own.  Stream order
-// is the blocking order, so any operand overlap the blocking calls allow is fine here.  Row-partitioned calls: every rank takes the same
-// verdicts (they come from the all-reduced Gram matrix), hence the same path through this loop and the same order of collectives.
+// call i + 1 (stream order: it starts when call i has finished), only the last call carries a completion kernel of its own.  That is the
+// blocking order only while calls i and i + 1 do not conflict (stream_order.h): a rejected call i runs its ladder AFTER attempt i + 1.  A
+// conflicting pair of a batch is issued in order instead -- call i (with a completion kernel of its own) is finished before call i + 1 is
+// submitted.  A loop over one triple keeps two calls in flight: a rejected call leaves A untouched, so attempt i + 1 saw that same matrix
+// and was rejected too; but when the triple feeds itself (q == a) the ladder of call i has since written its Q there, so call i + 1 is then
+// redone as a blocking call (row-partitioned: always after a ladder -- the ranks' operands may differ, their verdicts do not).
+// Row-partitioned calls: every rank takes the same verdicts (they come from the all-reduced Gram matrix), and a batch with a conflicting
+// pair on any rank never gets here (stream_of_calls), hence the same path through this loop and the same order of collectives.
+static bool attempt_stands(const tsqr_mi_ticket* t) { return t->verdict == 0 && !(t->n <= 16 && t->scond > 32.0f); }   // (as finish_impl)
 static int two_in_flight(const CallEnv& env, const Mats& mt, int count, const Call& cl) {
 	auto submit = [&](int i, tsqr_mi_ticket* t, tsqr_mi_ticket* announce, bool own_flag) {
 		return submit_impl(env, cl.mode, cl.reorth, mt.q(i), cl.ldq, mt.r(i), cl.ldr, mt.a(i), cl.lda, cl.m, cl.n, cl.wq, cl.wr, cl.h_wl, cl.stream, t, announce, own_flag);
 	};
+	const bool redo_after_ladder = mt.same() && (env.dist || [&] { const tsqr_order::Operands o = ops_of(mt, 0, cl, sizeof(float)); return tsqr_order::feeds(o, o); }());
 	tsqr_mi_ticket tk[2];
 	int first = 0;
-	int st = submit(0, &tk[0], nullptr, /*own_flag=*/count == 1);
+	bool ordered = pair_conflicts(mt, count, 0, cl);     // calls i and i + 1 conflict: call i is finished before call i + 1 is submitted
+	int st = submit(0, &tk[0], nullptr, /*own_flag=*/count == 1 || ordered);
 	if (st) { for (int k = 0; k < count; k++) mt.state(k, st); return st; }           // (invalid size / mode: the same for every call of the stream)
 	for (int i = 0; i < count; i++) {
 		tsqr_mi_ticket* cur = &tk[i & 1];
 		tsqr_mi_ticket* nxt = (i + 1 < count) ? &tk[(i + 1) & 1] : nullptr;
-		if (nxt) {
-			st = submit(i + 1, nxt, cur, /*own_flag=*/i + 2 == count);
+		const bool ordered_next = nxt && pair_conflicts(mt, count, i + 1, cl);
+		if (nxt && !ordered) {
+			st = submit(i + 1, nxt, cur, /*own_flag=*/i + 2 == count || ordered_next);
 			if (st) { (void)finish_impl(env, cur); return st; }
 		}
+		const bool had_attempt = cur->pending != 0;
 		st = finish_impl(env, cur);
 		mt.state(i, st);
 		if (st && !first) first = st;
-		if (st < 0 || (st && mt.same())) { if (nxt) (void)finish_impl(env, nxt); return st; }   // (a loop over one triple stops at its first non-zero state)
+		if (st < 0 || (st && mt.same())) { if (nxt && !ordered) (void)finish_impl(env, nxt); return st; }   // (a loop over one triple stops at its first non-zero state)
+		if (nxt && !ordered && redo_after_ladder && had_attempt && !attempt_stands(cur)) {
+			// the ladder of call i ran after attempt i + 1 (which the stream has drained): call i + 1 as the blocking call
+			nxt->pending = 0;
+			st = nxt->state = blocking_one(env, mt, i + 1, cl);
+			if (st < 0) return st;
+		}
+		if (nxt && ordered) {
+			st = submit(i + 1, nxt, nullptr, /*own_flag=*/i + 2 == count || ordered_next);
+			if (st) return st;
+		}
+		ordered = ordered_next;
 	}
 	return first;
+}
+
+// Row-partitioned batch: the ranks must take the same schedule, so whether ANY rank has a conflicting pair of calls is agreed on with one
+// all-reduce of one flag (blocking: the host needs the answer before it enqueues the next call)
+static int conflict_on_any_rank(const CallEnv& env, const Mats& mt, int count, const Call& cl, bool* any) {
+	bool mine = false;
+	for (int i = 0; i + 1 < count && !mine; i++) mine = pair_conflicts(mt, count, i, cl);
+	Ctx c;
+	env_ctx(c, env, cl.wq, cl.wr, cl.m, cl.n, nullptr, cl.stream, /*keep_in_flight=*/false);
+	hipLaunchKernelGGL(tsqrmi::set_f64_kernel, dim3(1), dim3(1), 0, c.st, c.gsum(), mine ? 1.0 : 0.0);
+	HIPCHK(hipGetLastError());
+	if (c.comm.allreduce_f64(c.gsum(), 1, c.st)) { t_last_error = "all-reduce of the operand-order flag failed"; return -1; }
+	double h = 0.0;
+	HIPCHK(hipMemcpyAsync(&h, c.gsum(), sizeof(double), hipMemcpyDeviceToHost, c.st));
+	HIPCHK(hipStreamSynchronize(c.st));
+	*any = h != 0.0;
+	return 0;
 }
 
 // `count` calls as a stream.  Depth 3: the chained schedules as far as they go -- a rejected call ends one, the stream goes on behind it
@@ -2059,7 +2126,12 @@ static int two_in_flight(const CallEnv& env, const Mats& mt, int count, const Ca
 static int stream_of_calls(const CallEnv& env, const Mats& mt, int count, const Call& cl) {
 	const int depth = g_set.loop_depth.load();
 	int first = 0;
-	if (count < 2 || depth < 2) {
+	bool in_order = count < 2 || depth < 2;
+	if (!in_order && env.dist && !mt.same()) {
+		const int rc = conflict_on_any_rank(env, mt, count, cl, &in_order);
+		if (rc) return rc;
+	}
+	if (in_order) {
 		for (int i = 0; i < count; i++) {
 			const int st = blocking_one(env, mt, i, cl);
 			mt.state(i, st);
@@ -2201,6 +2273,9 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 	if (emode < 0 || n > m || m == 0 || n == 0 || n > PW || n <= 16 || ldq < m || lda < m || ldr < n) return NOT_MINE;
 	for (int i = 0; i < (mt.same() ? 1 : count); i++)
 		if (!aligned16(mt.a(i), lda) || !aligned16(mt.q(i), ldq)) return NOT_MINE;
+	const Call cl{mode, 0, ldq, ldr, lda, m, n, wq_v, wr_v, h_wl, stream};
+	for (int i = 0; i + 1 < count; i++)                  // a pair of calls that conflict (stream_order.h): the batch runs as blocking calls
+		if (pair_conflicts(mt, count, i, cl, sizeof(_Float16))) return NOT_MINE;
 	Ctx c;
 	init_ctx(c, wq_v, wr_v, m, n, stream);
 	c.rows_global = (double)m;
@@ -2212,9 +2287,8 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 	unsigned seq[2] = {0, 0};
 	// n = 64, three calls or more: the chained schedule (tsqr_mi_qr_f32_loop's, with gram_h_chain_kernel) -- the R-factor chain of call i
 	// inside the Gram launch of call i + 1, two sets of partials
-	// (the chained launch order needs Q and R of call i clear of A of call i + 1, and two different matrices must share the Infinity Cache)
-	const Call cl{mode, 0, ldq, ldr, lda, m, n, wq_v, wr_v, h_wl, stream};
-	const bool chained = (n == PW && count >= 3 && g_set.loop_depth.load() >= 3 && chain_order_safe(mt, count, cl, sizeof(_Float16)) &&
+	// (the chained launch order needs a loop's Q and R clear of its A, and two different matrices must share the Infinity Cache)
+	const bool chained = (n == PW && count >= 3 && g_set.loop_depth.load() >= 3 && out_of_order(mt, count, cl, sizeof(_Float16)) &&
 	                      (mt.same() || (double)lda * (double)n * sizeof(_Float16) <= (double)g_set.chain_max_mib * 1048576.0));
 	const GramPlan g = gram_plan(m, n);
 	const int nelem = 10 * 256, nred = nelem / 16;
@@ -2412,7 +2486,7 @@ int tsqr_mi_qr_f32_dist_cb_loop(int count, int mode, int reorth, float* q, size_
 
 // `count` DIFFERENT row-partitioned matrices (every rank: its row block of each; one block height for all): the stream of calls of the
 // loop entries over one (q, r, a) triple per call.  Every rank passes the same count, the same loop depth and operands of the same
-// eligibility (alignment, overlap) on the same calls' positions -- the verdicts, and so the path through the batch, are the same on
+// eligibility (alignment) on the same calls' positions (operand overlap is agreed on by an all-reduce) -- the verdicts, and so the path through the batch, are the same on
 // all ranks by construction (they come from the all-reduced matrix).
 int tsqr_mi_qr_f32_dist_fn_batch(int count, int mode, int reorth, float* const* q, size_t ldq, float* const* r, size_t ldr, float* const* a, size_t lda,
                                  size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,

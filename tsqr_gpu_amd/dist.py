@@ -238,9 +238,8 @@ class HipBackend:
     def bind_batch(self, qs, ldq, rs, ldr, as_, lda, m_local, reorth):
         """`len(as_)` DIFFERENT row-partitioned matrices through one C call (tsqr_mi_qr_f32_dist_{fn,cb}_batch): returns a callable giving
         (first non-zero state, [states]).  Every rank binds the same number of matrices."""
+        bq.check_batch_operands(qs, ldq, rs, ldr, as_, lda, m_local, self.n)
         self._check_block(m_local)
-        if not (len(qs) == len(rs) == len(as_)):
-            raise ValueError("qr_batch: q, r and a must name the same number of matrices")
         st = torch.cuda.current_stream()
         count = len(as_)
         vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
