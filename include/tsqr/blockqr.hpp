@@ -284,6 +284,57 @@ inline state_t qr_batch(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_batch: ") + tsqr_mi_last_error());
 	return st;
 }
+
+// Not in the reference: double-precision tall-skinny QR, 1 <= n <= m, n <= 64 (tsqr_mi_qr_f64, include/tsqr_mi.h for the contract).
+// Reorthogonalize = false: one CholeskyQR sweep when the device's estimate of its loss of orthogonality is <= 1e-12, CholeskyQR2
+// otherwise; true: CholeskyQR2 at least.  Either falls back to shifted CholeskyQR3 on a Gram matrix the Cholesky step rejects.
+// Returns success_factorization, error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite.
+const state_t error_not_finite = TSQR_MI_ERROR_NOT_FINITE;
+
+template <bool Reorthogonalize>
+struct buffer_fp64 {
+	double* dwq;
+	double* dwr;
+	std::size_t total_memory_size;
+
+	buffer_fp64() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
+	~buffer_fp64() { destroy(); }
+	buffer_fp64(const buffer_fp64&) = delete;
+	buffer_fp64& operator=(const buffer_fp64&) = delete;
+
+	void allocate(const std::size_t m, const std::size_t n) {
+		if (dwq != nullptr || dwr != nullptr) {
+			throw std::runtime_error("The buffer has been already allocated");
+		}
+		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64(m, n);
+		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64(m, n);
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
+		total_memory_size = wq_size + wr_size;
+	}
+
+	void destroy() {
+		if (dwq) (void)hipFree(dwq);
+		dwq = nullptr;
+		if (dwr) (void)hipFree(dwr);
+		dwr = nullptr;
+	}
+
+	std::size_t get_device_memory_size() const { return total_memory_size; }
+};
+
+template <bool Reorthogonalize>
+inline state_t qr_fp64(
+		double* const q_ptr, const std::size_t ldq,
+		double* const r_ptr, const std::size_t ldr,
+		double* const a_ptr, const std::size_t lda,
+		const std::size_t m, const std::size_t n,
+		buffer_fp64<Reorthogonalize>& bf,
+		handle_t const stream = nullptr) {
+	const int st = tsqr_mi_qr_f64(Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
 }  // namespace qr
 }  // namespace mtk
 

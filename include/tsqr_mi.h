@@ -43,6 +43,7 @@ enum tsqr_mi_compute_mode {
 #define TSQR_MI_SUCCESS               0   /* success_factorization */
 #define TSQR_MI_ERROR_INVALID_SIZE    1   /* error_invalid_matrix_size: n > m, m == 0 or n == 0 */
 #define TSQR_MI_ERROR_UNSUPPORTED     2   /* new: compute_mode without a gfx950 implementation */
+#define TSQR_MI_ERROR_NOT_FINITE      3   /* new, tsqr_mi_qr_f64 only: A holds an Inf or NaN (or A^T A overflows); Q and R are undefined */
 /* negative return values: -(hipError_t) of the failing runtime call */
 
 int tsqr_mi_version(void);
@@ -299,6 +300,28 @@ int tsqr_mi_qr_f32_dist_cb_batch(int count, int mode, int reorth,
                                  size_t m_local, size_t n,
                                  void* wq, void* wr, float* gather_buf,
                                  tsqr_mi_allreduce_f64_cb allreduce, tsqr_mi_allgather_f32_cb allgather, void* user, int nranks, void* stream, int* states);
+
+/*
+ * Double-precision tall-skinny QR (not in the reference): q (m x n, ldq), r (n x n, ldr) and a (m x n, lda) hold doubles, column-major,
+ * device memory; 1 <= n <= 64, n <= m.  Blocking: returns when its work on `stream` has finished.  A is untouched unless q == a
+ * (in place, allowed with ldq == lda); Q and R must not overlap A otherwise, nor each other.  R: the full n x n block, exact zeros below
+ * the diagonal, a positive diagonal.  Bitwise deterministic (fixed reduction tree).  Work space: wq of tsqr_mi_working_q_size_f64(m, n)
+ * doubles, wr of tsqr_mi_working_r_size_f64(m, n) doubles.
+ * Sweeps of CholeskyQR on the fp64 matrix cores; the Cholesky step judges each Gram matrix on the device (the rule and its sources:
+ * CholArgs64 in tsqr_f64.hip):
+ *   reorth = 0  sweep 1 alone when its estimated ||Q^T Q - I||_F is <= 1e-12 (well-conditioned input: cond(A D^-1) <= 10 with D the column norms, always), else a
+ *               second sweep on Q (CholeskyQR2); a Gram matrix the rule rejects is factored shifted, and two plain sweeps follow
+ *               (shifted CholeskyQR3).  For cond(A) <= 1e12, m <= 2^23: ||Q^T Q - I||_F <= 1e-11, ||A - Q R||_F / ||A||_F <= 1e-13.
+ *   reorth = 1  at least two sweeps (CholeskyQR2), shifted CholeskyQR3 on rejection: ||Q^T Q - I||_F <= 1e-12, residual as above.
+ * Returns 0, 1 (n > m, m == 0, n == 0, or a leading dimension below its operand's rows), 2 (n > 64; tsqr_mi_last_error says so),
+ * 3 = TSQR_MI_ERROR_NOT_FINITE, or -(hipError_t).  Sizes are checked before any HIP call.
+ * tsqr_mi_last_sweeps_f64: sweeps of the calling thread's last tsqr_mi_qr_f64, plus 100 when it took the shifted path.
+ */
+size_t tsqr_mi_working_q_size_f64(size_t m, size_t n);
+size_t tsqr_mi_working_r_size_f64(size_t m, size_t n);
+int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                   size_t m, size_t n, void* wq, void* wr, void* stream);
+int tsqr_mi_last_sweeps_f64(void);
 
 /* Harness support (reference src/validation.cu:43-127, src/test.cu:147-165): accuracy metrics evaluated on the device in fp64.
  * scratch: n*n + 8 doubles of device memory.  out_host[0..4] = ||Q^T Q - I||_F^2, its diagonal part, its off-diagonal part,

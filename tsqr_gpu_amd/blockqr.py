@@ -36,6 +36,7 @@ tsqr_colmun_size = 16                 # reference src/blockqr.hpp:25 (name kept,
 success_factorization = 0             # reference src/blockqr.hpp:28
 error_invalid_matrix_size = 1         # reference src/blockqr.hpp:29
 error_unsupported_mode = 2            # new: modes without a gfx950 implementation
+error_not_finite = 3                  # new, qr_f64 only: A holds an Inf or NaN
 
 C_ABI_SYMBOLS = [
     "tsqr_mi_version", "tsqr_mi_last_error",
@@ -50,6 +51,7 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_qr_f16", "tsqr_mi_qr_f16_loop", "tsqr_mi_working_q_size_f16", "tsqr_mi_working_r_size_f16",
     "tsqr_mi_qr_f32_submit", "tsqr_mi_qr_f32_finish", "tsqr_mi_set_loop_depth", "tsqr_mi_qr_f32_batch", "tsqr_mi_qr_f16_batch",
     "tsqr_mi_qr_f32_dist_fn_batch", "tsqr_mi_qr_f32_dist_cb_batch",
+    "tsqr_mi_qr_f64", "tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64", "tsqr_mi_last_sweeps_f64",
 ]
 
 
@@ -174,6 +176,13 @@ def lib():
     L.tsqr_mi_set_tuning2.argtypes = [ci, ci]
     L.tsqr_mi_set_tuning.restype = None
     L.tsqr_mi_set_tuning.argtypes = [ci, ci]
+    for name in ("tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64"):
+        getattr(L, name).restype = sz
+        getattr(L, name).argtypes = [sz, sz]
+    L.tsqr_mi_qr_f64.restype = ci
+    L.tsqr_mi_qr_f64.argtypes = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp]
+    L.tsqr_mi_last_sweeps_f64.restype = ci
+    L.tsqr_mi_last_sweeps_f64.argtypes = []
     _lib = L
     return L
 
@@ -418,6 +427,88 @@ def bind_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream=None, mode=None, reo
 def qr_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream=None, mode=None, reorthogonalize=None):
     """One-shot form of bind_batch(): returns (first non-zero state, [states])."""
     return bind_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream, mode, reorthogonalize)()
+
+
+class buffer_f64:
+    """Work space of qr_f64 (tsqr_mi_working_{q,r}_size_f64 doubles on the GPU).  reorthogonalize: the reorth argument qr_f64 passes
+    unless told otherwise (False: one CholeskyQR sweep when the device's estimate allows it, True: CholeskyQR2 at least)."""
+
+    def __init__(self, reorthogonalize=False, device="cuda"):
+        self.reorthogonalize = bool(reorthogonalize)
+        self.device = device
+        self.dwq = self.dwr = None
+
+    def allocate(self, m, n):
+        import torch
+        if self.dwq is not None or self.dwr is not None:
+            raise RuntimeError("The buffer has been already allocated")
+        L = lib()
+        self.dwq = torch.empty(max(L.tsqr_mi_working_q_size_f64(m, n), 1), dtype=torch.float64, device=self.device)
+        self.dwr = torch.empty(max(L.tsqr_mi_working_r_size_f64(m, n), 1), dtype=torch.float64, device=self.device)
+
+    def free(self):
+        self.dwq = self.dwr = None
+
+    def get_device_memory_size(self):
+        return 0 if self.dwq is None else 8 * (self.dwq.numel() + self.dwr.numel())
+
+
+def check_f64_operands(m, n, ldq, ldr, lda, q, r, a):
+    """The size and overlap rules of qr_f64 on (address, elements) pairs: ld >= rows, room for (n - 1) ld + rows doubles, q either
+    the very operand a (same address and ld: in place) or apart from it, r apart from both.  Raises ValueError."""
+    ops = (("q", q, ldq, m), ("r", r, ldr, n), ("a", a, lda, m))
+    span = {}
+    for name, (addr, numel), ld, rows in ops:
+        if ld < rows:
+            raise ValueError("qr_f64: ld%s = %d is smaller than the %d rows of %s" % (name, ld, rows, name))
+        need = (n - 1) * ld + rows
+        if numel < need:
+            raise ValueError("qr_f64: %s holds %d elements, an operand of %d x %d with ld %d needs %d" % (name, numel, rows, n, ld, need))
+        span[name] = (addr, addr + 8 * need)
+    apart = lambda x, y: span[x][1] <= span[y][0] or span[y][1] <= span[x][0]
+    if not (q[0] == a[0] and ldq == lda) and not apart("q", "a"):
+        raise ValueError("qr_f64: q overlaps a without being a (in place needs q == a and ldq == lda)")
+    for other in ("q", "a"):
+        if not apart("r", other):
+            raise ValueError("qr_f64: r overlaps %s" % other)
+
+
+def qr_f64(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
+    """Double-precision tall-skinny QR (tsqr_mi_qr_f64), 1 <= n <= 64, n <= m: q, r, a are float64 GPU tensors holding column-major
+    data (only data_ptr and numel are used); q may be a itself (in place, ldq == lda).  Blocking; returns the state: 0,
+    error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite.  Operands are checked before anything is launched:
+    TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a leading dimension below the rows, or overlapping
+    operands.  last_sweeps_f64() tells how many sweeps the call took."""
+    import torch
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    for name, t in (("q", q), ("r", r), ("a", a)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError("qr_f64: %s must be a float64 tensor, got %s" % (name, getattr(t, "dtype", type(t).__name__)))
+    for name, t in (("q", q), ("r", r), ("a", a)):
+        if not t.is_cuda:
+            raise TypeError("qr_f64: %s is not a GPU tensor" % name)
+    if n > m or m == 0 or n == 0:
+        return error_invalid_matrix_size
+    if n > 64:
+        return lib().tsqr_mi_qr_f64(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
+    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
+    if bf.dwq is None:
+        raise RuntimeError("qr_f64: the buffer is not allocated")
+    L = lib()
+    if bf.dwq.numel() < L.tsqr_mi_working_q_size_f64(m, n) or bf.dwr.numel() < L.tsqr_mi_working_r_size_f64(m, n):
+        raise ValueError("qr_f64: the buffer was allocated for a smaller matrix")
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    st = L.tsqr_mi_qr_f64(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
+                          bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("tsqr_mi_qr_f64 failed: %s" % last_error())
+    return st
+
+
+def last_sweeps_f64():
+    """Sweeps of this thread's last qr_f64 call, plus 100 when it took the shifted path."""
+    return lib().tsqr_mi_last_sweeps_f64()
 
 
 def set_tuning(level0_waves=0, tree_chunks_per_wave=0):

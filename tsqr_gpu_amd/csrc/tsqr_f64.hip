@@ -1,0 +1,251 @@
+// tsqr_f64.hip -- the device side of the double-precision entry (tsqr_mi_qr_f64): CholeskyQR sweeps on fp64 data, n <= 64.
+// Included by tsqr_mi.hip after tsqr_kernels.hip, whose Gram reduction (gram_reduce1_kernel) and Cholesky body (chol_body16<double>)
+// it reuses unchanged.
+//   gram_f64_kernel   : per-workgroup partials of A^T A on v_mfma_f64_16x16x4_f64 -- gram_kernel with fp64 loads: the same chunk
+//                       interleave, the same (tile, reg, lane) accumulator order, the same workgroup sum
+//   chol_f64_kernel   : G -> R, Z = inverse(R) in fp64, the fp64 acceptance rule (CholArgs64), a rejected matrix factored again at
+//                       once with the shift of Fukaya et al.
+//   apply_f64_kernel  : Q = A Z on v_mfma_f64_16x16x4_f64, Z upper triangular (its zero blocks are skipped), in place allowed
+//   rmul_f64_kernel   : R <- R2 R on v_mfma_f64_16x16x4_f64, in place
+#include <hip/hip_runtime.h>
+
+namespace tsqrmi {
+
+typedef double f64x2u __attribute__((ext_vector_type(2), aligned(8)));   // 8-byte aligned 16-byte access (any lda)
+
+// the (c,q) chunk layout of load_chunk with fp64 elements: lane 16 q + c holds rows 16 rt + 4 q + i of column 16 ct + c in
+// p[ct][4 rt + i]; rows >= m and columns >= n read as zero
+template <int NT>
+__device__ __forceinline__ void load_chunk_f64(double (&p)[NT][16], const double* __restrict__ src, size_t ld, size_t row0, size_t m, int n,
+                                               int c, int q) {
+	const bool full = (row0 + 64 <= m);
+#pragma unroll
+	for (int ct = 0; ct < NT; ct++) {
+		const int col = 16 * ct + c;
+		const double* base = src + (size_t)col * ld + row0 + 4 * q;
+		if (col < n) {
+			if (full) {
+#pragma unroll
+				for (int rt = 0; rt < 4; rt++) {
+					const f64x2u v0 = *reinterpret_cast<const f64x2u*>(base + 16 * rt);
+					const f64x2u v1 = *reinterpret_cast<const f64x2u*>(base + 16 * rt + 2);
+					p[ct][4 * rt + 0] = v0[0]; p[ct][4 * rt + 1] = v0[1]; p[ct][4 * rt + 2] = v1[0]; p[ct][4 * rt + 3] = v1[1];
+				}
+			} else {
+#pragma unroll
+				for (int rt = 0; rt < 4; rt++)
+#pragma unroll
+					for (int i = 0; i < 4; i++) {
+						const size_t row = row0 + 16 * rt + 4 * q + i;
+						p[ct][4 * rt + i] = (row < m) ? base[16 * rt + i] : 0.0;
+					}
+			}
+		} else {
+#pragma unroll
+			for (int r = 0; r < 16; r++) p[ct][r] = 0.0;
+		}
+	}
+}
+
+struct GramArgs64 {
+	const double* a; size_t lda; size_t m; int n;
+	int nchunks; int nwaves;
+	double* part;                        // [gridDim.x][NTRI][256], the order of gram_kernel's partials
+};
+
+template <int NT>
+__global__ __launch_bounds__(256) void gram_f64_kernel(const GramArgs64 a) {
+	constexpr int NTRI = (NT * (NT + 1)) / 2;
+	__shared__ double red[2][NTRI * 256];
+	const int lane = threadIdx.x & 63;
+	const int wv = threadIdx.x >> 6;
+	const int gw = blockIdx.x * 4 + wv;
+	const int c = lane & 15, q = lane >> 4;
+	f64x4 acc[NTRI];
+#pragma unroll
+	for (int t = 0; t < NTRI; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+	if (gw < a.nwaves) {
+		double p[NT][16];
+		for (int ch = gw; ch < a.nchunks; ch += a.nwaves) {      // interleaved: consecutive chunks go to consecutive waves
+			load_chunk_f64<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
+#pragma unroll
+			for (int rho = 0; rho < 16; rho++) {
+				int idx = 0;
+#pragma unroll
+				for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+					for (int tj = ti; tj < NT; tj++) {
+						acc[idx] = __builtin_amdgcn_mfma_f64_16x16x4f64(p[ti][rho], p[tj][rho], acc[idx], 0, 0, 0);
+						idx++;
+					}
+			}
+		}
+	}
+	// workgroup sum (as gram_kernel): waves 2,3 -> LDS, waves 0,1 add; wave 1 -> LDS, wave 0 adds and stores the partial
+	if (wv >= 2) {
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) red[wv - 2][(t * 4 + r) * 64 + lane] = acc[t][r];
+	}
+	__syncthreads();
+	if (wv < 2) {
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) acc[t][r] += red[wv][(t * 4 + r) * 64 + lane];
+	}
+	__syncthreads();
+	if (wv == 1) {
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) red[0][(t * 4 + r) * 64 + lane] = acc[t][r];
+	}
+	__syncthreads();
+	if (wv == 0) {
+		double* out = a.part + (size_t)blockIdx.x * NTRI * 256;
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], acc[t][r] + red[0][(t * 4 + r) * 64 + lane]);
+	}
+}
+
+// The Cholesky step of the fp64 entry: chol_body16 with fp64 R and Z.  Level 4 of the ladder ("fp64 data"): the rule is stated on the
+// scaled conditioning S = ||D inverse(R)||_F^2 / n (D = diag(sqrt(g_jj)); chol_body16), with u = 2^-53 and rows = m:
+//   accepted for CholeskyQR2   every pivot positive and finite, and  64 n S u (m n + n (n + 1)) <= 1.  Yamamoto, Nakatsukasa, Yanagisawa
+//                              and Fukaya, "Roundoff error analysis of the CholeskyQR2 algorithm", ETNA 44 (2015): CholeskyQR2 gives
+//                              O(u) orthogonality when 8 kappa sqrt(m n u + n (n + 1) u) <= 1.  The Gram error of column-scaled data
+//                              is relative to the column norms, so kappa^2 is taken as ||(A D^-1)^+||_2^2 <= n S;
+//   accepted ALONE (one sweep) additionally when  4 n S u <= 1e-12: the estimated ||Q^T Q - I||_F of one CholeskyQR sweep, the rounding
+//                              of G (a few u relative to the column norms, per entry) carried through inverse(R) twice;
+//   rejected                   otherwise: the same launch factors G + s I, s = 11 (m n + n (n + 1)) u trace(G) (Fukaya, Kannan,
+//                              Nakatsukasa, Yamamoto and Yanagisawa, "Shifted Cholesky QR for computing the QR factorization of
+//                              ill-conditioned matrices", SISC 42 (2020)), accepted whenever every pivot is positive: two more sweeps
+//                              follow (shifted CholeskyQR3).  Rejected even so: non-finite input.
+// Sweeps after the first pass alone_max = max_scond = infinity: their input is Q of a sweep before, and only a breakdown sends them
+// to the shift.
+struct CholArgs64 {
+	double* r; size_t ldr;               // R out: n x n, full block written (zeros below the diagonal)
+	double* z;                           // Z = inverse(R) out: NP x NP column-major (ld NP), zero padded
+	unsigned* status;                    // device words [0] verdict, [1] min pivot ratio (float bits), [2] S (float bits), [3] one sweep suffices
+	unsigned* host_status;               // device-visible alias of pinned host words receiving the same four values at the end of the launch
+	const double* gsum;                  // summed Gram tiles, fp64 accumulator order (gram_f64_kernel + gram_reduce1_kernel)
+	double shift_coef;                   // 11 u (m n + n (n + 1)): s = shift_coef * trace(G)
+	float max_scond;                     // CholeskyQR2 bound on S (above)
+	float alone_max;                     // one-sweep bound on S (above); 0: never alone
+	int n, NT;
+};
+// verdict words: 0 accepted, 2 accepted after the shift, 1 rejected (non-finite input)
+__global__ __launch_bounds__(1024) void chol_f64_kernel(const CholArgs64 a) {
+	auto loadg = [&](int e) { return a.gsum[e]; };
+	chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, a.max_scond, 0.0, 0.0);
+	__shared__ unsigned again;
+	__syncthreads();
+	if (threadIdx.x == 0) {                              // (thread 0 wrote the verdict itself: program order)
+		again = a.status[0];
+		a.status[3] = (a.status[0] == 0u && __builtin_bit_cast(float, a.status[2]) <= a.alone_max) ? 1u : 0u;
+	}
+	__syncthreads();
+	if (again) {
+		chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, INFINITY, a.shift_coef, 0.0);
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			if (a.status[0] == 0u) a.status[0] = 2u;
+			a.status[3] = 0u;
+		}
+	}
+	if (threadIdx.x == 0) {
+		volatile unsigned* hs = a.host_status;
+		hs[1] = a.status[1];
+		hs[2] = a.status[2];
+		hs[3] = a.status[3];
+		hs[0] = a.status[0];
+	}
+}
+
+// Q = A Z, Z (ld NP) upper triangular.  Each wave owns 32-row blocks (two 16-row tiles; a persistent grid strides over them) and
+// computes Q^T tile by tile: D[j][r] = sum_k Z[k][j] A[r][k] -- MFMA operand A is Z^T (lane (li, lq) holds Z[4 kb + lq][16 jt + li]),
+// operand B is A^T (lane (li, lq) holds A[row0 + li][4 kb + lq]), so the C/D layout (col = lane & 15, row = (lane >> 4) + 4 reg)
+// puts sixteen consecutive ROWS of one column of Q in sixteen lanes: every load and store moves whole 128-byte column segments.
+// Output tile jt needs k < 16 (jt + 1) only: 2 NT (NT + 1) k-blocks of Z instead of 4 NT^2, held in registers for the whole kernel.
+// In place (q == a, ldq == lda) is safe: a wave reads all n columns of its rows before it writes any of them (every stored column
+// block depends on the loads of its own columns), and no two waves share a row.
+template <int NT>
+__global__ __launch_bounds__(256) void apply_f64_kernel(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n,
+                                                        const double* __restrict__ z, size_t nblocks) {
+	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1);
+	const int lane = threadIdx.x & 63, li = lane & 15, lq = lane >> 4;
+	const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (size_t)gridDim.x * 4;
+	double zop[NZ];
+	static_for<0, NT>([&](auto jt_) {
+		constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+#pragma unroll
+		for (int kb = 0; kb < 4 * (jt + 1); kb++) zop[base + kb] = z[(size_t)(16 * jt + li) * NP + 4 * kb + lq];
+	});
+	for (size_t blk = gw; blk < nblocks; blk += nw) {
+		const size_t row0 = blk * 32;
+		double av[2][KB];
+#pragma unroll
+		for (int rt = 0; rt < 2; rt++) {
+			const size_t row = row0 + 16 * rt + li;
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) {
+				const int col = 4 * kb + lq;
+				av[rt][kb] = (row < m && col < n) ? a[(size_t)col * lda + row] : 0.0;
+			}
+		}
+		f64x4 acc[2][NT];
+		static_for<0, NT>([&](auto jt_) {
+			constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+#pragma unroll
+			for (int rt = 0; rt < 2; rt++) {
+				acc[rt][jt] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+				for (int kb = 0; kb < 4 * (jt + 1); kb++)
+					acc[rt][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(zop[base + kb], av[rt][kb], acc[rt][jt], 0, 0, 0);
+			}
+		});
+#pragma unroll
+		for (int rt = 0; rt < 2; rt++) {
+			const size_t row = row0 + 16 * rt + li;
+#pragma unroll
+			for (int jt = 0; jt < NT; jt++)
+#pragma unroll
+				for (int reg = 0; reg < 4; reg++) {
+					const int col = 16 * jt + lq + 4 * reg;
+					if (row < m && col < n) q[(size_t)col * ldq + row] = acc[rt][jt][reg];
+				}
+		}
+	}
+}
+
+// R <- R2 R (n x n upper triangular, n <= 64; R2 packed with ld 64), in place: one workgroup of sixteen waves stages both factors
+// in LDS, wave w forms the 16 x 16 tile (w >> 2, w & 3) over the k range in which both are non-zero (rmul64_kernel's scheme with
+// fp64 I/O).  Every thread has read its entries before the barrier that precedes the first store.
+__global__ __launch_bounds__(1024) void rmul_f64_kernel(double* r, size_t ldr, const double* __restrict__ r2, int n) {
+	__shared__ double A2[64 * 65], A1[64 * 65];          // A2[i * 65 + k] = R2[i][k], A1[k * 65 + j] = R[k][j]; zero outside the upper triangles
+	const int t = threadIdx.x;
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		const bool in = i <= j && j < n;
+		A2[i * 65 + j] = in ? r2[(size_t)j * 64 + i] : 0.0;
+		A1[i * 65 + j] = in ? r[(size_t)j * ldr + i] : 0.0;
+	}
+	__syncthreads();
+	const int w = t >> 6, l = t & 63, ti = w >> 2, tj = w & 3, li = l & 15, lq = l >> 4;
+	f64x4 c = f64x4{0.0, 0.0, 0.0, 0.0};                // c[reg] = (R2 R)[16 ti + lq + 4 reg][16 tj + li]
+	if (ti <= tj) {
+		for (int ks = 4 * ti; ks < 4 * (tj + 1); ks++)
+			c = __builtin_amdgcn_mfma_f64_16x16x4f64(A2[(16 * ti + li) * 65 + 4 * ks + lq], A1[(4 * ks + lq) * 65 + 16 * tj + li], c, 0, 0, 0);
+	}
+#pragma unroll
+	for (int reg = 0; reg < 4; reg++) {
+		const int i = 16 * ti + lq + 4 * reg, j = 16 * tj + li;
+		if (i < n && j < n) r[(size_t)j * ldr + i] = (i <= j) ? c[reg] : 0.0;
+	}
+}
+
+}  // namespace tsqrmi

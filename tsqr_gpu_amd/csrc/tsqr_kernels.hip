@@ -1301,9 +1301,11 @@ __device__ __forceinline__ void chol_section4(double (&g)[4], double (&mm)[4], c
 //                host reads them only after the completion word of a LATER kernel on the stream, or after a stream synchronisation
 //                (a system-scope release here wrote back the whole L2 on the critical path of every call)
 //   gs_out     : receives the address of the fp64 LDS image of Z (chol_wide_kernel goes on with it)
+//   OT         : element type of R and Z in global memory -- float for the fp32 pipeline (rounded on the way out), double for the
+//                fp64 one (chol_f64_kernel, tsqr_f64.hip: the factorisation's own values leave unrounded)
 // ---------------------------------------------------------------------------------------------
-template <class LOADG>
-__device__ __forceinline__ void chol_body16(float* __restrict__ r, size_t ldr, float* __restrict__ z, unsigned* __restrict__ status,
+template <class OT, class LOADG>
+__device__ __forceinline__ void chol_body16(OT* __restrict__ r, size_t ldr, OT* __restrict__ z, unsigned* __restrict__ status,
                                             unsigned* __restrict__ host_status, LOADG loadg, int n, int NT, int f32_layout, float min_ratio,
                                             float max_scond, double shift_coef = 0.0, double min_diag = 0.0, double** gs_out = nullptr) {
 	__shared__ double Gs[64 * 65];               // symmetric G (assembly); afterwards the fp64 image of Z: Gs[K * 65 + j] = Z[j][K]
@@ -1328,7 +1330,7 @@ __device__ __forceinline__ void chol_body16(float* __restrict__ r, size_t ldr, f
 	}
 	if (NT < 4)
 		for (int i = t; i < 64 * 65; i += 1024) Gs[i] = 0.0;
-	for (int e = n * NP + t; e < NP * NP; e += 1024) z[e] = 0.0f;         // padding rows of Z
+	for (int e = n * NP + t; e < NP * NP; e += 1024) z[e] = (OT)0;        // padding rows of Z
 	__syncthreads();
 	if (t < 256) {
 		const int reg = t >> 6, l = t & 63;
@@ -1445,8 +1447,8 @@ __device__ __forceinline__ void chol_body16(float* __restrict__ r, size_t ldr, f
 				const int K = K0 + u;
 				const double rkj = rr[u * 64 + j], mkc = mr[u * 64 + j];
 				if (K < n) {
-					if (j < NP) z[(size_t)K * NP + j] = (j <= K) ? (float)mkc : 0.0f;     // Z[j][K] = M[K][j]
-					if (j < n) r[(size_t)j * ldr + K] = (j >= K) ? (float)rkj : 0.0f;
+					if (j < NP) z[(size_t)K * NP + j] = (j <= K) ? (OT)mkc : (OT)0;       // Z[j][K] = M[K][j]
+					if (j < n) r[(size_t)j * ldr + K] = (j >= K) ? (OT)rkj : (OT)0;
 					Gs[K * 65 + j] = (j <= K) ? mkc : 0.0;                                 // (fp64 image, read on by chol_wide_kernel)
 					if (j <= K) s_acc = fma(dgj * mkc, mkc, s_acc);                        // sum of g_jj * Z[j][K]^2
 				}
@@ -1503,7 +1505,8 @@ struct CholArgs {
 	double shift_coef;                   // > 0: shifted Cholesky, s = shift_coef * (rows * n + n (n + 1)) * trace(G)
 	int n, NT;
 	int level;                           // 2 bf16-split Gram matrix (f32 accumulator layout; pivot ratio > 2^-5, S bound, column norms >= 2^-90 rows),
-	                                     // 1 fp64 Gram matrix (f64 accumulator layout; ratio > 2^-40), 3 shifted fp64 (ratio > 0: rejects only non-finite input)
+	                                     // 1 fp64 Gram matrix (f64 accumulator layout; ratio > 2^-40), 3 shifted fp64 (ratio > 0: rejects only non-finite input);
+	                                     // level 4, fp64 DATA (tsqr_mi_qr_f64), has a launch of its own: chol_f64_kernel, rule in CholArgs64 (tsqr_f64.hip)
 	float scond_floor;                   // bf16 level: S <= min(128, max(scond_floor, 0.12 sqrt(rows)))
 	int relax;                           // level 2 only: 1 = ANOTHER SWEEP FOLLOWS on the Q this factor produces (reorthogonalised calls), so Q need
 	                                     // only come out well conditioned, not orthonormal: pivot ratio > 2^-20, S <= min(1.6e7, 8000 sqrt(rows))

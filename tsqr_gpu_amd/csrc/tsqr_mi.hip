@@ -33,6 +33,7 @@
 #include "stream_order.h"
 #include "tsqr_kernels.hip"
 #include "tsqr_wide.hip"
+#include "tsqr_f64.hip"
 #include "validate.hip"
 
 namespace {
@@ -2627,6 +2628,168 @@ int tsqr_mi_rmul_f32(float* r, size_t ldr, const float* r2, size_t ldr2, size_t 
 	launch_rmul(r, ldr, r2, ldr2, r1, n, n, st);
 	HIPCHK(hipGetLastError());
 	return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The fp64 entry (tsqr_mi_qr_f64): CholeskyQR sweeps on fp64 data, n <= 64 (kernels: tsqr_f64.hip).  A sweep is the Gram pass,
+// the reduction, the Cholesky step with its verdict and the apply pass; sweep k >= 2 factors the Q of sweep k - 1 in place and
+// multiplies R on the left.  The host reads the verdicts when the stream drains -- the blocking call waits there anyway -- and
+// enqueues more sweeps when they are needed: one wait for a one-sweep call, and one more each time the ladder has to go on.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int F64_GRAM_WAVES = 2048;                    // fixed (not tsqr_mi_set_tuning2): the work-space size must not follow a setting
+constexpr int F64_MAX_SWEEPS = 6;
+// wq (doubles): [Z: 4096][R of the sweep: 4096][summed tiles + row count][status words: 4 slots x 4 words]
+constexpr size_t F64_Z = 0, F64_R2 = 4096, F64_GSUM = 8192, F64_STATUS = F64_GSUM + GSUM_DOUBLES, F64_WQ = F64_STATUS + 8;
+
+struct F64Plan { int NT, ntri, nch, nwaves, nblocks; };
+F64Plan f64_plan(size_t m, size_t n) {
+	F64Plan g{};
+	g.NT = (int)(np_of(n) / 16);
+	g.ntri = g.NT * (g.NT + 1) / 2;
+	g.nch = (int)cdiv(m, 64);
+	const size_t cpw = std::max<size_t>(1, cdiv((size_t)g.nch, F64_GRAM_WAVES));
+	g.nwaves = (int)cdiv((size_t)g.nch, cpw);
+	g.nblocks = (g.nwaves + 3) / 4;
+	return g;
+}
+
+thread_local int t_sweeps64 = 0;
+thread_local OwnPinned t_own64;                         // the verdict words of the fp64 entry (slot k & 3 for sweep k)
+
+// Gram pass, reduction and Cholesky step of one sweep over src: R -> r (ldr), Z -> wq[F64_Z], verdict -> status slot `slot`
+int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t ld, size_t m, size_t n, double* r, size_t ldr,
+               bool first, int slot) {
+	const F64Plan g = f64_plan(m, n);
+	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	const tsqrmi::GramArgs64 ga{src, ld, m, (int)n, g.nch, g.nwaves, wr};
+	switch (g.NT) {
+		case 1: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<1>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+		case 2: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<2>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+		case 3: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<3>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+		default: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<4>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+	}
+	HIPCHK(hipGetLastError());
+	const int nelem = g.ntri * 256;
+	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, st, wq + F64_GSUM, wr, g.nblocks, nelem, (double)m,
+	                   nullptr, (size_t)0, nullptr, 0);
+	HIPCHK(hipGetLastError());
+	tsqrmi::CholArgs64 ca{};
+	ca.r = r; ca.ldr = ldr; ca.z = wq + F64_Z;
+	ca.status = reinterpret_cast<unsigned*>(wq + F64_STATUS) + 4 * slot;
+	ca.host_status = t_own64.dev + 4 * slot;
+	ca.gsum = wq + F64_GSUM;
+	const double u = 0x1p-53, mn = (double)m * (double)n + (double)n * (double)(n + 1);
+	ca.shift_coef = 11.0 * u * mn;                       // CholArgs64 states the rule and its sources
+	ca.max_scond = first ? (float)(1.0 / (64.0 * (double)n * u * mn)) : INFINITY;
+	ca.alone_max = first ? (float)(1e-12 / (4.0 * (double)n * u)) : 0.0f;
+	ca.n = (int)n; ca.NT = g.NT;
+	hipLaunchKernelGGL(tsqrmi::chol_f64_kernel, dim3(1), dim3(1024), 0, st, ca);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// Q = A Z on a persistent grid: as many workgroups as are resident at once, each wave striding over 32-row blocks
+template <int NT> int f64_apply(hipStream_t st, int dev, double* q, size_t ldq, const double* a, size_t lda, size_t m, size_t n, const double* z) {
+	static DevOnce once;
+	static std::atomic<int> resident[MAX_DEV];
+	if (once.need(dev)) {
+		int nb = 0, cus = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tsqrmi::apply_f64_kernel<NT>), 256, 0) != hipSuccess || nb < 1) {
+			(void)hipGetLastError(); nb = 1;
+		}
+		if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
+		resident[dev].store(nb * cus);
+		once.done(dev);
+	}
+	const size_t nblocks = cdiv(m, 32);
+	const size_t wgs = std::max<size_t>(1, std::min(cdiv(nblocks, 4), (size_t)resident[dev].load()));
+	hipLaunchKernelGGL(tsqrmi::apply_f64_kernel<NT>, dim3((unsigned)wgs), dim3(256), 0, st, q, ldq, a, lda, m, (int)n, z, nblocks);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// sweep k (0-based): sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R
+int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
+              double* wq, double* wr) {
+	const bool first = k == 0;
+	const double* src = first ? a : q;
+	const size_t lds = first ? lda : ldq;
+	int rc = f64_factor(st, wq, wr, src, lds, m, n, first ? r : wq + F64_R2, first ? ldr : 64, first, k & 3);
+	if (rc) return rc;
+	const double* z = wq + F64_Z;
+	switch (np_of(n) / 16) {
+		case 1: rc = f64_apply<1>(st, dev, q, ldq, src, lds, m, n, z); break;
+		case 2: rc = f64_apply<2>(st, dev, q, ldq, src, lds, m, n, z); break;
+		case 3: rc = f64_apply<3>(st, dev, q, ldq, src, lds, m, n, z); break;
+		default: rc = f64_apply<4>(st, dev, q, ldq, src, lds, m, n, z); break;
+	}
+	if (rc || first) return rc;
+	hipLaunchKernelGGL(tsqrmi::rmul_f64_kernel, dim3(1), dim3(1024), 0, st, r, ldr, wq + F64_R2, (int)n);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// The ladder (include/tsqr_mi.h): verdict 0 of sweep 0 with "one sweep suffices" ends a reorth = 0 call, any other accepted first
+// sweep is followed by one more (CholeskyQR2), a shifted sweep by two more (shifted CholeskyQR3), a rejected one ends the call (state 3).
+int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
+                hipStream_t st) {
+	t_sweeps64 = 0;
+	if (!t_own64.get()) { t_last_error = "could not allocate the pinned verdict words"; return -(int)hipErrorOutOfMemory; }
+	volatile unsigned* words = t_own64.host;
+	for (int i = 0; i < 16; i++) words[i] = 1u;          // (a sweep that never reported reads as rejected)
+	const int dev = cur_device();
+	int sweeps = 0, need = reorth ? 2 : 1, checked = 0;
+	bool shifted = false;
+	for (;;) {
+		while (sweeps < need) {
+			const int rc = f64_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr);
+			if (rc) return rc;
+			sweeps++;
+		}
+		HIPCHK(hipStreamSynchronize(st));
+		for (; checked < sweeps; checked++) {
+			const volatile unsigned* w = words + 4 * (checked & 3);
+			const unsigned v = w[0];
+			if (v == 1u) {
+				t_sweeps64 = checked + 1 + (shifted ? 100 : 0);
+				t_last_error = "non-finite input: the Cholesky step was rejected even with the shift";
+				return TSQR_MI_ERROR_NOT_FINITE;
+			}
+			if (v == 2u) { shifted = true; need = std::max(need, checked + 3); }
+			else if (checked == 0 && !(reorth == 0 && w[3] == 1u)) need = std::max(need, 2);
+		}
+		need = std::min(need, F64_MAX_SWEEPS);
+		if (sweeps >= need) break;
+	}
+	t_sweeps64 = sweeps + (shifted ? 100 : 0);
+	return TSQR_MI_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tsqr_mi_working_q_size_f64(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : F64_WQ; }
+size_t tsqr_mi_working_r_size_f64(size_t m, size_t n) {
+	if (m == 0 || n == 0) return 0;
+	const F64Plan g = f64_plan(m, std::min(n, PW));
+	return (size_t)g.nblocks * g.ntri * 256;
+}
+int tsqr_mi_last_sweeps_f64(void) { return t_sweeps64; }
+
+int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
+                   void* wq, void* wr, void* stream) {
+	t_sweeps64 = 0;
+	if (n > m || m == 0 || n == 0 || ldq < m || lda < m || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > PW) { t_last_error = "tsqr_mi_qr_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	if (rc) return rc;
+	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
+	                   reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
