@@ -335,6 +335,53 @@ inline state_t qr_fp64(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
+// Not in the reference: double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide, include/tsqr_mi.h for the
+// contract): qr_fp64 itself for n <= 64, whole-matrix CholeskyQR sweeps with the same ladder beyond.  Returns success_factorization,
+// error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.
+template <bool Reorthogonalize>
+struct buffer_fp64_wide {
+	double* dwq;
+	double* dwr;
+	std::size_t total_memory_size;
+
+	buffer_fp64_wide() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
+	~buffer_fp64_wide() { destroy(); }
+	buffer_fp64_wide(const buffer_fp64_wide&) = delete;
+	buffer_fp64_wide& operator=(const buffer_fp64_wide&) = delete;
+
+	void allocate(const std::size_t m, const std::size_t n) {
+		if (dwq != nullptr || dwr != nullptr) {
+			throw std::runtime_error("The buffer has been already allocated");
+		}
+		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_wide(m, n);
+		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_wide(m, n);
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
+		total_memory_size = wq_size + wr_size;
+	}
+
+	void destroy() {
+		if (dwq) (void)hipFree(dwq);
+		dwq = nullptr;
+		if (dwr) (void)hipFree(dwr);
+		dwr = nullptr;
+	}
+
+	std::size_t get_device_memory_size() const { return total_memory_size; }
+};
+
+template <bool Reorthogonalize>
+inline state_t qr_fp64_wide(
+		double* const q_ptr, const std::size_t ldq,
+		double* const r_ptr, const std::size_t ldr,
+		double* const a_ptr, const std::size_t lda,
+		const std::size_t m, const std::size_t n,
+		buffer_fp64_wide<Reorthogonalize>& bf,
+		handle_t const stream = nullptr) {
+	const int st = tsqr_mi_qr_f64_wide(Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64_wide: ") + tsqr_mi_last_error());
+	return st;
+}
 }  // namespace qr
 }  // namespace mtk
 

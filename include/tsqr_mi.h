@@ -323,6 +323,25 @@ int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, dou
                    size_t m, size_t n, void* wq, void* wr, void* stream);
 int tsqr_mi_last_sweeps_f64(void);
 
+/*
+ * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
+ * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
+ * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column
+ * blocks, a blocked Cholesky factorisation judged over the whole matrix on the device (the shifted refactorisation also on the device),
+ * Q = A inverse(R) (tsqr_f64_wide.hip).  Blocking; A is untouched unless q == a (in place, ldq == lda).
+ * R: the full n x n block, exact zeros below the diagonal, a positive diagonal.  Bitwise deterministic (fixed reduction trees).
+ * For cond(A) <= 1e12 and m n <= 2^26:
+ *   ||Q^T Q - I||_F <= 1e-11 max(1, n / 64)  (reorth = 0),  <= 1e-12 max(1, n / 64)  (reorth = 1);  ||A - Q R||_F / ||A||_F <= 1e-13.
+ * Work space: wq of tsqr_mi_working_q_size_f64_wide(m, n) doubles (six n x n block stores and a little more, independent of m), wr of
+ * tsqr_mi_working_r_size_f64_wide(m, n) doubles (Gram partials, at most 8 Mi doubles for every m).
+ * Returns 0, 1 (n > m, m == 0, n == 0, or a leading dimension below its operand's rows), 2 (n > 1024; tsqr_mi_last_error says so),
+ * 3 = TSQR_MI_ERROR_NOT_FINITE, or -(hipError_t).  Sizes are checked before any HIP call.  tsqr_mi_last_sweeps_f64 reports this entry too.
+ */
+size_t tsqr_mi_working_q_size_f64_wide(size_t m, size_t n);
+size_t tsqr_mi_working_r_size_f64_wide(size_t m, size_t n);
+int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                        size_t m, size_t n, void* wq, void* wr, void* stream);
+
 /* Harness support (reference src/validation.cu:43-127, src/test.cu:147-165): accuracy metrics evaluated on the device in fp64.
  * scratch: n*n + 8 doubles of device memory.  out_host[0..4] = ||Q^T Q - I||_F^2, its diagonal part, its off-diagonal part,
  * ||Q R - A||_F^2, ||A||_F^2 (the last two only when r and a are given).  gram_out_host: optional n*n doubles receiving Q^T Q. */

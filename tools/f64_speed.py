@@ -1,6 +1,7 @@
-"""Speed of the fp64 entry (tsqr_mi_qr_f64): median time of blocking calls per case, the sweep count, effective TB/s (24 m n bytes
-per sweep: the Gram pass reads A, the apply pass reads A and writes Q), and torch.linalg.qr(float64) on the same GPU for 2^20 x 64.
-Prints one JSON line.  Usage: python tools/f64_speed.py [--calls 50] [--warmup 5]"""
+"""Speed of the fp64 entries (tsqr_mi_qr_f64, n <= 64, and tsqr_mi_qr_f64_wide, the wide_* cases): median time of blocking calls per
+case, the sweep count, effective TB/s (24 m n bytes per sweep: the Gram pass reads A, the apply pass reads A and writes Q), for the wide
+cases the fp64 rate of one sweep's executed products (2 m n^2, Gram pass and apply pass together), and torch.linalg.qr(float64) on the
+same GPU for 2^20 x 64 and for every wide shape.  Prints one JSON line.  Usage: python tools/f64_speed.py [--calls 50] [--warmup 5]"""
 import argparse
 import json
 import os
@@ -20,19 +21,20 @@ def cond_matrix(torch, m, n, cond, seed):
     return (u * s) @ v.T
 
 
-def time_case(torch, bq, a_rm, reorth, calls, warmup):
+def time_case(torch, bq, a_rm, reorth, calls, warmup, wide=False):
     m, n = a_rm.shape
     a = a_rm.T.contiguous()                                 # (n, m): column-major m x n
     q = torch.empty_like(a)
     r = torch.empty(n, n, dtype=torch.float64, device="cuda")
-    bf = bq.buffer_f64(reorth)
+    bf = bq.buffer_f64_wide(reorth) if wide else bq.buffer_f64(reorth)
     bf.allocate(m, n)
+    entry = bq.qr_f64_wide if wide else bq.qr_f64
     for _ in range(warmup):
-        assert bq.qr_f64(q, m, r, n, a, m, m, n, bf) == 0, bq.last_error()
+        assert entry(q, m, r, n, a, m, m, n, bf) == 0, bq.last_error()
     ts = []
     for _ in range(calls):
         t0 = time.perf_counter()
-        st = bq.qr_f64(q, m, r, n, a, m, m, n, bf)
+        st = entry(q, m, r, n, a, m, m, n, bf)
         ts.append(time.perf_counter() - t0)
         assert st == 0
     ts.sort()
@@ -42,8 +44,23 @@ def time_case(torch, bq, a_rm, reorth, calls, warmup):
     eye = torch.eye(n, dtype=torch.float64, device="cuda")
     qm = q.T
     orth = torch.linalg.norm(qm.T @ qm - eye).item()
-    return {"m": m, "n": n, "reorth": reorth, "median_ms": med * 1e3, "min_ms": ts[0] * 1e3, "sweeps": sweeps,
-            "eff_TBps": 24.0 * m * n * nsw / med / 1e12, "orth_fro": orth}
+    out = {"m": m, "n": n, "reorth": reorth, "median_ms": med * 1e3, "min_ms": ts[0] * 1e3, "sweeps": sweeps,
+           "eff_TBps": 24.0 * m * n * nsw / med / 1e12, "orth_fro": orth}
+    if wide:
+        out["products_TFps"] = 2.0 * m * n * n * nsw / med / 1e12
+    return out
+
+
+def time_torch_qr(torch, a_rm, reps=3):
+    torch.linalg.qr(a_rm)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        torch.linalg.qr(a_rm)
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return sorted(ts)[len(ts) // 2] * 1e3
 
 
 def main():
@@ -61,27 +78,35 @@ def main():
     cases = [("gauss_2p20_r0", lambda: gauss(1 << 20, 1), 0), ("gauss_2p20_r1", lambda: gauss(1 << 20, 1), 1),
              ("cond1e12_2p20_r0", lambda: cond_matrix(torch, 1 << 20, n, 1e12, 2), 0),
              ("gauss_2p16_r0", lambda: gauss(1 << 16, 3), 0), ("gauss_2p23_r0", lambda: gauss(1 << 23, 4), 0)]
+    wgauss = lambda m, n, seed: torch.randn(m, n, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(seed))
+    wide_shapes = [("2p18x128", 1 << 18, 128), ("2p18x256", 1 << 18, 256), ("2p16x1024", 1 << 16, 1024)]
+    wide = []
+    for tag, m, wn in wide_shapes:
+        wide += [("wide_gauss_%s_r0" % tag, (lambda m=m, wn=wn: wgauss(m, wn, 5)), 0),
+                 ("wide_gauss_%s_r1" % tag, (lambda m=m, wn=wn: wgauss(m, wn, 5)), 1),
+                 ("wide_cond1e12_%s_r0" % tag, (lambda m=m, wn=wn: cond_matrix(torch, m, wn, 1e12, 6)), 0)]
     only = [c for c in args.cases.split(",") if c]
-    for name, make, reorth in cases:
+    for name, make, reorth in cases + wide:
         if only and name not in only:
             continue
-        res = time_case(torch, bq, make(), reorth, args.calls, args.warmup)
+        res = time_case(torch, bq, make(), reorth, args.calls, args.warmup, wide=name.startswith("wide_"))
         res["case"] = name
         out["cases"].append(res)
         torch.cuda.empty_cache()
     if args.no_torch:
         print(json.dumps(out))
         return
-    a = gauss(1 << 20, 1)
-    torch.linalg.qr(a)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        torch.linalg.qr(a)
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    out["torch_linalg_qr_f64_2p20x64_ms"] = sorted(ts)[1] * 1e3
+    if not only or any(not c.startswith("wide_") for c in only):
+        out["torch_linalg_qr_f64_2p20x64_ms"] = time_torch_qr(torch, gauss(1 << 20, 1))
+    for tag, m, wn in wide_shapes:
+        if only and not any(tag in c for c in only):
+            continue
+        out["torch_linalg_qr_f64_%s_ms" % tag] = time_torch_qr(torch, wgauss(m, wn, 5))
+        torch.cuda.empty_cache()
+    for c in out["cases"]:
+        tq = out.get("torch_linalg_qr_f64_2p%dx%d_ms" % (c["m"].bit_length() - 1, c["n"]))
+        if tq is not None and c["case"].startswith("wide_"):
+            c["speedup_vs_torch"] = tq / c["median_ms"]
     print(json.dumps(out))
 
 

@@ -52,6 +52,7 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_qr_f32_submit", "tsqr_mi_qr_f32_finish", "tsqr_mi_set_loop_depth", "tsqr_mi_qr_f32_batch", "tsqr_mi_qr_f16_batch",
     "tsqr_mi_qr_f32_dist_fn_batch", "tsqr_mi_qr_f32_dist_cb_batch",
     "tsqr_mi_qr_f64", "tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64", "tsqr_mi_last_sweeps_f64",
+    "tsqr_mi_qr_f64_wide", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide",
 ]
 
 
@@ -176,11 +177,12 @@ def lib():
     L.tsqr_mi_set_tuning2.argtypes = [ci, ci]
     L.tsqr_mi_set_tuning.restype = None
     L.tsqr_mi_set_tuning.argtypes = [ci, ci]
-    for name in ("tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64"):
+    for name in ("tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide"):
         getattr(L, name).restype = sz
         getattr(L, name).argtypes = [sz, sz]
-    L.tsqr_mi_qr_f64.restype = ci
-    L.tsqr_mi_qr_f64.argtypes = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp]
+    for name in ("tsqr_mi_qr_f64", "tsqr_mi_qr_f64_wide"):
+        getattr(L, name).restype = ci
+        getattr(L, name).argtypes = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp]
     L.tsqr_mi_last_sweeps_f64.restype = ci
     L.tsqr_mi_last_sweeps_f64.argtypes = []
     _lib = L
@@ -503,6 +505,49 @@ def qr_f64(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
                           bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
     if st < 0:
         raise RuntimeError("tsqr_mi_qr_f64 failed: %s" % last_error())
+    return st
+
+
+class buffer_f64_wide(buffer_f64):
+    """Work space of qr_f64_wide (tsqr_mi_working_{q,r}_size_f64_wide doubles on the GPU); reorthogonalize as in buffer_f64."""
+
+    def allocate(self, m, n):
+        import torch
+        if self.dwq is not None or self.dwr is not None:
+            raise RuntimeError("The buffer has been already allocated")
+        L = lib()
+        self.dwq = torch.empty(max(L.tsqr_mi_working_q_size_f64_wide(m, n), 1), dtype=torch.float64, device=self.device)
+        self.dwr = torch.empty(max(L.tsqr_mi_working_r_size_f64_wide(m, n), 1), dtype=torch.float64, device=self.device)
+
+
+def qr_f64_wide(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
+    """Double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide; qr_f64 itself for n <= 64): the arguments,
+    operand rules and states of qr_f64, error_unsupported_mode for n > 1024.  bf is a buffer_f64_wide.  Operands are checked before
+    anything is launched (TypeError / ValueError, check_f64_operands).  last_sweeps_f64() tells how many sweeps the call took."""
+    import torch
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    for name, t in (("q", q), ("r", r), ("a", a)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError("qr_f64_wide: %s must be a float64 tensor, got %s" % (name, getattr(t, "dtype", type(t).__name__)))
+    for name, t in (("q", q), ("r", r), ("a", a)):
+        if not t.is_cuda:
+            raise TypeError("qr_f64_wide: %s is not a GPU tensor" % name)
+    if n > m or m == 0 or n == 0:
+        return error_invalid_matrix_size
+    if n > 1024:
+        return lib().tsqr_mi_qr_f64_wide(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
+    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
+    if bf.dwq is None:
+        raise RuntimeError("qr_f64_wide: the buffer is not allocated")
+    L = lib()
+    if bf.dwq.numel() < L.tsqr_mi_working_q_size_f64_wide(m, n) or bf.dwr.numel() < L.tsqr_mi_working_r_size_f64_wide(m, n):
+        raise ValueError("qr_f64_wide: the buffer was allocated for a smaller matrix")
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    st = L.tsqr_mi_qr_f64_wide(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
+                               bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("tsqr_mi_qr_f64_wide failed: %s" % last_error())
     return st
 
 

@@ -34,6 +34,7 @@
 #include "tsqr_kernels.hip"
 #include "tsqr_wide.hip"
 #include "tsqr_f64.hip"
+#include "tsqr_f64_wide.hip"
 #include "validate.hip"
 
 namespace {
@@ -2733,10 +2734,14 @@ int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, 
 	return 0;
 }
 
+int f64w_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
+               double* wq, double* wr);
+
 // The ladder (include/tsqr_mi.h): verdict 0 of sweep 0 with "one sweep suffices" ends a reorth = 0 call, any other accepted first
 // sweep is followed by one more (CholeskyQR2), a shifted sweep by two more (shifted CholeskyQR3), a rejected one ends the call (state 3).
+// wide: the sweeps of tsqr_mi_qr_f64_wide for n > 64 (f64w_sweep); the verdict words and their meaning are the same.
 int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
-                hipStream_t st) {
+                hipStream_t st, bool wide = false) {
 	t_sweeps64 = 0;
 	if (!t_own64.get()) { t_last_error = "could not allocate the pinned verdict words"; return -(int)hipErrorOutOfMemory; }
 	volatile unsigned* words = t_own64.host;
@@ -2746,7 +2751,8 @@ int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double
 	bool shifted = false;
 	for (;;) {
 		while (sweeps < need) {
-			const int rc = f64_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr);
+			const int rc = wide ? f64w_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr)
+			                    : f64_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr);
 			if (rc) return rc;
 			sweeps++;
 		}
@@ -2785,11 +2791,151 @@ int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, dou
                    void* wq, void* wr, void* stream) {
 	t_sweeps64 = 0;
 	if (n > m || m == 0 || n == 0 || ldq < m || lda < m || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > PW) { t_last_error = "tsqr_mi_qr_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (n > PW) { t_last_error = "tsqr_mi_qr_f64 supports n <= 64 (tsqr_mi_qr_f64_wide: n <= 1024)"; return TSQR_MI_ERROR_UNSUPPORTED; }
 	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	if (rc) return rc;
 	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
 	                   reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The wide fp64 entry (tsqr_mi_qr_f64_wide): n <= 64 is tsqr_mi_qr_f64 itself; 64 < n <= 1024 runs the same ladder (qr_f64_core) with
+// whole-matrix sweeps on nb = ceil(n / 64) column blocks (kernels and block storage: tsqr_f64_wide.hip).  A sweep: the Gram pass and
+// its reduction; the blocked Cholesky step -- plain, then the shifted chain enqueued behind it, each of its launches skipping itself
+// when the plain verdict was 0 -- so that a one-sweep call still waits on the stream once; the apply pass; R out or R <- R_k R.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr size_t F64W_MAX_N = 1024;
+constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m
+constexpr int F64W_TARGET_WGS = 512;                    // two workgroups per CU
+
+struct F64WPlan {
+	int nb, npairs, ngroups, nslices;
+	size_t cps, nch;                                     // 16-row chunks per slice, chunks
+	size_t bs;                                           // doubles of one block store (npairs blocks)
+	size_t o_gs, o_w, o_rw, o_zw, o_ta, o_rc, o_zd, o_sb, o_bst, o_status, wq;
+};
+F64WPlan f64w_plan(size_t m, size_t n) {
+	F64WPlan g{};
+	g.nb = (int)cdiv(n, PW);
+	g.npairs = g.nb * (g.nb + 1) / 2;
+	g.ngroups = (int)cdiv((size_t)g.npairs, 4);
+	g.nch = cdiv(m, 16);
+	const size_t cap = F64W_WR_CAP / ((size_t)g.npairs * 4096);
+	const size_t want = std::max<size_t>(1, std::min({cdiv((size_t)F64W_TARGET_WGS, (size_t)g.ngroups), cap, g.nch}));
+	g.cps = cdiv(g.nch, want);
+	g.nslices = (int)cdiv(g.nch, g.cps);                 // (<= want)
+	g.bs = (size_t)g.npairs * 4096;
+	g.o_gs = 0;
+	g.o_w = g.o_gs + g.bs + 64;                          // (the reduction writes the row count behind the summed blocks)
+	g.o_rw = g.o_w + g.bs;
+	g.o_zw = g.o_rw + g.bs;
+	g.o_ta = g.o_zw + g.bs;
+	g.o_rc = g.o_ta + g.bs;
+	g.o_zd = g.o_rc + g.bs;
+	g.o_sb = g.o_zd + (size_t)g.nb * 4096;
+	g.o_bst = g.o_sb + (size_t)g.nb * (g.nb + 1);
+	g.o_status = g.o_bst + (size_t)g.nb * 2;
+	g.wq = g.o_status + 8;
+	return g;
+}
+
+// the blocked Cholesky step of one sweep, plain (shift_coef = 0, run_if = nullptr) or shifted
+int f64w_chain(hipStream_t st, tsqrmi::WideF64 wa) {
+	const int nb = wa.nb;
+	for (int k = 0; k < nb; k++) {
+		hipLaunchKernelGGL(tsqrmi::cholw_diag_kernel, dim3(1), dim3(1024), 0, st, wa, k);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(tsqrmi::cholw_row_kernel, dim3(nb), dim3(1024), 0, st, wa, k);
+		HIPCHK(hipGetLastError());
+		const int nt = nb - k - 1;
+		if (nt > 0) {
+			hipLaunchKernelGGL(tsqrmi::cholw_update_kernel, dim3(nt * (nt + 1) / 2 + (k + 1) * nt), dim3(1024), 0, st, wa, k);
+			HIPCHK(hipGetLastError());
+		}
+	}
+	hipLaunchKernelGGL(tsqrmi::cholw_verdict_kernel, dim3(1), dim3(64), 0, st, wa);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// sweep k (0-based) of the wide entry: sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R
+int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
+               double* wq, double* wr) {
+	const bool first = k == 0;
+	const double* src = first ? a : q;
+	const size_t lds = first ? lda : ldq;
+	const F64WPlan g = f64w_plan(m, n);
+	if (g.nslices <= 0 || g.npairs <= 0) { t_last_error = "fp64 wide Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	const tsqrmi::GramWideF64Args ga{src, lds, m, (int)n, g.npairs, g.ngroups, g.cps, g.nch, wr};
+	hipLaunchKernelGGL(tsqrmi::gram_wide_f64_kernel, dim3((unsigned)(g.ngroups * g.nslices)), dim3(256), 0, st, ga);
+	HIPCHK(hipGetLastError());
+	const int nelem = (int)g.bs;
+	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, st, wq + g.o_gs, wr, g.nslices, nelem, (double)m,
+	                   nullptr, (size_t)0, nullptr, 0);
+	HIPCHK(hipGetLastError());
+	tsqrmi::WideF64 wa{};
+	wa.gs = wq + g.o_gs; wa.w = wq + g.o_w; wa.rw = wq + g.o_rw; wa.zw = wq + g.o_zw; wa.ta = wq + g.o_ta; wa.zd = wq + g.o_zd;
+	wa.sb = wq + g.o_sb;
+	wa.bst = reinterpret_cast<unsigned*>(wq + g.o_bst);
+	const int slot = k & 3;
+	wa.status = reinterpret_cast<unsigned*>(wq + g.o_status) + 4 * slot;
+	wa.host_status = t_own64.dev + 4 * slot;
+	const double u = 0x1p-53, mn = (double)m * (double)n + (double)n * (double)(n + 1);
+	wa.max_scond = first ? (float)(1.0 / (64.0 * (double)n * u * mn)) : INFINITY;     // CholArgs64 (tsqr_f64.hip) states the rule
+	wa.alone_max = first ? (float)(1e-12 / (4.0 * (double)n * u)) : 0.0f;
+	wa.n = (int)n; wa.nb = g.nb;
+	wa.run_if = nullptr; wa.shift_coef = 0.0;
+	int rc = f64w_chain(st, wa);
+	if (rc) return rc;
+	wa.run_if = wa.status; wa.shift_coef = 11.0 * u * mn;
+	rc = f64w_chain(st, wa);
+	if (rc) return rc;
+	hipLaunchKernelGGL(tsqrmi::apply_wide_f64_kernel, dim3((unsigned)cdiv(m, 128)), dim3(256), 0, st, q, ldq, src, lds, m, (int)n, g.nb,
+	                   (const double*)(wq + g.o_zw));
+	HIPCHK(hipGetLastError());
+	if (first) {
+		hipLaunchKernelGGL(tsqrmi::rcopy_wide_f64_kernel, dim3((unsigned)cdiv(n * n, 256)), dim3(256), 0, st, r, ldr, (const double*)(wq + g.o_rw), (int)n);
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
+	hipLaunchKernelGGL(tsqrmi::rsave_wide_f64_kernel, dim3((unsigned)cdiv(g.bs, 256)), dim3(256), 0, st, wq + g.o_rc, (const double*)r, ldr, (int)n, g.npairs);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(tsqrmi::rmul_wide_f64_kernel, dim3((unsigned)g.npairs), dim3(1024), 0, st, r, ldr, (const double*)(wq + g.o_rw),
+	                   (const double*)(wq + g.o_rc), (int)n);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tsqr_mi_working_q_size_f64_wide(size_t m, size_t n) {
+	if (m == 0 || n == 0) return 0;
+	if (n <= PW) return tsqr_mi_working_q_size_f64(m, n);
+	return f64w_plan(m, std::min(n, F64W_MAX_N)).wq;
+}
+size_t tsqr_mi_working_r_size_f64_wide(size_t m, size_t n) {
+	if (m == 0 || n == 0) return 0;
+	if (n <= PW) return tsqr_mi_working_r_size_f64(m, n);
+	const F64WPlan g = f64w_plan(m, std::min(n, F64W_MAX_N));
+	return (size_t)g.nslices * g.bs;
+}
+
+int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
+                        void* wq, void* wr, void* stream) {
+	t_sweeps64 = 0;
+	if (n > m || m == 0 || n == 0 || ldq < m || lda < m || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > F64W_MAX_N) { t_last_error = "tsqr_mi_qr_f64_wide supports n <= 1024"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (n <= PW) return tsqr_mi_qr_f64(reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream);
+	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	if (rc) return rc;
+	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
+	                   reinterpret_cast<hipStream_t>(stream), true);
 }
 
 }  // extern "C"
