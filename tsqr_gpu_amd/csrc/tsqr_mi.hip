@@ -302,6 +302,16 @@ struct Ctx {
 	unsigned* status_dev(int s) const { return reinterpret_cast<unsigned*>(wq + L.status) + 16 * s; }
 	double* gsum() const { return reinterpret_cast<double*>(wq + L.gsum); }
 };
+// the pending announcement (Ctx::announce_word) rides in the Gram launch these arguments are for ...
+template <class GramArgsT> void carry_announcement(Ctx& c, GramArgsT& ga) {
+	ga.announce = c.announce_word; ga.announce_seq = c.announce_seq; c.announce_word = nullptr;
+}
+// ... or, where no Gram launch is left to carry it, in a one-thread kernel of its own
+void raise_announcement(Ctx& c) {
+	if (!c.announce_word) return;
+	hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.announce_word, c.announce_seq);
+	c.announce_word = nullptr;
+}
 
 // library-owned pinned words, one set per host thread (callers whose h_wl is not pinned or too small; staged API)
 struct OwnPinned {
@@ -339,6 +349,19 @@ void resolve_host_sig(Ctx& c, unsigned* h_wl, size_t m) {
 	if (t_own.get()) { c.hsig.host = t_own.host; c.hsig.dev = t_own.dev; }
 }
 
+// spin on a completion word of the pinned words (the stream is looked at now and then so that a failed launch cannot hang the caller)
+int wait_word(volatile unsigned* word, unsigned seq, hipStream_t st) {
+	for (;;) {
+		for (int k = 0; k < 20000; k++) {
+			if (*word == seq) return 0;
+			__builtin_ia32_pause();
+		}
+		const hipError_t e = hipStreamQuery(st);
+		if (e == hipSuccess) return 0;
+		if (e != hipErrorNotReady) HIPCHK(e);
+	}
+}
+
 // End of a call on the fast path: a one-thread kernel behind the last kernel raises word 3 of the pinned words; the host spins on
 // it (about 5 us cheaper than hipStreamSynchronize, tools/launch_cost.py, and free of its sporadic OS wake-up stalls) and polls
 // the stream now and then so that a failed launch cannot hang the caller.  Returns 1 when the flag path is not available.
@@ -350,15 +373,7 @@ int signal_and_wait(Ctx& c) {
 	*flag = 0;
 	hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.hsig.dev + 3, seq);
 	if (hipGetLastError() != hipSuccess) return 1;
-	for (;;) {
-		for (int i = 0; i < 20000; i++) {
-			if (*flag == seq) return 0;
-			__builtin_ia32_pause();
-		}
-		const hipError_t e = hipStreamQuery(c.st);
-		if (e == hipSuccess) return 0;
-		if (e != hipErrorNotReady) HIPCHK(e);
-	}
+	return wait_word(flag, seq, c.st);
 }
 int wait_done(Ctx& c) {
 	const int w = signal_and_wait(c);
@@ -375,18 +390,8 @@ thread_local unsigned t_submits = 0;
 int ticket_latch(tsqr_mi_ticket* t) {
 	if (!t || t->pending != 1) return 0;
 	volatile unsigned* w = reinterpret_cast<volatile unsigned*>(t->words) + 4 * t->slot;
-	hipStream_t st = reinterpret_cast<hipStream_t>(t->stream);
-	for (bool done = false; !done;) {
-		for (int i = 0; i < 20000 && !done; i++) {
-			done = (w[3] == t->seq);
-			if (!done) __builtin_ia32_pause();
-		}
-		if (!done) {                                     // (a failed launch must not hang the caller: look at the stream now and then)
-			const hipError_t e = hipStreamQuery(st);
-			if (e == hipSuccess) done = true;
-			else if (e != hipErrorNotReady) { t_pending[t->slot] = nullptr; t->pending = 0; t->state = -1; HIPCHK(e); }
-		}
-	}
+	const int rc = wait_word(w + 3, t->seq, reinterpret_cast<hipStream_t>(t->stream));
+	if (rc) { t_pending[t->slot] = nullptr; t->pending = 0; t->state = -1; return rc; }
 	t->verdict = w[0];
 	const unsigned b = w[2];
 	memcpy(&t->scond, &b, 4);
@@ -534,7 +539,7 @@ int gram_g(Ctx& c, const float* src, size_t ld, size_t m, size_t n, bool bf16, b
 	a.a = src; a.lda = ld; a.m = m; a.n = (int)n; a.nchunks = g.nch; a.cpw = g.cpw; a.nwaves = g.nwaves;
 	a.part = reinterpret_cast<double*>(c.wr);
 	a.skip_status = c.prev_slot >= 0 ? c.status_dev(c.prev_slot) : nullptr;
-	if (!(bf16 && c.gramq_ready)) { a.announce = c.announce_word; a.announce_seq = c.announce_seq; c.announce_word = nullptr; }
+	if (!(bf16 && c.gramq_ready)) carry_announcement(c, a);
 	int nparts = g.nblocks;                              // workgroups that wrote a partial
 	if (bf16 && c.gramq_ready) {                         // the previous sweep's apply kernel accumulated this very Gram matrix
 		c.gramq_ready = false;
@@ -1045,7 +1050,7 @@ int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, c
 			HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
 			attr.done(c.dev);
 		}
-		ga.announce = c.announce_word; ga.announce_seq = c.announce_seq; c.announce_word = nullptr;   // (the first launch carries it)
+		carry_announcement(c, ga);                       // (the first launch carries it)
 		if (wgs_fast) {
 			ga.blk0 = 0; ga.nblk = (int)nfull;
 			hipLaunchKernelGGL((tsqrmi::gram_wide_kernel<true>), dim3(wgs_fast), dim3(512), tsqrmi::GW_LDS_BYTES, c.st, ga);
@@ -1530,7 +1535,7 @@ static int submit_impl(const CallEnv& env, int mode, int reorth, float* q, size_
 	const int rc = narrow ? sweep(c, engine, 2, /*check_now=*/false, q, ldq, r, ldr, a, lda, m, n) : sweep_wide(c, engine, q, ldq, r, ldr, a, lda, m, n);
 	if (rc) return t->state = rc;
 	if (c.announce_word) {                               // (no kernel of the attempt carried the announcement: raise the word here)
-		hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.announce_word, c.announce_seq);
+		raise_announcement(c);
 		(void)hipGetLastError();
 	}
 	unsigned seq = ++g_seq;
@@ -1620,6 +1625,16 @@ struct Mats {
 		return t;
 	}
 };
+static Mats one_triple(float* q, float* r, float* a) {
+	Mats mt;
+	mt.q0 = q; mt.r0 = r; mt.a0 = a;
+	return mt;
+}
+static int triple_per_call(Mats& mt, int count, float* const* q, float* const* r, float* const* a, int* states) {
+	if (count < 0 || (count > 0 && (!q || !r || !a))) return TSQR_MI_ERROR_INVALID_SIZE;
+	mt.qs = q; mt.rs = r; mt.as = a; mt.states = states;
+	return 0;
+}
 struct Call { int mode, reorth; size_t ldq, ldr, lda, m, n; void* wq; void* wr; unsigned* h_wl; void* stream; };
 
 // Every schedule that enqueues call i + 1 before call i is finished follows one rule (stream_order.h): calls i and i + 1 must not conflict.
@@ -1642,21 +1657,58 @@ static bool out_of_order(const Mats& mt, int count, const Call& cl, size_t esz =
 }
 
 // A batch of different matrices takes a chained schedule only while two matrices share the Infinity Cache (Settings::chain_max_mib)
-static bool chain_fits_cache(const Mats& mt, const Call& cl) {
-	return mt.same() || (double)cl.lda * (double)cl.n * sizeof(float) <= (double)g_set.chain_max_mib * 1048576.0;
+static bool chain_fits_cache(const Mats& mt, const Call& cl, size_t esz = sizeof(float)) {
+	return mt.same() || (double)cl.lda * (double)cl.n * esz <= (double)g_set.chain_max_mib * 1048576.0;
+}
+// the chained Gram kernels read A in 16-byte pieces
+static bool a_aligned16(const Mats& mt, int count) {
+	for (int i = 0; i < (mt.same() ? 1 : count); i++)
+		if ((reinterpret_cast<uintptr_t>(mt.a(i)) & 15) != 0) return false;
+	return true;
 }
 
-// spin on a completion word of the pinned words (the stream is looked at now and then so that a failed launch cannot hang the caller)
-static int wait_word(volatile unsigned* word, unsigned seq, hipStream_t st) {
-	for (;;) {
-		for (int k = 0; k < 20000; k++) {
-			if (*word == seq) return 0;
-			__builtin_ia32_pause();
-		}
-		const hipError_t e = hipStreamQuery(st);
-		if (e == hipSuccess) return 0;
-		if (e != hipErrorNotReady) HIPCHK(e);
+// The completion-word protocol of a stream of calls.  Call i owns half i & 1 of the pinned words: its Cholesky kernel writes the verdict
+// into word 0 of the half, and word 3 is raised to the call's sequence number when its last kernel has finished -- by the Gram launch of
+// call i + 1 (stream order: it starts then; a one-thread kernel less per call), or by a one-thread kernel behind the last call.  The
+// announcement waits in Ctx::announce_word, where gram_g and sweep_wide find it as well as the schedules' own Gram launches.
+struct Completion {
+	Ctx& c;
+	volatile unsigned* words;
+	unsigned seq[2] = {0, 0};
+	explicit Completion(Ctx& ctx) : c(ctx), words(reinterpret_cast<volatile unsigned*>(ctx.hsig.host)) {}
+	// behind the last launch of call i: a fresh non-zero sequence number for its word, announced by call i + 1 or (the last call) here
+	int close(int i, bool last) {
+		unsigned sq = ++g_seq;
+		if (sq == 0) sq = ++g_seq;
+		seq[i & 1] = sq;
+		words[4 * (i & 1) + 3] = 0;
+		c.announce_word = c.hsig.dev + 4 * (i & 1) + 3; c.announce_seq = sq;
+		if (last) raise_announcement(c);
+		HIPCHK(hipGetLastError());
+		return 0;
 	}
+	int wait(int i) const { return wait_word(words + 4 * (i & 1) + 3, seq[i & 1], c.st); }
+	bool rejected(int i) const { return words[4 * (i & 1)] != 0; }       // (after wait(i), or on an idle stream)
+};
+
+// The issue-ahead loop of every schedule: step(i) enqueues the launches of call i and closes it (Completion::close); the host stays one
+// call ahead of the call it waits for.  A rejected verdict ends the schedule with tail(i) -- the schedule's own policy for call i and the
+// ones behind it; *done = accepted calls so far.  `engine` is what tsqr_mi_last_engine reports after a stream of accepted calls.
+extern "C++" template <class Step, class Tail>       // (a template among the entry points' C linkage)
+static int run_chained(const Completion& comp, const Mats& mt, int count, int engine, Step step, Tail tail, int* done) {
+	int rc = step(0);
+	if (rc) return rc;
+	for (int i = 0; i < count; i++) {
+		if (i + 1 < count) { rc = step(i + 1); if (rc) return rc; }
+		rc = comp.wait(i);
+		if (rc) return rc;
+		if (comp.rejected(i)) return tail(i);
+		mt.state(i, TSQR_MI_SUCCESS);
+		*done = i + 1;
+	}
+	t_last_engine = engine;
+	prof_collect();
+	return TSQR_MI_SUCCESS;
 }
 
 // one call of the stream as a plain blocking call with its whole ladder
@@ -1673,10 +1725,10 @@ static int blocking_one(const CallEnv& env, const Mats& mt, int i, const Call& c
 // (it may have been factored in place -- an accepted call is never redone) and gets its ladder otherwise.  *done = calls dealt with; the
 // caller goes on from there.  A loop over one triple would see every further attempt rejected as well: the rest of its count runs as
 // blocking calls.  (Row-partitioned: the verdicts come from the all-reduced matrix -- every rank walks through here alike.)
-static int rejected_tail(const CallEnv& env, const Mats& mt, int count, const Call& cl, int i, volatile unsigned* words, hipStream_t st, int* done) {
-	HIPCHK(hipStreamSynchronize(st));
+static int rejected_tail(const CallEnv& env, const Mats& mt, int count, const Call& cl, int i, const Completion& comp, int* done) {
+	HIPCHK(hipStreamSynchronize(comp.c.st));
 	prof_collect();
-	const bool next = i + 1 < count, next_rejected = next && words[4 * ((i + 1) & 1)] != 0;     // (read before a blocking call reuses the words)
+	const bool next = i + 1 < count, next_rejected = next && comp.rejected(i + 1);     // (read before a blocking call reuses the words)
 	int first = 0;
 	if (mt.same()) {
 		for (int k = i; k < count; k++) {
@@ -1703,6 +1755,41 @@ static int rejected_tail(const CallEnv& env, const Mats& mt, int count, const Ca
 	return first;
 }
 
+// ---- what the 64-column chained schedules share (chained64, chained_dist, the fp16 stream) ----
+// the shapes gram_blk_kernel takes: a full 64-column block of 128 k <= 2^20 rows, no second sweep
+static bool blk_shape(const Call& cl) {
+	return !cl.reorth && cl.n == PW && cl.m % 128 == 0 && cl.m <= ((size_t)1 << 20) && cl.lda % 4 == 0 && cl.lda <= ((size_t)1 << 24) &&
+	       cl.lda >= cl.m && cl.ldq >= cl.m && cl.ldr >= cl.n;
+}
+static int blk_kernel_attrs(int dev) {
+	static DevOnce attr;
+	if (attr.need(dev)) {
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
+		attr.done(dev);
+	}
+	return 0;
+}
+// the Gram pass over `a` into `part`; it carries the pending announcement
+static tsqrmi::GramArgs gram_args_64(Ctx& c, const float* a, const Call& cl, int nchunks, const GramPlan& g, double* part) {
+	tsqrmi::GramArgs ga{};
+	ga.a = a; ga.lda = cl.lda; ga.m = cl.m; ga.n = (int)cl.n; ga.nchunks = nchunks; ga.cpw = g.cpw; ga.nwaves = g.nwaves;
+	ga.part = part;
+	carry_announcement(c, ga);
+	return ga;
+}
+// the bf16-split level's factorisation of call i: status and verdict words of half i & 1
+static tsqrmi::CholArgs chol_args_64(const Ctx& c, float* r, size_t ldr, int i, size_t n) {
+	tsqrmi::CholArgs ca{};
+	ca.r = r; ca.ldr = ldr; ca.z = c.wq + c.L.z;
+	ca.status = c.status_dev(i & 1);
+	ca.host_status = c.hsig.dev + 4 * (i & 1);
+	ca.gsum = c.gsum();
+	ca.rows = c.rows_global;
+	ca.n = (int)n; ca.NT = 4; ca.level = 2; ca.scond_floor = g_set.bf16_scond_floor;
+	return ca;
+}
+
 // The stream for full 64-column matrices of up to 2^20 rows (the shapes gram_blk_kernel takes): the R-factor chain of call i (reduction,
 // Cholesky, verdict) runs inside the launch that is the Gram pass of call i + 1 (gram_blk_chain_kernel), so a call costs its two
 // streaming passes and nothing else:
@@ -1712,99 +1799,51 @@ static int rejected_tail(const CallEnv& env, const Mats& mt, int count, const Ca
 // (nothing enqueued).  A rejected verdict ends the schedule at that call (rejected_tail); *done tells the caller how far the stream got.
 static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 	*done = 0;
-	const size_t m = cl.m, n = cl.n, lda = cl.lda, ldq = cl.ldq, ldr = cl.ldr;
+	const size_t m = cl.m, n = cl.n;
 	const int engine = engine_of(cl.mode);
-	if (count < 3 || engine < 0 || cl.reorth || n != PW || m % 128 != 0 || m > ((size_t)1 << 20) || lda % 4 != 0 || lda > ((size_t)1 << 24) ||
-	    lda < m || ldq < m || ldr < n)
-		return NOT_MINE;
-	for (int i = 0; i < (mt.same() ? 1 : count); i++)
-		if ((reinterpret_cast<uintptr_t>(mt.a(i)) & 15) != 0) return NOT_MINE;
+	if (count < 3 || engine < 0 || !blk_shape(cl) || !a_aligned16(mt, count)) return NOT_MINE;
 	if (!out_of_order(mt, count, cl) || !chain_fits_cache(mt, cl)) return NOT_MINE;
 	Ctx c;
-	init_ctx(c, cl.wq, cl.wr, m, n, cl.stream);
-	c.rows_global = (double)m;
-	resolve_host_sig(c, cl.h_wl, m);
+	env_ctx(c, CallEnv{}, cl.wq, cl.wr, m, n, cl.h_wl, cl.stream, /*keep_in_flight=*/false);
 	if (!(c.policy == 0 && c.gram_level == 2 && c.hsig.dev && !g_set.debug)) return NOT_MINE;
 	c.fold_cor = (engine == 1);
-	static DevOnce attr;
-	if (attr.need(c.dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
-		attr.done(c.dev);
-	}
+	int rc = blk_kernel_attrs(c.dev);
+	if (rc) return rc;
 	const GramPlan g = gram_plan(m, n);
 	const int nchunks = (int)(m / 128), nparts = std::min(nchunks, g.nblocks), nelem = 10 * 256, nred = nelem / 16;
 	double* part[2] = {reinterpret_cast<double*>(c.wr), reinterpret_cast<double*>(c.wr) + (size_t)g.nblocks * nelem};
 	unsigned* ticket = c.status_dev(0) + 8;              // (a word of the status area no kernel uses)
 	HIPCHK(hipMemsetAsync(ticket, 0, sizeof(unsigned), c.st));
-	volatile unsigned* words = reinterpret_cast<volatile unsigned*>(c.hsig.host);
-	unsigned seq[2] = {0, 0};
-	unsigned* announce = nullptr; unsigned announce_seq = 0;             // completion word the next launch raises
-	auto gram_args = [&](int i) {
-		tsqrmi::GramArgs ga{};
-		ga.a = mt.a(i); ga.lda = lda; ga.m = m; ga.n = (int)n; ga.nchunks = nchunks; ga.cpw = g.cpw; ga.nwaves = g.nwaves;
-		ga.part = part[i & 1];
-		ga.announce = announce; ga.announce_seq = announce_seq; announce = nullptr;
-		return ga;
-	};
-	auto chol_args = [&](int i) {
-		tsqrmi::CholArgs ca{};
-		ca.r = mt.r(i); ca.ldr = ldr; ca.z = c.wq + c.L.z;
-		ca.status = c.status_dev(i & 1);
-		ca.host_status = c.hsig.dev + 4 * (i & 1);
-		ca.gsum = c.gsum();
-		ca.rows = c.rows_global;
-		ca.n = (int)n; ca.NT = 4; ca.level = 2; ca.scond_floor = g_set.bf16_scond_floor;
-		return ca;
-	};
+	Completion comp(c);
 	// one step = the launches of call i behind its Gram pass: chain(i) (with the Gram pass of call i + 1 when there is one), apply(i)
 	auto step = [&](int i) -> int {
 		if (i + 1 < count) {
 			tsqrmi::ChainArgs ch{};
-			ch.chol = chol_args(i);
+			ch.chol = chol_args_64(c, mt.r(i), cl.ldr, i, n);
 			ch.part = part[i & 1]; ch.nparts = nparts; ch.ticket = ticket; ch.nred = nred;
 			ProfScope ps(KC_GRAM, c.st);
-			hipLaunchKernelGGL(tsqrmi::gram_blk_chain_kernel, dim3(nred + nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args(i + 1), ch);
+			hipLaunchKernelGGL(tsqrmi::gram_blk_chain_kernel, dim3(nred + nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st,
+			                   gram_args_64(c, mt.a(i + 1), cl, nchunks, g, part[(i + 1) & 1]), ch);
 		} else {
 			// the last call: no Gram pass left to hide behind -- the chain as launches of its own (and the completion word of the call
 			// before, which no Gram kernel is there to raise)
-			if (announce) { hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, announce, announce_seq); announce = nullptr; }
+			raise_announcement(c);
 			ProfScope ps(KC_CHOL, c.st);
 			hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nred), dim3(256), 0, c.st, c.gsum(), part[i & 1], nparts, nelem, (double)m,
 			                   nullptr, (size_t)0, nullptr, 0);
-			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(i));
+			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args_64(c, mt.r(i), cl.ldr, i, n));
 		}
 		HIPCHK(hipGetLastError());
 		c.slot = i & 1;
-		const int rc = apply_rinv(c, engine, mt.q(i), ldq, mt.a(i), lda, mt.r(i), ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
-		if (rc) return rc;
-		unsigned sq = ++g_seq;
-		if (sq == 0) sq = ++g_seq;
-		seq[i & 1] = sq;
-		words[4 * (i & 1) + 3] = 0;
-		if (i + 1 < count) { announce = c.hsig.dev + 4 * (i & 1) + 3; announce_seq = sq; }   // raised by the first launch of step i + 1
-		else hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.hsig.dev + 4 * (i & 1) + 3, sq);
-		HIPCHK(hipGetLastError());
-		return 0;
+		const int rc2 = apply_rinv(c, engine, mt.q(i), cl.ldq, mt.a(i), cl.lda, mt.r(i), cl.ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
+		return rc2 ? rc2 : comp.close(i, i + 1 == count);
 	};
 	{
 		ProfScope ps(KC_GRAM, c.st);
-		hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args(0));
+		hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args_64(c, mt.a(0), cl, nchunks, g, part[0]));
 	}
 	HIPCHK(hipGetLastError());
-	int rc = step(0);
-	if (rc) return rc;
-	for (int i = 0; i < count; i++) {
-		if (i + 1 < count) { rc = step(i + 1); if (rc) return rc; }
-		rc = wait_word(words + 4 * (i & 1) + 3, seq[i & 1], c.st);
-		if (rc) return rc;
-		if (words[4 * (i & 1)] != 0) return rejected_tail(CallEnv{}, mt, count, cl, i, words, c.st, done);
-		mt.state(i, TSQR_MI_SUCCESS);
-		*done = i + 1;
-	}
-	t_last_engine = 3;
-	prof_collect();
-	return TSQR_MI_SUCCESS;
+	return run_chained(comp, mt, count, 3, step, [&](int i) { return rejected_tail(CallEnv{}, mt, count, cl, i, comp, done); }, done);
 }
 
 // The chained schedule for a stream of 128-column calls (one GPU; every 64-row block full: m % 64 == 0, the fast Gram form): the
@@ -1818,15 +1857,11 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 	const size_t m = cl.m, n = cl.n, lda = cl.lda, ldq = cl.ldq, ldr = cl.ldr;
 	const int engine = engine_of(cl.mode);
 	if (count < 3 || engine < 0 || cl.reorth || n != 2 * PW || m < n || m % 64 != 0 || m / 64 < 2 * (size_t)WIDE_MAX_WGS || lda > ((size_t)1 << 23) ||
-	    lda < m || ldq < m || ldr < n || lda % 4 != 0)
+	    lda < m || ldq < m || ldr < n || lda % 4 != 0 || !a_aligned16(mt, count))
 		return NOT_MINE;
-	for (int i = 0; i < (mt.same() ? 1 : count); i++)
-		if ((reinterpret_cast<uintptr_t>(mt.a(i)) & 15) != 0) return NOT_MINE;
 	if (!out_of_order(mt, count, cl) || !chain_fits_cache(mt, cl)) return NOT_MINE;
 	Ctx c;
-	init_ctx(c, cl.wq, cl.wr, m, n, cl.stream);
-	c.rows_global = (double)m;
-	resolve_host_sig(c, cl.h_wl, m);
+	env_ctx(c, CallEnv{}, cl.wq, cl.wr, m, n, cl.h_wl, cl.stream, /*keep_in_flight=*/false);
 	if (!(c.wide && c.policy == 0 && c.gram_level == 2 && c.hsig.dev && !g_set.debug)) return NOT_MINE;
 	static DevOnce attr;
 	if (attr.need(c.dev)) {
@@ -1840,13 +1875,11 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 	float* zf2 = w + WIDE_OFF_ZF2;
 	const int nblk = (int)(m / 64), wgs = WIDE_MAX_WGS, nelem = 36 * 256;
 	double* part = reinterpret_cast<double*>(c.wr);
-	volatile unsigned* words = reinterpret_cast<volatile unsigned*>(c.hsig.host);
-	unsigned seq[2] = {0, 0};
-	unsigned* announce = nullptr; unsigned announce_seq = 0;
+	Completion comp(c);
 	auto gram_args = [&](int i) {
 		tsqrmi::GramWideArgs ga{};
 		ga.a = mt.a(i); ga.lda = lda; ga.m = m; ga.n = (int)n; ga.blk0 = 0; ga.nblk = nblk; ga.part = part;
-		ga.announce = announce; ga.announce_seq = announce_seq; announce = nullptr;
+		carry_announcement(c, ga);
 		return ga;
 	};
 	auto chol_args = [&](int i) {
@@ -1869,7 +1902,7 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 			}
 			reduce();
 		} else {
-			if (announce) { hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, announce, announce_seq); announce = nullptr; }
+			raise_announcement(c);
 			ProfScope ps(KC_CHOL, c.st);
 			hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(i));
 		}
@@ -1883,14 +1916,7 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 		}
 		if (rc) return rc;
 		HIPCHK(hipGetLastError());
-		unsigned sq = ++g_seq;
-		if (sq == 0) sq = ++g_seq;
-		seq[i & 1] = sq;
-		words[4 * (i & 1) + 3] = 0;
-		if (i + 1 < count) { announce = c.hsig.dev + 4 * (i & 1) + 3; announce_seq = sq; }
-		else hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.hsig.dev + 4 * (i & 1) + 3, sq);
-		HIPCHK(hipGetLastError());
-		return 0;
+		return comp.close(i, i + 1 == count);
 	};
 	{
 		ProfScope ps(KC_GRAM, c.st);
@@ -1898,19 +1924,7 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 	}
 	reduce();
 	HIPCHK(hipGetLastError());
-	int rc = step(0);
-	if (rc) return rc;
-	for (int i = 0; i < count; i++) {
-		if (i + 1 < count) { rc = step(i + 1); if (rc) return rc; }
-		rc = wait_word(words + 4 * (i & 1) + 3, seq[i & 1], c.st);
-		if (rc) return rc;
-		if (words[4 * (i & 1)] != 0) return rejected_tail(CallEnv{}, mt, count, cl, i, words, c.st, done);
-		mt.state(i, TSQR_MI_SUCCESS);
-		*done = i + 1;
-	}
-	t_last_engine = 5;
-	prof_collect();
-	return TSQR_MI_SUCCESS;
+	return run_chained(comp, mt, count, 5, step, [&](int i) { return rejected_tail(CallEnv{}, mt, count, cl, i, comp, done); }, done);
 }
 
 // The chained schedule of a ROW-PARTITIONED stream (every rank: a full 64-column block of 128 k <= 2^20 rows).  The all-reduce sits inside
@@ -1926,42 +1940,22 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 // A rejected verdict -- the same on every rank -- ends the schedule at that call (rejected_tail).
 static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Call& cl, int* done) {
 	*done = 0;
-	const size_t m = cl.m, n = cl.n, lda = cl.lda, ldq = cl.ldq, ldr = cl.ldr;
+	const size_t m = cl.m, n = cl.n;
 	const int engine = engine_of(cl.mode);
 	if (engine < 0 || m == 0 || n == 0 || n > PW || env.nranks < 1 || env.nranks > 255) return NOT_MINE;   // (conditions every rank shares; the plain path reports errors)
 	Ctx c;
 	env_ctx(c, env, cl.wq, cl.wr, m, n, nullptr, cl.stream, /*keep_in_flight=*/false);
-	bool mine = c.hsig.dev && !cl.reorth && n == PW && m % 128 == 0 && m <= ((size_t)1 << 20) && lda % 4 == 0 && lda <= ((size_t)1 << 24) && lda >= m && ldq >= m &&
-	            ldr >= n && c.policy == 0 && c.gram_level == 2 && !g_set.debug && out_of_order(mt, count, cl);
-	for (int i = 0; mine && i < (mt.same() ? 1 : count); i++) mine = (reinterpret_cast<uintptr_t>(mt.a(i)) & 15) == 0;
+	const bool mine = c.hsig.dev && blk_shape(cl) && c.policy == 0 && c.gram_level == 2 && !g_set.debug && out_of_order(mt, count, cl) && a_aligned16(mt, count);
 	c.fold_cor = (engine == 1);
-	static DevOnce attr;
-	if (attr.need(c.dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
-		attr.done(c.dev);
-	}
+	int rc = blk_kernel_attrs(c.dev);
+	if (rc) return rc;
 	const GramPlan g = gram_plan(m, PW);
 	const int nchunks = (int)(m / 128), nparts = std::min(nchunks, g.nblocks), nelem = 10 * 256;
 	double* part = reinterpret_cast<double*>(c.wr);
-	volatile unsigned* words = reinterpret_cast<volatile unsigned*>(c.hsig.host);
-	unsigned seq[2] = {0, 0};
-	unsigned* announce = nullptr; unsigned announce_seq = 0;
-	auto gram_args = [&](int i) {
-		tsqrmi::GramArgs ga{};
-		ga.a = mt.a(i); ga.lda = lda; ga.m = m; ga.n = (int)n; ga.nchunks = nchunks; ga.cpw = g.cpw; ga.nwaves = g.nwaves; ga.part = part;
-		ga.announce = announce; ga.announce_seq = announce_seq; announce = nullptr;
-		return ga;
-	};
+	Completion comp(c);
 	auto chol_args = [&](int i) {
-		tsqrmi::CholArgs ca{};
-		ca.r = mt.r(i); ca.ldr = ldr; ca.z = c.wq + c.L.z;
-		ca.status = c.status_dev(i & 1);
-		ca.host_status = c.hsig.dev + 4 * (i & 1);
-		ca.gsum = c.gsum();
+		tsqrmi::CholArgs ca = chol_args_64(c, mt.r(i), cl.ldr, i, n);
 		ca.rows_dev = c.gsum() + nelem;                  // the all-reduced row count (as chol_from_g)
-		ca.rows = c.rows_global;
-		ca.n = (int)n; ca.NT = 4; ca.level = 2; ca.scond_floor = g_set.bf16_scond_floor;
 		return ca;
 	};
 	auto reduce_allreduce = [&](int extra) -> int {      // partials of the Gram pass just enqueued -> summed tiles + row count (+ `extra` doubles), over all ranks
@@ -1977,11 +1971,10 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 		return 0;
 	};
 	// ---- call 0 up to its all-reduce, with the vote in the payload ----
-	int rc = 0;
 	if (mine) {
 		{
 			ProfScope ps(KC_GRAM, c.st);
-			hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args(0));
+			hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args_64(c, mt.a(0), cl, nchunks, g, part));
 		}
 		HIPCHK(hipGetLastError());
 		rc = reduce_allreduce(1);
@@ -1993,20 +1986,20 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 	if (c.hsig.dev) {
 		unsigned vs = ++g_seq;
 		if ((vs & 0xffffffu) == 0) vs = ++g_seq;
-		words[8] = 0;
+		comp.words[8] = 0;
 		hipLaunchKernelGGL(tsqrmi::vote_out_kernel, dim3(1), dim3(1), 0, c.st, c.gsum() + nelem + 1, c.hsig.dev + 8, vs);
 		HIPCHK(hipGetLastError());
 		unsigned w = 0;
-		for (;;) {
+		for (;;) {                                       // (as wait_word, for a word that holds the count next to the sequence number)
 			bool seen = false;
 			for (int k = 0; k < 20000 && !seen; k++) {
-				w = words[8];
+				w = comp.words[8];
 				seen = (w >> 8) == (vs & 0xffffffu);
 				if (!seen) __builtin_ia32_pause();
 			}
 			if (seen) break;
 			const hipError_t e = hipStreamQuery(c.st);
-			if (e == hipSuccess) { w = words[8]; break; }
+			if (e == hipSuccess) { w = comp.words[8]; break; }
 			if (e != hipErrorNotReady) HIPCHK(e);
 		}
 		if ((int)(w & 0xffu) != env.nranks || (w >> 8) != (vs & 0xffffffu)) { prof_collect(); return NOT_MINE; }
@@ -2020,42 +2013,23 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 			ch.chol = chol_args(i); ch.direct = 1;
 			{
 				ProfScope ps(KC_GRAM, c.st);
-				hipLaunchKernelGGL(tsqrmi::gram_blk_chain_kernel, dim3(1 + nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args(i + 1), ch);
+				hipLaunchKernelGGL(tsqrmi::gram_blk_chain_kernel, dim3(1 + nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st,
+				                   gram_args_64(c, mt.a(i + 1), cl, nchunks, g, part), ch);
 			}
 			HIPCHK(hipGetLastError());
 			const int rc2 = reduce_allreduce(0);
 			if (rc2) return rc2;
 		} else {
-			if (announce) { hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, announce, announce_seq); announce = nullptr; }
+			raise_announcement(c);
 			ProfScope ps(KC_CHOL, c.st);
 			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(i));
 			HIPCHK(hipGetLastError());
 		}
 		c.slot = i & 1;
-		const int rc2 = apply_rinv(c, engine, mt.q(i), ldq, mt.a(i), lda, mt.r(i), ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
-		if (rc2) return rc2;
-		unsigned sq = ++g_seq;
-		if (sq == 0) sq = ++g_seq;
-		seq[i & 1] = sq;
-		words[4 * (i & 1) + 3] = 0;
-		if (i + 1 < count) { announce = c.hsig.dev + 4 * (i & 1) + 3; announce_seq = sq; }   // raised by the chained launch of step i + 1
-		else hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.hsig.dev + 4 * (i & 1) + 3, sq);
-		HIPCHK(hipGetLastError());
-		return 0;
+		const int rc2 = apply_rinv(c, engine, mt.q(i), cl.ldq, mt.a(i), cl.lda, mt.r(i), cl.ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
+		return rc2 ? rc2 : comp.close(i, i + 1 == count);
 	};
-	rc = step(0);
-	if (rc) return rc;
-	for (int i = 0; i < count; i++) {
-		if (i + 1 < count) { rc = step(i + 1); if (rc) return rc; }
-		rc = wait_word(words + 4 * (i & 1) + 3, seq[i & 1], c.st);
-		if (rc) return rc;
-		if (words[4 * (i & 1)] != 0) return rejected_tail(env, mt, count, cl, i, words, c.st, done);
-		mt.state(i, TSQR_MI_SUCCESS);
-		*done = i + 1;
-	}
-	t_last_engine = 3;
-	prof_collect();
-	return TSQR_MI_SUCCESS;
+	return run_chained(comp, mt, count, 3, step, [&](int i) { return rejected_tail(env, mt, count, cl, i, comp, done); }, done);
 }
 
 // Two calls in flight: call i + 1 is submitted before call i is finished; the completion word of call i is raised by the first kernel of
@@ -2172,9 +2146,7 @@ void tsqr_mi_set_loop_depth(int depth) { g_set.loop_depth = depth < 2 ? 1 : (dep
 int tsqr_mi_qr_f32_loop(int count, int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
                         size_t m, size_t n, void* wq_v, void* wr_v, float* reorth_w, unsigned* d_wl, unsigned* h_wl, void* stream) {
 	(void)reorth_w; (void)d_wl;
-	Mats mt;
-	mt.q0 = q; mt.r0 = r; mt.a0 = a;
-	return stream_of_calls(CallEnv{}, mt, count, Call{mode, reorth, ldq, ldr, lda, m, n, wq_v, wr_v, h_wl, stream});
+	return stream_of_calls(CallEnv{}, one_triple(q, r, a), count, Call{mode, reorth, ldq, ldr, lda, m, n, wq_v, wr_v, h_wl, stream});
 }
 
 // `count` DIFFERENT matrices of one shape (include/tsqr_mi.h): the caller of mtk::qr::qr with many matrices -- the stream of calls above
@@ -2182,9 +2154,8 @@ int tsqr_mi_qr_f32_loop(int count, int mode, int reorth, float* q, size_t ldq, f
 int tsqr_mi_qr_f32_batch(int count, int mode, int reorth, float* const* q, size_t ldq, float* const* r, size_t ldr, float* const* a, size_t lda,
                          size_t m, size_t n, void* wq_v, void* wr_v, float* reorth_w, unsigned* d_wl, unsigned* h_wl, void* stream, int* states) {
 	(void)reorth_w; (void)d_wl;
-	if (count < 0 || (count > 0 && (!q || !r || !a))) return TSQR_MI_ERROR_INVALID_SIZE;
 	Mats mt;
-	mt.qs = q; mt.rs = r; mt.as = a; mt.states = states;
+	if (const int rc = triple_per_call(mt, count, q, r, a, states)) return rc;
 	return stream_of_calls(CallEnv{}, mt, count, Call{mode, reorth, ldq, ldr, lda, m, n, wq_v, wr_v, h_wl, stream});
 }
 
@@ -2265,7 +2236,7 @@ int tsqr_mi_qr_f16(int mode, int reorth, void* q, size_t ldq, void* r, size_t ld
 
 // The fp16 calls as a stream, two in flight (the native path only: one panel, no reorth, aligned halves): Gram pass on the halves, reduction,
 // Cholesky + verdict, apply pass (which also rounds R), the completion word of call i raised by the Gram kernel of call i + 1.  The
-// verdict words alternate between the two halves of the pinned words.  Returns -2 when the call is not one for the native path
+// verdict words alternate between the two halves of the pinned words.  Returns NOT_MINE when the call is not one for the native path
 // (nothing enqueued); a rejected verdict drains the stream and finishes the count with blocking calls (conversion path, whole ladder).
 // (mt: the half-typed operands of the calls, carried as float* -- one triple for a loop, one per call for a batch)
 static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, size_t ldr, size_t lda,
@@ -2279,113 +2250,71 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 	for (int i = 0; i + 1 < count; i++)                  // a pair of calls that conflict (stream_order.h): the batch runs as blocking calls
 		if (pair_conflicts(mt, count, i, cl, sizeof(_Float16))) return NOT_MINE;
 	Ctx c;
-	init_ctx(c, wq_v, wr_v, m, n, stream);
-	c.rows_global = (double)m;
-	resolve_host_sig(c, h_wl, m);
+	env_ctx(c, CallEnv{}, wq_v, wr_v, m, n, h_wl, stream, /*keep_in_flight=*/false);
 	if (!(c.policy == 0 && c.gram_level == 2 && c.hsig.dev && !t_prof.on && !g_set.debug)) return NOT_MINE;
 	float* r32 = reinterpret_cast<float*>(wq_v) + f16_tail_offset(m, n) + 2 * f16_ld(m) * n;
 	const int engine = engine_of(emode);
-	volatile unsigned* words = reinterpret_cast<volatile unsigned*>(c.hsig.host);
-	unsigned seq[2] = {0, 0};
+	Completion comp(c);
+	// behind the R factor of call i, in either schedule: its apply pass (which also rounds R to halves), then its completion word
+	auto apply_and_close = [&](int i) -> int {
+		const int rc = apply_rinv(c, engine, mt.q(i), ldq, mt.a(i), lda, r32, n, m, n, /*z_ready=*/true, c.status_dev(i & 1), /*io_half=*/true, mt.r(i), ldr);
+		return rc ? rc : comp.close(i, i + 1 == count);
+	};
+	// rejected (its apply pass skipped itself: A and Q untouched): drain; this call as a blocking call (conversion path, whole
+	// ladder); the call behind it, enqueued in full, stands if it was accepted; the rest of the count as blocking calls
+	auto tail = [&](int i) -> int {
+		HIPCHK(hipStreamSynchronize(c.st));
+		const bool next_ok = i + 1 < count && !comp.rejected(i + 1);
+		int first = 0;
+		for (int k = i; k < count; k++) {
+			int st = 0;
+			if (!(k == i + 1 && next_ok))
+				st = tsqr_mi_qr_f16(mode, 0, mt.q(k), ldq, mt.r(k), ldr, mt.a(k), lda, m, n, wq_v, wr_v, nullptr, nullptr, h_wl, stream);
+			if (st < 0) return st;
+			mt.state(k, st);
+			if (st && !first) first = st;
+			if (st && mt.same()) return st;
+		}
+		return first;
+	};
+	int done = 0;
 	// n = 64, three calls or more: the chained schedule (tsqr_mi_qr_f32_loop's, with gram_h_chain_kernel) -- the R-factor chain of call i
 	// inside the Gram launch of call i + 1, two sets of partials
 	// (the chained launch order needs a loop's Q and R clear of its A, and two different matrices must share the Infinity Cache)
-	const bool chained = (n == PW && count >= 3 && g_set.loop_depth.load() >= 3 && out_of_order(mt, count, cl, sizeof(_Float16)) &&
-	                      (mt.same() || (double)lda * (double)n * sizeof(_Float16) <= (double)g_set.chain_max_mib * 1048576.0));
+	if (!(n == PW && count >= 3 && g_set.loop_depth.load() >= 3 && out_of_order(mt, count, cl, sizeof(_Float16)) && chain_fits_cache(mt, cl, sizeof(_Float16)))) {
+		// two in flight: every launch of call i; call i - 1's completion word rides in its Gram kernel (gram_g)
+		auto step = [&](int i) -> int {
+			c.slot = i & 1; c.prev_slot = -1;
+			int rc = gram_g(c, mt.a(i), lda, m, n, /*bf16=*/true, /*io_half=*/true);
+			if (!rc) rc = chol_from_g(c, r32, n, n, 2);
+			return rc ? rc : apply_and_close(i);
+		};
+		return run_chained(comp, mt, count, 3, step, tail, &done);
+	}
 	const GramPlan g = gram_plan(m, n);
 	const int nelem = 10 * 256, nred = nelem / 16;
 	double* part[2] = {reinterpret_cast<double*>(c.wr), reinterpret_cast<double*>(c.wr) + (size_t)g.nblocks * nelem};
 	unsigned* ticket = c.status_dev(0) + 8;
-	if (chained) HIPCHK(hipMemsetAsync(ticket, 0, sizeof(unsigned), c.st));
-	auto gram_h_args = [&](int i) {
-		tsqrmi::GramArgs ga{};
-		ga.a = mt.a(i); ga.lda = lda; ga.m = m; ga.n = (int)n; ga.nchunks = g.nch; ga.cpw = g.cpw; ga.nwaves = g.nwaves;
-		ga.part = part[i & 1];
-		ga.announce = c.announce_word; ga.announce_seq = c.announce_seq; c.announce_word = nullptr;
-		return ga;
-	};
-	auto chol_h_args = [&](int i) {
-		tsqrmi::CholArgs ca{};
-		ca.r = r32; ca.ldr = n; ca.z = c.wq + c.L.z;
-		ca.status = c.status_dev(i & 1);
-		ca.host_status = c.hsig.dev + 4 * (i & 1);
-		ca.gsum = c.gsum();
-		ca.rows = c.rows_global;
-		ca.n = (int)n; ca.NT = 4; ca.level = 2; ca.scond_floor = g_set.bf16_scond_floor;
-		return ca;
-	};
-	if (chained) {
-		hipLaunchKernelGGL(tsqrmi::gram_h_kernel<4>, dim3(g.nblocks), dim3(256), 0, c.st, gram_h_args(0));
-		HIPCHK(hipGetLastError());
-	}
-	auto step = [&](int i) -> int {                      // every launch of call i; c.announce_word (call i - 1's completion word) rides in its Gram kernel
+	HIPCHK(hipMemsetAsync(ticket, 0, sizeof(unsigned), c.st));
+	hipLaunchKernelGGL(tsqrmi::gram_h_kernel<4>, dim3(g.nblocks), dim3(256), 0, c.st, gram_args_64(c, mt.a(0), cl, g.nch, g, part[0]));
+	HIPCHK(hipGetLastError());
+	auto step = [&](int i) -> int {
 		c.slot = i & 1; c.prev_slot = -1;
-		int rc = 0;
-		if (chained) {
-			if (i + 1 < count) {
-				tsqrmi::ChainArgs ch{};
-				ch.chol = chol_h_args(i);
-				ch.part = part[i & 1]; ch.nparts = g.nblocks; ch.ticket = ticket; ch.nred = nred;
-				hipLaunchKernelGGL(tsqrmi::gram_h_chain_kernel, dim3(nred + g.nblocks), dim3(256), 0, c.st, gram_h_args(i + 1), ch);
-			} else {
-				if (c.announce_word) { hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.announce_word, c.announce_seq); c.announce_word = nullptr; }
-				hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nred), dim3(256), 0, c.st, c.gsum(), part[i & 1], g.nblocks, nelem, (double)m,
-				                   nullptr, (size_t)0, nullptr, 0);
-				hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_h_args(i));
-			}
-			HIPCHK(hipGetLastError());
+		if (i + 1 < count) {
+			tsqrmi::ChainArgs ch{};
+			ch.chol = chol_args_64(c, r32, n, i, n);
+			ch.part = part[i & 1]; ch.nparts = g.nblocks; ch.ticket = ticket; ch.nred = nred;
+			hipLaunchKernelGGL(tsqrmi::gram_h_chain_kernel, dim3(nred + g.nblocks), dim3(256), 0, c.st, gram_args_64(c, mt.a(i + 1), cl, g.nch, g, part[(i + 1) & 1]), ch);
 		} else {
-			rc = gram_g(c, mt.a(i), lda, m, n, /*bf16=*/true, /*io_half=*/true);
-			if (!rc) rc = chol_from_g(c, r32, n, n, 2);
+			raise_announcement(c);
+			hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nred), dim3(256), 0, c.st, c.gsum(), part[i & 1], g.nblocks, nelem, (double)m,
+			                   nullptr, (size_t)0, nullptr, 0);
+			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args_64(c, r32, n, i, n));
 		}
-		if (!rc) rc = apply_rinv(c, engine, mt.q(i), ldq, mt.a(i), lda, r32, n, m, n, /*z_ready=*/true,
-		                         c.status_dev(c.slot), /*io_half=*/true, mt.r(i), ldr);
-		if (rc) return rc;
-		unsigned sq = ++g_seq;
-		if (sq == 0) sq = ++g_seq;
-		seq[i & 1] = sq;
-		words[4 * (i & 1) + 3] = 0;
-		if (i + 1 < count) { c.announce_word = c.hsig.dev + 4 * (i & 1) + 3; c.announce_seq = sq; }
-		else hipLaunchKernelGGL(tsqrmi::host_flag_kernel, dim3(1), dim3(1), 0, c.st, c.hsig.dev + 4 * (i & 1) + 3, sq);
 		HIPCHK(hipGetLastError());
-		return 0;
+		return apply_and_close(i);
 	};
-	int rc = step(0);
-	if (rc) return rc;
-	for (int i = 0; i < count; i++) {
-		if (i + 1 < count) { rc = step(i + 1); if (rc) return rc; }
-		for (bool done = false; !done;) {
-			for (int k = 0; k < 20000 && !done; k++) {
-				done = (words[4 * (i & 1) + 3] == seq[i & 1]);
-				if (!done) __builtin_ia32_pause();
-			}
-			if (!done) {
-				const hipError_t e = hipStreamQuery(c.st);
-				if (e == hipSuccess) done = true;
-				else if (e != hipErrorNotReady) HIPCHK(e);
-			}
-		}
-		if (words[4 * (i & 1)] != 0) {
-			// rejected (its apply pass skipped itself: A and Q untouched): drain; this call as a blocking call (conversion path, whole
-			// ladder); the call behind it, enqueued in full, stands if it was accepted; the rest of the count as blocking calls
-			HIPCHK(hipStreamSynchronize(c.st));
-			const bool next_ok = i + 1 < count && words[4 * ((i + 1) & 1)] == 0;
-			int first = 0;
-			for (int k = i; k < count; k++) {
-				int st = 0;
-				if (!(k == i + 1 && next_ok))
-					st = tsqr_mi_qr_f16(mode, 0, mt.q(k), ldq, mt.r(k), ldr, mt.a(k), lda, m, n, wq_v, wr_v, nullptr, nullptr, h_wl, stream);
-				if (st < 0) return st;
-				mt.state(k, st);
-				if (st && !first) first = st;
-				if (st && mt.same()) return st;
-			}
-			return first;
-		}
-		mt.state(i, TSQR_MI_SUCCESS);
-	}
-	t_last_engine = 3;
-	return TSQR_MI_SUCCESS;
+	return run_chained(comp, mt, count, 3, step, tail, &done);
 }
 
 static int calls_f16(const Mats& mt, int count, int mode, int reorth, size_t ldq, size_t ldr, size_t lda, size_t m, size_t n,
@@ -2405,35 +2334,46 @@ static int calls_f16(const Mats& mt, int count, int mode, int reorth, size_t ldq
 }
 int tsqr_mi_qr_f16_loop(int count, int mode, int reorth, void* q, size_t ldq, void* r, size_t ldr, const void* a, size_t lda,
                         size_t m, size_t n, void* wq_v, void* wr_v, void* reorth_w, unsigned* d_wl, unsigned* h_wl, void* stream) {
-	Mats mt;
-	mt.q0 = reinterpret_cast<float*>(q); mt.r0 = reinterpret_cast<float*>(r); mt.a0 = const_cast<float*>(reinterpret_cast<const float*>(a));
+	const Mats mt = one_triple(reinterpret_cast<float*>(q), reinterpret_cast<float*>(r), const_cast<float*>(reinterpret_cast<const float*>(a)));
 	return calls_f16(mt, count, mode, reorth, ldq, ldr, lda, m, n, wq_v, wr_v, reorth_w, d_wl, h_wl, stream);
 }
 // `count` DIFFERENT half-typed matrices of one shape (tsqr_mi_qr_f32_batch's counterpart for the fp16 I/O modes): calls the native path
 // takes are issued as a stream, everything else as blocking calls; the same halves either way
 int tsqr_mi_qr_f16_batch(int count, int mode, int reorth, void* const* q, size_t ldq, void* const* r, size_t ldr, const void* const* a, size_t lda,
                          size_t m, size_t n, void* wq_v, void* wr_v, void* reorth_w, unsigned* d_wl, unsigned* h_wl, void* stream, int* states) {
-	if (count < 0 || (count > 0 && (!q || !r || !a))) return TSQR_MI_ERROR_INVALID_SIZE;
 	Mats mt;                                             // (pointer arrays of the same layout: void* / float*, const or not)
-	mt.qs = reinterpret_cast<float* const*>(q); mt.rs = reinterpret_cast<float* const*>(r); mt.as = reinterpret_cast<float* const*>(const_cast<void* const*>(a));
-	mt.states = states;
+	if (const int rc = triple_per_call(mt, count, reinterpret_cast<float* const*>(q), reinterpret_cast<float* const*>(r),
+	                                   reinterpret_cast<float* const*>(const_cast<void* const*>(a)), states)) return rc;
 	return calls_f16(mt, count, mode, reorth, ldq, ldr, lda, m, n, wq_v, wr_v, reorth_w, d_wl, h_wl, stream);
 }
 
 // ---- row-partitioned TSQR: one call per rank, the same ladder as tsqr_mi_qr_f32 with the exchange hooks switched on ----
-int tsqr_mi_qr_f32_dist_fn(int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
-                           size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
-                           void* nccl_comm, void* nccl_allreduce_fn, void* nccl_allgather_fn, int nranks, void* stream) {
+// (CallEnv of a row-partitioned call from the caller's transport: an ncclComm_t with its entry points, or callbacks)
+static int env_of_nccl(CallEnv& env, void* nccl_comm, void* nccl_allreduce_fn, void* nccl_allgather_fn, float* gather_buf, int nranks) {
 	if (!nccl_comm || !nccl_allreduce_fn || !nccl_allgather_fn) {
 		t_last_error = "row-partitioned call needs an ncclComm_t and the ncclAllReduce / ncclAllGather entry points of the library that created it";
 		return TSQR_MI_ERROR_UNSUPPORTED;
 	}
-	Ctx c;
-	c.comm.nccl = nccl_comm;
-	c.comm.nccl_allreduce = reinterpret_cast<nccl_allreduce_t>(nccl_allreduce_fn);
-	c.comm.nccl_allgather = reinterpret_cast<nccl_allgather_t>(nccl_allgather_fn);
-	c.comm.gather_buf = gather_buf;
-	return qr_dist_common(c, mode, reorth, q, ldq, r, ldr, a, lda, m_local, n, wq_v, wr_v, nranks, stream);
+	env.dist = true; env.nranks = nranks;
+	env.comm.nccl = nccl_comm;
+	env.comm.nccl_allreduce = reinterpret_cast<nccl_allreduce_t>(nccl_allreduce_fn);
+	env.comm.nccl_allgather = reinterpret_cast<nccl_allgather_t>(nccl_allgather_fn);
+	env.comm.gather_buf = gather_buf;
+	return 0;
+}
+static int env_of_callbacks(CallEnv& env, tsqr_mi_allreduce_f64_cb allreduce, tsqr_mi_allgather_f32_cb allgather, void* user, float* gather_buf, int nranks) {
+	if (!allreduce || !allgather) return TSQR_MI_ERROR_UNSUPPORTED;
+	env.dist = true; env.nranks = nranks;
+	env.comm.cb_allreduce = allreduce; env.comm.cb_allgather = allgather; env.comm.cb_user = user;
+	env.comm.gather_buf = gather_buf;
+	return 0;
+}
+int tsqr_mi_qr_f32_dist_fn(int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
+                           size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
+                           void* nccl_comm, void* nccl_allreduce_fn, void* nccl_allgather_fn, int nranks, void* stream) {
+	CallEnv env;
+	if (const int rc = env_of_nccl(env, nccl_comm, nccl_allreduce_fn, nccl_allgather_fn, gather_buf, nranks)) return rc;
+	return blocking_one(env, one_triple(q, r, a), 0, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
 }
 int tsqr_mi_qr_f32_dist(int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
                         size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
@@ -2450,40 +2390,23 @@ int tsqr_mi_qr_f32_dist(int mode, int reorth, float* q, size_t ldq, float* r, si
 int tsqr_mi_qr_f32_dist_cb(int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
                            size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
                            tsqr_mi_allreduce_f64_cb allreduce, tsqr_mi_allgather_f32_cb allgather, void* user, int nranks, void* stream) {
-	if (!allreduce || !allgather) return TSQR_MI_ERROR_UNSUPPORTED;
-	Ctx c;
-	c.comm.cb_allreduce = allreduce; c.comm.cb_allgather = allgather; c.comm.cb_user = user;
-	c.comm.gather_buf = gather_buf;
-	return qr_dist_common(c, mode, reorth, q, ldq, r, ldr, a, lda, m_local, n, wq_v, wr_v, nranks, stream);
+	CallEnv env;
+	if (const int rc = env_of_callbacks(env, allreduce, allgather, user, gather_buf, nranks)) return rc;
+	return blocking_one(env, one_triple(q, r, a), 0, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
 }
 int tsqr_mi_qr_f32_dist_fn_loop(int count, int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
                                 size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
                                 void* nccl_comm, void* nccl_allreduce_fn, void* nccl_allgather_fn, int nranks, void* stream) {
-	if (!nccl_comm || !nccl_allreduce_fn || !nccl_allgather_fn) {
-		t_last_error = "row-partitioned call needs an ncclComm_t and the ncclAllReduce / ncclAllGather entry points of the library that created it";
-		return TSQR_MI_ERROR_UNSUPPORTED;
-	}
 	CallEnv env;
-	env.dist = true; env.nranks = nranks;
-	env.comm.nccl = nccl_comm;
-	env.comm.nccl_allreduce = reinterpret_cast<nccl_allreduce_t>(nccl_allreduce_fn);
-	env.comm.nccl_allgather = reinterpret_cast<nccl_allgather_t>(nccl_allgather_fn);
-	env.comm.gather_buf = gather_buf;
-	Mats mt;
-	mt.q0 = q; mt.r0 = r; mt.a0 = a;
-	return stream_of_calls(env, mt, count, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
+	if (const int rc = env_of_nccl(env, nccl_comm, nccl_allreduce_fn, nccl_allgather_fn, gather_buf, nranks)) return rc;
+	return stream_of_calls(env, one_triple(q, r, a), count, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
 }
 int tsqr_mi_qr_f32_dist_cb_loop(int count, int mode, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda,
                                 size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
                                 tsqr_mi_allreduce_f64_cb allreduce, tsqr_mi_allgather_f32_cb allgather, void* user, int nranks, void* stream) {
-	if (!allreduce || !allgather) return TSQR_MI_ERROR_UNSUPPORTED;
 	CallEnv env;
-	env.dist = true; env.nranks = nranks;
-	env.comm.cb_allreduce = allreduce; env.comm.cb_allgather = allgather; env.comm.cb_user = user;
-	env.comm.gather_buf = gather_buf;
-	Mats mt;
-	mt.q0 = q; mt.r0 = r; mt.a0 = a;
-	return stream_of_calls(env, mt, count, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
+	if (const int rc = env_of_callbacks(env, allreduce, allgather, user, gather_buf, nranks)) return rc;
+	return stream_of_calls(env, one_triple(q, r, a), count, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
 }
 
 // `count` DIFFERENT row-partitioned matrices (every rank: its row block of each; one block height for all): the stream of calls of the
@@ -2493,32 +2416,19 @@ int tsqr_mi_qr_f32_dist_cb_loop(int count, int mode, int reorth, float* q, size_
 int tsqr_mi_qr_f32_dist_fn_batch(int count, int mode, int reorth, float* const* q, size_t ldq, float* const* r, size_t ldr, float* const* a, size_t lda,
                                  size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
                                  void* nccl_comm, void* nccl_allreduce_fn, void* nccl_allgather_fn, int nranks, void* stream, int* states) {
-	if (!nccl_comm || !nccl_allreduce_fn || !nccl_allgather_fn) {
-		t_last_error = "row-partitioned call needs an ncclComm_t and the ncclAllReduce / ncclAllGather entry points of the library that created it";
-		return TSQR_MI_ERROR_UNSUPPORTED;
-	}
-	if (count < 0 || (count > 0 && (!q || !r || !a))) return TSQR_MI_ERROR_INVALID_SIZE;
 	CallEnv env;
-	env.dist = true; env.nranks = nranks;
-	env.comm.nccl = nccl_comm;
-	env.comm.nccl_allreduce = reinterpret_cast<nccl_allreduce_t>(nccl_allreduce_fn);
-	env.comm.nccl_allgather = reinterpret_cast<nccl_allgather_t>(nccl_allgather_fn);
-	env.comm.gather_buf = gather_buf;
+	if (const int rc = env_of_nccl(env, nccl_comm, nccl_allreduce_fn, nccl_allgather_fn, gather_buf, nranks)) return rc;
 	Mats mt;
-	mt.qs = q; mt.rs = r; mt.as = a; mt.states = states;
+	if (const int rc = triple_per_call(mt, count, q, r, a, states)) return rc;
 	return stream_of_calls(env, mt, count, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
 }
 int tsqr_mi_qr_f32_dist_cb_batch(int count, int mode, int reorth, float* const* q, size_t ldq, float* const* r, size_t ldr, float* const* a, size_t lda,
                                  size_t m_local, size_t n, void* wq_v, void* wr_v, float* gather_buf,
                                  tsqr_mi_allreduce_f64_cb allreduce, tsqr_mi_allgather_f32_cb allgather, void* user, int nranks, void* stream, int* states) {
-	if (!allreduce || !allgather) return TSQR_MI_ERROR_UNSUPPORTED;
-	if (count < 0 || (count > 0 && (!q || !r || !a))) return TSQR_MI_ERROR_INVALID_SIZE;
 	CallEnv env;
-	env.dist = true; env.nranks = nranks;
-	env.comm.cb_allreduce = allreduce; env.comm.cb_allgather = allgather; env.comm.cb_user = user;
-	env.comm.gather_buf = gather_buf;
+	if (const int rc = env_of_callbacks(env, allreduce, allgather, user, gather_buf, nranks)) return rc;
 	Mats mt;
-	mt.qs = q; mt.rs = r; mt.as = a; mt.states = states;
+	if (const int rc = triple_per_call(mt, count, q, r, a, states)) return rc;
 	return stream_of_calls(env, mt, count, Call{mode, reorth, ldq, ldr, lda, m_local, n, wq_v, wr_v, nullptr, stream});
 }
 
