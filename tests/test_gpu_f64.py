@@ -143,3 +143,50 @@ def test_f64_non_finite(bq):
     st, q, r, _ = _run(bq, a_host, 0)
     assert st == 0
     _check(bq, a_host, q, r, 0, np.linalg.cond(a_host))
+
+
+# ---- the ladder: S_ref prescribed on both sides of both thresholds of the acceptance rule -------------------------------------------------
+@pytest.mark.parametrize("n", [16, 64])
+def test_f64_ladder_sweep_counts(bq, n):
+    """A with S_ref = mean(1 / sigma_i(A D^-1)^2) at alone_max / 2, 2 alone_max, max_scond / 4 and 4 max_scond (thresholds from
+    CholArgs64's formulas and the shape, pass_refs_f64.rule; the margins 2 and 4 are conditions: at the CholeskyQR2 bound S moves by
+    about 1/64 with the rounding of G; tests/test_pass_refs_f64.py checks on the CPU that every matrix lands on its side): the sweep
+    count exactly -- 1, 2, 2, 103 (reorth = 1: 2, 2, 2, 103) -- and the bands of the header.  Where the first sweep ends the call the
+    measured ||QtQ-I||_F is printed next to the rule's estimate 4 n S u."""
+    from tests import pass_refs_f64 as p64
+    m = 4096
+    for name, target, s0, s1 in p64.ladder_targets(m, n):
+        a_host, s_ref = p64.ladder_matrix(m, n, target, n)
+        cond = np.linalg.cond(a_host)
+        for reorth, want in ((0, s0), (1, s1)):
+            st, q, r, _ = _run(bq, a_host, reorth)
+            assert st == 0, (st, bq.last_error())
+            sweeps = bq.last_sweeps_f64()
+            orth, res = _check(bq, a_host, q, r, reorth, cond)
+            print("ladder %d x %d  S_ref = %s = %.4g  reorth %d: sweeps %d  ||QtQ-I||_F %.2e  residual %.2e%s" % (
+                m, n, name, s_ref, reorth, sweeps, orth, res,
+                "  one-sweep estimate 4nSu %.2e" % (4 * n * s_ref * U53) if sweeps == 1 else ""))
+            assert sweeps == want, (name, reorth, sweeps, want)
+
+
+def test_f64_limit_2p23_x_64_in_place(bq):
+    """the documented limit m = 2^23 at n = 64, in place, Gaussian data generated on the device: the bands of the header"""
+    torch = _torch()
+    m, n = 1 << 23, 64
+    g = torch.Generator(device="cuda").manual_seed(23)
+    a0 = torch.randn(n, m, dtype=torch.float64, device="cuda", generator=g)      # column-major m x n, lda = m
+    a = a0.clone()
+    r = torch.full((n, n + 2), float("nan"), dtype=torch.float64, device="cuda")
+    for reorth in (0, 1):
+        a.copy_(a0)
+        bf = bq.buffer_f64(reorth)
+        bf.allocate(m, n)
+        st = bq.qr_f64(a, m, r, n + 2, a, m, m, n, bf)
+        torch.cuda.synchronize()
+        assert st == 0, (st, bq.last_error())
+        rt = r[:, :n]                                                             # R^T
+        orth = torch.linalg.norm(a @ a.T - torch.eye(n, dtype=torch.float64, device="cuda")).item()
+        res = (torch.linalg.norm(a0 - rt @ a) / torch.linalg.norm(a0)).item()
+        print("2^23 x 64 in place reorth %d: sweeps %d  ||QtQ-I||_F %.2e  residual %.2e" % (reorth, bq.last_sweeps_f64(), orth, res))
+        assert torch.isnan(r[:, n:]).all() and torch.all(torch.triu(rt, 1) == 0) and torch.all(torch.diagonal(rt) > 0)   # (rt is R^T)
+        assert orth <= (1e-12 if reorth else 1e-11) and res <= 1e-13

@@ -178,3 +178,45 @@ def test_f64_wide_non_finite(bq):
     assert st == 0, (st, bq.last_error())
     assert bq.last_sweeps_f64() == 1
     _check(a_dev, q, r, 0)
+
+
+# ---- the ladder: S_ref prescribed on both sides of both thresholds of the acceptance rule -------------------------------------------------
+@pytest.mark.parametrize("n", [128, 200])
+def test_f64_wide_ladder_sweep_counts(bq, n):
+    """as tests/test_gpu_f64.py::test_f64_ladder_sweep_counts, through tsqr_mi_qr_f64_wide: S is summed over block pairs here, and a
+    sum without its off-diagonal terms would take one sweep where CholeskyQR2 is needed.  Sweep counts exactly: 1, 2, 2, 103
+    (reorth = 1: 2, 2, 2, 103), and the bands of the header."""
+    from tests import pass_refs_f64 as p64
+    torch = _torch()
+    m = 4096
+    for name, target, s0, s1 in p64.ladder_targets(m, n):
+        a_host, s_ref = p64.ladder_matrix(m, n, target, n)
+        a_dev = torch.from_numpy(a_host).cuda()
+        cond = np.linalg.cond(a_host)
+        for reorth, want in ((0, s0), (1, s1)):
+            st, q, r, _ = _run(bq, a_dev, reorth)
+            assert st == 0, (st, bq.last_error())
+            sweeps = bq.last_sweeps_f64()
+            orth, res, _ = _check(a_dev, q, r, reorth, cond)
+            print("ladder %d x %d  S_ref = %s = %.4g  reorth %d: sweeps %d  ||QtQ-I||_F %.2e  residual %.2e%s" % (
+                m, n, name, s_ref, reorth, sweeps, orth, res,
+                "  one-sweep estimate 4nSu %.2e" % (4 * n * s_ref * U53) if sweeps == 1 else ""))
+            assert sweeps == want, (name, reorth, sweeps, want)
+
+
+def test_f64_wide_limit_2p16_x_1024(bq):
+    """the documented limit m n = 2^26 at n = 1024, Gaussian data generated on the device: the bands of the header"""
+    torch = _torch()
+    m, n = 1 << 16, 1024
+    a_dev = _gauss(m, n, 26)
+    I = torch.eye(n, dtype=torch.float64, device="cuda")
+    for reorth in (0, 1):
+        st, q, r, _ = _run(bq, a_dev, reorth)
+        assert st == 0, (st, bq.last_error())
+        assert torch.isnan(q[:, m:]).all() and torch.isnan(r[:, n:]).all()
+        Q, Rd = q[:, :m].T, r[:, :n].T
+        orth = torch.linalg.norm(Q.T @ Q - I).item()
+        res = (torch.linalg.norm(a_dev - Q @ Rd) / torch.linalg.norm(a_dev)).item()
+        print("2^16 x 1024 reorth %d: sweeps %d  ||QtQ-I||_F %.2e  residual %.2e" % (reorth, bq.last_sweeps_f64(), orth, res))
+        assert torch.all(torch.tril(Rd, -1) == 0) and torch.all(torch.diagonal(Rd) > 0)
+        assert orth <= (1e-12 if reorth else 1e-11) * n / 64 and res <= 1e-13

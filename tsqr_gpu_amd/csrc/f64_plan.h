@@ -1,0 +1,130 @@
+// f64_plan.h -- the host side that the fp64 entries (tsqr_mi_qr_f64, tsqr_mi_qr_f64_wide) share with the test library: the launch plans of
+// the Gram and apply passes, the work-space offsets and the launch sequence of the blocked Cholesky step.  ONE definition, compiled into
+// libtsqr_mi.so (tsqr_mi.hip) and into libtsqr_selftest.so (selftest.hip), so that the per-pass tests run the product's kernels with the
+// product's plan and never a copy of it.  Included after tsqr_kernels.hip, tsqr_wide.hip, tsqr_f64.hip and tsqr_f64_wide.hip.
+// The including file defines fail(): what a function returns, through HIPCHK, when a HIP call did not succeed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+
+namespace {
+
+constexpr size_t PW = 64;          // panel width
+
+inline int fail(hipError_t e, const char* what);
+#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(e_, #expr); } while (0)
+
+inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
+inline size_t np_of(size_t n) { return 16 * cdiv(std::min(n, PW), 16); }
+
+constexpr size_t GSUM_DOUBLES = 16 * 256 + 8;          // 16 tiles (coupling) or 10 (Gram) + the row-count word of a row-partitioned run
+
+// ---- tsqr_mi_qr_f64 (n <= 64) --------------------------------------------------------------------------------------------------------
+constexpr int F64_GRAM_WAVES = 2048;                    // fixed (not tsqr_mi_set_tuning2): the work-space size must not follow a setting
+// wq (doubles): [Z: 4096][R of the sweep: 4096][summed tiles + row count][status words: 4 slots x 4 words]
+constexpr size_t F64_Z = 0, F64_R2 = 4096, F64_GSUM = 8192, F64_STATUS = F64_GSUM + GSUM_DOUBLES, F64_WQ = F64_STATUS + 8;
+
+struct F64Plan { int NT, ntri, nch, nwaves, nblocks; };
+F64Plan f64_plan(size_t m, size_t n) {
+	F64Plan g{};
+	g.NT = (int)(np_of(n) / 16);
+	g.ntri = g.NT * (g.NT + 1) / 2;
+	g.nch = (int)cdiv(m, 64);
+	const size_t cpw = std::max<size_t>(1, cdiv((size_t)g.nch, F64_GRAM_WAVES));
+	g.nwaves = (int)cdiv((size_t)g.nch, cpw);
+	g.nblocks = (g.nwaves + 3) / 4;
+	return g;
+}
+
+// The acceptance rule of a sweep over an m x n matrix (CholArgs64, tsqr_f64.hip, states it and its sources): the bounds on S of a FIRST
+// sweep (later sweeps: max_scond = infinity, never alone) and the coefficient of the shift, s = shift_coef * trace(G)
+struct F64Rule { double shift_coef; float max_scond, alone_max; };
+inline F64Rule f64_rule(size_t m, size_t n, bool first) {
+	F64Rule r{};
+	const double u = 0x1p-53, mn = (double)m * (double)n + (double)n * (double)(n + 1);
+	r.shift_coef = 11.0 * u * mn;
+	r.max_scond = first ? (float)(1.0 / (64.0 * (double)n * u * mn)) : INFINITY;
+	r.alone_max = first ? (float)(1e-12 / (4.0 * (double)n * u)) : 0.0f;
+	return r;
+}
+
+// the Gram pass of the n <= 64 entry on stream st: gram_f64_kernel<NT> on the plan's grid
+inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramArgs64& ga) {
+	switch (g.NT) {
+		case 1: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<1>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+		case 2: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<2>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+		case 3: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<3>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+		default: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<4>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
+	}
+}
+
+// the apply pass of the n <= 64 entry runs on a persistent grid: the workgroups resident at once on device dev ...
+template <int NT> int f64_apply_resident(int dev) {
+	int nb = 0, cus = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tsqrmi::apply_f64_kernel<NT>), 256, 0) != hipSuccess || nb < 1) {
+		(void)hipGetLastError(); nb = 1;
+	}
+	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
+	return nb * cus;
+}
+// ... but no more than one wave per 32-row block
+inline size_t f64_apply_wgs(size_t nblocks, size_t resident) { return std::max<size_t>(1, std::min(cdiv(nblocks, 4), resident)); }
+
+// ---- tsqr_mi_qr_f64_wide (64 < n <= 1024) ----------------------------------------------------------------------------------------------
+constexpr size_t F64W_MAX_N = 1024;
+constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m
+constexpr int F64W_TARGET_WGS = 512;                    // two workgroups per CU
+
+struct F64WPlan {
+	int nb, npairs, ngroups, nslices;
+	size_t cps, nch;                                     // 16-row chunks per slice, chunks
+	size_t bs;                                           // doubles of one block store (npairs blocks)
+	size_t o_gs, o_w, o_rw, o_zw, o_ta, o_rc, o_zd, o_sb, o_bst, o_status, wq;
+};
+F64WPlan f64w_plan(size_t m, size_t n) {
+	F64WPlan g{};
+	g.nb = (int)cdiv(n, PW);
+	g.npairs = g.nb * (g.nb + 1) / 2;
+	g.ngroups = (int)cdiv((size_t)g.npairs, 4);
+	g.nch = cdiv(m, 16);
+	const size_t cap = F64W_WR_CAP / ((size_t)g.npairs * 4096);
+	const size_t want = std::max<size_t>(1, std::min({cdiv((size_t)F64W_TARGET_WGS, (size_t)g.ngroups), cap, g.nch}));
+	g.cps = cdiv(g.nch, want);
+	g.nslices = (int)cdiv(g.nch, g.cps);                 // (<= want)
+	g.bs = (size_t)g.npairs * 4096;
+	g.o_gs = 0;
+	g.o_w = g.o_gs + g.bs + 64;                          // (the reduction writes the row count behind the summed blocks)
+	g.o_rw = g.o_w + g.bs;
+	g.o_zw = g.o_rw + g.bs;
+	g.o_ta = g.o_zw + g.bs;
+	g.o_rc = g.o_ta + g.bs;
+	g.o_zd = g.o_rc + g.bs;
+	g.o_sb = g.o_zd + (size_t)g.nb * 4096;
+	g.o_bst = g.o_sb + (size_t)g.nb * (g.nb + 1);
+	g.o_status = g.o_bst + (size_t)g.nb * 2;
+	g.wq = g.o_status + 8;
+	return g;
+}
+
+// the blocked Cholesky step of one sweep, plain (shift_coef = 0, run_if = nullptr) or shifted
+int f64w_chain(hipStream_t st, tsqrmi::WideF64 wa) {
+	const int nb = wa.nb;
+	for (int k = 0; k < nb; k++) {
+		hipLaunchKernelGGL(tsqrmi::cholw_diag_kernel, dim3(1), dim3(1024), 0, st, wa, k);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(tsqrmi::cholw_row_kernel, dim3(nb), dim3(1024), 0, st, wa, k);
+		HIPCHK(hipGetLastError());
+		const int nt = nb - k - 1;
+		if (nt > 0) {
+			hipLaunchKernelGGL(tsqrmi::cholw_update_kernel, dim3(nt * (nt + 1) / 2 + (k + 1) * nt), dim3(1024), 0, st, wa, k);
+			HIPCHK(hipGetLastError());
+		}
+	}
+	hipLaunchKernelGGL(tsqrmi::cholw_verdict_kernel, dim3(1), dim3(64), 0, st, wa);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+}  // namespace

@@ -5,6 +5,14 @@
 #include <vector>
 #include "tsqr_kernels.hip"
 #include "tsqr_wide.hip"
+#include "tsqr_f64.hip"
+#include "tsqr_f64_wide.hip"
+#include "f64_plan.h"
+
+namespace {
+inline int fail(hipError_t e, const char*) { return -(int)e; }     // (HIPCHK of f64_plan.h: the entries return minus the HIP error)
+}  // namespace
+#include "selftest_f64.hip"
 
 namespace {
 using namespace tsqrmi;

@@ -1,0 +1,178 @@
+// selftest_f64.hip -- one entry per pass of the fp64 entries (tsqr_mi_qr_f64: tsqr_f64.hip; tsqr_mi_qr_f64_wide: tsqr_f64_wide.hip), for
+// tests/test_gpu_f64_passes.py.  Included by selftest.hip.  Every entry launches the product's kernels with the product's plan
+// (f64_plan.h: the definitions libtsqr_mi.so is built from), the way f64_factor / f64_sweep / f64w_sweep of tsqr_mi.hip do, waits, and
+// returns 0, minus a HIP error, or -100 when an operand of the caller is too small for the plan.  The Gram and apply entries take an
+// override of the partition (0: the product's), so that a matrix of a few hundred rows reaches every edge of it.
+
+namespace {
+inline int f64_sync() {
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipDeviceSynchronize());
+	return 0;
+}
+}  // namespace
+
+// apply_f64_kernel<NT>: q = a z (z: NP x NP).  wgs > 0 overrides the grid; 0: the resident workgroups, as f64_apply takes them
+namespace {
+template <int NT> int selftest_f64_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* z, int wgs_over) {
+	const size_t nblocks = cdiv(m, 32);
+	size_t wgs = (size_t)wgs_over;
+	if (wgs_over <= 0) {
+		int dev = 0;
+		(void)hipGetDevice(&dev);
+		wgs = f64_apply_wgs(nblocks, (size_t)f64_apply_resident<NT>(dev));
+	}
+	hipLaunchKernelGGL(tsqrmi::apply_f64_kernel<NT>, dim3((unsigned)wgs), dim3(256), 0, 0, q, ldq, a, lda, m, n, z, nblocks);
+	return f64_sync();
+}
+}  // namespace
+
+extern "C" {
+
+// out[0..7]: NT, ntri, nch, nwaves, nblocks, doubles of wq, doubles of wr (the partials), F64_GRAM_WAVES.  Host only.
+int tsqr_selftest_f64_plan(size_t m, size_t n, long long* out) {
+	if (m == 0 || n == 0 || n > PW) return -100;
+	const F64Plan g = f64_plan(m, n);
+	out[0] = g.NT; out[1] = g.ntri; out[2] = g.nch; out[3] = g.nwaves; out[4] = g.nblocks;
+	out[5] = (long long)F64_WQ; out[6] = (long long)g.nblocks * g.ntri * 256; out[7] = F64_GRAM_WAVES;
+	return 0;
+}
+
+// the acceptance rule of an m x n sweep as the launches take it (f64_rule): out[0] max_scond, [1] alone_max, [2] shift_coef.  Host only.
+int tsqr_selftest_f64_rule(size_t m, size_t n, int first, double* out) {
+	if (m == 0 || n == 0 || n > F64W_MAX_N) return -100;
+	const F64Rule r = f64_rule(m, n, first != 0);
+	out[0] = (double)r.max_scond; out[1] = (double)r.alone_max; out[2] = r.shift_coef;
+	return 0;
+}
+
+// out[0..19]: nb, npairs, ngroups, nslices, cps, nch, bs, o_gs, o_w, o_rw, o_zw, o_ta, o_rc, o_zd, o_sb, o_bst, o_status, wq,
+// doubles of wr (the partials), F64W_WR_CAP.  Host only.
+int tsqr_selftest_f64w_plan(size_t m, size_t n, long long* out) {
+	if (m == 0 || n <= PW || n > F64W_MAX_N) return -100;
+	const F64WPlan g = f64w_plan(m, n);
+	const long long v[20] = {g.nb, g.npairs, g.ngroups, g.nslices, (long long)g.cps, (long long)g.nch, (long long)g.bs, (long long)g.o_gs,
+	                         (long long)g.o_w, (long long)g.o_rw, (long long)g.o_zw, (long long)g.o_ta, (long long)g.o_rc, (long long)g.o_zd,
+	                         (long long)g.o_sb, (long long)g.o_bst, (long long)g.o_status, (long long)g.wq,
+	                         (long long)((size_t)g.nslices * g.bs), (long long)F64W_WR_CAP};
+	for (int i = 0; i < 20; i++) out[i] = v[i];
+	return 0;
+}
+
+// ---- n <= 64 --------------------------------------------------------------------------------------------------------------------------
+// Gram pass + reduction: gsum[ntri * 256 + 1] (the row count behind the tiles).  nwaves > 0 overrides the plan's wave count;
+// part holds part_cap doubles.
+int tsqr_selftest_f64_gram(double* gsum, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, int nwaves) {
+	if (m == 0 || n <= 0 || n > (int)PW || lda < m) return -100;
+	F64Plan g = f64_plan(m, (size_t)n);
+	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
+	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
+	const tsqrmi::GramArgs64 ga{a, lda, m, n, g.nch, g.nwaves, part};
+	f64_gram_launch(0, g, ga);
+	HIPCHK(hipGetLastError());
+	const int nelem = g.ntri * 256;
+	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, 0, gsum, part, g.nblocks, nelem, (double)m,
+	                   nullptr, (size_t)0, nullptr, 0);
+	return f64_sync();
+}
+
+// chol_f64_kernel with the thresholds and the shift of an m x n first sweep (first = 1) or of a later one (0): r (n x n, ldr),
+// z (NP x NP), status[4], host_words[4] (device memory standing in for the pinned words)
+int tsqr_selftest_f64_chol(double* r, size_t ldr, double* z, unsigned* status, unsigned* host_words, const double* gsum, size_t m, int n,
+                           int first) {
+	if (m == 0 || n <= 0 || n > (int)PW || ldr < (size_t)n) return -100;
+	tsqrmi::CholArgs64 ca{};
+	ca.r = r; ca.ldr = ldr; ca.z = z; ca.status = status; ca.host_status = host_words; ca.gsum = gsum;
+	const F64Rule rule = f64_rule(m, (size_t)n, first != 0);
+	ca.shift_coef = rule.shift_coef; ca.max_scond = rule.max_scond; ca.alone_max = rule.alone_max;
+	ca.n = n; ca.NT = (int)(np_of((size_t)n) / 16);
+	hipLaunchKernelGGL(tsqrmi::chol_f64_kernel, dim3(1), dim3(1024), 0, 0, ca);
+	return f64_sync();
+}
+
+int tsqr_selftest_f64_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* z, int wgs) {
+	if (m == 0 || n <= 0 || n > (int)PW || lda < m || ldq < m || wgs > 65535) return -100;
+	switch (np_of((size_t)n) / 16) {
+		case 1: return selftest_f64_apply<1>(q, ldq, a, lda, m, n, z, wgs);
+		case 2: return selftest_f64_apply<2>(q, ldq, a, lda, m, n, z, wgs);
+		case 3: return selftest_f64_apply<3>(q, ldq, a, lda, m, n, z, wgs);
+		default: return selftest_f64_apply<4>(q, ldq, a, lda, m, n, z, wgs);
+	}
+}
+
+// rmul_f64_kernel: r <- r2 r (r2 packed with ld 64), in place
+int tsqr_selftest_f64_rmul(double* r, size_t ldr, const double* r2, int n) {
+	if (n <= 0 || n > (int)PW || ldr < (size_t)n) return -100;
+	hipLaunchKernelGGL(tsqrmi::rmul_f64_kernel, dim3(1), dim3(1024), 0, 0, r, ldr, r2, n);
+	return f64_sync();
+}
+
+// ---- 64 < n <= 1024 ---------------------------------------------------------------------------------------------------------------------
+// Gram pass + reduction: gs[bs + 1] in the block store's layout.  cps > 0 overrides the chunks per slice; part holds part_cap doubles.
+int tsqr_selftest_f64w_gram(double* gs, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, size_t cps) {
+	if (m == 0 || n <= (int)PW || n > (int)F64W_MAX_N || lda < m) return -100;
+	F64WPlan g = f64w_plan(m, (size_t)n);
+	if (cps > 0) { g.cps = cps; g.nslices = (int)cdiv(g.nch, g.cps); }
+	if (g.nslices <= 0 || g.npairs <= 0 || (size_t)g.nslices * g.bs > part_cap) return -100;
+	const tsqrmi::GramWideF64Args ga{a, lda, m, n, g.npairs, g.ngroups, g.cps, g.nch, part};
+	hipLaunchKernelGGL(tsqrmi::gram_wide_f64_kernel, dim3((unsigned)(g.ngroups * g.nslices)), dim3(256), 0, 0, ga);
+	HIPCHK(hipGetLastError());
+	const int nelem = (int)g.bs;
+	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, 0, gs, part, g.nslices, nelem, (double)m,
+	                   nullptr, (size_t)0, nullptr, 0);
+	return f64_sync();
+}
+
+// The blocked Cholesky step on the work space wq (f64w_plan(m, n).wq doubles, the summed blocks at o_gs), status slot 0, with the
+// thresholds and the shift of an m x n first sweep.  mode 0: the plain chain; 1: the shifted chain alone (it looks at the verdict word
+// the caller left in the status slot); 2: plain, then shifted, as f64w_sweep enqueues them.
+int tsqr_selftest_f64w_chain(double* wq, size_t m, int n, int mode, unsigned* host_words) {
+	if (m == 0 || n <= (int)PW || n > (int)F64W_MAX_N || mode < 0 || mode > 2) return -100;
+	const F64WPlan g = f64w_plan(m, (size_t)n);
+	tsqrmi::WideF64 wa{};
+	wa.gs = wq + g.o_gs; wa.w = wq + g.o_w; wa.rw = wq + g.o_rw; wa.zw = wq + g.o_zw; wa.ta = wq + g.o_ta; wa.zd = wq + g.o_zd;
+	wa.sb = wq + g.o_sb;
+	wa.bst = reinterpret_cast<unsigned*>(wq + g.o_bst);
+	wa.status = reinterpret_cast<unsigned*>(wq + g.o_status);
+	wa.host_status = host_words;
+	const F64Rule rule = f64_rule(m, (size_t)n, true);
+	wa.max_scond = rule.max_scond; wa.alone_max = rule.alone_max;
+	wa.n = n; wa.nb = g.nb;
+	wa.run_if = nullptr; wa.shift_coef = 0.0;
+	if (mode != 1) {
+		const int rc = f64w_chain(0, wa);
+		if (rc) return rc;
+	}
+	if (mode != 0) {
+		wa.run_if = wa.status; wa.shift_coef = rule.shift_coef;
+		const int rc = f64w_chain(0, wa);
+		if (rc) return rc;
+	}
+	return f64_sync();
+}
+
+// apply_wide_f64_kernel: q = a Z, Z in the block store zw
+int tsqr_selftest_f64w_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* zw) {
+	if (m == 0 || n <= (int)PW || n > (int)F64W_MAX_N || lda < m || ldq < m) return -100;
+	hipLaunchKernelGGL(tsqrmi::apply_wide_f64_kernel, dim3((unsigned)cdiv(m, 128)), dim3(256), 0, 0, q, ldq, a, lda, m, n, (int)cdiv((size_t)n, PW), zw);
+	return f64_sync();
+}
+
+// rcopy_wide_f64_kernel: r (n x n, ldr) = R of the block store rw
+int tsqr_selftest_f64w_rcopy(double* r, size_t ldr, const double* rw, int n) {
+	if (n <= (int)PW || n > (int)F64W_MAX_N || ldr < (size_t)n) return -100;
+	hipLaunchKernelGGL(tsqrmi::rcopy_wide_f64_kernel, dim3((unsigned)cdiv((size_t)n * n, 256)), dim3(256), 0, 0, r, ldr, rw, n);
+	return f64_sync();
+}
+
+// rsave_wide_f64_kernel + rmul_wide_f64_kernel: r <- RW r through the block store rc (both bs doubles)
+int tsqr_selftest_f64w_rmul(double* r, size_t ldr, const double* rw, double* rc, int n) {
+	if (n <= (int)PW || n > (int)F64W_MAX_N || ldr < (size_t)n) return -100;
+	const F64WPlan g = f64w_plan((size_t)n, (size_t)n);
+	hipLaunchKernelGGL(tsqrmi::rsave_wide_f64_kernel, dim3((unsigned)cdiv(g.bs, 256)), dim3(256), 0, 0, rc, (const double*)r, ldr, n, g.npairs);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(tsqrmi::rmul_wide_f64_kernel, dim3((unsigned)g.npairs), dim3(1024), 0, 0, r, ldr, rw, (const double*)rc, n);
+	return f64_sync();
+}
+
+}  // extern "C"

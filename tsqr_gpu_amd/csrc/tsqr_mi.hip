@@ -35,6 +35,7 @@
 #include "tsqr_wide.hip"
 #include "tsqr_f64.hip"
 #include "tsqr_f64_wide.hip"
+#include "f64_plan.h"
 #include "validate.hip"
 
 namespace {
@@ -102,17 +103,14 @@ void prof_collect() {              // after the stream is idle
 	t_prof.n = 0;
 }
 
-constexpr size_t PW = 64;          // panel width
 constexpr int MAX_DEV = 64;
 
+// (PW, cdiv, np_of, GSUM_DOUBLES and HIPCHK: f64_plan.h, shared with the test library)
 inline int fail(hipError_t e, const char* what) {
 	t_last_error = std::string(what) + ": " + hipGetErrorString(e);
 	return -(int)e;
 }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(e_, #expr); } while (0)
 
-inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
-inline size_t np_of(size_t n) { return 16 * cdiv(std::min(n, PW), 16); }
 inline int cur_device() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < MAX_DEV) ? d : 0; }
 
 // per-kernel, per-device launch attributes: hipFuncSetAttribute once per (kernel instance, device); lock-free (the call is idempotent)
@@ -202,7 +200,7 @@ constexpr int WIDE_MAX_WGS = 255;                       // gram_wide_kernel: one
 inline size_t wide_part_floats(size_t m) { return (std::min<size_t>((m + 63) / 64, WIDE_MAX_WGS) + 1) * 36 * 256 * 2; }
 
 // layout of wq (floats): [stack_b][Z: 4096][S: 4096][R1 copy: n*n][R2: n*n][r3, r4, r5, r6: 4096 each][summed tiles + row count][status]
-constexpr size_t GSUM_DOUBLES = 16 * 256 + 8;          // 16 tiles (coupling) or 10 (Gram) + the row-count word of a row-partitioned run
+// (the summed tiles + row count take GSUM_DOUBLES: f64_plan.h)
 struct WqLayout { size_t z, s, r1, r2, r3, r4, r5, r6, gsum, status, wide, smulti, gmulti, total; };
 WqLayout wq_layout(size_t m, size_t n) {
 	const Plan p = make_plan(m, n);
@@ -2551,22 +2549,8 @@ int tsqr_mi_rmul_f32(float* r, size_t ldr, const float* r2, size_t ldr2, size_t 
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int F64_GRAM_WAVES = 2048;                    // fixed (not tsqr_mi_set_tuning2): the work-space size must not follow a setting
 constexpr int F64_MAX_SWEEPS = 6;
-// wq (doubles): [Z: 4096][R of the sweep: 4096][summed tiles + row count][status words: 4 slots x 4 words]
-constexpr size_t F64_Z = 0, F64_R2 = 4096, F64_GSUM = 8192, F64_STATUS = F64_GSUM + GSUM_DOUBLES, F64_WQ = F64_STATUS + 8;
-
-struct F64Plan { int NT, ntri, nch, nwaves, nblocks; };
-F64Plan f64_plan(size_t m, size_t n) {
-	F64Plan g{};
-	g.NT = (int)(np_of(n) / 16);
-	g.ntri = g.NT * (g.NT + 1) / 2;
-	g.nch = (int)cdiv(m, 64);
-	const size_t cpw = std::max<size_t>(1, cdiv((size_t)g.nch, F64_GRAM_WAVES));
-	g.nwaves = (int)cdiv((size_t)g.nch, cpw);
-	g.nblocks = (g.nwaves + 3) / 4;
-	return g;
-}
+// (F64_GRAM_WAVES, the wq offsets F64_Z .. F64_WQ, F64Plan and f64_plan: f64_plan.h)
 
 thread_local int t_sweeps64 = 0;
 thread_local OwnPinned t_own64;                         // the verdict words of the fp64 entry (slot k & 3 for sweep k)
@@ -2577,12 +2561,7 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
 	const F64Plan g = f64_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
 	const tsqrmi::GramArgs64 ga{src, ld, m, (int)n, g.nch, g.nwaves, wr};
-	switch (g.NT) {
-		case 1: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<1>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-		case 2: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<2>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-		case 3: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<3>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-		default: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<4>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-	}
+	f64_gram_launch(st, g, ga);
 	HIPCHK(hipGetLastError());
 	const int nelem = g.ntri * 256;
 	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, st, wq + F64_GSUM, wr, g.nblocks, nelem, (double)m,
@@ -2593,10 +2572,8 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
 	ca.status = reinterpret_cast<unsigned*>(wq + F64_STATUS) + 4 * slot;
 	ca.host_status = t_own64.dev + 4 * slot;
 	ca.gsum = wq + F64_GSUM;
-	const double u = 0x1p-53, mn = (double)m * (double)n + (double)n * (double)(n + 1);
-	ca.shift_coef = 11.0 * u * mn;                       // CholArgs64 states the rule and its sources
-	ca.max_scond = first ? (float)(1.0 / (64.0 * (double)n * u * mn)) : INFINITY;
-	ca.alone_max = first ? (float)(1e-12 / (4.0 * (double)n * u)) : 0.0f;
+	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64 states the rule and its sources)
+	ca.shift_coef = rule.shift_coef; ca.max_scond = rule.max_scond; ca.alone_max = rule.alone_max;
 	ca.n = (int)n; ca.NT = g.NT;
 	hipLaunchKernelGGL(tsqrmi::chol_f64_kernel, dim3(1), dim3(1024), 0, st, ca);
 	HIPCHK(hipGetLastError());
@@ -2608,16 +2585,11 @@ template <int NT> int f64_apply(hipStream_t st, int dev, double* q, size_t ldq, 
 	static DevOnce once;
 	static std::atomic<int> resident[MAX_DEV];
 	if (once.need(dev)) {
-		int nb = 0, cus = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tsqrmi::apply_f64_kernel<NT>), 256, 0) != hipSuccess || nb < 1) {
-			(void)hipGetLastError(); nb = 1;
-		}
-		if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
-		resident[dev].store(nb * cus);
+		resident[dev].store(f64_apply_resident<NT>(dev));
 		once.done(dev);
 	}
 	const size_t nblocks = cdiv(m, 32);
-	const size_t wgs = std::max<size_t>(1, std::min(cdiv(nblocks, 4), (size_t)resident[dev].load()));
+	const size_t wgs = f64_apply_wgs(nblocks, (size_t)resident[dev].load());
 	hipLaunchKernelGGL(tsqrmi::apply_f64_kernel<NT>, dim3((unsigned)wgs), dim3(256), 0, st, q, ldq, a, lda, m, (int)n, z, nblocks);
 	HIPCHK(hipGetLastError());
 	return 0;
@@ -2718,59 +2690,7 @@ int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, dou
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr size_t F64W_MAX_N = 1024;
-constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m
-constexpr int F64W_TARGET_WGS = 512;                    // two workgroups per CU
-
-struct F64WPlan {
-	int nb, npairs, ngroups, nslices;
-	size_t cps, nch;                                     // 16-row chunks per slice, chunks
-	size_t bs;                                           // doubles of one block store (npairs blocks)
-	size_t o_gs, o_w, o_rw, o_zw, o_ta, o_rc, o_zd, o_sb, o_bst, o_status, wq;
-};
-F64WPlan f64w_plan(size_t m, size_t n) {
-	F64WPlan g{};
-	g.nb = (int)cdiv(n, PW);
-	g.npairs = g.nb * (g.nb + 1) / 2;
-	g.ngroups = (int)cdiv((size_t)g.npairs, 4);
-	g.nch = cdiv(m, 16);
-	const size_t cap = F64W_WR_CAP / ((size_t)g.npairs * 4096);
-	const size_t want = std::max<size_t>(1, std::min({cdiv((size_t)F64W_TARGET_WGS, (size_t)g.ngroups), cap, g.nch}));
-	g.cps = cdiv(g.nch, want);
-	g.nslices = (int)cdiv(g.nch, g.cps);                 // (<= want)
-	g.bs = (size_t)g.npairs * 4096;
-	g.o_gs = 0;
-	g.o_w = g.o_gs + g.bs + 64;                          // (the reduction writes the row count behind the summed blocks)
-	g.o_rw = g.o_w + g.bs;
-	g.o_zw = g.o_rw + g.bs;
-	g.o_ta = g.o_zw + g.bs;
-	g.o_rc = g.o_ta + g.bs;
-	g.o_zd = g.o_rc + g.bs;
-	g.o_sb = g.o_zd + (size_t)g.nb * 4096;
-	g.o_bst = g.o_sb + (size_t)g.nb * (g.nb + 1);
-	g.o_status = g.o_bst + (size_t)g.nb * 2;
-	g.wq = g.o_status + 8;
-	return g;
-}
-
-// the blocked Cholesky step of one sweep, plain (shift_coef = 0, run_if = nullptr) or shifted
-int f64w_chain(hipStream_t st, tsqrmi::WideF64 wa) {
-	const int nb = wa.nb;
-	for (int k = 0; k < nb; k++) {
-		hipLaunchKernelGGL(tsqrmi::cholw_diag_kernel, dim3(1), dim3(1024), 0, st, wa, k);
-		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL(tsqrmi::cholw_row_kernel, dim3(nb), dim3(1024), 0, st, wa, k);
-		HIPCHK(hipGetLastError());
-		const int nt = nb - k - 1;
-		if (nt > 0) {
-			hipLaunchKernelGGL(tsqrmi::cholw_update_kernel, dim3(nt * (nt + 1) / 2 + (k + 1) * nt), dim3(1024), 0, st, wa, k);
-			HIPCHK(hipGetLastError());
-		}
-	}
-	hipLaunchKernelGGL(tsqrmi::cholw_verdict_kernel, dim3(1), dim3(64), 0, st, wa);
-	HIPCHK(hipGetLastError());
-	return 0;
-}
+// (F64W_MAX_N, F64W_WR_CAP, F64W_TARGET_WGS, F64WPlan, f64w_plan and the blocked Cholesky step f64w_chain: f64_plan.h)
 
 // sweep k (0-based) of the wide entry: sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R
 int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
@@ -2794,14 +2714,13 @@ int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double
 	const int slot = k & 3;
 	wa.status = reinterpret_cast<unsigned*>(wq + g.o_status) + 4 * slot;
 	wa.host_status = t_own64.dev + 4 * slot;
-	const double u = 0x1p-53, mn = (double)m * (double)n + (double)n * (double)(n + 1);
-	wa.max_scond = first ? (float)(1.0 / (64.0 * (double)n * u * mn)) : INFINITY;     // CholArgs64 (tsqr_f64.hip) states the rule
-	wa.alone_max = first ? (float)(1e-12 / (4.0 * (double)n * u)) : 0.0f;
+	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64, tsqr_f64.hip, states the rule)
+	wa.max_scond = rule.max_scond; wa.alone_max = rule.alone_max;
 	wa.n = (int)n; wa.nb = g.nb;
 	wa.run_if = nullptr; wa.shift_coef = 0.0;
 	int rc = f64w_chain(st, wa);
 	if (rc) return rc;
-	wa.run_if = wa.status; wa.shift_coef = 11.0 * u * mn;
+	wa.run_if = wa.status; wa.shift_coef = rule.shift_coef;
 	rc = f64w_chain(st, wa);
 	if (rc) return rc;
 	hipLaunchKernelGGL(tsqrmi::apply_wide_f64_kernel, dim3((unsigned)cdiv(m, 128)), dim3(256), 0, st, q, ldq, src, lds, m, (int)n, g.nb,
