@@ -219,6 +219,22 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _call_args(q, ldq, r, ldr, a, lda, m, n, bf, stream, mode, reorthogonalize, fp32_only=None):
+    """What qr, submit, bind and bind_loop share: mode and reorth (the buffer's unless given), the stream (the current one unless given)
+    and the sixteen arguments of tsqr_mi_qr_f32, marshalled once.  fp32_only: the TypeError text for an fp16 I/O mode."""
+    import torch
+    mode = bf.mode if mode is None else compute_mode(mode)
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    if fp32_only and mode in FP16_MODES:
+        raise TypeError(fp32_only)
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    args = (ci(int(mode)), ci(int(reorth)), vp(_ptr(q)), sz(ldq), vp(_ptr(r)), sz(ldr), vp(_ptr(a)), sz(lda), sz(m), sz(n),
+            vp(_ptr(bf.dwq)), vp(_ptr(bf.dwr)), vp(_ptr(bf.dw_reorth_r)), vp(_ptr(bf.dl)), vp(_ptr(bf.hl)), vp(stream.cuda_stream))
+    return mode, stream, args
+
+
 class buffer:
     """mtk::qr::buffer<mode, Reorthogonalize>, reference src/blockqr.hpp:59-140.
 
@@ -267,10 +283,7 @@ def qr(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, mode=None, reorthogonalize
     Runtime failures raise RuntimeError (the reference throws std::runtime_error from CUTF_CHECK_ERROR).
     """
     import torch
-    mode = bf.mode if mode is None else compute_mode(mode)
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    if stream is None:
-        stream = torch.cuda.current_stream()
+    mode, stream, args = _call_args(q, ldq, r, ldr, a, lda, m, n, bf, stream, mode, reorthogonalize)
     if mode in FP16_MODES:
         for t in (q, r, a):
             if t is not None and t.dtype != torch.float16:
@@ -280,8 +293,7 @@ def qr(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, mode=None, reorthogonalize
         fn, name = lib().tsqr_mi_qr_f16, "tsqr_mi_qr_f16"
     else:
         fn, name = lib().tsqr_mi_qr_f32, "tsqr_mi_qr_f32"
-    st = fn(int(mode), int(reorth), _ptr(q), ldq, _ptr(r), ldr, _ptr(a), lda, m, n,
-            _ptr(bf.dwq), _ptr(bf.dwr), _ptr(bf.dw_reorth_r), _ptr(bf.dl), _ptr(bf.hl), stream.cuda_stream)
+    st = fn(*args)
     if st < 0:
         raise RuntimeError("%s failed: %s" % (name, last_error()))
     return st
@@ -291,19 +303,12 @@ def submit(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, mode=None, reorthogona
     """Stream-asynchronous qr() (tsqr_mi_qr_f32_submit): enqueues the call's first attempt and returns a ticket; finish(ticket) waits,
     completes the ladder for a rejected matrix and returns state_t.  Up to two calls of a thread are in flight; tickets are finished in
     submission order by the submitting thread.  fp32 I/O modes."""
-    import torch
-    mode = bf.mode if mode is None else compute_mode(mode)
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    if mode in FP16_MODES:
-        raise TypeError("submit() takes the fp32 I/O modes")
-    if stream is None:
-        stream = torch.cuda.current_stream()
     import threading
+    mode, stream, args = _call_args(q, ldq, r, ldr, a, lda, m, n, bf, stream, mode, reorthogonalize, fp32_only="submit() takes the fp32 I/O modes")
     t = Ticket()
     t._keep = (q, r, a, bf, stream)
     t._tid = threading.get_ident()
-    st = lib().tsqr_mi_qr_f32_submit(int(mode), int(reorth), _ptr(q), ldq, _ptr(r), ldr, _ptr(a), lda, m, n,
-                                     _ptr(bf.dwq), _ptr(bf.dwr), _ptr(bf.dw_reorth_r), _ptr(bf.dl), _ptr(bf.hl), stream.cuda_stream, ctypes.byref(t))
+    st = lib().tsqr_mi_qr_f32_submit(*args, ctypes.byref(t))
     if st < 0:
         raise RuntimeError("tsqr_mi_qr_f32_submit failed: %s" % last_error())
     return t
@@ -326,15 +331,8 @@ def bind(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, mode=None, reorthogonali
     """qr() with every argument marshalled once: returns a zero-argument callable that issues exactly one C-ABI call
     (tsqr_mi_qr_f32) per invocation -- what a C++ caller's loop looks like, without per-call Python/ctypes conversions.
     The tensors, the buffer and the stream must stay alive and unchanged while the callable is in use."""
-    import torch
-    mode = bf.mode if mode is None else compute_mode(mode)
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    if stream is None:
-        stream = torch.cuda.current_stream()
-    vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    mode, stream, args = _call_args(q, ldq, r, ldr, a, lda, m, n, bf, stream, mode, reorthogonalize)
     fn = lib().tsqr_mi_qr_f32
-    args = (ci(int(mode)), ci(int(reorth)), vp(_ptr(q)), sz(ldq), vp(_ptr(r)), sz(ldr), vp(_ptr(a)), sz(lda), sz(m), sz(n),
-            vp(_ptr(bf.dwq)), vp(_ptr(bf.dwr)), vp(_ptr(bf.dw_reorth_r)), vp(_ptr(bf.dl)), vp(_ptr(bf.hl)), vp(stream.cuda_stream))
     keep = (q, r, a, bf, stream)
 
     def call():
@@ -350,19 +348,12 @@ def bind_loop(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, mode=None, reorthog
     """Like bind(), but the callable takes a count k and issues k calls from ONE C loop (tsqr_mi_qr_f32_loop): the reference's speed
     protocol (src/test.cu:299-309) without interpreter time between the calls.  The fp32 loop keeps two calls in flight (submit /
     finish) unless set_loop_depth(1)."""
-    import torch
-    mode = bf.mode if mode is None else compute_mode(mode)
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    if stream is None:
-        stream = torch.cuda.current_stream()
-    vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    mode, stream, args = _call_args(q, ldq, r, ldr, a, lda, m, n, bf, stream, mode, reorthogonalize)
     fn = lib().tsqr_mi_qr_f16_loop if mode in FP16_MODES else lib().tsqr_mi_qr_f32_loop      # (float16 tensors for the fp16 I/O modes)
-    args = (ci(int(mode)), ci(int(reorth)), vp(_ptr(q)), sz(ldq), vp(_ptr(r)), sz(ldr), vp(_ptr(a)), sz(lda), sz(m), sz(n),
-            vp(_ptr(bf.dwq)), vp(_ptr(bf.dwr)), vp(_ptr(bf.dw_reorth_r)), vp(_ptr(bf.dl)), vp(_ptr(bf.hl)), vp(stream.cuda_stream))
     keep = (q, r, a, bf, stream)
 
     def call(k=1):
-        st = fn(ci(int(k)), *args)
+        st = fn(ctypes.c_int(int(k)), *args)
         if st < 0:
             raise RuntimeError("tsqr_mi_qr_f32 failed: %s" % last_error())
         return st
@@ -431,9 +422,15 @@ def qr_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream=None, mode=None, reort
     return bind_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream, mode, reorthogonalize)()
 
 
+# the two fp64 entries: (Python name, widest n, C entry, its work-space size functions)
+_F64 = ("qr_f64", 64, "tsqr_mi_qr_f64", "tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64")
+_F64_WIDE = ("qr_f64_wide", 1024, "tsqr_mi_qr_f64_wide", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide")
+
+
 class buffer_f64:
     """Work space of qr_f64 (tsqr_mi_working_{q,r}_size_f64 doubles on the GPU).  reorthogonalize: the reorth argument qr_f64 passes
     unless told otherwise (False: one CholeskyQR sweep when the device's estimate allows it, True: CholeskyQR2 at least)."""
+    _entry = _F64
 
     def __init__(self, reorthogonalize=False, device="cuda"):
         self.reorthogonalize = bool(reorthogonalize)
@@ -444,9 +441,8 @@ class buffer_f64:
         import torch
         if self.dwq is not None or self.dwr is not None:
             raise RuntimeError("The buffer has been already allocated")
-        L = lib()
-        self.dwq = torch.empty(max(L.tsqr_mi_working_q_size_f64(m, n), 1), dtype=torch.float64, device=self.device)
-        self.dwr = torch.empty(max(L.tsqr_mi_working_r_size_f64(m, n), 1), dtype=torch.float64, device=self.device)
+        self.dwq, self.dwr = (torch.empty(max(getattr(lib(), size_fn)(m, n), 1), dtype=torch.float64, device=self.device)
+                              for size_fn in self._entry[3:])
 
     def free(self):
         self.dwq = self.dwr = None
@@ -475,80 +471,55 @@ def check_f64_operands(m, n, ldq, ldr, lda, q, r, a):
             raise ValueError("qr_f64: r overlaps %s" % other)
 
 
+def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize):
+    """The body of qr_f64 (entry _F64) and qr_f64_wide (_F64_WIDE)."""
+    import torch
+    name, nmax, qr_fn, wq_fn, wr_fn = entry
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    for opname, t in (("q", q), ("r", r), ("a", a)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError("%s: %s must be a float64 tensor, got %s" % (name, opname, getattr(t, "dtype", type(t).__name__)))
+    for opname, t in (("q", q), ("r", r), ("a", a)):
+        if not t.is_cuda:
+            raise TypeError("%s: %s is not a GPU tensor" % (name, opname))
+    if n > m or m == 0 or n == 0:
+        return error_invalid_matrix_size
+    if n > nmax:
+        return getattr(lib(), qr_fn)(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
+    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
+    if bf.dwq is None:
+        raise RuntimeError("%s: the buffer is not allocated" % name)
+    L = lib()
+    if bf.dwq.numel() < getattr(L, wq_fn)(m, n) or bf.dwr.numel() < getattr(L, wr_fn)(m, n):
+        raise ValueError("%s: the buffer was allocated for a smaller matrix" % name)
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    st = getattr(L, qr_fn)(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
+                           bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("%s failed: %s" % (qr_fn, last_error()))
+    return st
+
+
 def qr_f64(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
     """Double-precision tall-skinny QR (tsqr_mi_qr_f64), 1 <= n <= 64, n <= m: q, r, a are float64 GPU tensors holding column-major
     data (only data_ptr and numel are used); q may be a itself (in place, ldq == lda).  Blocking; returns the state: 0,
     error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite.  Operands are checked before anything is launched:
     TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a leading dimension below the rows, or overlapping
     operands.  last_sweeps_f64() tells how many sweeps the call took."""
-    import torch
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    for name, t in (("q", q), ("r", r), ("a", a)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise TypeError("qr_f64: %s must be a float64 tensor, got %s" % (name, getattr(t, "dtype", type(t).__name__)))
-    for name, t in (("q", q), ("r", r), ("a", a)):
-        if not t.is_cuda:
-            raise TypeError("qr_f64: %s is not a GPU tensor" % name)
-    if n > m or m == 0 or n == 0:
-        return error_invalid_matrix_size
-    if n > 64:
-        return lib().tsqr_mi_qr_f64(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
-    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
-    if bf.dwq is None:
-        raise RuntimeError("qr_f64: the buffer is not allocated")
-    L = lib()
-    if bf.dwq.numel() < L.tsqr_mi_working_q_size_f64(m, n) or bf.dwr.numel() < L.tsqr_mi_working_r_size_f64(m, n):
-        raise ValueError("qr_f64: the buffer was allocated for a smaller matrix")
-    if stream is None:
-        stream = torch.cuda.current_stream()
-    st = L.tsqr_mi_qr_f64(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
-                          bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
-    if st < 0:
-        raise RuntimeError("tsqr_mi_qr_f64 failed: %s" % last_error())
-    return st
+    return _qr_f64(_F64, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize)
 
 
 class buffer_f64_wide(buffer_f64):
     """Work space of qr_f64_wide (tsqr_mi_working_{q,r}_size_f64_wide doubles on the GPU); reorthogonalize as in buffer_f64."""
-
-    def allocate(self, m, n):
-        import torch
-        if self.dwq is not None or self.dwr is not None:
-            raise RuntimeError("The buffer has been already allocated")
-        L = lib()
-        self.dwq = torch.empty(max(L.tsqr_mi_working_q_size_f64_wide(m, n), 1), dtype=torch.float64, device=self.device)
-        self.dwr = torch.empty(max(L.tsqr_mi_working_r_size_f64_wide(m, n), 1), dtype=torch.float64, device=self.device)
+    _entry = _F64_WIDE
 
 
 def qr_f64_wide(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
     """Double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide; qr_f64 itself for n <= 64): the arguments,
     operand rules and states of qr_f64, error_unsupported_mode for n > 1024.  bf is a buffer_f64_wide.  Operands are checked before
     anything is launched (TypeError / ValueError, check_f64_operands).  last_sweeps_f64() tells how many sweeps the call took."""
-    import torch
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    for name, t in (("q", q), ("r", r), ("a", a)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise TypeError("qr_f64_wide: %s must be a float64 tensor, got %s" % (name, getattr(t, "dtype", type(t).__name__)))
-    for name, t in (("q", q), ("r", r), ("a", a)):
-        if not t.is_cuda:
-            raise TypeError("qr_f64_wide: %s is not a GPU tensor" % name)
-    if n > m or m == 0 or n == 0:
-        return error_invalid_matrix_size
-    if n > 1024:
-        return lib().tsqr_mi_qr_f64_wide(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
-    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
-    if bf.dwq is None:
-        raise RuntimeError("qr_f64_wide: the buffer is not allocated")
-    L = lib()
-    if bf.dwq.numel() < L.tsqr_mi_working_q_size_f64_wide(m, n) or bf.dwr.numel() < L.tsqr_mi_working_r_size_f64_wide(m, n):
-        raise ValueError("qr_f64_wide: the buffer was allocated for a smaller matrix")
-    if stream is None:
-        stream = torch.cuda.current_stream()
-    st = L.tsqr_mi_qr_f64_wide(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
-                               bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
-    if st < 0:
-        raise RuntimeError("tsqr_mi_qr_f64_wide failed: %s" % last_error())
-    return st
+    return _qr_f64(_F64_WIDE, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize)
 
 
 def last_sweeps_f64():

@@ -2,19 +2,17 @@
 // the Gram and apply passes, the work-space offsets and the launch sequence of the blocked Cholesky step.  ONE definition, compiled into
 // libtsqr_mi.so (tsqr_mi.hip) and into libtsqr_selftest.so (selftest.hip), so that the per-pass tests run the product's kernels with the
 // product's plan and never a copy of it.  Included after tsqr_kernels.hip, tsqr_wide.hip, tsqr_f64.hip and tsqr_f64_wide.hip.
-// The including file defines fail(): what a function returns, through HIPCHK, when a HIP call did not succeed.
+// HIPCHK and the dispatch on the tile count: launch_util.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include "launch_util.h"
 
 namespace {
 
 constexpr size_t PW = 64;          // panel width
-
-inline int fail(hipError_t e, const char* what);
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(e_, #expr); } while (0)
 
 inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
 inline size_t np_of(size_t n) { return 16 * cdiv(std::min(n, PW), 16); }
@@ -52,12 +50,7 @@ inline F64Rule f64_rule(size_t m, size_t n, bool first) {
 
 // the Gram pass of the n <= 64 entry on stream st: gram_f64_kernel<NT> on the plan's grid
 inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramArgs64& ga) {
-	switch (g.NT) {
-		case 1: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<1>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-		case 2: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<2>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-		case 3: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<3>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-		default: hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<4>, dim3(g.nblocks), dim3(256), 0, st, ga); break;
-	}
+	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
 }
 
 // the apply pass of the n <= 64 entry runs on a persistent grid: the workgroups resident at once on device dev ...

@@ -8,9 +8,10 @@
 #include "tsqr_f64.hip"
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
+#include "launch_util.h"
 
 namespace {
-inline int fail(hipError_t e, const char*) { return -(int)e; }     // (HIPCHK of f64_plan.h: the entries return minus the HIP error)
+inline int fail(hipError_t e, const char*) { return -(int)e; }     // (HIPCHK of launch_util.h: the entries return minus the HIP error)
 }  // namespace
 #include "selftest_f64.hip"
 
@@ -112,7 +113,7 @@ extern "C" int tsqr_selftest_chain(const float* a, size_t lda, size_t m, int npa
 		return c;
 	};
 	hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, 0, ga);
-	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nred), dim3(256), 0, 0, gsum1, partA, nparts, nelem, (double)m, nullptr, (size_t)0, nullptr, 0);
+	launch_reduce1(0, gsum1, partA, nparts, nelem, (double)m);
 	hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, 0, chol(0, gsum1));
 	tsqrmi::ChainArgs ch{};
 	ch.chol = chol(1, gsum2); ch.part = partA; ch.nparts = nparts; ch.ticket = ticket; ch.nred = nred;
@@ -206,7 +207,7 @@ extern "C" int tsqr_selftest_wide_chain(const float* a, size_t lda, size_t m, in
 		return c;
 	};
 	hipLaunchKernelGGL(tsqrmi::gram_wide_kernel<true>, dim3(nwg), dim3(512), tsqrmi::GW_LDS_BYTES, 0, ga);
-	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nelem / 16), dim3(256), 0, 0, gsum, partA, nwg, nelem, (double)m, nullptr, (size_t)0, nullptr, 0);
+	launch_reduce1(0, gsum, partA, nwg, nelem, (double)m);
 	hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, 0, cw(0));
 	ga.part = partB;
 	hipLaunchKernelGGL(tsqrmi::gram_wide_chain_kernel, dim3(1 + nwg), dim3(512), tsqrmi::GWC_LDS_BYTES, 0, ga, cw(1));

@@ -71,8 +71,7 @@ int tsqr_selftest_f64_gram(double* gsum, const double* a, size_t lda, size_t m, 
 	f64_gram_launch(0, g, ga);
 	HIPCHK(hipGetLastError());
 	const int nelem = g.ntri * 256;
-	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, 0, gsum, part, g.nblocks, nelem, (double)m,
-	                   nullptr, (size_t)0, nullptr, 0);
+	launch_reduce1(0, gsum, part, g.nblocks, nelem, (double)m);
 	return f64_sync();
 }
 
@@ -92,12 +91,7 @@ int tsqr_selftest_f64_chol(double* r, size_t ldr, double* z, unsigned* status, u
 
 int tsqr_selftest_f64_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* z, int wgs) {
 	if (m == 0 || n <= 0 || n > (int)PW || lda < m || ldq < m || wgs > 65535) return -100;
-	switch (np_of((size_t)n) / 16) {
-		case 1: return selftest_f64_apply<1>(q, ldq, a, lda, m, n, z, wgs);
-		case 2: return selftest_f64_apply<2>(q, ldq, a, lda, m, n, z, wgs);
-		case 3: return selftest_f64_apply<3>(q, ldq, a, lda, m, n, z, wgs);
-		default: return selftest_f64_apply<4>(q, ldq, a, lda, m, n, z, wgs);
-	}
+	return with_nt((int)(np_of((size_t)n) / 16), [&](auto nt) { return selftest_f64_apply<decltype(nt)::value>(q, ldq, a, lda, m, n, z, wgs); });
 }
 
 // rmul_f64_kernel: r <- r2 r (r2 packed with ld 64), in place
@@ -117,9 +111,7 @@ int tsqr_selftest_f64w_gram(double* gs, const double* a, size_t lda, size_t m, i
 	const tsqrmi::GramWideF64Args ga{a, lda, m, n, g.npairs, g.ngroups, g.cps, g.nch, part};
 	hipLaunchKernelGGL(tsqrmi::gram_wide_f64_kernel, dim3((unsigned)(g.ngroups * g.nslices)), dim3(256), 0, 0, ga);
 	HIPCHK(hipGetLastError());
-	const int nelem = (int)g.bs;
-	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, 0, gs, part, g.nslices, nelem, (double)m,
-	                   nullptr, (size_t)0, nullptr, 0);
+	launch_reduce1(0, gs, part, g.nslices, (int)g.bs, (double)m);
 	return f64_sync();
 }
 

@@ -36,6 +36,7 @@
 #include "tsqr_f64.hip"
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
+#include "launch_util.h"
 #include "validate.hip"
 
 namespace {
@@ -105,7 +106,7 @@ void prof_collect() {              // after the stream is idle
 
 constexpr int MAX_DEV = 64;
 
-// (PW, cdiv, np_of, GSUM_DOUBLES and HIPCHK: f64_plan.h, shared with the test library)
+// (PW, cdiv, np_of and GSUM_DOUBLES: f64_plan.h; HIPCHK: launch_util.h -- both shared with the test library)
 inline int fail(hipError_t e, const char* what) {
 	t_last_error = std::string(what) + ": " + hipGetErrorString(e);
 	return -(int)e;
@@ -119,6 +120,30 @@ struct DevOnce {
 	bool need(int dev) const { return !(mask.load(std::memory_order_acquire) >> dev & 1ull); }
 	void done(int dev) { mask.fetch_or(1ull << dev, std::memory_order_release); }
 };
+
+// The dynamic-LDS sizes of the two Gram kernel families, set once per device for every schedule that launches one of them -- the blocking
+// call as well as the chained streams (the test library, libtsqr_selftest.so, sets them itself before each of its launches: it is a
+// separate shared object without this table).  The 64-column block kernel and its chained form ...
+int blk_kernel_attrs(int dev) {
+	static DevOnce attr;
+	if (attr.need(dev)) {
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
+		attr.done(dev);
+	}
+	return 0;
+}
+// ... and the 128-column kernel in its fast, general and chained forms
+int wide_kernel_attrs(int dev) {
+	static DevOnce attr;
+	if (attr.need(dev)) {
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GWC_LDS_BYTES));
+		attr.done(dev);
+	}
+	return 0;
+}
 
 // ---- reference-compatible size rules (reference src/tsqr.cu:39-60, src/blockqr.cu:34-42) ----
 size_t ref_bs_log2(size_t m) {
@@ -347,17 +372,10 @@ void resolve_host_sig(Ctx& c, unsigned* h_wl, size_t m) {
 	if (t_own.get()) { c.hsig.host = t_own.host; c.hsig.dev = t_own.dev; }
 }
 
-// spin on a completion word of the pinned words (the stream is looked at now and then so that a failed launch cannot hang the caller)
+// spin on a completion word of the pinned words (spin_until; an idle stream means the word has been raised)
 int wait_word(volatile unsigned* word, unsigned seq, hipStream_t st) {
-	for (;;) {
-		for (int k = 0; k < 20000; k++) {
-			if (*word == seq) return 0;
-			__builtin_ia32_pause();
-		}
-		const hipError_t e = hipStreamQuery(st);
-		if (e == hipSuccess) return 0;
-		if (e != hipErrorNotReady) HIPCHK(e);
-	}
+	const int w = spin_until([&] { return *word == seq; }, st);
+	return w < 0 ? w : 0;
 }
 
 // End of a call on the fast path: a one-thread kernel behind the last kernel raises word 3 of the pinned words; the host spins on
@@ -448,12 +466,7 @@ template <int NT> int launch_fold(const tsqrmi::FoldArgs& a, hipStream_t st) {
 	return 0;
 }
 int dispatch_fold(int NT, const tsqrmi::FoldArgs& a, hipStream_t st) {
-	switch (NT) {
-		case 1: return launch_fold<1>(a, st);
-		case 2: return launch_fold<2>(a, st);
-		case 3: return launch_fold<3>(a, st);
-		default: return launch_fold<4>(a, st);
-	}
+	return with_nt(NT, [&](auto nt) { return launch_fold<decltype(nt)::value>(a, st); });
 }
 
 // the R-stack reduction (fold_coop_kernel): nblocks upper-triangular 64 x 64 blocks of `stack` -> R, ping-ponging between `stack` and
@@ -526,6 +539,10 @@ template <int NT> void launch_gram(const tsqrmi::GramArgs& a, int nblocks, bool 
 	if (bf16) hipLaunchKernelGGL(tsqrmi::gram_bf16_kernel<NT>, dim3(nblocks), dim3(256), 0, st, a);
 	else hipLaunchKernelGGL(tsqrmi::gram_kernel<NT>, dim3(nblocks), dim3(256), 0, st, a);
 }
+// the operands gram_blk_kernel takes: a full 64-column block of 128 k <= 2^20 rows, columns 16-byte aligned, 32-bit buffer offsets
+inline bool blk_gram_ok(const float* a, size_t lda, size_t m, size_t n) {
+	return n == PW && m % 128 == 0 && m <= ((size_t)1 << 20) && lda % 4 == 0 && lda <= ((size_t)1 << 24) && (reinterpret_cast<uintptr_t>(a) & 15) == 0;
+}
 
 // Gram matrix of src (m x n) in MFMA-accumulator order -> c.gsum() (ntri*256 doubles + the local row count behind them), summed
 // over the ranks of a row-partitioned call.  bf16 = true: bf16x3-split MFMA (memory-bound, f32 C/D layout), false: fp64 MFMA.
@@ -544,41 +561,27 @@ int gram_g(Ctx& c, const float* src, size_t ld, size_t m, size_t n, bool bf16, b
 		nparts = c.gramq_nparts;
 	} else if (io_half) {
 		ProfScope ps(KC_GRAM, c.st);
-		switch (NT) {
-			case 1: hipLaunchKernelGGL(tsqrmi::gram_h_kernel<1>, dim3(g.nblocks), dim3(256), 0, c.st, a); break;
-			case 2: hipLaunchKernelGGL(tsqrmi::gram_h_kernel<2>, dim3(g.nblocks), dim3(256), 0, c.st, a); break;
-			case 3: hipLaunchKernelGGL(tsqrmi::gram_h_kernel<3>, dim3(g.nblocks), dim3(256), 0, c.st, a); break;
-			default: hipLaunchKernelGGL(tsqrmi::gram_h_kernel<4>, dim3(g.nblocks), dim3(256), 0, c.st, a); break;
-		}
-	} else if (bf16 && n == 64 && m % 128 == 0 && m <= ((size_t)1 << 20) && ld % 4 == 0 && ld <= ((size_t)1 << 24) && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+		with_nt(NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gram_h_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, c.st, a); });
+	} else if (bf16 && blk_gram_ok(src, ld, m, n)) {
 		// full 64-column matrices that fit the 256 MiB Infinity Cache: block-pattern loads + LDS staging (gram_blk_kernel); everything
 		// else: gram_bf16_kernel.  (Measured, kernel / call period under the profiler: 2^21 rows 93.8 / 322.6 vs 95.8 / 319.4 us,
 		// 2^22 rows 190.0 / 621.2 vs 192.0 / 621.0, 2^23 rows 421 / 1310 vs 381 / 1266 -- beyond the cache the chunk kernel is as good
 		// or better; at 2^20 rows the call is 3-5 us faster with the block kernel, profiles/r03_experiment_log.md.)
-		static DevOnce attr;
-		if (attr.need(c.dev)) {
-			HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
-			attr.done(c.dev);
-		}
+		const int rc = blk_kernel_attrs(c.dev);
+		if (rc) return rc;
 		a.nchunks = (int)(m / 128);
 		nparts = std::min(a.nchunks, g.nblocks);
 		ProfScope ps(KC_GRAM, c.st);
 		hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, a);
 	} else {
 		ProfScope ps(KC_GRAM, c.st);
-		switch (NT) {
-			case 1: launch_gram<1>(a, g.nblocks, bf16, c.st); break;
-			case 2: launch_gram<2>(a, g.nblocks, bf16, c.st); break;
-			case 3: launch_gram<3>(a, g.nblocks, bf16, c.st); break;
-			default: launch_gram<4>(a, g.nblocks, bf16, c.st); break;
-		}
+		with_nt(NT, [&](auto nt) { launch_gram<decltype(nt)::value>(a, g.nblocks, bf16, c.st); });
 	}
 	HIPCHK(hipGetLastError());
 	const int nelem = g.ntri * 256;
 	{
 		ProfScope ps(KC_CHOL, c.st);
-		hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, c.st, c.gsum(), a.part, nparts, nelem, (double)m,
-		                   nullptr, (size_t)0, nullptr, 0);
+		launch_reduce1(c.st, c.gsum(), a.part, nparts, nelem, (double)m);
 	}
 	HIPCHK(hipGetLastError());
 	if (c.comm.active()) {
@@ -590,12 +593,13 @@ int gram_g(Ctx& c, const float* src, size_t ld, size_t m, size_t n, bool bf16, b
 	return 0;
 }
 
-// R = chol(G) (n x n, ldr), Z = inverse(R) (NP x NP in wq[L.z]), status words -> slot c.slot.  level: 2 bf16, 1 fp64, 3 shifted fp64.
-int chol_from_g(Ctx& c, float* r, size_t ldr, size_t n, int level) {
+// The arguments of chol16_kernel: R = chol(G) (n x n, ldr), Z = inverse(R) (NP x NP in wq[L.z]), status words -> slot `slot` (the chained
+// schedules: half i & 1 of call i).  level: 2 bf16, 1 fp64, 3 shifted fp64.
+tsqrmi::CholArgs chol_args(const Ctx& c, float* r, size_t ldr, size_t n, int level, int slot) {
 	tsqrmi::CholArgs a{};
 	a.r = r; a.ldr = ldr; a.z = c.wq + c.L.z;
-	a.status = c.status_dev(c.slot);
-	a.host_status = c.hsig.dev ? c.hsig.dev + 4 * c.slot : nullptr;
+	a.status = c.status_dev(slot);
+	a.host_status = c.hsig.dev ? c.hsig.dev + 4 * slot : nullptr;
 	a.gsum = c.gsum();
 	a.prev_status = c.prev_slot >= 0 ? c.status_dev(c.prev_slot) : nullptr;
 	const int NT = (int)(np_of(n) / 16);
@@ -604,9 +608,12 @@ int chol_from_g(Ctx& c, float* r, size_t ldr, size_t n, int level) {
 	a.shift_coef = (level == 3) ? 11.0 * 1.1102230246251565e-16 : 0.0;
 	a.n = (int)n; a.NT = NT; a.level = level; a.scond_floor = g_set.bf16_scond_floor;
 	if (level == 2) { a.relax = c.chol_relax; a.retry_shift = c.chol_retry_shift; }
+	return a;
+}
+int chol_from_g(Ctx& c, float* r, size_t ldr, size_t n, int level) {
 	{
 		ProfScope ps(KC_CHOL, c.st);
-		hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, a);
+		hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, r, ldr, n, level, c.slot));
 	}
 	HIPCHK(hipGetLastError());
 	return 0;
@@ -739,20 +746,10 @@ template <int E, int NT> int launch_apply_h(Ctx& c, tsqrmi::ApplyArgs a) {
 	return 0;
 }
 template <int E> int dispatch_apply_h(Ctx& c, int NT, const tsqrmi::ApplyArgs& a) {
-	switch (NT) {
-		case 1: return launch_apply_h<E, 1>(c, a);
-		case 2: return launch_apply_h<E, 2>(c, a);
-		case 3: return launch_apply_h<E, 3>(c, a);
-		default: return launch_apply_h<E, 4>(c, a);
-	}
+	return with_nt(NT, [&](auto nt) { return launch_apply_h<E, decltype(nt)::value>(c, a); });
 }
 template <int E> int dispatch_apply_nt(Ctx& c, int NT, const tsqrmi::ApplyArgs& a) {
-	switch (NT) {
-		case 1: return launch_apply_any<E, 1, false>(c, a);
-		case 2: return launch_apply_any<E, 2, false>(c, a);
-		case 3: return launch_apply_any<E, 3, false>(c, a);
-		default: return launch_apply_any<E, 4, false>(c, a);
-	}
+	return with_nt(NT, [&](auto nt) { return launch_apply_any<E, decltype(nt)::value, false>(c, a); });
 }
 
 // q = a * inverse(r); n <= 64; Z in wq[L.z] (computed here from r unless z_ready)
@@ -775,8 +772,12 @@ int apply_rinv(Ctx& c, int engine, float* q, size_t ldq, const float* a, size_t 
 	int rc;
 	{
 		ProfScope ps(KC_APPLY, c.st);
-		if (io_half) rc = (engine == 1) ? dispatch_apply_h<1>(c, NT, aa) : dispatch_apply_h<2>(c, NT, aa);
-		else rc = (engine == 0) ? dispatch_apply_nt<0>(c, NT, aa) : (engine == 1 ? dispatch_apply_nt<1>(c, NT, aa) : dispatch_apply_nt<2>(c, NT, aa));
+		rc = with_engine(engine, [&](auto e) {
+			constexpr int E = decltype(e)::value;
+			if (!io_half) return dispatch_apply_nt<E>(c, NT, aa);
+			if constexpr (E == 1) return dispatch_apply_h<1>(c, NT, aa);
+			else return dispatch_apply_h<2>(c, NT, aa);  // (halves: the bf16x3 engine or the single-fp16-product one)
+		});
 	}
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
@@ -991,8 +992,7 @@ int sweep(Ctx& c, int engine, int r_engine, bool check_now, float* q, size_t ldq
 		tsqrmi::ApplyArgs ua{};
 		ua.a = q + Pc * ldq; ua.lda = ldq; ua.q = a + T0 * lda; ua.ldq = lda; ua.m = m; ua.n = (int)PW; ua.z = sm;
 		ua.n_out = (int)std::min(PW, ntc); ua.multi_cols = (int)ntc;
-		const int rc2 = (engine == 0) ? launch_apply_any<0, 4, true>(c, ua)
-		                              : (engine == 1 ? launch_apply_any<1, 4, true>(c, ua) : launch_apply_any<2, 4, true>(c, ua));
+		const int rc2 = with_engine(engine, [&](auto e) { return launch_apply_any<decltype(e)::value, 4, true>(c, ua); });
 		if (rc2) return rc2;
 		HIPCHK(hipGetLastError());
 		}
@@ -1027,30 +1027,55 @@ template <int E> int launch_apply_wide(Ctx& c, tsqrmi::ApplyArgs a) {
 	else hipLaunchKernelGGL(tsqrmi::apply_wide_kernel<E>, dim3(a.nwaves), dim3(THREADS), lds, c.st, a);
 	return 0;
 }
-int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, const float* a, size_t lda, size_t m, size_t n) {
+// the one-panel path's arguments, shared by the blocking call (sweep_wide) and the stream of 128-column calls (chained128); verdict and
+// skip word: status slot `slot`
+struct WideWs { double* gsum; float* zw; float* zf2; };  // summed tiles, Z (128 x 128), Z22 in the work space behind WqLayout::wide
+WideWs wide_ws(const Ctx& c) {
 	float* w = c.wq + c.L.wide;
-	double* gsum = reinterpret_cast<double*>(w);
-	float* zw = w + WIDE_OFF_ZW;
-	float* zf2 = w + WIDE_OFF_ZF2;
-	unsigned* st1 = c.status_dev(2); unsigned* st2 = c.status_dev(3);
+	return WideWs{reinterpret_cast<double*>(w), w + WIDE_OFF_ZW, w + WIDE_OFF_ZF2};
+}
+// the Gram pass over the first nblk 64-row blocks of a; it carries the pending announcement
+tsqrmi::GramWideArgs gram_wide_args(Ctx& c, const float* a, size_t lda, size_t m, size_t n, int nblk) {
+	tsqrmi::GramWideArgs ga{};
+	ga.a = a; ga.lda = lda; ga.m = m; ga.n = (int)n; ga.blk0 = 0; ga.nblk = nblk; ga.part = reinterpret_cast<double*>(c.wr);
+	carry_announcement(c, ga);
+	return ga;
+}
+// chol(G11) -> Schur complement -> chol(G22') -> Z12 + verdict: one workgroup, one launch (chol_wide_kernel)
+tsqrmi::CholWideArgs chol_wide_args(const Ctx& c, float* r, size_t ldr, size_t m, size_t n, int slot) {
+	const WideWs w = wide_ws(c);
+	tsqrmi::CholWideArgs wa{};
+	wa.gsum = w.gsum; wa.r = r; wa.ldr = ldr; wa.n = (int)n; wa.zf1 = c.wq + c.L.z; wa.zf2 = w.zf2; wa.zw = w.zw;
+	wa.st1 = c.status_dev(2); wa.st2 = c.status_dev(3); wa.status = c.status_dev(slot);
+	wa.host_status = c.hsig.dev ? c.hsig.dev + 4 * slot : nullptr;
+	wa.prev_status = c.prev_slot >= 0 ? c.status_dev(c.prev_slot) : nullptr;
+	wa.rows = (double)m; wa.scond_floor = g_set.bf16_scond_floor;
+	return wa;
+}
+// Q = A * inverse(R) of the one-panel path; skips itself when the verdict in `slot` rejects
+int apply_wide(Ctx& c, int engine, float* q, size_t ldq, const float* a, size_t lda, size_t m, size_t n, int slot) {
+	tsqrmi::ApplyArgs aa{};
+	aa.a = a; aa.lda = lda; aa.q = q; aa.ldq = ldq; aa.m = m; aa.n = (int)n; aa.z = wide_ws(c).zw; aa.skip_status = c.status_dev(slot);
+	int rc;
+	{
+		ProfScope ps(KC_APPLY, c.st);
+		rc = with_engine(engine, [&](auto e) { return launch_apply_wide<decltype(e)::value>(c, aa); });
+	}
+	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, const float* a, size_t lda, size_t m, size_t n) {
 	// full 64-row blocks of a 128-column matrix go to the fast form of the Gram kernel, whatever is left (ragged last rows, or the
 	// whole matrix when n < 128) to the general form; both write per-workgroup partials, one after the other
 	const size_t nfull = (n == 2 * PW && lda <= ((size_t)1 << 23)) ? m / 64 : 0, nrest = cdiv(m, 64) - nfull;   // (fast form: 32-bit buffer offsets)
 	const int wgs_fast = (int)std::min<size_t>(nfull, WIDE_MAX_WGS), wgs_rest = (int)std::min<size_t>(nrest, WIDE_MAX_WGS);
-	const int wgs = wgs_fast + wgs_rest;
+	const int rca = wide_kernel_attrs(c.dev);
+	if (rca) return rca;
 	{
 		ProfScope ps(KC_GRAM, c.st);
-		tsqrmi::GramWideArgs ga{};
-		ga.a = a; ga.lda = lda; ga.m = m; ga.n = (int)n; ga.part = reinterpret_cast<double*>(c.wr);
-		static DevOnce attr;
-		if (attr.need(c.dev)) {
-			HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
-			HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
-			attr.done(c.dev);
-		}
-		carry_announcement(c, ga);                       // (the first launch carries it)
+		tsqrmi::GramWideArgs ga = gram_wide_args(c, a, lda, m, n, (int)nfull);   // (the first launch carries the announcement)
 		if (wgs_fast) {
-			ga.blk0 = 0; ga.nblk = (int)nfull;
 			hipLaunchKernelGGL((tsqrmi::gram_wide_kernel<true>), dim3(wgs_fast), dim3(512), tsqrmi::GW_LDS_BYTES, c.st, ga);
 			ga.announce = nullptr;
 		}
@@ -1062,29 +1087,11 @@ int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, c
 	HIPCHK(hipGetLastError());
 	{
 		ProfScope ps(KC_CHOL, c.st);
-		const int nelem = 36 * 256;
-		hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nelem / 16), dim3(256), 0, c.st, gsum, reinterpret_cast<const double*>(c.wr), wgs, nelem, (double)m,
-		                   nullptr, (size_t)0, nullptr, 0);
-		// chol(G11) -> Schur complement -> chol(G22') -> Z12 + verdict: one workgroup, one launch (chol_wide_kernel)
-		tsqrmi::CholWideArgs wa{};
-		wa.gsum = gsum; wa.r = r; wa.ldr = ldr; wa.n = (int)n; wa.zf1 = c.wq + c.L.z; wa.zf2 = zf2; wa.zw = zw;
-		wa.st1 = st1; wa.st2 = st2; wa.status = c.status_dev(c.slot);
-		wa.host_status = c.hsig.dev ? c.hsig.dev + 4 * c.slot : nullptr;
-		wa.prev_status = c.prev_slot >= 0 ? c.status_dev(c.prev_slot) : nullptr;
-		wa.rows = (double)m; wa.scond_floor = g_set.bf16_scond_floor;
-		hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, c.st, wa);
+		launch_reduce1(c.st, wide_ws(c).gsum, reinterpret_cast<const double*>(c.wr), wgs_fast + wgs_rest, 36 * 256, (double)m);
+		hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, c.st, chol_wide_args(c, r, ldr, m, n, c.slot));
 	}
 	HIPCHK(hipGetLastError());
-	tsqrmi::ApplyArgs aa{};
-	aa.a = a; aa.lda = lda; aa.q = q; aa.ldq = ldq; aa.m = m; aa.n = (int)n; aa.z = zw; aa.skip_status = c.status_dev(c.slot);
-	int rc;
-	{
-		ProfScope ps(KC_APPLY, c.st);
-		rc = (engine == 0) ? launch_apply_wide<0>(c, aa) : (engine == 1 ? launch_apply_wide<1>(c, aa) : launch_apply_wide<2>(c, aa));
-	}
-	if (rc) return rc;
-	HIPCHK(hipGetLastError());
-	return 0;
+	return apply_wide(c, engine, q, ldq, a, lda, m, n, c.slot);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1183,14 +1190,10 @@ int qr_core(Ctx& c, int engine, int reorth, float* q, size_t ldq, float* r, size
 				c.chol_relax = 0; c.chol_retry_shift = 0;
 				const bool have_gramq = c.gramq_nparts > 0;
 				if (rc) { c.gramq_part = nullptr; c.gramq_cap = 0; return rc; }
-				unsigned v0 = PENDING;
-				for (;;) {                                       // sweep 1's verdict (its apply pass is running meanwhile)
-					for (int i = 0; i < 20000 && v0 == PENDING; i++) { v0 = hw[0]; if (v0 == PENDING) __builtin_ia32_pause(); }
-					if (v0 != PENDING) break;
-					const hipError_t e = hipStreamQuery(c.st);
-					if (e == hipSuccess) { v0 = hw[0]; if (v0 == PENDING) v0 = 1u; break; }
-					if (e != hipErrorNotReady) { c.gramq_part = nullptr; c.gramq_cap = 0; HIPCHK(e); }
-				}
+				unsigned v0 = PENDING;                           // sweep 1's verdict (its apply pass is running meanwhile)
+				const int seen = spin_until([&] { return (v0 = hw[0]) != PENDING; }, c.st);
+				if (seen < 0) { c.gramq_part = nullptr; c.gramq_cap = 0; return seen; }
+				if (seen == 1 && (v0 = hw[0]) == PENDING) v0 = 1u;   // (the stream is idle and nothing reported: rejected)
 				unsigned s1 = 1u, s2 = 1u;
 				if (v0 == 0u) {
 					c.gramq_part = nullptr; c.gramq_cap = 0;
@@ -1603,6 +1606,10 @@ int tsqr_mi_qr_f32_finish(tsqr_mi_ticket* t) {
 	return finish_impl(CallEnv{}, t);
 }
 
+}  // extern "C"
+
+namespace {
+
 // ---- a stream of calls: `count` factorisations of ONE shape on one stream with one set of work buffers.  The loop entries pass the same
 // (q, r, a) every time (the reference's speed protocol, src/test.cu:299-309), the batch entry one triple per call (a caller with many
 // matrices, reference README.md:52-87 in a loop).  Mats hides the difference; Call carries what all calls of the stream share. ----
@@ -1692,7 +1699,7 @@ struct Completion {
 // The issue-ahead loop of every schedule: step(i) enqueues the launches of call i and closes it (Completion::close); the host stays one
 // call ahead of the call it waits for.  A rejected verdict ends the schedule with tail(i) -- the schedule's own policy for call i and the
 // ones behind it; *done = accepted calls so far.  `engine` is what tsqr_mi_last_engine reports after a stream of accepted calls.
-extern "C++" template <class Step, class Tail>       // (a template among the entry points' C linkage)
+template <class Step, class Tail>
 static int run_chained(const Completion& comp, const Mats& mt, int count, int engine, Step step, Tail tail, int* done) {
 	int rc = step(0);
 	if (rc) return rc;
@@ -1707,6 +1714,21 @@ static int run_chained(const Completion& comp, const Mats& mt, int count, int en
 	t_last_engine = engine;
 	prof_collect();
 	return TSQR_MI_SUCCESS;
+}
+
+// Calls from .. count - 1 of a stream as blocking calls, one(k) each -- except call `stands` (-1: none), which an attempt already enqueued
+// has settled (state 0).  Every call's state is recorded; a negative state ends the stream, and so does the first non-zero state of a loop
+// over one triple (every further call would end alike).  Returns that state, else the first non-zero state (0: none).
+template <class One>
+static int rest_blocking(const Mats& mt, int from, int count, int stands, One one) {
+	int first = 0;
+	for (int k = from; k < count; k++) {
+		const int st = (k == stands) ? 0 : one(k);
+		mt.state(k, st);
+		if (st && !first) first = st;
+		if (st < 0 || (st && mt.same())) return st;
+	}
+	return first;
 }
 
 // one call of the stream as a plain blocking call with its whole ladder
@@ -1727,21 +1749,14 @@ static int rejected_tail(const CallEnv& env, const Mats& mt, int count, const Ca
 	HIPCHK(hipStreamSynchronize(comp.c.st));
 	prof_collect();
 	const bool next = i + 1 < count, next_rejected = next && comp.rejected(i + 1);     // (read before a blocking call reuses the words)
-	int first = 0;
 	if (mt.same()) {
-		for (int k = i; k < count; k++) {
-			const int s = blocking_one(env, mt, k, cl);
-			if (s < 0) return s;
-			mt.state(k, s);
-			if (s && !first) first = s;
-		}
 		*done = count;
-		return first;
+		return rest_blocking(mt, i, count, -1, [&](int k) { return blocking_one(env, mt, k, cl); });
 	}
 	int s = blocking_one(env, mt, i, cl);
 	if (s < 0) return s;
 	mt.state(i, s);
-	first = s;
+	int first = s;
 	*done = i + 1;
 	if (next) {
 		s = 0;
@@ -1754,19 +1769,12 @@ static int rejected_tail(const CallEnv& env, const Mats& mt, int count, const Ca
 }
 
 // ---- what the 64-column chained schedules share (chained64, chained_dist, the fp16 stream) ----
-// the shapes gram_blk_kernel takes: a full 64-column block of 128 k <= 2^20 rows, no second sweep
-static bool blk_shape(const Call& cl) {
-	return !cl.reorth && cl.n == PW && cl.m % 128 == 0 && cl.m <= ((size_t)1 << 20) && cl.lda % 4 == 0 && cl.lda <= ((size_t)1 << 24) &&
-	       cl.lda >= cl.m && cl.ldq >= cl.m && cl.ldr >= cl.n;
-}
-static int blk_kernel_attrs(int dev) {
-	static DevOnce attr;
-	if (attr.need(dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
-		attr.done(dev);
-	}
-	return 0;
+// the streams gram_blk_kernel takes: every A an operand for it (blk_gram_ok), no second sweep, leading dimensions that hold the operands
+static bool blk_shape(const Mats& mt, int count, const Call& cl) {
+	if (cl.reorth || cl.lda < cl.m || cl.ldq < cl.m || cl.ldr < cl.n) return false;
+	for (int i = 0; i < (mt.same() ? 1 : count); i++)
+		if (!blk_gram_ok(mt.a(i), cl.lda, cl.m, cl.n)) return false;
+	return true;
 }
 // the Gram pass over `a` into `part`; it carries the pending announcement
 static tsqrmi::GramArgs gram_args_64(Ctx& c, const float* a, const Call& cl, int nchunks, const GramPlan& g, double* part) {
@@ -1775,17 +1783,6 @@ static tsqrmi::GramArgs gram_args_64(Ctx& c, const float* a, const Call& cl, int
 	ga.part = part;
 	carry_announcement(c, ga);
 	return ga;
-}
-// the bf16-split level's factorisation of call i: status and verdict words of half i & 1
-static tsqrmi::CholArgs chol_args_64(const Ctx& c, float* r, size_t ldr, int i, size_t n) {
-	tsqrmi::CholArgs ca{};
-	ca.r = r; ca.ldr = ldr; ca.z = c.wq + c.L.z;
-	ca.status = c.status_dev(i & 1);
-	ca.host_status = c.hsig.dev + 4 * (i & 1);
-	ca.gsum = c.gsum();
-	ca.rows = c.rows_global;
-	ca.n = (int)n; ca.NT = 4; ca.level = 2; ca.scond_floor = g_set.bf16_scond_floor;
-	return ca;
 }
 
 // The stream for full 64-column matrices of up to 2^20 rows (the shapes gram_blk_kernel takes): the R-factor chain of call i (reduction,
@@ -1799,7 +1796,7 @@ static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 	*done = 0;
 	const size_t m = cl.m, n = cl.n;
 	const int engine = engine_of(cl.mode);
-	if (count < 3 || engine < 0 || !blk_shape(cl) || !a_aligned16(mt, count)) return NOT_MINE;
+	if (count < 3 || engine < 0 || !blk_shape(mt, count, cl)) return NOT_MINE;
 	if (!out_of_order(mt, count, cl) || !chain_fits_cache(mt, cl)) return NOT_MINE;
 	Ctx c;
 	env_ctx(c, CallEnv{}, cl.wq, cl.wr, m, n, cl.h_wl, cl.stream, /*keep_in_flight=*/false);
@@ -1817,7 +1814,7 @@ static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 	auto step = [&](int i) -> int {
 		if (i + 1 < count) {
 			tsqrmi::ChainArgs ch{};
-			ch.chol = chol_args_64(c, mt.r(i), cl.ldr, i, n);
+			ch.chol = chol_args(c, mt.r(i), cl.ldr, n, 2, i & 1);
 			ch.part = part[i & 1]; ch.nparts = nparts; ch.ticket = ticket; ch.nred = nred;
 			ProfScope ps(KC_GRAM, c.st);
 			hipLaunchKernelGGL(tsqrmi::gram_blk_chain_kernel, dim3(nred + nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st,
@@ -1827,9 +1824,8 @@ static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 			// before, which no Gram kernel is there to raise)
 			raise_announcement(c);
 			ProfScope ps(KC_CHOL, c.st);
-			hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nred), dim3(256), 0, c.st, c.gsum(), part[i & 1], nparts, nelem, (double)m,
-			                   nullptr, (size_t)0, nullptr, 0);
-			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args_64(c, mt.r(i), cl.ldr, i, n));
+			launch_reduce1(c.st, c.gsum(), part[i & 1], nparts, nelem, (double)m);
+			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, mt.r(i), cl.ldr, n, 2, i & 1));
 		}
 		HIPCHK(hipGetLastError());
 		c.slot = i & 1;
@@ -1861,36 +1857,15 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 	Ctx c;
 	env_ctx(c, CallEnv{}, cl.wq, cl.wr, m, n, cl.h_wl, cl.stream, /*keep_in_flight=*/false);
 	if (!(c.wide && c.policy == 0 && c.gram_level == 2 && c.hsig.dev && !g_set.debug)) return NOT_MINE;
-	static DevOnce attr;
-	if (attr.need(c.dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GWC_LDS_BYTES));
-		attr.done(c.dev);
-	}
-	float* w = c.wq + c.L.wide;
-	double* gsum = reinterpret_cast<double*>(w);
-	float* zw = w + WIDE_OFF_ZW;
-	float* zf2 = w + WIDE_OFF_ZF2;
-	const int nblk = (int)(m / 64), wgs = WIDE_MAX_WGS, nelem = 36 * 256;
-	double* part = reinterpret_cast<double*>(c.wr);
+	const int rca = wide_kernel_attrs(c.dev);
+	if (rca) return rca;
+	const int nblk = (int)(m / 64), wgs = WIDE_MAX_WGS;
 	Completion comp(c);
-	auto gram_args = [&](int i) {
-		tsqrmi::GramWideArgs ga{};
-		ga.a = mt.a(i); ga.lda = lda; ga.m = m; ga.n = (int)n; ga.blk0 = 0; ga.nblk = nblk; ga.part = part;
-		carry_announcement(c, ga);
-		return ga;
-	};
-	auto chol_args = [&](int i) {
-		tsqrmi::CholWideArgs wa{};
-		wa.gsum = gsum; wa.r = mt.r(i); wa.ldr = ldr; wa.n = (int)n; wa.zf1 = c.wq + c.L.z; wa.zf2 = zf2; wa.zw = zw;
-		wa.st1 = c.status_dev(2); wa.st2 = c.status_dev(3); wa.status = c.status_dev(i & 1);
-		wa.host_status = c.hsig.dev + 4 * (i & 1);
-		wa.rows = (double)m; wa.scond_floor = g_set.bf16_scond_floor;
-		return wa;
-	};
+	auto gram_args = [&](int i) { return gram_wide_args(c, mt.a(i), lda, m, n, nblk); };
+	auto chol_args = [&](int i) { return chol_wide_args(c, mt.r(i), ldr, m, n, i & 1); };
 	auto reduce = [&]() {
 		ProfScope ps(KC_CHOL, c.st);
-		hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nelem / 16), dim3(256), 0, c.st, gsum, part, wgs, nelem, (double)m, nullptr, (size_t)0, nullptr, 0);
+		launch_reduce1(c.st, wide_ws(c).gsum, reinterpret_cast<const double*>(c.wr), wgs, 36 * 256, (double)m);
 	};
 	auto step = [&](int i) -> int {
 		if (i + 1 < count) {
@@ -1905,16 +1880,8 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 			hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(i));
 		}
 		HIPCHK(hipGetLastError());
-		tsqrmi::ApplyArgs aa{};
-		aa.a = mt.a(i); aa.lda = lda; aa.q = mt.q(i); aa.ldq = ldq; aa.m = m; aa.n = (int)n; aa.z = zw; aa.skip_status = c.status_dev(i & 1);
-		int rc;
-		{
-			ProfScope ps(KC_APPLY, c.st);
-			rc = (engine == 0) ? launch_apply_wide<0>(c, aa) : (engine == 1 ? launch_apply_wide<1>(c, aa) : launch_apply_wide<2>(c, aa));
-		}
-		if (rc) return rc;
-		HIPCHK(hipGetLastError());
-		return comp.close(i, i + 1 == count);
+		const int rc = apply_wide(c, engine, mt.q(i), ldq, mt.a(i), lda, m, n, i & 1);
+		return rc ? rc : comp.close(i, i + 1 == count);
 	};
 	{
 		ProfScope ps(KC_GRAM, c.st);
@@ -1943,7 +1910,7 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 	if (engine < 0 || m == 0 || n == 0 || n > PW || env.nranks < 1 || env.nranks > 255) return NOT_MINE;   // (conditions every rank shares; the plain path reports errors)
 	Ctx c;
 	env_ctx(c, env, cl.wq, cl.wr, m, n, nullptr, cl.stream, /*keep_in_flight=*/false);
-	const bool mine = c.hsig.dev && blk_shape(cl) && c.policy == 0 && c.gram_level == 2 && !g_set.debug && out_of_order(mt, count, cl) && a_aligned16(mt, count);
+	const bool mine = c.hsig.dev && blk_shape(mt, count, cl) && c.policy == 0 && c.gram_level == 2 && !g_set.debug && out_of_order(mt, count, cl);
 	c.fold_cor = (engine == 1);
 	int rc = blk_kernel_attrs(c.dev);
 	if (rc) return rc;
@@ -1951,16 +1918,11 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 	const int nchunks = (int)(m / 128), nparts = std::min(nchunks, g.nblocks), nelem = 10 * 256;
 	double* part = reinterpret_cast<double*>(c.wr);
 	Completion comp(c);
-	auto chol_args = [&](int i) {
-		tsqrmi::CholArgs ca = chol_args_64(c, mt.r(i), cl.ldr, i, n);
-		ca.rows_dev = c.gsum() + nelem;                  // the all-reduced row count (as chol_from_g)
-		return ca;
-	};
+	auto chol_of = [&](int i) { return chol_args(c, mt.r(i), cl.ldr, n, 2, i & 1); };   // (rows_dev: the all-reduced row count)
 	auto reduce_allreduce = [&](int extra) -> int {      // partials of the Gram pass just enqueued -> summed tiles + row count (+ `extra` doubles), over all ranks
 		{
 			ProfScope ps(KC_CHOL, c.st);
-			hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nelem / 16), dim3(256), 0, c.st, c.gsum(), part, nparts, nelem, (double)m,
-			                   nullptr, (size_t)0, nullptr, 0);
+			launch_reduce1(c.st, c.gsum(), part, nparts, nelem, (double)m);
 		}
 		HIPCHK(hipGetLastError());
 		if (extra) hipLaunchKernelGGL(tsqrmi::set_f64_kernel, dim3(1), dim3(1), 0, c.st, c.gsum() + nelem + 1, 1.0);
@@ -1987,19 +1949,10 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 		comp.words[8] = 0;
 		hipLaunchKernelGGL(tsqrmi::vote_out_kernel, dim3(1), dim3(1), 0, c.st, c.gsum() + nelem + 1, c.hsig.dev + 8, vs);
 		HIPCHK(hipGetLastError());
-		unsigned w = 0;
-		for (;;) {                                       // (as wait_word, for a word that holds the count next to the sequence number)
-			bool seen = false;
-			for (int k = 0; k < 20000 && !seen; k++) {
-				w = comp.words[8];
-				seen = (w >> 8) == (vs & 0xffffffu);
-				if (!seen) __builtin_ia32_pause();
-			}
-			if (seen) break;
-			const hipError_t e = hipStreamQuery(c.st);
-			if (e == hipSuccess) { w = comp.words[8]; break; }
-			if (e != hipErrorNotReady) HIPCHK(e);
-		}
+		unsigned w = 0;                                  // (as wait_word, for a word that holds the count next to the sequence number)
+		const int seen = spin_until([&] { w = comp.words[8]; return (w >> 8) == (vs & 0xffffffu); }, c.st);
+		if (seen < 0) return seen;
+		if (seen == 1) w = comp.words[8];
 		if ((int)(w & 0xffu) != env.nranks || (w >> 8) != (vs & 0xffffffu)) { prof_collect(); return NOT_MINE; }
 	} else {                                             // (no pinned words on this rank: it voted "no"; it still has to leave with an idle stream)
 		HIPCHK(hipStreamSynchronize(c.st));
@@ -2008,7 +1961,7 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 	auto step = [&](int i) -> int {
 		if (i + 1 < count) {
 			tsqrmi::ChainArgs ch{};
-			ch.chol = chol_args(i); ch.direct = 1;
+			ch.chol = chol_of(i); ch.direct = 1;
 			{
 				ProfScope ps(KC_GRAM, c.st);
 				hipLaunchKernelGGL(tsqrmi::gram_blk_chain_kernel, dim3(1 + nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st,
@@ -2020,7 +1973,7 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 		} else {
 			raise_announcement(c);
 			ProfScope ps(KC_CHOL, c.st);
-			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(i));
+			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_of(i));
 			HIPCHK(hipGetLastError());
 		}
 		c.slot = i & 1;
@@ -2099,22 +2052,13 @@ static int conflict_on_any_rank(const CallEnv& env, const Mats& mt, int count, c
 // with a fresh one (after a second rejection: two in flight for the rest, every attempt of a chained schedule would be thrown away).
 static int stream_of_calls(const CallEnv& env, const Mats& mt, int count, const Call& cl) {
 	const int depth = g_set.loop_depth.load();
-	int first = 0;
 	bool in_order = count < 2 || depth < 2;
 	if (!in_order && env.dist && !mt.same()) {
 		const int rc = conflict_on_any_rank(env, mt, count, cl, &in_order);
 		if (rc) return rc;
 	}
-	if (in_order) {
-		for (int i = 0; i < count; i++) {
-			const int st = blocking_one(env, mt, i, cl);
-			mt.state(i, st);
-			if (st && !first) first = st;
-			if (st < 0 || (st && mt.same())) return st;
-		}
-		return first;
-	}
-	int pos = 0, rejections = 0;
+	if (in_order) return rest_blocking(mt, 0, count, -1, [&](int i) { return blocking_one(env, mt, i, cl); });
+	int first = 0, pos = 0, rejections = 0;
 	while (depth >= 3 && count - pos >= 3 && rejections < 2) {
 		const Mats sub = mt.from(pos);
 		int done = 0, st;
@@ -2136,6 +2080,10 @@ static int stream_of_calls(const CallEnv& env, const Mats& mt, int count, const 
 	}
 	return first;
 }
+
+}  // namespace
+
+extern "C" {
 
 void tsqr_mi_set_loop_depth(int depth) { g_set.loop_depth = depth < 2 ? 1 : (depth == 2 ? 2 : 3); }
 
@@ -2263,17 +2211,9 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 	auto tail = [&](int i) -> int {
 		HIPCHK(hipStreamSynchronize(c.st));
 		const bool next_ok = i + 1 < count && !comp.rejected(i + 1);
-		int first = 0;
-		for (int k = i; k < count; k++) {
-			int st = 0;
-			if (!(k == i + 1 && next_ok))
-				st = tsqr_mi_qr_f16(mode, 0, mt.q(k), ldq, mt.r(k), ldr, mt.a(k), lda, m, n, wq_v, wr_v, nullptr, nullptr, h_wl, stream);
-			if (st < 0) return st;
-			mt.state(k, st);
-			if (st && !first) first = st;
-			if (st && mt.same()) return st;
-		}
-		return first;
+		return rest_blocking(mt, i, count, next_ok ? i + 1 : -1, [&](int k) {
+			return tsqr_mi_qr_f16(mode, 0, mt.q(k), ldq, mt.r(k), ldr, mt.a(k), lda, m, n, wq_v, wr_v, nullptr, nullptr, h_wl, stream);
+		});
 	};
 	int done = 0;
 	// n = 64, three calls or more: the chained schedule (tsqr_mi_qr_f32_loop's, with gram_h_chain_kernel) -- the R-factor chain of call i
@@ -2300,14 +2240,13 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 		c.slot = i & 1; c.prev_slot = -1;
 		if (i + 1 < count) {
 			tsqrmi::ChainArgs ch{};
-			ch.chol = chol_args_64(c, r32, n, i, n);
+			ch.chol = chol_args(c, r32, n, n, 2, i & 1);
 			ch.part = part[i & 1]; ch.nparts = g.nblocks; ch.ticket = ticket; ch.nred = nred;
 			hipLaunchKernelGGL(tsqrmi::gram_h_chain_kernel, dim3(nred + g.nblocks), dim3(256), 0, c.st, gram_args_64(c, mt.a(i + 1), cl, g.nch, g, part[(i + 1) & 1]), ch);
 		} else {
 			raise_announcement(c);
-			hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3(nred), dim3(256), 0, c.st, c.gsum(), part[i & 1], g.nblocks, nelem, (double)m,
-			                   nullptr, (size_t)0, nullptr, 0);
-			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args_64(c, r32, n, i, n));
+			launch_reduce1(c.st, c.gsum(), part[i & 1], g.nblocks, nelem, (double)m);
+			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, r32, n, n, 2, i & 1));
 		}
 		HIPCHK(hipGetLastError());
 		return apply_and_close(i);
@@ -2321,14 +2260,9 @@ static int calls_f16(const Mats& mt, int count, int mode, int reorth, size_t ldq
 		const int st = stream_of_calls_f16(mt, count, mode, ldq, ldr, lda, m, n, wq_v, wr_v, h_wl, stream);
 		if (st != NOT_MINE) return st;
 	}
-	int first = 0;
-	for (int i = 0; i < count; i++) {
-		const int st = tsqr_mi_qr_f16(mode, reorth, mt.q(i), ldq, mt.r(i), ldr, mt.a(i), lda, m, n, wq_v, wr_v, reorth_w, d_wl, h_wl, stream);
-		mt.state(i, st);
-		if (st && !first) first = st;
-		if (st < 0 || (st && mt.same())) return st;
-	}
-	return first;
+	return rest_blocking(mt, 0, count, -1, [&](int i) {
+		return tsqr_mi_qr_f16(mode, reorth, mt.q(i), ldq, mt.r(i), ldr, mt.a(i), lda, m, n, wq_v, wr_v, reorth_w, d_wl, h_wl, stream);
+	});
 }
 int tsqr_mi_qr_f16_loop(int count, int mode, int reorth, void* q, size_t ldq, void* r, size_t ldr, const void* a, size_t lda,
                         size_t m, size_t n, void* wq_v, void* wr_v, void* reorth_w, unsigned* d_wl, unsigned* h_wl, void* stream) {
@@ -2564,8 +2498,7 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
 	f64_gram_launch(st, g, ga);
 	HIPCHK(hipGetLastError());
 	const int nelem = g.ntri * 256;
-	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, st, wq + F64_GSUM, wr, g.nblocks, nelem, (double)m,
-	                   nullptr, (size_t)0, nullptr, 0);
+	launch_reduce1(st, wq + F64_GSUM, wr, g.nblocks, nelem, (double)m);
 	HIPCHK(hipGetLastError());
 	tsqrmi::CholArgs64 ca{};
 	ca.r = r; ca.ldr = ldr; ca.z = wq + F64_Z;
@@ -2604,12 +2537,7 @@ int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, 
 	int rc = f64_factor(st, wq, wr, src, lds, m, n, first ? r : wq + F64_R2, first ? ldr : 64, first, k & 3);
 	if (rc) return rc;
 	const double* z = wq + F64_Z;
-	switch (np_of(n) / 16) {
-		case 1: rc = f64_apply<1>(st, dev, q, ldq, src, lds, m, n, z); break;
-		case 2: rc = f64_apply<2>(st, dev, q, ldq, src, lds, m, n, z); break;
-		case 3: rc = f64_apply<3>(st, dev, q, ldq, src, lds, m, n, z); break;
-		default: rc = f64_apply<4>(st, dev, q, ldq, src, lds, m, n, z); break;
-	}
+	rc = with_nt((int)(np_of(n) / 16), [&](auto nt) { return f64_apply<decltype(nt)::value>(st, dev, q, ldq, src, lds, m, n, z); });
 	if (rc || first) return rc;
 	hipLaunchKernelGGL(tsqrmi::rmul_f64_kernel, dim3(1), dim3(1024), 0, st, r, ldr, wq + F64_R2, (int)n);
 	HIPCHK(hipGetLastError());
@@ -2704,8 +2632,7 @@ int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double
 	hipLaunchKernelGGL(tsqrmi::gram_wide_f64_kernel, dim3((unsigned)(g.ngroups * g.nslices)), dim3(256), 0, st, ga);
 	HIPCHK(hipGetLastError());
 	const int nelem = (int)g.bs;
-	hipLaunchKernelGGL(tsqrmi::gram_reduce1_kernel, dim3((nelem + 15) / 16), dim3(256), 0, st, wq + g.o_gs, wr, g.nslices, nelem, (double)m,
-	                   nullptr, (size_t)0, nullptr, 0);
+	launch_reduce1(st, wq + g.o_gs, wr, g.nslices, nelem, (double)m);
 	HIPCHK(hipGetLastError());
 	tsqrmi::WideF64 wa{};
 	wa.gs = wq + g.o_gs; wa.w = wq + g.o_w; wa.rw = wq + g.o_rw; wa.zw = wq + g.o_zw; wa.ta = wq + g.o_ta; wa.zd = wq + g.o_zd;
