@@ -1,8 +1,7 @@
 // tsqr_f64.hip -- the device side of the double-precision entry (tsqr_mi_qr_f64): CholeskyQR sweeps on fp64 data, n <= 64.
 // Included by tsqr_mi.hip after tsqr_kernels.hip, whose Gram reduction (gram_reduce1_kernel) and Cholesky body (chol_body16<double>)
 // it reuses unchanged.
-//   gram_f64_kernel   : per-workgroup partials of A^T A on v_mfma_f64_16x16x4_f64 -- gram_kernel with fp64 loads: the same chunk
-//                       interleave, the same (tile, reg, lane) accumulator order, the same workgroup sum
+//   gram_f64_kernel   : per-workgroup partials of A^T A on v_mfma_f64_16x16x4_f64 -- gram_kernel's body (gram_body) with fp64 loads
 //   chol_f64_kernel   : G -> R, Z = inverse(R) in fp64, the fp64 acceptance rule (CholArgs64), a rejected matrix factored again at
 //                       once with the shift of Fukaya et al.
 //   apply_f64_kernel  : Q = A Z on v_mfma_f64_16x16x4_f64, Z upper triangular (its zero blocks are skipped), in place allowed
@@ -10,42 +9,6 @@
 #include <hip/hip_runtime.h>
 
 namespace tsqrmi {
-
-typedef double f64x2u __attribute__((ext_vector_type(2), aligned(8)));   // 8-byte aligned 16-byte access (any lda)
-
-// the (c,q) chunk layout of load_chunk with fp64 elements: lane 16 q + c holds rows 16 rt + 4 q + i of column 16 ct + c in
-// p[ct][4 rt + i]; rows >= m and columns >= n read as zero
-template <int NT>
-__device__ __forceinline__ void load_chunk_f64(double (&p)[NT][16], const double* __restrict__ src, size_t ld, size_t row0, size_t m, int n,
-                                               int c, int q) {
-	const bool full = (row0 + 64 <= m);
-#pragma unroll
-	for (int ct = 0; ct < NT; ct++) {
-		const int col = 16 * ct + c;
-		const double* base = src + (size_t)col * ld + row0 + 4 * q;
-		if (col < n) {
-			if (full) {
-#pragma unroll
-				for (int rt = 0; rt < 4; rt++) {
-					const f64x2u v0 = *reinterpret_cast<const f64x2u*>(base + 16 * rt);
-					const f64x2u v1 = *reinterpret_cast<const f64x2u*>(base + 16 * rt + 2);
-					p[ct][4 * rt + 0] = v0[0]; p[ct][4 * rt + 1] = v0[1]; p[ct][4 * rt + 2] = v1[0]; p[ct][4 * rt + 3] = v1[1];
-				}
-			} else {
-#pragma unroll
-				for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-					for (int i = 0; i < 4; i++) {
-						const size_t row = row0 + 16 * rt + 4 * q + i;
-						p[ct][4 * rt + i] = (row < m) ? base[16 * rt + i] : 0.0;
-					}
-			}
-		} else {
-#pragma unroll
-			for (int r = 0; r < 16; r++) p[ct][r] = 0.0;
-		}
-	}
-}
 
 struct GramArgs64 {
 	const double* a; size_t lda; size_t m; int n;
@@ -56,60 +19,8 @@ struct GramArgs64 {
 template <int NT>
 __global__ __launch_bounds__(256) void gram_f64_kernel(const GramArgs64 a) {
 	constexpr int NTRI = (NT * (NT + 1)) / 2;
-	__shared__ double red[2][NTRI * 256];
-	const int lane = threadIdx.x & 63;
-	const int wv = threadIdx.x >> 6;
-	const int gw = blockIdx.x * 4 + wv;
-	const int c = lane & 15, q = lane >> 4;
-	f64x4 acc[NTRI];
-#pragma unroll
-	for (int t = 0; t < NTRI; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-	if (gw < a.nwaves) {
-		double p[NT][16];
-		for (int ch = gw; ch < a.nchunks; ch += a.nwaves) {      // interleaved: consecutive chunks go to consecutive waves
-			load_chunk_f64<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
-#pragma unroll
-			for (int rho = 0; rho < 16; rho++) {
-				int idx = 0;
-#pragma unroll
-				for (int ti = 0; ti < NT; ti++)
-#pragma unroll
-					for (int tj = ti; tj < NT; tj++) {
-						acc[idx] = __builtin_amdgcn_mfma_f64_16x16x4f64(p[ti][rho], p[tj][rho], acc[idx], 0, 0, 0);
-						idx++;
-					}
-			}
-		}
-	}
-	// workgroup sum (as gram_kernel): waves 2,3 -> LDS, waves 0,1 add; wave 1 -> LDS, wave 0 adds and stores the partial
-	if (wv >= 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[wv - 2][(t * 4 + r) * 64 + lane] = acc[t][r];
-	}
-	__syncthreads();
-	if (wv < 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) acc[t][r] += red[wv][(t * 4 + r) * 64 + lane];
-	}
-	__syncthreads();
-	if (wv == 1) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[0][(t * 4 + r) * 64 + lane] = acc[t][r];
-	}
-	__syncthreads();
-	if (wv == 0) {
-		double* out = a.part + (size_t)blockIdx.x * NTRI * 256;
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], acc[t][r] + red[0][(t * 4 + r) * 64 + lane]);
-	}
+	__shared__ double red[2 * NTRI * 256];
+	gram_body<NT, double>(a, red);
 }
 
 // The Cholesky step of the fp64 entry: chol_body16 with fp64 R and Z.  Level 4 of the ladder ("fp64 data"): the rule is stated on the

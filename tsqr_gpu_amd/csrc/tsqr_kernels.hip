@@ -94,6 +94,42 @@ __device__ __forceinline__ void load_chunk(float (&p)[NT][16], const float* __re
 	}
 }
 
+typedef double f64x2u __attribute__((ext_vector_type(2), aligned(8)));   // 8-byte aligned 16-byte access (any lda)
+
+// the (c,q) chunk layout of load_chunk with fp64 elements: lane 16 q + c holds rows 16 rt + 4 q + i of column 16 ct + c in
+// p[ct][4 rt + i]; rows >= m and columns >= n read as zero
+template <int NT>
+__device__ __forceinline__ void load_chunk_f64(double (&p)[NT][16], const double* __restrict__ src, size_t ld, size_t row0, size_t m, int n,
+                                               int c, int q) {
+	const bool full = (row0 + 64 <= m);
+#pragma unroll
+	for (int ct = 0; ct < NT; ct++) {
+		const int col = 16 * ct + c;
+		const double* base = src + (size_t)col * ld + row0 + 4 * q;
+		if (col < n) {
+			if (full) {
+#pragma unroll
+				for (int rt = 0; rt < 4; rt++) {
+					const f64x2u v0 = *reinterpret_cast<const f64x2u*>(base + 16 * rt);
+					const f64x2u v1 = *reinterpret_cast<const f64x2u*>(base + 16 * rt + 2);
+					p[ct][4 * rt + 0] = v0[0]; p[ct][4 * rt + 1] = v0[1]; p[ct][4 * rt + 2] = v1[0]; p[ct][4 * rt + 3] = v1[1];
+				}
+			} else {
+#pragma unroll
+				for (int rt = 0; rt < 4; rt++)
+#pragma unroll
+					for (int i = 0; i < 4; i++) {
+						const size_t row = row0 + 16 * rt + 4 * q + i;
+						p[ct][4 * rt + i] = (row < m) ? base[16 * rt + i] : 0.0;
+					}
+			}
+		} else {
+#pragma unroll
+			for (int r = 0; r < 16; r++) p[ct][r] = 0.0;
+		}
+	}
+}
+
 // ---- bf16 split helpers (shared by the fold, Gram and apply kernels) ----
 __device__ __forceinline__ unsigned f2bf(float x) {    // round-to-nearest-even bf16 bits (finite inputs)
 	const unsigned u = __builtin_bit_cast(unsigned, x);
@@ -125,6 +161,43 @@ __device__ __forceinline__ void split3_pair(float a, float b, unsigned& h, unsig
 	const f32x2_t mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xffff0000u)};
 	const f32x2_t t = r - mf;
 	l = cvt_pk_bf16(t[0], t[1]);
+}
+// one MFMA operand (a K-step of 32 rows: eight values per lane) as its three bf16 images, four split3_pair in register order
+__device__ __forceinline__ void split3_operand(f32x4 x0, f32x4 x1, bf16x8& h, bf16x8& m, bf16x8& l) {
+	u32x4 hh, mm, ll;
+	unsigned ph, pm, pl;
+	split3_pair(x0[0], x0[1], ph, pm, pl); hh[0] = ph; mm[0] = pm; ll[0] = pl;
+	split3_pair(x0[2], x0[3], ph, pm, pl); hh[1] = ph; mm[1] = pm; ll[1] = pl;
+	split3_pair(x1[0], x1[1], ph, pm, pl); hh[2] = ph; mm[2] = pm; ll[2] = pl;
+	split3_pair(x1[2], x1[3], ph, pm, pl); hh[3] = ph; mm[3] = pm; ll[3] = pl;
+	h = __builtin_bit_cast(bf16x8, hh);
+	m = __builtin_bit_cast(bf16x8, mm);
+	l = __builtin_bit_cast(bf16x8, ll);
+}
+// the same for registers 8 kt .. 8 kt + 7 of a (c,q) tile: K-step kt of its 64 rows  (written out: through vector temporaries and the
+// form above, fold_kernel's packed subtractions compile to other instructions -- profiles/refactor_gram_blocks_device_code.md)
+__device__ __forceinline__ void split3_operand(const float (&p)[16], int kt, bf16x8& h, bf16x8& m, bf16x8& l) {
+	u32x4 hh, mm, ll;
+#pragma unroll
+	for (int jp = 0; jp < 4; jp++) {
+		unsigned ph, pm, pl;
+		split3_pair(p[8 * kt + 2 * jp], p[8 * kt + 2 * jp + 1], ph, pm, pl);
+		hh[jp] = ph; mm[jp] = pm; ll[jp] = pl;
+	}
+	h = __builtin_bit_cast(bf16x8, hh);
+	m = __builtin_bit_cast(bf16x8, mm);
+	l = __builtin_bit_cast(bf16x8, ll);
+}
+
+// The product table of every split product A B with A = ah + am + al, B = bh + bm + bl: six of the nine partial products, one per
+// `pass` = 3 .. 8, smallest first -- mm hl lh hm mh hh (ml lm ll, of the order of 2^-24 of the product and below, are left out) -- so
+// that the small terms are summed before the large one absorbs them.  The callers run `pass` as the OUTER loop
+// over their tiles: consecutive MFMAs then go to different accumulators and none waits for the one before it.
+__device__ __forceinline__ constexpr const bf16x8& split_a(int pass, const bf16x8& h, const bf16x8& m, const bf16x8& l) {
+	return (pass == 4 || pass == 6 || pass == 8) ? h : ((pass == 3 || pass == 7) ? m : l);
+}
+__device__ __forceinline__ constexpr const bf16x8& split_b(int pass, const bf16x8& h, const bf16x8& m, const bf16x8& l) {
+	return (pass == 5 || pass == 7 || pass == 8) ? h : ((pass == 3 || pass == 6) ? m : l);
 }
 
 // 3-way bf16 split of NPAIR independent pairs, written stage by stage (scheduling barriers in between) so that the
@@ -363,14 +436,8 @@ __device__ __forceinline__ void trail_update_cor(float (&pj)[16], const bf16x8 (
 #pragma unroll
 	for (int kt = 0; kt < 2; kt++)
 		if (!TRI || 2 * kt <= glim) {                    // rows 32 kt .. are zero in a triangular block beyond row tile glim
-			u32x4 hh, mm, ll;
-#pragma unroll
-			for (int jp = 0; jp < 4; jp++) {
-				unsigned h, m, lo;
-				split3_pair(pj[8 * kt + 2 * jp], pj[8 * kt + 2 * jp + 1], h, m, lo);
-				hh[jp] = h; mm[jp] = m; ll[jp] = lo;
-			}
-			const bf16x8 bh = __builtin_bit_cast(bf16x8, hh), bm = __builtin_bit_cast(bf16x8, mm), bl = __builtin_bit_cast(bf16x8, ll);
+			bf16x8 bh, bm, bl;
+			split3_operand(pj, kt, bh, bm, bl);
 			w = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vm[kt], bm, w, 0, 0, 0);
 			w = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh[kt], bl, w, 0, 0, 0);
 			w = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vl[kt], bh, w, 0, 0, 0);
@@ -460,16 +527,7 @@ __device__ __forceinline__ void fold_one(float (&p)[NT][16], float* __restrict__
 			if constexpr (COR) {
 				bf16x8 vh[2], vm[2], vl[2], th[4], tm[4], tl[4];
 #pragma unroll
-				for (int kt = 0; kt < 2; kt++) {
-					u32x4 hh, mm, ll;
-#pragma unroll
-					for (int jp = 0; jp < 4; jp++) {
-						unsigned h, m, lo;
-						split3_pair(p[0][8 * kt + 2 * jp], p[0][8 * kt + 2 * jp + 1], h, m, lo);
-						hh[jp] = h; mm[jp] = m; ll[jp] = lo;
-					}
-					vh[kt] = __builtin_bit_cast(bf16x8, hh); vm[kt] = __builtin_bit_cast(bf16x8, mm); vl[kt] = __builtin_bit_cast(bf16x8, ll);
-				}
+				for (int kt = 0; kt < 2; kt++) split3_operand(p[0], kt, vh[kt], vm[kt], vl[kt]);
 #pragma unroll
 				for (int rt = 0; rt < 4; rt++) {
 					unsigned h0, m0, l0, h1, m1, l1;
@@ -637,6 +695,41 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void part_store(double* p, double v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ double part_load(const double* p) { return __builtin_nontemporal_load(p); }
 
+// The workgroup sum of four waves' tile accumulators and the store of the workgroup's partial: waves 2, 3 -> LDS, waves 0, 1 add;
+// wave 1 -> LDS, wave 0 adds and stores.  This fixes the layout gram_reduce1_body reads: a partial is NTRI tiles of 256 doubles,
+// entry (tile t, register r, lane) at (t * 4 + r) * 64 + lane.  The sums are taken in the accumulators' type T and widened at the store.
+// red: 2 * NTRI * 256 elements of LDS; where it aliases LDS still being read, the caller puts a barrier in front.  acc is consumed.
+template <int NTRI, class V, class T>                   // V: four values of type T per tile, a vector or an array
+__device__ __forceinline__ void wg_sum4_store(V (&acc)[NTRI], T* red, double* out, const int wv, const int lane) {
+	if (wv >= 2) {
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) red[(wv - 2) * NTRI * 256 + (t * 4 + r) * 64 + lane] = acc[t][r];
+	}
+	__syncthreads();
+	if (wv < 2) {
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) acc[t][r] += red[wv * NTRI * 256 + (t * 4 + r) * 64 + lane];
+	}
+	__syncthreads();
+	if (wv == 1) {
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) red[(t * 4 + r) * 64 + lane] = acc[t][r];
+	}
+	__syncthreads();
+	if (wv == 0) {
+#pragma unroll
+		for (int t = 0; t < NTRI; t++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], (double)(acc[t][r] + red[(t * 4 + r) * 64 + lane]));
+	}
+}
+
 struct GramArgs {
 	const float* a; size_t lda; size_t m; int n;
 	int nchunks; int cpw; int nwaves;
@@ -654,12 +747,10 @@ __device__ __forceinline__ void announce_previous_call(unsigned* word, unsigned 
 	if (word && blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<volatile unsigned*>(word) = seq;
 }
 
-template <int NT>
-__global__ __launch_bounds__(256) void gram_kernel(const GramArgs a) {
+// The body of gram_kernel (GramArgs: fp32 data, widened on the way to the MFMA) and of gram_f64_kernel (GramArgs64, tsqr_f64.hip).
+template <int NT, class T, class ARGS>                  // T: the element type of a.a
+__device__ __forceinline__ void gram_body(const ARGS& a, double* red) {
 	constexpr int NTRI = (NT * (NT + 1)) / 2;
-	__shared__ double red[2][NTRI * 256];
-	announce_previous_call(a.announce, a.announce_seq);
-	if (a.skip_status && a.skip_status[0] != 0) return;
 	const int lane = threadIdx.x & 63;
 	const int wv = threadIdx.x >> 6;
 	const int gw = blockIdx.x * 4 + wv;
@@ -668,10 +759,10 @@ __global__ __launch_bounds__(256) void gram_kernel(const GramArgs a) {
 #pragma unroll
 	for (int t = 0; t < NTRI; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
 	if (gw < a.nwaves) {
-		float p[NT][16];
-		const int ch_end = a.nchunks, ch_step = a.nwaves, ch_begin = gw;      // interleaved: consecutive chunks go to consecutive waves
-		for (int ch = ch_begin; ch < ch_end; ch += ch_step) {
-			load_chunk<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
+		T p[NT][16];
+		for (int ch = gw; ch < a.nchunks; ch += a.nwaves) {      // interleaved: consecutive chunks go to consecutive waves
+			if constexpr (std::is_same_v<T, float>) load_chunk<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
+			else load_chunk_f64<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
 #pragma unroll
 			for (int rho = 0; rho < 16; rho++) {
 				double pd[NT];
@@ -688,35 +779,15 @@ __global__ __launch_bounds__(256) void gram_kernel(const GramArgs a) {
 			}
 		}
 	}
-	// workgroup sum: waves 2,3 -> LDS, waves 0,1 add; wave 1 -> LDS, wave 0 adds and stores the partial
-	if (wv >= 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[wv - 2][(t * 4 + r) * 64 + lane] = acc[t][r];
-	}
-	__syncthreads();
-	if (wv < 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) acc[t][r] += red[wv][(t * 4 + r) * 64 + lane];
-	}
-	__syncthreads();
-	if (wv == 1) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[0][(t * 4 + r) * 64 + lane] = acc[t][r];
-	}
-	__syncthreads();
-	if (wv == 0) {
-		double* out = a.part + (size_t)blockIdx.x * NTRI * 256;
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], acc[t][r] + red[0][(t * 4 + r) * 64 + lane]);
-	}
+	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NTRI * 256, wv, lane);
+}
+template <int NT>
+__global__ __launch_bounds__(256) void gram_kernel(const GramArgs a) {
+	constexpr int NTRI = (NT * (NT + 1)) / 2;
+	__shared__ double red[2 * NTRI * 256];
+	announce_previous_call(a.announce, a.announce_seq);
+	if (a.skip_status && a.skip_status[0] != 0) return;
+	gram_body<NT, float>(a, red);
 }
 
 // gram_bf16_kernel: the same Gram tiles on v_mfma_f32_16x16x32_bf16 with the 3-way bf16 split of both operands
@@ -734,7 +805,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const GramArgs a) {
 template <int NT>
 __global__ __launch_bounds__(256) void gram_bf16_kernel(const GramArgs a) {
 	constexpr int NTRI = (NT * (NT + 1)) / 2;
-	__shared__ double red[2][NTRI * 256];
+	__shared__ double red[2 * NTRI * 256];
 	announce_previous_call(a.announce, a.announce_seq);
 	if (a.skip_status && a.skip_status[0] != 0) return;
 	const int lane = threadIdx.x & 63;
@@ -759,30 +830,16 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(const GramArgs a) {
 			for (int kt = 0; kt < 2; kt++) {             // K-step of 32 rows: registers 8kt .. 8kt+7 of every lane
 				bf16x8 oh[NT], om[NT], ol[NT];
 #pragma unroll
-				for (int t = 0; t < NT; t++) {
-					u32x4 hh, mm, ll;
+				for (int t = 0; t < NT; t++) split3_operand(p[t], kt, oh[t], om[t], ol[t]);
 #pragma unroll
-					for (int jp = 0; jp < 4; jp++) {
-						unsigned h, m, lo;
-						split3_pair(p[t][8 * kt + 2 * jp], p[t][8 * kt + 2 * jp + 1], h, m, lo);
-						hh[jp] = h; mm[jp] = m; ll[jp] = lo;
-					}
-					oh[t] = __builtin_bit_cast(bf16x8, hh);
-					om[t] = __builtin_bit_cast(bf16x8, mm);
-					ol[t] = __builtin_bit_cast(bf16x8, ll);
-				}
-				// six of the nine partial products of (h+m+l)x(h+m+l), smallest first: mm hl lh hm mh hh; consecutive MFMAs hit
-				// different accumulators
-#pragma unroll
-				for (int pass = 3; pass < 9; pass++) {
+				for (int pass = 3; pass < 9; pass++) {       // (split_a: the six products, smallest first)
 					int idx = 0;
 #pragma unroll
 					for (int ti = 0; ti < NT; ti++)
 #pragma unroll
 						for (int tj = ti; tj < NT; tj++) {
-							const bf16x8 av = (pass == 4 || pass == 6 || pass == 8) ? oh[ti] : ((pass == 3 || pass == 7) ? om[ti] : ol[ti]);
-							const bf16x8 bv = (pass == 5 || pass == 7 || pass == 8) ? oh[tj] : ((pass == 3 || pass == 6) ? om[tj] : ol[tj]);
-							acc[idx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[idx], 0, 0, 0);
+							acc[idx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(split_a(pass, oh[ti], om[ti], ol[ti]), split_b(pass, oh[tj], om[tj], ol[tj]),
+							                                                   acc[idx], 0, 0, 0);
 							idx++;
 						}
 				}
@@ -795,40 +852,14 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(const GramArgs a) {
 			}
 		}
 	}
-	// workgroup sum in fp64: waves 2,3 -> LDS, waves 0,1 add; wave 1 -> LDS, wave 0 adds and stores the partial
+	// (an identity copy that stays: with tot passed directly gram_bf16_kernel<2> takes 90 registers instead of 84 --
+	// profiles/refactor_gram_blocks_device_code.md)
 	double dacc[NTRI][4];
 #pragma unroll
 	for (int t = 0; t < NTRI; t++)
 #pragma unroll
 		for (int r = 0; r < 4; r++) dacc[t][r] = (double)tot[t][r];
-	if (wv >= 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[wv - 2][(t * 4 + r) * 64 + lane] = dacc[t][r];
-	}
-	__syncthreads();
-	if (wv < 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) dacc[t][r] += red[wv][(t * 4 + r) * 64 + lane];
-	}
-	__syncthreads();
-	if (wv == 1) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[0][(t * 4 + r) * 64 + lane] = dacc[t][r];
-	}
-	__syncthreads();
-	if (wv == 0) {
-		double* out = a.part + (size_t)blockIdx.x * NTRI * 256;
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], dacc[t][r] + red[0][(t * 4 + r) * 64 + lane]);
-	}
+	wg_sum4_store(dacc, red, a.part + (size_t)blockIdx.x * NTRI * 256, wv, lane);
 }
 
 // gram_h_kernel (round 3, fp16 I/O modes): the Gram tiles of an fp16 matrix straight from its halves -- lane (c,q) loads rows
@@ -901,7 +932,8 @@ __device__ __forceinline__ void gram_h_body(const GramArgs& a, double (*red)[((N
 			}
 		}
 	}
-	// workgroup sum in fp64: waves 2,3 -> LDS, waves 0,1 add; wave 1 -> LDS, wave 0 adds and stores the partial
+	// wg_sum4_store written out (the parent's text): through the helper the fp16 workload measured slower than the parent by more than
+	// the parent's own spread -- profiles/refactor_gram_blocks_ab.md
 	if (wv >= 2) {
 #pragma unroll
 		for (int t = 0; t < NTRI; t++)
@@ -1008,19 +1040,10 @@ __device__ __forceinline__ void gram_blk_body(const GramArgs& a, float* gb_as, c
 #pragma unroll
 		for (int t = 0; t < 4; t++) {
 			const float* src = &buf[(16 * t + c) * GB_RS + 32 * wv + 8 * q];
-			const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
-			u32x4 hh, mm, ll;
-			unsigned h, m, lo;
-			split3_pair(x0[0], x0[1], h, m, lo); hh[0] = h; mm[0] = m; ll[0] = lo;
-			split3_pair(x0[2], x0[3], h, m, lo); hh[1] = h; mm[1] = m; ll[1] = lo;
-			split3_pair(x1[0], x1[1], h, m, lo); hh[2] = h; mm[2] = m; ll[2] = lo;
-			split3_pair(x1[2], x1[3], h, m, lo); hh[3] = h; mm[3] = m; ll[3] = lo;
-			oh[t] = __builtin_bit_cast(bf16x8, hh);
-			om[t] = __builtin_bit_cast(bf16x8, mm);
-			ol[t] = __builtin_bit_cast(bf16x8, ll);
+			split3_operand(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), oh[t], om[t], ol[t]);
 		}
 		// tile pairs in the order of the partials, in two groups of five accumulators: (0,0) (0,1) (0,2) (0,3) (1,1) | (1,2) (1,3)
-		// (2,2) (2,3) (3,3); per pair six of the nine partial products, smallest first: mm hl lh hm mh hh (as gram_bf16_kernel).
+		// (2,2) (2,3) (3,3); per pair the six products of split_a.
 		// (A software-pipelined order -- split of tile t+1 interleaved with the MFMAs of the pairs that need only tiles <= t; vector
 		// instructions do issue in the shadow of MFMAs, tools/issue_overlap.py -- measured the same call time: not kept.)
 		static_for<0, 2>([&](auto gg) {
@@ -1034,9 +1057,8 @@ __device__ __forceinline__ void gram_blk_body(const GramArgs& a, float* gb_as, c
 					constexpr int idx = 5 * g + decltype(ii)::value;
 					constexpr int ti = idx < 4 ? 0 : (idx < 7 ? 1 : (idx < 9 ? 2 : 3));
 					constexpr int tj = idx < 4 ? idx : (idx < 7 ? idx - 3 : (idx < 9 ? idx - 5 : 3));
-					const bf16x8 av = (pass == 4 || pass == 6 || pass == 8) ? oh[ti] : ((pass == 3 || pass == 7) ? om[ti] : ol[ti]);
-					const bf16x8 bv = (pass == 5 || pass == 7 || pass == 8) ? oh[tj] : ((pass == 3 || pass == 6) ? om[tj] : ol[tj]);
-					acc[idx - 5 * g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[idx - 5 * g], 0, 0, 0);
+					acc[idx - 5 * g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(split_a(pass, oh[ti], om[ti], ol[ti]), split_b(pass, oh[tj], om[tj], ol[tj]),
+					                                                           acc[idx - 5 * g], 0, 0, 0);
 				});
 #pragma unroll
 			for (int i = 0; i < 5; i++)
@@ -1069,37 +1091,8 @@ __device__ __forceinline__ void gram_blk_body(const GramArgs& a, float* gb_as, c
 		if (bi >= bend) break;
 		stage(vx, gb_as + (it & 1) * BUF);
 	}
-	// workgroup sum in fp64: waves 2,3 -> LDS, waves 0,1 add; wave 1 -> LDS, wave 0 adds and stores the partial
-	__syncthreads();
-	double* red = reinterpret_cast<double*>(gb_as);      // [2][NTRI * 256]
-	if (wv >= 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[(wv - 2) * NTRI * 256 + (t * 4 + r) * 64 + lane] = tot[t][r];
-	}
-	__syncthreads();
-	if (wv < 2) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) tot[t][r] += red[wv * NTRI * 256 + (t * 4 + r) * 64 + lane];
-	}
-	__syncthreads();
-	if (wv == 1) {
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[(t * 4 + r) * 64 + lane] = tot[t][r];
-	}
-	__syncthreads();
-	if (wv == 0) {
-		double* out = a.part + (size_t)wg * NTRI * 256;
-#pragma unroll
-		for (int t = 0; t < NTRI; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], tot[t][r] + red[(t * 4 + r) * 64 + lane]);
-	}
+	__syncthreads();                                     // the workgroup sum aliases the block buffers
+	wg_sum4_store(tot, reinterpret_cast<double*>(gb_as), a.part + (size_t)wg * NTRI * 256, wv, lane);
 }
 __global__ __launch_bounds__(256, 2) void gram_blk_kernel(const GramArgs a) {
 	extern __shared__ __attribute__((aligned(16))) float gb_as[];        // [buffer][column][GB_RS]
@@ -1851,7 +1844,7 @@ struct CrossArgs {
 };
 
 __global__ __launch_bounds__(256, 2) void cross_kernel(const CrossArgs a) {
-	__shared__ float red[2][16 * 256];
+	__shared__ float red[2 * 16 * 256];
 	const int lane = threadIdx.x & 63;
 	const int wv = threadIdx.x >> 6;
 	const int gw = blockIdx.x * 4 + wv;
@@ -1872,64 +1865,23 @@ __global__ __launch_bounds__(256, 2) void cross_kernel(const CrossArgs a) {
 				bf16x8 xh[4], xm[4], xl[4], yh[4], ym[4], yl[4];
 #pragma unroll
 				for (int t = 0; t < 4; t++) {
-					u32x4 hh, mm, ll;
-#pragma unroll
-					for (int jp = 0; jp < 4; jp++) {
-						unsigned h, m, lo;
-						split3_pair(px[t][8 * kt + 2 * jp], px[t][8 * kt + 2 * jp + 1], h, m, lo);
-						hh[jp] = h; mm[jp] = m; ll[jp] = lo;
-					}
-					xh[t] = __builtin_bit_cast(bf16x8, hh); xm[t] = __builtin_bit_cast(bf16x8, mm); xl[t] = __builtin_bit_cast(bf16x8, ll);
-#pragma unroll
-					for (int jp = 0; jp < 4; jp++) {
-						unsigned h, m, lo;
-						split3_pair(py[t][8 * kt + 2 * jp], py[t][8 * kt + 2 * jp + 1], h, m, lo);
-						hh[jp] = h; mm[jp] = m; ll[jp] = lo;
-					}
-					yh[t] = __builtin_bit_cast(bf16x8, hh); ym[t] = __builtin_bit_cast(bf16x8, mm); yl[t] = __builtin_bit_cast(bf16x8, ll);
+					split3_operand(px[t], kt, xh[t], xm[t], xl[t]);
+					split3_operand(py[t], kt, yh[t], ym[t], yl[t]);
 				}
-				// six split products per tile, smallest first (mm hl lh hm mh hh); fp32 accumulation over this wave's rows as before
+				// the six products of split_a per tile; fp32 accumulation over this wave's rows
 #pragma unroll
 				for (int pass = 3; pass < 9; pass++)
 #pragma unroll
 					for (int ti = 0; ti < 4; ti++)
 #pragma unroll
-						for (int tj = 0; tj < 4; tj++) {
-							const bf16x8 av = (pass == 4 || pass == 6 || pass == 8) ? xh[ti] : ((pass == 3 || pass == 7) ? xm[ti] : xl[ti]);
-							const bf16x8 bv = (pass == 5 || pass == 7 || pass == 8) ? yh[tj] : ((pass == 3 || pass == 6) ? ym[tj] : yl[tj]);
-							acc[4 * ti + tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[4 * ti + tj], 0, 0, 0);
-						}
+						for (int tj = 0; tj < 4; tj++)
+							acc[4 * ti + tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(split_a(pass, xh[ti], xm[ti], xl[ti]), split_b(pass, yh[tj], ym[tj], yl[tj]),
+							                                                           acc[4 * ti + tj], 0, 0, 0);
 			}
 		}
 	}
-	if (wv >= 2) {
-#pragma unroll
-		for (int t = 0; t < 16; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[wv - 2][(t * 4 + r) * 64 + lane] = acc[t][r];
-	}
-	__syncthreads();
-	if (wv < 2) {
-#pragma unroll
-		for (int t = 0; t < 16; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) acc[t][r] += red[wv][(t * 4 + r) * 64 + lane];
-	}
-	__syncthreads();
-	if (wv == 1) {
-#pragma unroll
-		for (int t = 0; t < 16; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) red[0][(t * 4 + r) * 64 + lane] = acc[t][r];
-	}
-	__syncthreads();
-	if (wv == 0) {
-		double* out = a.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 * 256;
-#pragma unroll
-		for (int t = 0; t < 16; t++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], (double)(acc[t][r] + red[0][(t * 4 + r) * 64 + lane]));
-	}
+	// (the waves' sums in fp32, as the accumulators; the partial is the fp32 sum widened)
+	wg_sum4_store(acc, red, a.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 * 256, wv, lane);
 }
 
 // the reduction of cross_kernel's partials for ALL trailing panels of a finished panel in one launch (grid (256, trailing panels)):
@@ -2431,31 +2383,21 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 #pragma unroll
 				for (int t = 0; t < NT; t++) {
 					const int col = 16 * t + c;
-					const f32x4 x0 = *reinterpret_cast<const f32x4*>(&As[col * RS + (rbk ^ swz(col))]);
-					const f32x4 x1 = *reinterpret_cast<const f32x4*>(&As[col * RS + ((rbk + 4) ^ swz(col))]);
-					u32x4 hh, mm, ll;
-					unsigned h, m, lo;
-					split3_pair(x0[0], x0[1], h, m, lo); hh[0] = h; mm[0] = m; ll[0] = lo;
-					split3_pair(x0[2], x0[3], h, m, lo); hh[1] = h; mm[1] = m; ll[1] = lo;
-					split3_pair(x1[0], x1[1], h, m, lo); hh[2] = h; mm[2] = m; ll[2] = lo;
-					split3_pair(x1[2], x1[3], h, m, lo); hh[3] = h; mm[3] = m; ll[3] = lo;
-					oh[t] = __builtin_bit_cast(bf16x8, hh);
-					om[t] = __builtin_bit_cast(bf16x8, mm);
-					ol[t] = __builtin_bit_cast(bf16x8, ll);
+					split3_operand(*reinterpret_cast<const f32x4*>(&As[col * RS + (rbk ^ swz(col))]),
+					               *reinterpret_cast<const f32x4*>(&As[col * RS + ((rbk + 4) ^ swz(col))]), oh[t], om[t], ol[t]);
 				}
 				f32x4 gacc[NTRI];
 #pragma unroll
 				for (int t = 0; t < NTRI; t++) gacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-				for (int pass = 3; pass < 9; pass++) {       // mm hl lh hm mh hh (smallest first), as in gram_bf16_kernel
+				for (int pass = 3; pass < 9; pass++) {       // (split_a: the six products, smallest first)
 					int idx = 0;
 #pragma unroll
 					for (int ti = 0; ti < NT; ti++)
 #pragma unroll
 						for (int tj = ti; tj < NT; tj++) {
-							const bf16x8 av = (pass == 4 || pass == 6 || pass == 8) ? oh[ti] : ((pass == 3 || pass == 7) ? om[ti] : ol[ti]);
-							const bf16x8 bv = (pass == 5 || pass == 7 || pass == 8) ? oh[tj] : ((pass == 3 || pass == 6) ? om[tj] : ol[tj]);
-							gacc[idx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, gacc[idx], 0, 0, 0);
+							gacc[idx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(split_a(pass, oh[ti], om[ti], ol[ti]), split_b(pass, oh[tj], om[tj], ol[tj]),
+							                                                    gacc[idx], 0, 0, 0);
 							idx++;
 						}
 				}
@@ -2504,36 +2446,8 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 		__syncthreads();
 	}
 	if constexpr (GRAMQ) {
-		// workgroup sum in fp64 (LDS aliases As / the Z image: every wave has passed the loop's last barrier), as in gram_bf16_kernel
-		double* red = reinterpret_cast<double*>(smem);   // [2][NTRI*256]
-		if (wv >= 2) {
-#pragma unroll
-			for (int t = 0; t < NTRI; t++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) red[(size_t)(wv - 2) * NTRI * 256 + (t * 4 + r) * 64 + lane] = gtot[t][r];
-		}
-		__syncthreads();
-		if (wv < 2) {
-#pragma unroll
-			for (int t = 0; t < NTRI; t++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) gtot[t][r] += red[(size_t)wv * NTRI * 256 + (t * 4 + r) * 64 + lane];
-		}
-		__syncthreads();
-		if (wv == 1) {
-#pragma unroll
-			for (int t = 0; t < NTRI; t++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) red[(t * 4 + r) * 64 + lane] = gtot[t][r];
-		}
-		__syncthreads();
-		if (wv == 0) {
-			double* out = a.gpart + (size_t)blockIdx.x * NTRI * 256;
-#pragma unroll
-			for (int t = 0; t < NTRI; t++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) part_store(&out[(t * 4 + r) * 64 + lane], gtot[t][r] + red[(t * 4 + r) * 64 + lane]);
-		}
+		// the workgroup sum aliases As / the Z image: every wave has passed the loop's last barrier
+		wg_sum4_store(gtot, reinterpret_cast<double*>(smem), a.gpart + (size_t)blockIdx.x * NTRI * 256, wv, lane);
 	}
 }
 

@@ -87,7 +87,7 @@ __device__ __forceinline__ void gram_wide_step(f32x4 (&acc)[9], const unsigned* 
 		if constexpr (b + 1 < R.ncol) fetch_col((b + 1) & 1, R.col[b + 1]);
 		__builtin_amdgcn_sched_barrier(0);
 		const bf16x8 bh = bimg[b & 1][0], bm = bimg[b & 1][1], bl = bimg[b & 1][2];
-		// six of the nine partial products, smallest first: mm hl lh hm mh hh (as gram_bf16_kernel)
+		// the six products of split_a (tsqr_kernels.hip)
 		static_for<3, 9>([&](auto pp) {
 			constexpr int pass = decltype(pp)::value;
 			static_for<0, 9>([&](auto ii) {
@@ -97,9 +97,7 @@ __device__ __forceinline__ void gram_wide_step(f32x4 (&acc)[9], const unsigned* 
 					bf16x8 ah_, am_, al_;
 					if constexpr (ta < 0) { ah_ = bh; am_ = bm; al_ = bl; }
 					else { ah_ = rh[ta]; am_ = rm[ta]; al_ = rl[ta]; }
-					const bf16x8 av = (pass == 4 || pass == 6 || pass == 8) ? ah_ : ((pass == 3 || pass == 7) ? am_ : al_);
-					const bf16x8 bv = (pass == 5 || pass == 7 || pass == 8) ? bh : ((pass == 3 || pass == 6) ? bm : bl);
-					acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[p], 0, 0, 0);
+					acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(split_a(pass, ah_, am_, al_), split_b(pass, bh, bm, bl), acc[p], 0, 0, 0);
 				}
 			});
 		});
