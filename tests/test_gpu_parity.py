@@ -187,6 +187,79 @@ def test_ill_conditioned_reorth(bq, oracle, torch_cuda, cond, mode):
         assert oracle.orthogonality_fro(q0) < 3 * max(oracle.orthogonality_fro(q_o0), 2e-6)
 
 
+@pytest.mark.parametrize("case,want_engine", [("policy4", 1), ("policy4_cond1e9", 2), ("profile", 3), ("two_equal_columns", 4),
+                                              ("zero_column", 4), ("nan", 2)])
+def test_reorth_ladder_branches(bq, oracle, torch_cuda, case, want_engine):
+    """Reorthogonalize = true, one panel, down the branches of the two-sweep ladder no other test enters: the optimistic attempt (policy 4:
+    the fp64 Gram level first) accepted and rejected; the checked two-sweep path a profiled call takes (its engine code is the unprofiled
+    call's, so the launch counts of the profile tell it apart: ONE Gram pass for two sweeps, the second sweep takes the partials of the
+    first one's apply launch); two equal columns, which the shifted three-sweep schedule absorbs; a zero column, where Q1 is rank
+    deficient, both attempts of sweep 2 are rejected and checked sweeps on Q in place finish the call (the engine code is the same 4:
+    which of the two ran is known from the recorded launch lists, profiles/refactor_sweep_opts_digests.md); and a sweep 1 that is
+    rejected outright (a NaN: the checked ladder from the fp64 level, which ends in the Householder engine).  State, engine and the
+    bands of the neighbouring tests."""
+    m, n = 4096, 48
+    a = oracle.matrix_with_cond(m, n, 1e9, seed=5) if case == "policy4_cond1e9" else oracle.uniform_matrix(m, n, seed=21)
+    if case == "two_equal_columns":
+        a[:, n - 1] = a[:, 1]
+    if case == "zero_column":
+        a[:, n - 1] = 0.0
+    if case == "nan":
+        a[m // 3, n // 2] = np.nan
+    bq.set_policy(bq.POLICY_AUTO_NO_BF16 if case.startswith("policy4") else bq.POLICY_AUTO)
+    bq.profile_enable(case == "profile")
+    try:
+        st, q, r = run_gpu(bq, torch_cuda, a, bq.compute_mode.fp32_tc_cor, True)
+        eng = bq.last_engine()
+        prof = bq.profile_read()
+    finally:
+        bq.profile_enable(False)
+        bq.set_policy(bq.POLICY_AUTO)
+    assert st == bq.success_factorization and eng == want_engine, (st, eng)
+    assert np.abs(np.tril(r, -1)).max() == 0.0
+    if case == "profile":
+        assert prof["gram"][1] == 1 and prof["apply"][1] == 2, prof
+    if case == "nan":
+        return                                                       # (no factors to measure)
+    assert np.isfinite(q).all()
+    well = case in ("policy4", "profile")
+    assert oracle.residual(a, q, r) < (RES_TOL if well else 2e-6)
+    if case not in ("two_equal_columns", "zero_column"):              # (a dependent column has no orthonormal direction of its own)
+        assert oracle.orthogonality_fro(q) < (ORTH_TOL if well else 1e-5)
+
+
+def test_small_n_second_sweep_behind_an_accepted_bf16_level(bq, oracle, torch_cuda):
+    """n <= 16 without reorthogonalisation, the bf16-split level ACCEPTS and reports S > 32: the second sweep on Q in place runs, in the
+    blocking call and -- the attempt of submit() stands, finish() enters the ladder with nothing but that sweep left -- through
+    submit / finish.  The bf16 level accepts S <= 0.12 sqrt(rows), so the smallest such matrix has 2^17 rows (bound 43.4).  Gaussian columns
+    e_j + w e_0 (j > 0) next to e_0 have S = mean_j g_jj (G^-1)_jj = 1 + 2 (n - 1) w^2 / n: 37.3 for n = 16, w = 4.4."""
+    torch = torch_cuda
+    m, n, w = 1 << 17, 16, 4.4
+    rng = np.random.default_rng(7)
+    a = rng.standard_normal((m, n)).astype(np.float32)
+    a[:, 1:] += np.float32(w) * a[:, :1]
+    md = bq.compute_mode.fp32_tc_cor
+    bq.profile_enable(True)
+    try:
+        st, q, r = run_gpu(bq, torch, a, md, False)
+        prof = bq.profile_read()
+    finally:
+        bq.profile_enable(False)
+    assert st == 0 and bq.last_engine() == 3
+    assert prof["gram"][1] == 2 and prof["apply"][1] == 2, prof          # two sweeps, both at the bf16 level
+    assert np.abs(np.tril(r, -1)).max() == 0.0
+    assert oracle.residual(a, q, r) < 2e-6 and oracle.orthogonality_fro(q) < 5e-6      # (the bands of test_small_n_ill_conditioned_without_reorth)
+    d_a = torch.from_numpy(np.ascontiguousarray(a.T)).cuda()
+    d_q = torch.zeros(n, m, device="cuda"); d_r = torch.zeros(n, n, device="cuda")
+    bf = bq.buffer(md, False)
+    bf.allocate(m, n)
+    t = bq.submit(d_q, m, d_r, n, d_a, m, m, n, bf)
+    assert t.pending == 1                                            # (a speculative attempt is in flight)
+    assert bq.finish(t) == 0 and bq.last_engine() == 3
+    assert t.verdict == 0 and 32.0 < t.scond < 0.12 * np.sqrt(m)      # accepted with S > 32: only the second sweep was left to finish()
+    assert np.array_equal(d_q.cpu().numpy().T, q) and np.array_equal(d_r.cpu().numpy().T, r)      # the blocking call's launches, bit for bit
+
+
 def test_error_codes_on_gpu(bq, torch_cuda):
     torch = torch_cuda
     t = torch.zeros(64, device="cuda")

@@ -295,6 +295,16 @@ void* rccl_symbol(const char* name) { return dlsym(RTLD_DEFAULT, name); }
 // per-call context
 // ---------------------------------------------------------------------------------------------------------------------------
 struct HostSig { unsigned* host = nullptr; unsigned* dev = nullptr; };
+// What ONE sweep is told (Ctx: what holds for the whole call).  Built where the sweep is enqueued and handed down by reference; nothing
+// below writes to it.  The stream schedules and the staged entry points, which enqueue the launches of a sweep themselves, say {slot}.
+struct SweepOpts {
+	int slot = 0, prev_slot = -1;                        // status slot its verdicts go to / of the sweep it depends on (-1: none; rejected there: this one skips itself)
+	int gramq_ready = 0;                                 // > 0: so many partials of this sweep's bf16-level Gram matrix are in place already (the pass is skipped)
+	double* gramq_part = nullptr; int gramq_cap = 0;     // non-null: the apply launch writes per-workgroup Gram partials of its output there, gramq_cap at the most
+	int relax = 0;                                       // bf16-level Cholesky launches use the relaxed rule (CholArgs::relax: another sweep follows)
+	int retry_shift = 0;                                 // ... and factor a rejected matrix again at once, shifted (CholArgs::retry_shift)
+	bool q_read_back = false;                            // Q is read back at once by the next sweep: plain stores, ascending block order (ApplyArgs::plain_q / forward)
+};
 struct Ctx {
 	hipStream_t st = nullptr;
 	int dev = 0;
@@ -306,10 +316,6 @@ struct Ctx {
 	int min_level = 2;                                   // lowest R-factor engine level used (2 bf16 Gram, 1 fp64 Gram, 0 Householder)
 	bool used_shift = false, used_householder = false;
 	bool wide = true;                                    // 64 < n <= 128: try the one-panel path first
-	int slot = 0, prev_slot = -1;                        // status slot of the sweep being enqueued / of the sweep it depends on (-1: none)
-	double* gramq_part = nullptr;                        // non-null: apply launches write per-workgroup Gram partials of their output there
-	int gramq_cap = 0, gramq_nparts = 0;
-	bool gramq_ready = false;                            // the next bf16-level Gram request can skip its pass (partials are in place)
 	Comm comm;
 	bool fold_cor = false;                               // Householder engine: block reflectors on the error-corrected bf16x3 MFMA (fp32_tc_cor)
 	bool resume_accepted = false;                        // tsqr_mi_qr_f32_finish: the first attempt ran already and was accepted with
@@ -317,9 +323,6 @@ struct Ctx {
 	int start_level = -1;                                // tsqr_mi_qr_f32_finish: the ladder resumes at this level (the ones above were rejected)
 	unsigned* announce_word = nullptr;                   // completion word of the call in front of this one, raised by this call's first
 	unsigned announce_seq = 0;                           // Gram kernel (consumed by the launch that carries it)
-	bool q_for_next_sweep = false;                       // apply launches write Q for a sweep that reads it back at once: plain stores, ascending block order (ApplyArgs)
-	int chol_relax = 0;                                  // the next bf16-level Cholesky launches use the relaxed rule (CholArgs::relax: another sweep follows)
-	int chol_retry_shift = 0;                            // ... and factor a rejected matrix again at once, shifted (CholArgs::retry_shift)
 	double rows_global = 0.0;                            // host's view of the global row count (the device thresholds of a row-partitioned
 	                                                     // call use the all-reduced count instead)
 	unsigned* status_dev(int s) const { return reinterpret_cast<unsigned*>(wq + L.status) + 16 * s; }
@@ -547,19 +550,18 @@ inline bool blk_gram_ok(const float* a, size_t lda, size_t m, size_t n) {
 // Gram matrix of src (m x n) in MFMA-accumulator order -> c.gsum() (ntri*256 doubles + the local row count behind them), summed
 // over the ranks of a row-partitioned call.  bf16 = true: bf16x3-split MFMA (memory-bound, f32 C/D layout), false: fp64 MFMA.
 // io_half: src holds halves (fp16 I/O modes, bf16 level only): gram_h_kernel takes them as MFMA operands directly.
-int gram_g(Ctx& c, const float* src, size_t ld, size_t m, size_t n, bool bf16, bool io_half = false) {
+int gram_g(Ctx& c, const SweepOpts& o, const float* src, size_t ld, size_t m, size_t n, bool bf16, bool io_half = false) {
 	const GramPlan g = gram_plan(m, n);
 	const int NT = (int)(np_of(n) / 16);
 	tsqrmi::GramArgs a{};
 	a.a = src; a.lda = ld; a.m = m; a.n = (int)n; a.nchunks = g.nch; a.cpw = g.cpw; a.nwaves = g.nwaves;
 	a.part = reinterpret_cast<double*>(c.wr);
-	a.skip_status = c.prev_slot >= 0 ? c.status_dev(c.prev_slot) : nullptr;
-	if (!(bf16 && c.gramq_ready)) carry_announcement(c, a);
+	a.skip_status = o.prev_slot >= 0 ? c.status_dev(o.prev_slot) : nullptr;
+	const bool ready = bf16 && o.gramq_ready > 0;        // the previous sweep's apply kernel accumulated this very Gram matrix (fp64-level requests never take it)
+	if (!ready) carry_announcement(c, a);
 	int nparts = g.nblocks;                              // workgroups that wrote a partial
-	if (bf16 && c.gramq_ready) {                         // the previous sweep's apply kernel accumulated this very Gram matrix
-		c.gramq_ready = false;
-		nparts = c.gramq_nparts;
-	} else if (io_half) {
+	if (ready) nparts = o.gramq_ready;
+	else if (io_half) {
 		ProfScope ps(KC_GRAM, c.st);
 		with_nt(NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gram_h_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, c.st, a); });
 	} else if (bf16 && blk_gram_ok(src, ld, m, n)) {
@@ -593,38 +595,38 @@ int gram_g(Ctx& c, const float* src, size_t ld, size_t m, size_t n, bool bf16, b
 	return 0;
 }
 
-// The arguments of chol16_kernel: R = chol(G) (n x n, ldr), Z = inverse(R) (NP x NP in wq[L.z]), status words -> slot `slot` (the chained
+// The arguments of chol16_kernel: R = chol(G) (n x n, ldr), Z = inverse(R) (NP x NP in wq[L.z]), status words -> slot o.slot (the chained
 // schedules: half i & 1 of call i).  level: 2 bf16, 1 fp64, 3 shifted fp64.
-tsqrmi::CholArgs chol_args(const Ctx& c, float* r, size_t ldr, size_t n, int level, int slot) {
+tsqrmi::CholArgs chol_args(const Ctx& c, const SweepOpts& o, float* r, size_t ldr, size_t n, int level) {
 	tsqrmi::CholArgs a{};
 	a.r = r; a.ldr = ldr; a.z = c.wq + c.L.z;
-	a.status = c.status_dev(slot);
-	a.host_status = c.hsig.dev ? c.hsig.dev + 4 * slot : nullptr;
+	a.status = c.status_dev(o.slot);
+	a.host_status = c.hsig.dev ? c.hsig.dev + 4 * o.slot : nullptr;
 	a.gsum = c.gsum();
-	a.prev_status = c.prev_slot >= 0 ? c.status_dev(c.prev_slot) : nullptr;
+	a.prev_status = o.prev_slot >= 0 ? c.status_dev(o.prev_slot) : nullptr;
 	const int NT = (int)(np_of(n) / 16);
 	a.rows_dev = c.comm.active() ? c.gsum() + (size_t)(NT * (NT + 1) / 2) * 256 : nullptr;
 	a.rows = c.rows_global;
 	a.shift_coef = (level == 3) ? 11.0 * 1.1102230246251565e-16 : 0.0;
 	a.n = (int)n; a.NT = NT; a.level = level; a.scond_floor = g_set.bf16_scond_floor;
-	if (level == 2) { a.relax = c.chol_relax; a.retry_shift = c.chol_retry_shift; }
+	if (level == 2) { a.relax = o.relax; a.retry_shift = o.retry_shift; }
 	return a;
 }
-int chol_from_g(Ctx& c, float* r, size_t ldr, size_t n, int level) {
+int chol_from_g(Ctx& c, const SweepOpts& o, float* r, size_t ldr, size_t n, int level) {
 	{
 		ProfScope ps(KC_CHOL, c.st);
-		hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, r, ldr, n, level, c.slot));
+		hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, o, r, ldr, n, level));
 	}
 	HIPCHK(hipGetLastError());
 	return 0;
 }
 
-// apply_wg_kernel launcher: args.nchunks = row blocks of ROWS, args.nwaves = workgroups (persistent grid)
+// apply_wg_kernel launcher: args.nchunks = row blocks of ROWS, args.nwaves = workgroups (persistent grid); GRAMQ: their number -> *gramq_nparts
 template <int E, int NT, bool UPD, int ROWS, bool GRAMQ> constexpr auto apply_wg_entry() {
 	if constexpr (GRAMQ) return &tsqrmi::apply_wg_gramq_kernel<E, NT, UPD, ROWS>;
 	else return &tsqrmi::apply_wg_kernel<E, NT, UPD, ROWS>;
 }
-template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_apply_wg(Ctx& c, tsqrmi::ApplyArgs a) {
+template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_apply_wg(Ctx& c, const SweepOpts& o, int* gramq_nparts, tsqrmi::ApplyArgs a) {
 	constexpr auto kernel = apply_wg_entry<E, NT, UPD, ROWS, GRAMQ>();
 	constexpr int NP = 16 * NT, KT = (NP + 31) / 32;
 	constexpr int NB = (!UPD && NT == 4) ? 6 : KT * NT;  // operand blocks of Z kept in LDS (apply_wg_kernel: COMPACT)
@@ -655,9 +657,9 @@ template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_appl
 	a.nwaves = (int)std::min<size_t>(nblk, want);
 	a.cpw = 0;
 	if constexpr (GRAMQ) {
-		a.nwaves = std::min(a.nwaves, c.gramq_cap);      // one partial per workgroup: never more than the buffer holds
-		a.gpart = c.gramq_part;
-		c.gramq_nparts = a.nwaves;
+		a.nwaves = std::min(a.nwaves, o.gramq_cap);      // one partial per workgroup: never more than the buffer holds
+		a.gpart = o.gramq_part;
+		if (gramq_nparts) *gramq_nparts = a.nwaves;
 	}
 	if constexpr (!UPD && !GRAMQ && ROWS == 64) {
 		// Four workgroups per CU on the whole chip: uneven shares by XCD parity and by dispatch round (apply_wg_body; round 3, on every box
@@ -709,15 +711,15 @@ template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_appl
 	hipLaunchKernelGGL(kernel, dim3(a.nwaves, gy), dim3(256), lds, c.st, a);
 	return 0;
 }
-template <int E, int NT, bool UPD> int launch_apply_any(Ctx& c, const tsqrmi::ApplyArgs& a) {
+template <int E, int NT, bool UPD> int launch_apply_any(Ctx& c, const SweepOpts& o, int* gramq_nparts, const tsqrmi::ApplyArgs& a) {
 	if constexpr (!UPD && E != 0) {                      // (the fp32-MFMA engine's fused variant spills and loses: 0.29 vs 0.22 ms per apply)
-		if (c.gramq_part && c.gramq_cap > 0) return launch_apply_wg<E, NT, UPD, 128, true>(c, a);
+		if (o.gramq_part && o.gramq_cap > 0) return launch_apply_wg<E, NT, UPD, 128, true>(c, o, gramq_nparts, a);
 	}
 	// block height per engine (measured, profiles/r02_experiment_log.md): the bf16x3 engine streams best with 64-row blocks, four
 	// workgroups per CU and two blocks in flight (88 vs 92 us at 2^20 x 64); the exact-fp32 and fp16 engines and the coupling
 	// update (UPD) use 128-row blocks
-	if constexpr (!UPD && E == 1) return launch_apply_wg<E, NT, UPD, 64>(c, a);
-	else return launch_apply_wg<E, NT, UPD, 128>(c, a);
+	if constexpr (!UPD && E == 1) return launch_apply_wg<E, NT, UPD, 64>(c, o, gramq_nparts, a);
+	else return launch_apply_wg<E, NT, UPD, 128>(c, o, gramq_nparts, a);
 }
 // fp16 I/O modes: the plain product with halves at both ends -- bf16x3 engine 1 (fp16_notc) or single-fp16-product engine 2
 // (fp16_tc_nocor); 64- / 128-row blocks as in the fp32 call, two blocks in flight
@@ -748,13 +750,13 @@ template <int E, int NT> int launch_apply_h(Ctx& c, tsqrmi::ApplyArgs a) {
 template <int E> int dispatch_apply_h(Ctx& c, int NT, const tsqrmi::ApplyArgs& a) {
 	return with_nt(NT, [&](auto nt) { return launch_apply_h<E, decltype(nt)::value>(c, a); });
 }
-template <int E> int dispatch_apply_nt(Ctx& c, int NT, const tsqrmi::ApplyArgs& a) {
-	return with_nt(NT, [&](auto nt) { return launch_apply_any<E, decltype(nt)::value, false>(c, a); });
+template <int E> int dispatch_apply_nt(Ctx& c, const SweepOpts& o, int* gramq_nparts, int NT, const tsqrmi::ApplyArgs& a) {
+	return with_nt(NT, [&](auto nt) { return launch_apply_any<E, decltype(nt)::value, false>(c, o, gramq_nparts, a); });
 }
 
 // q = a * inverse(r); n <= 64; Z in wq[L.z] (computed here from r unless z_ready)
-// io_half: a and q hold halves (fp16 I/O modes; engines 1 and 2)
-int apply_rinv(Ctx& c, int engine, float* q, size_t ldq, const float* a, size_t lda, const float* r, size_t ldr,
+// io_half: a and q hold halves (fp16 I/O modes; engines 1 and 2).  gramq_nparts (may be null): see launch_apply_wg
+int apply_rinv(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, float* q, size_t ldq, const float* a, size_t lda, const float* r, size_t ldr,
                size_t m, size_t n, bool z_ready = false, const unsigned* skip_status = nullptr, bool io_half = false,
                void* r16 = nullptr, size_t ldr16 = 0) {
 	const size_t NP = np_of(n);
@@ -768,13 +770,13 @@ int apply_rinv(Ctx& c, int engine, float* q, size_t ldq, const float* a, size_t 
 	tsqrmi::ApplyArgs aa{};
 	aa.a = a; aa.lda = lda; aa.q = q; aa.ldq = ldq; aa.m = m; aa.n = (int)n; aa.z = z_buf; aa.skip_status = skip_status;
 	aa.r32 = r; aa.r16 = r16; aa.ldr16 = ldr16;         // (io_half with r16: r is then a packed n x n factor, ld n)
-	aa.plain_q = aa.forward = c.q_for_next_sweep ? 1 : 0;
+	aa.plain_q = aa.forward = o.q_read_back ? 1 : 0;
 	int rc;
 	{
 		ProfScope ps(KC_APPLY, c.st);
 		rc = with_engine(engine, [&](auto e) {
 			constexpr int E = decltype(e)::value;
-			if (!io_half) return dispatch_apply_nt<E>(c, NT, aa);
+			if (!io_half) return dispatch_apply_nt<E>(c, o, gramq_nparts, NT, aa);
 			if constexpr (E == 1) return dispatch_apply_h<1>(c, NT, aa);
 			else return dispatch_apply_h<2>(c, NT, aa);  // (halves: the bf16x3 engine or the single-fp16-product one)
 		});
@@ -840,28 +842,30 @@ constexpr int R_SHIFT_DIRECT = 9;
 // R factor and Q of one <= 64-column panel.  r_engine: first Gram level (2 / 1), 0 = Householder, R_SHIFT_DIRECT = the caller has
 // just seen the fp64 Gram level reject this very panel (its Gram matrix is still in the work buffer): shifted-Cholesky step at once.
 // check_now: read each verdict immediately (one wait) and escalate on rejection; otherwise enqueue speculatively.
-int panel_qr(Ctx& c, int engine, int r_engine, bool check_now, float* qp, size_t ldq, float* rpp, size_t ldr, const float* ap, size_t lda,
+int panel_qr(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, int r_engine, bool check_now, float* qp, size_t ldq, float* rpp, size_t ldr, const float* ap, size_t lda,
              size_t m, size_t cc) {
 	int rc;
 	const bool direct_shift = (r_engine == R_SHIFT_DIRECT);
 	if (direct_shift) r_engine = 0;
 	for (int e = r_engine; e >= 1; e--) {                // 2: bf16-split Gram, 1: fp64 Gram; with check_now a rejected level escalates
-		rc = gram_g(c, ap, lda, m, cc, e == 2);
+		// (o.gramq_ready: only the bf16-level request, e == 2, takes ready partials, and this loop makes one such request at the most.  Sweeps
+		// are fused for n <= 64 alone -- one panel, one call of this function -- so the sweep's value can be forwarded as it is.)
+		rc = gram_g(c, o, ap, lda, m, cc, e == 2);
 		if (rc) return rc;
-		rc = chol_from_g(c, rpp, ldr, cc, e);
+		rc = chol_from_g(c, o, rpp, ldr, cc, e);
 		if (rc) return rc;
 		bool ok = true;
 		if (check_now) {
 			unsigned status = 0;
-			rc = read_status(c, c.slot, &status);
+			rc = read_status(c, o.slot, &status);
 			if (rc) return rc;
 			ok = (status == 0);
 		}
 		if (ok) {
 			c.min_level = std::min(c.min_level, e);
 			// speculative (unchecked) launch under the auto policy: the kernel itself skips the pass when the level was rejected
-			const unsigned* skip = (!check_now && c.policy == 0) ? c.status_dev(c.slot) : nullptr;
-			return apply_rinv(c, engine, qp, ldq, ap, lda, rpp, ldr, m, cc, /*z_ready=*/true, skip);
+			const unsigned* skip = (!check_now && c.policy == 0) ? c.status_dev(o.slot) : nullptr;
+			return apply_rinv(c, o, gramq_nparts, engine, qp, ldq, ap, lda, rpp, ldr, m, cc, /*z_ready=*/true, skip);
 		}
 	}
 	if ((direct_shift || (r_engine >= 1 && check_now)) && c.policy == 0) {
@@ -870,38 +874,38 @@ int panel_qr(Ctx& c, int engine, int r_engine, bool check_now, float* qp, size_t
 		// sweep on Q1 in place finishes the panel: A = Q (R2 R1).  About 2x faster than the Householder fold below and, after that
 		// second step, at least as orthogonal as its single indirect sweep.
 		float* r1 = c.wq + c.L.r3; float* r2 = c.wq + c.L.r4;
-		rc = chol_from_g(c, r1, cc, cc, 3);
+		rc = chol_from_g(c, o, r1, cc, cc, 3);
 		if (rc) return rc;
 		unsigned status = 0;
-		rc = read_status(c, c.slot, &status);
+		rc = read_status(c, o.slot, &status);
 		if (rc) return rc;
 		if (status == 0) {
-			rc = apply_rinv(c, engine, qp, ldq, ap, lda, r1, cc, m, cc, /*z_ready=*/true);
+			rc = apply_rinv(c, o, gramq_nparts, engine, qp, ldq, ap, lda, r1, cc, m, cc, /*z_ready=*/true);
 			if (rc) return rc;
-			rc = gram_g(c, qp, ldq, m, cc, /*bf16=*/false);
+			rc = gram_g(c, o, qp, ldq, m, cc, /*bf16=*/false);
 			if (rc) return rc;
-			rc = chol_from_g(c, r2, cc, cc, 1);
+			rc = chol_from_g(c, o, r2, cc, cc, 1);
 			if (rc) return rc;
-			rc = read_status(c, c.slot, &status);
+			rc = read_status(c, o.slot, &status);
 			if (rc) return rc;
 			if (status == 0) {
-				rc = apply_rinv(c, engine, qp, ldq, qp, ldq, r2, cc, m, cc, /*z_ready=*/true);
+				rc = apply_rinv(c, o, gramq_nparts, engine, qp, ldq, qp, ldq, r2, cc, m, cc, /*z_ready=*/true);
 			} else {
 				// Q1 is still numerically rank deficient: the input has an (almost) exactly dependent column whose rounding residue is
 				// itself dependent (e.g. two constant columns).  No triangular solve can make an orthonormal column out of that; a
 				// second SHIFTED step keeps everything bounded instead -- the other columns come out orthonormal, the residual stays
 				// at rounding level, R shows the deficiency as a tiny diagonal entry and that one column of Q is left un-normalised.
-				rc = chol_from_g(c, r2, cc, cc, 3);
+				rc = chol_from_g(c, o, r2, cc, cc, 3);
 				if (rc) return rc;
-				rc = read_status(c, c.slot, &status);
+				rc = read_status(c, o.slot, &status);
 				if (rc) return rc;
 				if (status == 0) {
-					rc = apply_rinv(c, engine, qp, ldq, qp, ldq, r2, cc, m, cc, /*z_ready=*/true);
+					rc = apply_rinv(c, o, gramq_nparts, engine, qp, ldq, qp, ldq, r2, cc, m, cc, /*z_ready=*/true);
 				} else {                                     // non-finite data: last resort, the Householder engine on Q1
 					c.used_householder = true;
 					rc = householder_r(c, r2, cc, qp, ldq, m, cc);
 					if (rc) return rc;
-					rc = apply_rinv(c, engine, qp, ldq, qp, ldq, r2, cc, m, cc);
+					rc = apply_rinv(c, o, gramq_nparts, engine, qp, ldq, qp, ldq, r2, cc, m, cc);
 				}
 			}
 			if (rc) return rc;
@@ -916,10 +920,10 @@ int panel_qr(Ctx& c, int engine, int r_engine, bool check_now, float* qp, size_t
 	c.used_householder = true;
 	rc = householder_r(c, rpp, ldr, ap, lda, m, cc);
 	if (rc) return rc;
-	return apply_rinv(c, engine, qp, ldq, ap, lda, rpp, ldr, m, cc);
+	return apply_rinv(c, o, gramq_nparts, engine, qp, ldq, ap, lda, rpp, ldr, m, cc);
 }
 
-int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, const float* a, size_t lda, size_t m, size_t n);
+int sweep_wide(Ctx& c, const SweepOpts& o, int engine, float* q, size_t ldq, float* r, size_t ldr, const float* a, size_t lda, size_t m, size_t n);
 
 // one sweep of 64-wide-panel block QR:  (q, r) <- qr(a);  a is overwritten for n > 64; q may alias a.
 // Panels are coupled by block MODIFIED Gram-Schmidt on the matrix cores (the role of the reference's cuBLAS GEMMs, src/blockqr.cu:92-116),
@@ -929,7 +933,8 @@ int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, c
 // same sequence, every S_j is summed in the same grouping: bit for bit the same factors), but one update launch per PANEL instead of one
 // per panel pair, and the S launches grouped as far as the work space goes: at small row counts the launches finally have the chip's
 // worth of workgroups (same-box A/B of the two builds, profiles/r04_experiment_log.md: 4096 x 1024 3.36 -> 1.07 ms, 32768 x 1024 3.87 -> 1.89 ms).
-int sweep(Ctx& c, int engine, int r_engine, bool check_now, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda, size_t m, size_t n) {
+// gramq_nparts (may be null): the number of Gram partials the apply launch wrote to o.gramq_part (untouched when it wrote none)
+int sweep(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, int r_engine, bool check_now, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda, size_t m, size_t n) {
 	const size_t npanels = cdiv(n, PW);
 	// 128-COLUMN BLOCKS (round 4): while the bf16-split level accepts them, two neighbouring panels are factored at once by the one-panel
 	// path of 64 < n <= 128 (sweep_wide: ONE Gram pass over 128 columns, the two-block Cholesky factor, ONE apply pass -- speculative, A
@@ -943,16 +948,16 @@ int sweep(Ctx& c, int engine, int r_engine, bool check_now, float* q, size_t ldq
 		bool wide_blk = false;
 		if (try_wide && n - P > PW) {
 			const size_t w = std::min(2 * PW, n - P);
-			int rcw = sweep_wide(c, engine, q + P * ldq, ldq, r + P * ldr + P, ldr, a + P * lda, lda, m, w);
+			int rcw = sweep_wide(c, o, engine, q + P * ldq, ldq, r + P * ldr + P, ldr, a + P * lda, lda, m, w);
 			if (rcw) return rcw;
 			unsigned stw = 1u;
-			rcw = read_status(c, c.slot, &stw);
+			rcw = read_status(c, o.slot, &stw);
 			if (rcw) return rcw;
 			if (stw == 0) { wide_blk = true; blockw = w; c.min_level = std::min(c.min_level, 2); }
 			else try_wide = false;
 		}
 		if (!wide_blk) {
-			const int rc = panel_qr(c, engine, r_engine, check_now, q + P * ldq, ldq, r + P * ldr + P, ldr, a + P * lda, lda, m, cc);
+			const int rc = panel_qr(c, o, gramq_nparts, engine, r_engine, check_now, q + P * ldq, ldq, r + P * ldr + P, ldr, a + P * lda, lda, m, cc);
 			if (rc) return rc;
 		}
 		pi += cdiv(blockw, PW);
@@ -992,7 +997,7 @@ int sweep(Ctx& c, int engine, int r_engine, bool check_now, float* q, size_t ldq
 		tsqrmi::ApplyArgs ua{};
 		ua.a = q + Pc * ldq; ua.lda = ldq; ua.q = a + T0 * lda; ua.ldq = lda; ua.m = m; ua.n = (int)PW; ua.z = sm;
 		ua.n_out = (int)std::min(PW, ntc); ua.multi_cols = (int)ntc;
-		const int rc2 = with_engine(engine, [&](auto e) { return launch_apply_any<decltype(e)::value, 4, true>(c, ua); });
+		const int rc2 = with_engine(engine, [&](auto e) { return launch_apply_any<decltype(e)::value, 4, true>(c, o, nullptr, ua); });
 		if (rc2) return rc2;
 		HIPCHK(hipGetLastError());
 		}
@@ -1003,7 +1008,7 @@ int sweep(Ctx& c, int engine, int r_engine, bool check_now, float* q, size_t ldq
 // ---------------------------------------------------------------------------------------------------------------------------
 // 64 < n <= 128 as ONE Cholesky-QR panel (tsqr_wide.hip): Gram tiles of all n columns in one pass, the 128 x 128 Cholesky factor in
 // two 64 x 64 blocks, Q = A * inverse(R) in one pass.  Everything is enqueued speculatively: the verdict over both blocks lands in
-// slot c.slot (and its pinned alias), the apply pass skips itself on rejection, A is untouched (q == a is allowed: every workgroup
+// slot o.slot (and its pinned alias), the apply pass skips itself on rejection, A is untouched (q == a is allowed: every workgroup
 // has its block in LDS before it writes).  r receives the full n x n factor.
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int E> int launch_apply_wide(Ctx& c, tsqrmi::ApplyArgs a) {
@@ -1028,7 +1033,7 @@ template <int E> int launch_apply_wide(Ctx& c, tsqrmi::ApplyArgs a) {
 	return 0;
 }
 // the one-panel path's arguments, shared by the blocking call (sweep_wide) and the stream of 128-column calls (chained128); verdict and
-// skip word: status slot `slot`
+// skip word: status slot o.slot
 struct WideWs { double* gsum; float* zw; float* zf2; };  // summed tiles, Z (128 x 128), Z22 in the work space behind WqLayout::wide
 WideWs wide_ws(const Ctx& c) {
 	float* w = c.wq + c.L.wide;
@@ -1042,20 +1047,20 @@ tsqrmi::GramWideArgs gram_wide_args(Ctx& c, const float* a, size_t lda, size_t m
 	return ga;
 }
 // chol(G11) -> Schur complement -> chol(G22') -> Z12 + verdict: one workgroup, one launch (chol_wide_kernel)
-tsqrmi::CholWideArgs chol_wide_args(const Ctx& c, float* r, size_t ldr, size_t m, size_t n, int slot) {
+tsqrmi::CholWideArgs chol_wide_args(const Ctx& c, const SweepOpts& o, float* r, size_t ldr, size_t m, size_t n) {
 	const WideWs w = wide_ws(c);
 	tsqrmi::CholWideArgs wa{};
 	wa.gsum = w.gsum; wa.r = r; wa.ldr = ldr; wa.n = (int)n; wa.zf1 = c.wq + c.L.z; wa.zf2 = w.zf2; wa.zw = w.zw;
-	wa.st1 = c.status_dev(2); wa.st2 = c.status_dev(3); wa.status = c.status_dev(slot);
-	wa.host_status = c.hsig.dev ? c.hsig.dev + 4 * slot : nullptr;
-	wa.prev_status = c.prev_slot >= 0 ? c.status_dev(c.prev_slot) : nullptr;
+	wa.st1 = c.status_dev(2); wa.st2 = c.status_dev(3); wa.status = c.status_dev(o.slot);
+	wa.host_status = c.hsig.dev ? c.hsig.dev + 4 * o.slot : nullptr;
+	wa.prev_status = o.prev_slot >= 0 ? c.status_dev(o.prev_slot) : nullptr;
 	wa.rows = (double)m; wa.scond_floor = g_set.bf16_scond_floor;
 	return wa;
 }
-// Q = A * inverse(R) of the one-panel path; skips itself when the verdict in `slot` rejects
-int apply_wide(Ctx& c, int engine, float* q, size_t ldq, const float* a, size_t lda, size_t m, size_t n, int slot) {
+// Q = A * inverse(R) of the one-panel path; skips itself when the verdict in o.slot rejects
+int apply_wide(Ctx& c, const SweepOpts& o, int engine, float* q, size_t ldq, const float* a, size_t lda, size_t m, size_t n) {
 	tsqrmi::ApplyArgs aa{};
-	aa.a = a; aa.lda = lda; aa.q = q; aa.ldq = ldq; aa.m = m; aa.n = (int)n; aa.z = wide_ws(c).zw; aa.skip_status = c.status_dev(slot);
+	aa.a = a; aa.lda = lda; aa.q = q; aa.ldq = ldq; aa.m = m; aa.n = (int)n; aa.z = wide_ws(c).zw; aa.skip_status = c.status_dev(o.slot);
 	int rc;
 	{
 		ProfScope ps(KC_APPLY, c.st);
@@ -1065,7 +1070,7 @@ int apply_wide(Ctx& c, int engine, float* q, size_t ldq, const float* a, size_t 
 	HIPCHK(hipGetLastError());
 	return 0;
 }
-int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, const float* a, size_t lda, size_t m, size_t n) {
+int sweep_wide(Ctx& c, const SweepOpts& o, int engine, float* q, size_t ldq, float* r, size_t ldr, const float* a, size_t lda, size_t m, size_t n) {
 	// full 64-row blocks of a 128-column matrix go to the fast form of the Gram kernel, whatever is left (ragged last rows, or the
 	// whole matrix when n < 128) to the general form; both write per-workgroup partials, one after the other
 	const size_t nfull = (n == 2 * PW && lda <= ((size_t)1 << 23)) ? m / 64 : 0, nrest = cdiv(m, 64) - nfull;   // (fast form: 32-bit buffer offsets)
@@ -1088,10 +1093,167 @@ int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, c
 	{
 		ProfScope ps(KC_CHOL, c.st);
 		launch_reduce1(c.st, wide_ws(c).gsum, reinterpret_cast<const double*>(c.wr), wgs_fast + wgs_rest, 36 * 256, (double)m);
-		hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, c.st, chol_wide_args(c, r, ldr, m, n, c.slot));
+		hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, c.st, chol_wide_args(c, o, r, ldr, m, n));
 	}
 	HIPCHK(hipGetLastError());
-	return apply_wide(c, engine, q, ldq, a, lda, m, n, c.slot);
+	return apply_wide(c, o, engine, q, ldq, a, lda, m, n);
+}
+
+// A speculative two-sweep attempt of a reorthogonalised call (R1, R2: qr_two_sweeps) ends in an error (the return value), with the call finished
+// (*next_level = LADDER_DONE: Q and R final, stream drained) or with nothing done (*next_level = L: A intact, the checked ladder goes on from level L).
+constexpr int LADDER_DONE = -1;
+
+// Round 4: CholeskyQR2 / shifted CholeskyQR3 on the bf16-split Gram matrix, decided on the device, no pass wasted.
+//  sweep 1  Gram pass of A -> Cholesky under the RELAXED rule (another sweep follows: Q1 must come out well conditioned, not
+//           orthonormal) -- and when even that rule rejects, the same launch factors G + s I at once (shifted Cholesky QR,
+//           Fukaya et al. 2020).  s = c trace(G), c = 8 * 2^-23 / sqrt(rows): four times the Frobenius bound of the bf16-split Gram
+//           matrix's own error (products good to 2^-23, errors averaging over the rows: |dG_ij| ~ 2^-22 / sqrt(rows) sqrt(g_ii g_jj),
+//           measured as 8e-6 S / sqrt(rows) in Q^T Q), so the fp64 Gram pass of A (108 us) and its rejected Cholesky are not needed.
+//           -> Q1 = A inverse(R1), Gram tiles of Q1 from the same launch; Q1 leaves with plain stores in ASCENDING block order, so
+//           that sweep 2 (descending) starts with the half of Q1 the Infinity Cache still holds (ApplyArgs::forward).
+//  The host reads sweep 1's verdict word WHILE the apply pass of sweep 1 runs, then enqueues
+//  accepted plain   : sweep 2 under the strict rule -> Q, R = R2 R1 (CholeskyQR2: what rounds 1-3 did for such input);
+//  accepted shifted : sweep 2 under the relaxed rule (cond(Q1) ~ 1 / sqrt(c): 1e3 .. 4e3) with Gram tiles of Q2 from its
+//                     apply launch, sweep 3 under the strict rule -> Q, R = R3 R2 R1 (shifted CholeskyQR3);
+//  rejected         : (non-finite input, or columns near the fp32 denormal range) the checked ladder, from the fp64 Gram level.
+// Every launch behind a rejected Cholesky skips itself; A is never written.  (One panel, auto policy, pinned words.)
+int two_sweeps_device_decided(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda, size_t m, size_t n, int* next_level) {
+	constexpr unsigned PENDING = 0xffffffffu;
+	volatile unsigned* hw = reinterpret_cast<volatile unsigned*>(c.hsig.host);
+	float* r1 = c.wq + c.L.r1; float* r2 = c.wq + c.L.r2;
+	float* r3 = c.wq + c.L.r5; float* r4 = c.wq + c.L.r6;    // (L.r3 / L.r4 belong to panel_qr's own shifted two-step)
+	double* const gq = reinterpret_cast<double*>(c.wr); const int gq_cap = gram_plan(m, n).nblocks;   // Gram partials of a sweep's output, for the sweep behind it
+	const bool q_back = (double)ldq * (double)n * sizeof(float) <= 300.0e6;      // (a Q the Infinity Cache can hold half of)
+	*next_level = LADDER_DONE;
+	hw[0] = PENDING;
+	int nq1 = 0;                                         // partials of Q1^T Q1 (none from the fp32-MFMA engine: its apply launch is not fused)
+	int rc = sweep(c, SweepOpts{/*slot=*/0, /*prev_slot=*/-1, /*gramq_ready=*/0, /*gramq_part=*/gq, /*gramq_cap=*/gq_cap, /*relax=*/1, /*retry_shift=*/1, /*q_read_back=*/q_back}, &nq1, engine, 2, /*check_now=*/false, q, ldq, r1, n, a, lda, m, n);
+	if (rc) return rc;
+	unsigned v0 = PENDING;                               // sweep 1's verdict (its apply pass is running meanwhile)
+	const int seen = spin_until([&] { return (v0 = hw[0]) != PENDING; }, c.st);
+	if (seen < 0) return seen;
+	if (seen == 1 && (v0 = hw[0]) == PENDING) v0 = 1u;   // (the stream is idle and nothing reported: rejected)
+	unsigned s1 = 1u, s2 = 1u;
+	if (v0 == 0u) {
+		rc = sweep(c, SweepOpts{/*slot=*/1, /*prev_slot=*/0, /*gramq_ready=*/nq1}, nullptr, engine, 2, /*check_now=*/false, q, ldq, r2, n, q, ldq, m, n);
+		if (rc) return rc;
+		launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
+		HIPCHK(hipGetLastError());
+		rc = read_status(c, 1, &s1);
+		if (rc || s1 == 0) return rc;                    // both sweeps accepted: done (min_level was set by panel_qr)
+		// the first sweep stands (Q holds Q1, r1 is valid); only the second one must be redone, checked, one level down
+		c.min_level = 2;
+		rc = sweep(c, SweepOpts{}, nullptr, engine, 1, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
+		if (rc) return rc;
+		c.min_level = std::min(c.min_level, 2);
+		launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
+		HIPCHK(hipGetLastError());
+		return wait_done(c);
+	}
+	if (v0 == 2u) {
+		// shifted: cond(Q1) ~ sqrt(c n / 3) cond(A).  Sweep 2 first tries the bf16-split Gram matrix of Q1 -- free, its tiles came out
+		// of sweep 1's apply launch -- under the relaxed rule (large row counts: c is small enough for cond(A) up to ~1e8); when
+		// that is rejected (Q still holds Q1: the apply pass skipped itself) it takes the fp64 Gram matrix of Q1 in a pass of its
+		// own.  Sweeps 2 and 3 are enqueued together, speculatively; sweep 3 (strict rule) reuses slot 0, whose first verdict
+		// has been read.
+		bool done3 = false;
+		for (int att = nq1 > 0 ? 0 : 1; att < 2; att++) {
+			int nq2 = 0;                                 // partials of Q2^T Q2 (the same apply variant as in sweep 1: fused for every engine but the fp32-MFMA one)
+			rc = sweep(c, SweepOpts{/*slot=*/1, /*prev_slot=*/-1, /*gramq_ready=*/att == 0 ? nq1 : 0, /*gramq_part=*/gq, /*gramq_cap=*/gq_cap, /*relax=*/1}, &nq2, engine, att == 0 ? 2 : 1, /*check_now=*/false,
+			           q, ldq, r2, n, q, ldq, m, n);       // (no dependency: sweep 1 is known to be accepted)
+			if (!rc) rc = sweep(c, SweepOpts{/*slot=*/0, /*prev_slot=*/1, /*gramq_ready=*/nq2}, nullptr, engine, 2, /*check_now=*/false, q, ldq, r3, n, q, ldq, m, n);
+			if (rc) return rc;
+			launch_rmul3(r, ldr, r3, r2, r1, r4, n, c.st);
+			HIPCHK(hipGetLastError());
+			rc = read_status(c, 0, &s2);
+			if (!rc) rc = read_status(c, 1, &s1, nullptr, /*wait=*/false);
+			if (rc) return rc;
+			if (s1 == 0 && s2 == 0) { done3 = true; break; }
+			if (s1 == 0) break;                          // sweep 3 alone was rejected: Q holds Q2 (checked sweep below)
+		}
+		if (!done3) {
+			// Q1 is numerically rank deficient (e.g. exactly dependent columns), or sweep 3 found Q2 short of the strict rule.
+			// Q holds Q1 (sweep 2 rejected: its apply pass skipped itself) or Q2 -- A may be gone (q may alias a), so the rest is
+			// done on Q in place by checked sweeps, which escalate per panel (fp64 Gram -> shifted -> Householder)
+			if (s1 != 0) {
+				rc = sweep(c, SweepOpts{}, nullptr, engine, 1, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
+				if (rc) return rc;
+			}
+			rc = sweep(c, SweepOpts{}, nullptr, engine, 2, /*check_now=*/true, q, ldq, r3, n, q, ldq, m, n);
+			if (rc) return rc;
+			launch_rmul3(r, ldr, r3, r2, r1, r4, n, c.st);
+			HIPCHK(hipGetLastError());
+			rc = wait_done(c);
+			if (rc) return rc;
+		}
+		c.min_level = 0; c.used_shift = true;
+		return 0;
+	}
+	rc = wait_done(c);                                   // rejected (non-finite input, columns near the denormal range): everything enqueued skipped itself
+	if (rc) return rc;
+	c.min_level = 2;
+	*next_level = 1;                                     // the checked ladder, from the fp64 Gram level, on the untouched A
+	return 0;
+}
+
+// Optimistic attempt: both sweeps at `level`, the R product and the completion flag are enqueued without looking at a verdict.
+// Device-side chain: apply 1 skips when Cholesky 1 rejected; Cholesky 2 then reports "rejected" at once; apply 2 (in
+// place) skips when Cholesky 2 rejected -- so A stays intact and Q holds Q1 or garbage, never a half-applied state.
+// (One panel, auto policy; without pinned words, or with the fp64 Gram level first.)
+int two_sweeps_optimistic(Ctx& c, int engine, int level, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda, size_t m, size_t n, int* next_level) {
+	float* r1 = c.wq + c.L.r1; float* r2 = c.wq + c.L.r2;
+	const bool fuse = level == 2;                        // (as in qr_two_sweeps)
+	*next_level = LADDER_DONE;
+	int nq = 0;
+	int rc = sweep(c, SweepOpts{/*slot=*/0, /*prev_slot=*/-1, /*gramq_ready=*/0, /*gramq_part=*/fuse ? reinterpret_cast<double*>(c.wr) : nullptr, /*gramq_cap=*/fuse ? gram_plan(m, n).nblocks : 0}, &nq, engine, level, /*check_now=*/false,
+	               q, ldq, r1, n, a, lda, m, n);
+	if (!rc) rc = sweep(c, SweepOpts{/*slot=*/1, /*prev_slot=*/0, /*gramq_ready=*/nq}, nullptr, engine, level, /*check_now=*/false, q, ldq, r2, n, q, ldq, m, n);
+	if (rc) return rc;
+	launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
+	HIPCHK(hipGetLastError());
+	unsigned s0 = 1u, s1 = 1u;
+	rc = read_status(c, 0, &s0);
+	if (!rc) rc = read_status(c, 1, &s1, nullptr, /*wait=*/false);
+	if (rc) return rc;
+	if (s0 == 0 && s1 == 0) return 0;                    // both sweeps accepted: done (min_level was set by panel_qr)
+	c.min_level = 2;
+	if (s0 != 0) { *next_level = std::max(level - 1, 0); return 0; }   // first sweep rejected at this level: checked path from the next one
+	// the first sweep stands (Q holds Q1, r1 is valid); only the second one must be redone, now checked and below
+	// the level that was just rejected
+	rc = sweep(c, SweepOpts{}, nullptr, engine, level - 1, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
+	if (rc) return rc;
+	c.min_level = std::min(c.min_level, level);          // (first sweep ran at `level`)
+	launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
+	HIPCHK(hipGetLastError());
+	return wait_done(c);
+}
+
+// two sweeps: A = Q1 R1, then Q1 = Q R2 in place, R = R2 * R1 (the reference's BCGS2 plays this role).  R1 and R2 live in
+// the work buffer (packed, ld n); every sweep writes their upper triangles in full and rmul_kernel reads nothing else,
+// so neither needs zero-filling, and the product is written straight into the caller's r (zeros below the diagonal)
+int qr_two_sweeps(Ctx& c, int engine, int level, int first_level, bool check_now, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda, size_t m, size_t n) {
+	const bool one_panel_auto = n <= PW && c.policy == 0;
+	if (one_panel_auto && level == first_level && !t_prof.on) {
+		int next = LADDER_DONE;
+		const int rc = (level == 2 && c.hsig.dev) ? two_sweeps_device_decided(c, engine, q, ldq, r, ldr, a, lda, m, n, &next)
+		                                          : two_sweeps_optimistic(c, engine, level, q, ldq, r, ldr, a, lda, m, n, &next);
+		if (rc || next == LADDER_DONE) return rc;
+		level = next;
+	}
+	float* r1 = c.wq + c.L.r1; float* r2 = c.wq + c.L.r2;
+	// single panel: the first sweep's (last) apply launch accumulates Q^T Q while the block is in LDS, so that the second
+	// sweep's bf16-level Gram pass over Q is not needed
+	const bool fuse = one_panel_auto && first_level == 2;
+	int nq = 0;
+	int rc = sweep(c, SweepOpts{/*slot=*/0, /*prev_slot=*/-1, /*gramq_ready=*/0, /*gramq_part=*/fuse ? reinterpret_cast<double*>(c.wr) : nullptr, /*gramq_cap=*/fuse ? gram_plan(m, n).nblocks : 0}, &nq, engine, level, check_now,
+	               q, ldq, r1, n, a, lda, m, n);
+	if (rc) return rc;
+	// the second sweep always starts at the first level again (Q1 is well conditioned)
+	rc = sweep(c, SweepOpts{/*slot=*/0, /*prev_slot=*/-1, /*gramq_ready=*/nq}, nullptr, engine, first_level, check_now, q, ldq, r2, n, q, ldq, m, n);
+	if (rc) return rc;
+	launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
+	HIPCHK(hipGetLastError());
+	return wait_done(c);                                 // completion flag in the pinned words, or a plain stream sync
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1099,6 +1261,7 @@ int sweep_wide(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, c
 // ---------------------------------------------------------------------------------------------------------------------------
 int qr_core(Ctx& c, int engine, int reorth, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda, size_t m, size_t n) {
 	const WqLayout& L = c.L;
+	const SweepOpts plain{};                             // every sweep enqueued here: slot 0, no dependency, nothing fused (the two-sweep schedules build their own)
 	c.fold_cor = (engine == 1);
 	// auto policy: every mode starts at the bf16-split Gram level (exact products, fp64 accumulation across K-steps: more accurate
 	// than any plain fp32 evaluation of A^T A, accepted only for well-conditioned panels), then the fp64 Gram level, the shifted
@@ -1122,17 +1285,17 @@ int qr_core(Ctx& c, int engine, int reorth, float* q, size_t ldq, float* r, size
 		// one Cholesky-QR panel over all n columns; rejected (ill conditioned) -> the 64-column panel path below, A is still intact
 		float* r1 = c.wq + L.r1; float* r2 = c.wq + L.r2;
 		unsigned st = 1u;
-		int rc = sweep_wide(c, engine, q, ldq, reorth ? r1 : r, reorth ? n : ldr, a, lda, m, n);
+		int rc = sweep_wide(c, plain, engine, q, ldq, reorth ? r1 : r, reorth ? n : ldr, a, lda, m, n);
 		if (rc) return rc;
-		rc = read_status(c, c.slot, &st);
+		rc = read_status(c, 0, &st);
 		if (rc) return rc;
 		if (st == 0 && reorth) {
-			rc = sweep_wide(c, engine, q, ldq, r2, n, q, ldq, m, n);
+			rc = sweep_wide(c, plain, engine, q, ldq, r2, n, q, ldq, m, n);
 			if (rc) return rc;
-			rc = read_status(c, c.slot, &st);
+			rc = read_status(c, 0, &st);
 			if (rc) return rc;
 			if (st != 0) {                               // (Q1 is well conditioned: not expected) second sweep on the panel path
-				rc = sweep(c, engine, first_level, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
+				rc = sweep(c, plain, nullptr, engine, first_level, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
 				if (rc) return rc;
 				hipLaunchKernelGGL(tsqrmi::zero_lower_kernel, dim3(gb), dim3(256), 0, c.st, r2, n, (int)n);
 			}
@@ -1145,185 +1308,20 @@ int qr_core(Ctx& c, int engine, int reorth, float* q, size_t ldq, float* r, size
 		wide_done = (st == 0);
 	}
 	if (c.resume_accepted) scond1 = c.resume_scond;
-	for (int level = (c.start_level >= 0 ? std::min(c.start_level, first_level) : first_level); level >= 0 && !wide_done && !c.resume_accepted; level--) {
-		int rc;
-		if (!reorth) {
-			// level 0 reached in the speculative (deferred) mode: both Gram levels were rejected and the fp64 Gram matrix of A is
-			// still in the work buffer: panel_qr takes the shifted-Cholesky path on it before the Householder fold
-			const bool retry_checked = (level == 0 && deferred && first_level >= 1);
-			rc = sweep(c, engine, retry_checked ? R_SHIFT_DIRECT : level, check_now || retry_checked, q, ldq, r, ldr, a, lda, m, n);
-			if (rc) return rc;
-			if (n > PW) hipLaunchKernelGGL(tsqrmi::zero_lower_kernel, dim3(gb), dim3(256), 0, c.st, r, ldr, (int)n);
-		} else {
-			// two sweeps: A = Q1 R1, then Q1 = Q R2 in place, R = R2 * R1 (the reference's BCGS2 plays this role).  R1 and R2 live in
-			// the work buffer (packed, ld n); every sweep writes their upper triangles in full and rmul_kernel reads nothing else,
-			// so neither needs zero-filling, and the product is written straight into the caller's r (zeros below the diagonal)
-			float* r1 = c.wq + L.r1; float* r2 = c.wq + L.r2;
-			// single panel: the first sweep's (last) apply launch accumulates Q^T Q while the block is in LDS, so that the second
-			// sweep's bf16-level Gram pass over Q is not needed
-			const bool fuse = n <= PW && c.policy == 0 && level == 2;
-			if (n <= PW && c.policy == 0 && level == first_level && level == 2 && !t_prof.on && c.hsig.dev) {
-				// Round 4: CholeskyQR2 / shifted CholeskyQR3 on the bf16-split Gram matrix, decided on the device, no pass wasted.
-				//  sweep 1  Gram pass of A -> Cholesky under the RELAXED rule (another sweep follows: Q1 must come out well conditioned, not
-				//           orthonormal) -- and when even that rule rejects, the same launch factors G + s I at once (shifted Cholesky QR,
-				//           Fukaya et al. 2020).  s = c trace(G), c = 8 * 2^-23 / sqrt(rows): four times the Frobenius bound of the bf16-split Gram
-				//           matrix's own error (products good to 2^-23, errors averaging over the rows: |dG_ij| ~ 2^-22 / sqrt(rows) sqrt(g_ii g_jj),
-				//           measured as 8e-6 S / sqrt(rows) in Q^T Q), so the fp64 Gram pass of A (108 us) and its rejected Cholesky are not needed.
-				//           -> Q1 = A inverse(R1), Gram tiles of Q1 from the same launch; Q1 leaves with plain stores in ASCENDING block order, so
-				//           that sweep 2 (descending) starts with the half of Q1 the Infinity Cache still holds (ApplyArgs::forward).
-				//  The host reads sweep 1's verdict word WHILE the apply pass of sweep 1 runs, then enqueues
-				//  accepted plain   : sweep 2 under the strict rule -> Q, R = R2 R1 (CholeskyQR2: what rounds 1-3 did for such input);
-				//  accepted shifted : sweep 2 under the relaxed rule (cond(Q1) ~ 1 / sqrt(c): 1e3 .. 4e3) with Gram tiles of Q2 from its
-				//                     apply launch, sweep 3 under the strict rule -> Q, R = R3 R2 R1 (shifted CholeskyQR3);
-				//  rejected         : (non-finite input, or columns near the fp32 denormal range) the checked ladder below, from scratch.
-				// Every launch behind a rejected Cholesky skips itself; A is never written.
-				constexpr unsigned PENDING = 0xffffffffu;
-				volatile unsigned* hw = reinterpret_cast<volatile unsigned*>(c.hsig.host);
-				float* r3 = c.wq + L.r5; float* r4 = c.wq + L.r6;    // (L.r3 / L.r4 belong to panel_qr's own shifted two-step)
-				c.gramq_part = reinterpret_cast<double*>(c.wr); c.gramq_cap = gram_plan(m, n).nblocks; c.gramq_nparts = 0;
-				c.slot = 0; c.prev_slot = -1;
-				hw[0] = PENDING;
-				c.chol_relax = 1; c.chol_retry_shift = 1;
-				c.q_for_next_sweep = (double)ldq * (double)n * sizeof(float) <= 300.0e6;      // (a Q the Infinity Cache can hold half of)
-				rc = sweep(c, engine, 2, /*check_now=*/false, q, ldq, r1, n, a, lda, m, n);
-				c.q_for_next_sweep = false;
-				c.chol_relax = 0; c.chol_retry_shift = 0;
-				const bool have_gramq = c.gramq_nparts > 0;
-				if (rc) { c.gramq_part = nullptr; c.gramq_cap = 0; return rc; }
-				unsigned v0 = PENDING;                           // sweep 1's verdict (its apply pass is running meanwhile)
-				const int seen = spin_until([&] { return (v0 = hw[0]) != PENDING; }, c.st);
-				if (seen < 0) { c.gramq_part = nullptr; c.gramq_cap = 0; return seen; }
-				if (seen == 1 && (v0 = hw[0]) == PENDING) v0 = 1u;   // (the stream is idle and nothing reported: rejected)
-				unsigned s1 = 1u, s2 = 1u;
-				if (v0 == 0u) {
-					c.gramq_part = nullptr; c.gramq_cap = 0;
-					c.gramq_ready = have_gramq;
-					c.slot = 1; c.prev_slot = 0;
-					rc = sweep(c, engine, 2, /*check_now=*/false, q, ldq, r2, n, q, ldq, m, n);
-					c.gramq_ready = false;
-					c.slot = 0; c.prev_slot = -1;
-					if (rc) return rc;
-					launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
-					HIPCHK(hipGetLastError());
-					rc = read_status(c, 1, &s1);
-					if (rc) return rc;
-					if (s1 == 0) break;                          // both sweeps accepted: done (min_level was set by panel_qr)
-					// the first sweep stands (Q holds Q1, r1 is valid); only the second one must be redone, checked, one level down
-					c.min_level = 2;
-					rc = sweep(c, engine, 1, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
-					if (rc) return rc;
-					c.min_level = std::min(c.min_level, 2);
-					launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
-					HIPCHK(hipGetLastError());
-					rc = wait_done(c);
-					if (rc) return rc;
-					break;
-				}
-				if (v0 == 2u) {
-					// shifted: cond(Q1) ~ sqrt(c n / 3) cond(A).  Sweep 2 first tries the bf16-split Gram matrix of Q1 -- free, its tiles came out
-					// of sweep 1's apply launch -- under the relaxed rule (large row counts: c is small enough for cond(A) up to ~1e8); when
-					// that is rejected (Q still holds Q1: the apply pass skipped itself) it takes the fp64 Gram matrix of Q1 in a pass of its
-					// own.  Sweeps 2 and 3 are enqueued together, speculatively; sweep 3 (strict rule) reuses slot 0, whose first verdict
-					// has been read.
-					bool done3 = false;
-					for (int att = have_gramq ? 0 : 1; att < 2; att++) {
-						c.gramq_part = reinterpret_cast<double*>(c.wr); c.gramq_cap = gram_plan(m, n).nblocks;
-						c.gramq_ready = (att == 0);
-						c.slot = 1; c.prev_slot = -1;            // (sweep 1 is known to be accepted)
-						c.chol_relax = 1;
-						rc = sweep(c, engine, att == 0 ? 2 : 1, /*check_now=*/false, q, ldq, r2, n, q, ldq, m, n);
-						c.chol_relax = 0; c.gramq_ready = false;
-						c.gramq_part = nullptr; c.gramq_cap = 0;
-						if (!rc) {
-							c.gramq_ready = have_gramq;          // (the same apply variant ran: fused for every engine but the fp32-MFMA one)
-							c.slot = 0; c.prev_slot = 1;
-							rc = sweep(c, engine, 2, /*check_now=*/false, q, ldq, r3, n, q, ldq, m, n);
-							c.gramq_ready = false;
-						}
-						c.slot = 0; c.prev_slot = -1;
-						if (rc) return rc;
-						launch_rmul3(r, ldr, r3, r2, r1, r4, n, c.st);
-						HIPCHK(hipGetLastError());
-						rc = read_status(c, 0, &s2);
-						if (rc) return rc;
-						rc = read_status(c, 1, &s1, nullptr, /*wait=*/false);
-						if (rc) return rc;
-						if (s1 == 0 && s2 == 0) { done3 = true; break; }
-						if (s1 == 0) break;                      // sweep 3 alone was rejected: Q holds Q2 (checked sweep below)
-					}
-					if (!done3) {
-						// Q1 is numerically rank deficient (e.g. exactly dependent columns), or sweep 3 found Q2 short of the strict rule.
-						// Q holds Q1 (sweep 2 rejected: its apply pass skipped itself) or Q2 -- A may be gone (q may alias a), so the rest is
-						// done on Q in place by checked sweeps, which escalate per panel (fp64 Gram -> shifted -> Householder)
-						if (s1 != 0) {
-							rc = sweep(c, engine, 1, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
-							if (rc) return rc;
-						}
-						rc = sweep(c, engine, 2, /*check_now=*/true, q, ldq, r3, n, q, ldq, m, n);
-						if (rc) return rc;
-						launch_rmul3(r, ldr, r3, r2, r1, r4, n, c.st);
-						HIPCHK(hipGetLastError());
-						rc = wait_done(c);
-						if (rc) return rc;
-					}
-					c.min_level = 0; c.used_shift = true;
-					break;
-				}
-				c.gramq_part = nullptr; c.gramq_cap = 0;
-				rc = wait_done(c);                               // rejected (non-finite input, columns near the denormal range): everything enqueued skipped itself
-				if (rc) return rc;
-				c.min_level = 2;
-				level = 1;                                       // the checked ladder, from the fp64 Gram level, on the untouched A
-			} else if (n <= PW && c.policy == 0 && level == first_level && !t_prof.on) {
-				// Optimistic attempt: both sweeps, the R product and the completion flag are enqueued without looking at a verdict.
-				// Device-side chain: apply 1 skips when Cholesky 1 rejected; Cholesky 2 then reports "rejected" at once; apply 2 (in
-				// place) skips when Cholesky 2 rejected -- so A stays intact and Q holds Q1 or garbage, never a half-applied state.
-				if (fuse) { c.gramq_part = reinterpret_cast<double*>(c.wr); c.gramq_cap = gram_plan(m, n).nblocks; c.gramq_nparts = 0; }
-				c.slot = 0; c.prev_slot = -1;
-				rc = sweep(c, engine, level, /*check_now=*/false, q, ldq, r1, n, a, lda, m, n);
-				c.gramq_part = nullptr; c.gramq_cap = 0;
-				if (!rc) {
-					c.gramq_ready = fuse && c.gramq_nparts > 0;
-					c.slot = 1; c.prev_slot = 0;
-					rc = sweep(c, engine, level, /*check_now=*/false, q, ldq, r2, n, q, ldq, m, n);
-					c.gramq_ready = false;
-				}
-				c.slot = 0; c.prev_slot = -1;
-				if (rc) return rc;
-				launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
-				HIPCHK(hipGetLastError());
-				unsigned s0 = 1u, s1 = 1u;
-				rc = read_status(c, 0, &s0);
-				if (rc) return rc;
-				rc = read_status(c, 1, &s1, nullptr, /*wait=*/false);
-				if (rc) return rc;
-				if (s0 == 0 && s1 == 0) break;               // both sweeps accepted: done (min_level was set by panel_qr)
-				c.min_level = 2;
-				if (s0 == 0) {
-					// the first sweep stands (Q holds Q1, r1 is valid); only the second one must be redone, now checked and below
-					// the level that was just rejected
-					rc = sweep(c, engine, level - 1, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
-					if (rc) return rc;
-					c.min_level = std::min(c.min_level, level);  // (first sweep ran at `level`)
-					launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
-					HIPCHK(hipGetLastError());
-					rc = wait_done(c);
-					if (rc) return rc;
-					break;
-				}
-				level = std::max(level - 1, 0);              // first sweep rejected at this level: checked path from the next one
-			}
-			const bool fuse2 = n <= PW && c.policy == 0 && first_level == 2;
-			if (fuse2) { c.gramq_part = reinterpret_cast<double*>(c.wr); c.gramq_cap = gram_plan(m, n).nblocks; c.gramq_nparts = 0; }
-			rc = sweep(c, engine, level, check_now, q, ldq, r1, n, a, lda, m, n);
-			c.gramq_part = nullptr; c.gramq_cap = 0;
-			if (rc) return rc;
-			c.gramq_ready = fuse2 && c.gramq_nparts > 0;     // the second sweep always starts at the first level again (Q1 is well conditioned)
-			rc = sweep(c, engine, first_level, check_now, q, ldq, r2, n, q, ldq, m, n);
-			c.gramq_ready = false;
-			if (rc) return rc;
-			launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
-		}
+	int level = c.start_level >= 0 ? std::min(c.start_level, first_level) : first_level;
+	if (wide_done || c.resume_accepted) level = -1;      // (nothing left for the ladder)
+	if (reorth && level >= 0) {
+		const int rc = qr_two_sweeps(c, engine, level, first_level, check_now, q, ldq, r, ldr, a, lda, m, n);
+		if (rc) return rc;
+		level = -1;
+	}
+	for (; level >= 0; level--) {
+		// level 0 reached in the speculative (deferred) mode: both Gram levels were rejected and the fp64 Gram matrix of A is
+		// still in the work buffer: panel_qr takes the shifted-Cholesky path on it before the Householder fold
+		const bool retry_checked = (level == 0 && deferred && first_level >= 1);
+		int rc = sweep(c, plain, nullptr, engine, retry_checked ? R_SHIFT_DIRECT : level, check_now || retry_checked, q, ldq, r, ldr, a, lda, m, n);
+		if (rc) return rc;
+		if (n > PW) hipLaunchKernelGGL(tsqrmi::zero_lower_kernel, dim3(gb), dim3(256), 0, c.st, r, ldr, (int)n);
 		HIPCHK(hipGetLastError());
 		if (level > 0 && deferred) {
 			unsigned status = 0;
@@ -1343,7 +1341,7 @@ int qr_core(Ctx& c, int engine, int reorth, float* q, size_t ldq, float* r, size
 		float* r1 = c.wq + L.r1; float* r2 = c.wq + L.r2;
 		hipLaunchKernelGGL(tsqrmi::copy2d_kernel, dim3(gb), dim3(256), 0, c.st, r1, n, r, ldr, (int)n, (int)n);
 		HIPCHK(hipGetLastError());
-		int rc = sweep(c, engine, first_level, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
+		int rc = sweep(c, plain, nullptr, engine, first_level, /*check_now=*/true, q, ldq, r2, n, q, ldq, m, n);
 		if (rc) return rc;
 		launch_rmul(r, ldr, r2, n, r1, n, n, c.st);
 		HIPCHK(hipGetLastError());
@@ -1522,7 +1520,6 @@ static int submit_impl(const CallEnv& env, int mode, int reorth, float* q, size_
 	if (t_pending[slot]) { const int rc = ticket_latch(t_pending[slot]); if (rc) return t->state = rc; }
 	c.fold_cor = (engine == 1);
 	c.min_level = 2;
-	c.slot = slot; c.prev_slot = -1;
 	if (announce && announce->pending == 1 && !announce->own_flag) {
 		if (announce->words == c.hsig.host && announce->stream == stream) {
 			c.announce_word = c.hsig.dev + 4 * announce->slot + 3;
@@ -1533,7 +1530,8 @@ static int submit_impl(const CallEnv& env, int mode, int reorth, float* q, size_
 			(void)hipGetLastError();
 		}
 	}
-	const int rc = narrow ? sweep(c, engine, 2, /*check_now=*/false, q, ldq, r, ldr, a, lda, m, n) : sweep_wide(c, engine, q, ldq, r, ldr, a, lda, m, n);
+	const SweepOpts o{slot};                             // (the ticket's half of the status words, no dependency)
+	const int rc = narrow ? sweep(c, o, nullptr, engine, 2, /*check_now=*/false, q, ldq, r, ldr, a, lda, m, n) : sweep_wide(c, o, engine, q, ldq, r, ldr, a, lda, m, n);
 	if (rc) return t->state = rc;
 	if (c.announce_word) {                               // (no kernel of the attempt carried the announcement: raise the word here)
 		raise_announcement(c);
@@ -1812,9 +1810,10 @@ static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 	Completion comp(c);
 	// one step = the launches of call i behind its Gram pass: chain(i) (with the Gram pass of call i + 1 when there is one), apply(i)
 	auto step = [&](int i) -> int {
+		const SweepOpts o{i & 1};                            // (verdict words: half i & 1, no dependency)
 		if (i + 1 < count) {
 			tsqrmi::ChainArgs ch{};
-			ch.chol = chol_args(c, mt.r(i), cl.ldr, n, 2, i & 1);
+			ch.chol = chol_args(c, o, mt.r(i), cl.ldr, n, 2);
 			ch.part = part[i & 1]; ch.nparts = nparts; ch.ticket = ticket; ch.nred = nred;
 			ProfScope ps(KC_GRAM, c.st);
 			hipLaunchKernelGGL(tsqrmi::gram_blk_chain_kernel, dim3(nred + nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st,
@@ -1825,11 +1824,10 @@ static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 			raise_announcement(c);
 			ProfScope ps(KC_CHOL, c.st);
 			launch_reduce1(c.st, c.gsum(), part[i & 1], nparts, nelem, (double)m);
-			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, mt.r(i), cl.ldr, n, 2, i & 1));
+			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, o, mt.r(i), cl.ldr, n, 2));
 		}
 		HIPCHK(hipGetLastError());
-		c.slot = i & 1;
-		const int rc2 = apply_rinv(c, engine, mt.q(i), cl.ldq, mt.a(i), cl.lda, mt.r(i), cl.ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
+		const int rc2 = apply_rinv(c, o, nullptr, engine, mt.q(i), cl.ldq, mt.a(i), cl.lda, mt.r(i), cl.ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
 		return rc2 ? rc2 : comp.close(i, i + 1 == count);
 	};
 	{
@@ -1862,7 +1860,7 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 	const int nblk = (int)(m / 64), wgs = WIDE_MAX_WGS;
 	Completion comp(c);
 	auto gram_args = [&](int i) { return gram_wide_args(c, mt.a(i), lda, m, n, nblk); };
-	auto chol_args = [&](int i) { return chol_wide_args(c, mt.r(i), ldr, m, n, i & 1); };
+	auto chol_args = [&](int i) { return chol_wide_args(c, SweepOpts{/*slot=*/i & 1}, mt.r(i), ldr, m, n); };
 	auto reduce = [&]() {
 		ProfScope ps(KC_CHOL, c.st);
 		launch_reduce1(c.st, wide_ws(c).gsum, reinterpret_cast<const double*>(c.wr), wgs, 36 * 256, (double)m);
@@ -1880,7 +1878,7 @@ static int chained128(const Mats& mt, int count, const Call& cl, int* done) {
 			hipLaunchKernelGGL(tsqrmi::chol_wide_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(i));
 		}
 		HIPCHK(hipGetLastError());
-		const int rc = apply_wide(c, engine, mt.q(i), ldq, mt.a(i), lda, m, n, i & 1);
+		const int rc = apply_wide(c, SweepOpts{/*slot=*/i & 1}, engine, mt.q(i), ldq, mt.a(i), lda, m, n);
 		return rc ? rc : comp.close(i, i + 1 == count);
 	};
 	{
@@ -1918,7 +1916,7 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 	const int nchunks = (int)(m / 128), nparts = std::min(nchunks, g.nblocks), nelem = 10 * 256;
 	double* part = reinterpret_cast<double*>(c.wr);
 	Completion comp(c);
-	auto chol_of = [&](int i) { return chol_args(c, mt.r(i), cl.ldr, n, 2, i & 1); };   // (rows_dev: the all-reduced row count)
+	auto chol_of = [&](int i) { return chol_args(c, SweepOpts{/*slot=*/i & 1}, mt.r(i), cl.ldr, n, 2); };   // (rows_dev: the all-reduced row count)
 	auto reduce_allreduce = [&](int extra) -> int {      // partials of the Gram pass just enqueued -> summed tiles + row count (+ `extra` doubles), over all ranks
 		{
 			ProfScope ps(KC_CHOL, c.st);
@@ -1976,8 +1974,7 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_of(i));
 			HIPCHK(hipGetLastError());
 		}
-		c.slot = i & 1;
-		const int rc2 = apply_rinv(c, engine, mt.q(i), cl.ldq, mt.a(i), cl.lda, mt.r(i), cl.ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
+		const int rc2 = apply_rinv(c, SweepOpts{/*slot=*/i & 1}, nullptr, engine, mt.q(i), cl.ldq, mt.a(i), cl.lda, mt.r(i), cl.ldr, m, n, /*z_ready=*/true, c.status_dev(i & 1));
 		return rc2 ? rc2 : comp.close(i, i + 1 == count);
 	};
 	return run_chained(comp, mt, count, 3, step, [&](int i) { return rejected_tail(env, mt, count, cl, i, comp, done); }, done);
@@ -2150,12 +2147,12 @@ int tsqr_mi_qr_f16(int mode, int reorth, void* q, size_t ldq, void* r, size_t ld
 		init_ctx(c, wq_v, wr_v, m, n, stream);
 		c.rows_global = (double)m;
 		resolve_host_sig(c, h_wl, m);
-		c.slot = 0; c.prev_slot = -1;
-		int rc = gram_g(c, reinterpret_cast<const float*>(a), lda, m, n, /*bf16=*/true, /*io_half=*/true);
-		if (!rc) rc = chol_from_g(c, r32, n, n, 2);
+		const SweepOpts o{};                                 // (slot 0, no dependency)
+		int rc = gram_g(c, o, reinterpret_cast<const float*>(a), lda, m, n, /*bf16=*/true, /*io_half=*/true);
+		if (!rc) rc = chol_from_g(c, o, r32, n, n, 2);
 		// (R to fp16: workgroup 0 of the apply pass does it -- scattered 2-byte stores inside the Cholesky kernel cost that 5 us, a
 		// launch of its own 4.8 us)
-		if (!rc) rc = apply_rinv(c, engine_of(f16_engine_mode(mode)), reinterpret_cast<float*>(q), ldq, reinterpret_cast<const float*>(a), lda,
+		if (!rc) rc = apply_rinv(c, o, nullptr, engine_of(f16_engine_mode(mode)), reinterpret_cast<float*>(q), ldq, reinterpret_cast<const float*>(a), lda,
 		                         r32, n, m, n, /*z_ready=*/true, c.status_dev(0), /*io_half=*/true, r, ldr);
 		if (rc) return rc;
 		unsigned status = 1u;
@@ -2203,7 +2200,7 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 	Completion comp(c);
 	// behind the R factor of call i, in either schedule: its apply pass (which also rounds R to halves), then its completion word
 	auto apply_and_close = [&](int i) -> int {
-		const int rc = apply_rinv(c, engine, mt.q(i), ldq, mt.a(i), lda, r32, n, m, n, /*z_ready=*/true, c.status_dev(i & 1), /*io_half=*/true, mt.r(i), ldr);
+		const int rc = apply_rinv(c, SweepOpts{/*slot=*/i & 1}, nullptr, engine, mt.q(i), ldq, mt.a(i), lda, r32, n, m, n, /*z_ready=*/true, c.status_dev(i & 1), /*io_half=*/true, mt.r(i), ldr);
 		return rc ? rc : comp.close(i, i + 1 == count);
 	};
 	// rejected (its apply pass skipped itself: A and Q untouched): drain; this call as a blocking call (conversion path, whole
@@ -2222,9 +2219,9 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 	if (!(n == PW && count >= 3 && g_set.loop_depth.load() >= 3 && out_of_order(mt, count, cl, sizeof(_Float16)) && chain_fits_cache(mt, cl, sizeof(_Float16)))) {
 		// two in flight: every launch of call i; call i - 1's completion word rides in its Gram kernel (gram_g)
 		auto step = [&](int i) -> int {
-			c.slot = i & 1; c.prev_slot = -1;
-			int rc = gram_g(c, mt.a(i), lda, m, n, /*bf16=*/true, /*io_half=*/true);
-			if (!rc) rc = chol_from_g(c, r32, n, n, 2);
+			const SweepOpts o{i & 1};
+			int rc = gram_g(c, o, mt.a(i), lda, m, n, /*bf16=*/true, /*io_half=*/true);
+			if (!rc) rc = chol_from_g(c, o, r32, n, n, 2);
 			return rc ? rc : apply_and_close(i);
 		};
 		return run_chained(comp, mt, count, 3, step, tail, &done);
@@ -2237,16 +2234,16 @@ static int stream_of_calls_f16(const Mats& mt, int count, int mode, size_t ldq, 
 	hipLaunchKernelGGL(tsqrmi::gram_h_kernel<4>, dim3(g.nblocks), dim3(256), 0, c.st, gram_args_64(c, mt.a(0), cl, g.nch, g, part[0]));
 	HIPCHK(hipGetLastError());
 	auto step = [&](int i) -> int {
-		c.slot = i & 1; c.prev_slot = -1;
+		const SweepOpts o{i & 1};
 		if (i + 1 < count) {
 			tsqrmi::ChainArgs ch{};
-			ch.chol = chol_args(c, r32, n, n, 2, i & 1);
+			ch.chol = chol_args(c, o, r32, n, n, 2);
 			ch.part = part[i & 1]; ch.nparts = g.nblocks; ch.ticket = ticket; ch.nred = nred;
 			hipLaunchKernelGGL(tsqrmi::gram_h_chain_kernel, dim3(nred + g.nblocks), dim3(256), 0, c.st, gram_args_64(c, mt.a(i + 1), cl, g.nch, g, part[(i + 1) & 1]), ch);
 		} else {
 			raise_announcement(c);
 			launch_reduce1(c.st, c.gsum(), part[i & 1], g.nblocks, nelem, (double)m);
-			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, r32, n, n, 2, i & 1));
+			hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, c.st, chol_args(c, o, r32, n, n, 2));
 		}
 		HIPCHK(hipGetLastError());
 		return apply_and_close(i);
@@ -2380,7 +2377,7 @@ int tsqr_mi_apply_rinv_f32(int mode, float* q, size_t ldq, const float* a, size_
 	if (engine < 0) return TSQR_MI_ERROR_UNSUPPORTED;
 	Ctx c;
 	init_ctx(c, wq, nullptr, m, n, stream);
-	return apply_rinv(c, engine, q, ldq, a, lda, r, ldr, m, n);
+	return apply_rinv(c, SweepOpts{}, nullptr, engine, q, ldq, a, lda, r, ldr, m, n);
 }
 
 size_t tsqr_mi_gram_elems(size_t n) { const size_t NT = np_of(n) / 16; return NT * (NT + 1) / 2 * 256; }
@@ -2389,7 +2386,7 @@ int tsqr_mi_gram_f32(int level, double* gsum, const float* a, size_t lda, size_t
 	if (m == 0 || n == 0 || n > PW || (level != 1 && level != 2)) return TSQR_MI_ERROR_INVALID_SIZE;
 	Ctx c;
 	init_ctx(c, wq, wr, m, n, stream);
-	const int rc = gram_g(c, a, lda, m, n, level == 2);
+	const int rc = gram_g(c, SweepOpts{}, a, lda, m, n, level == 2);
 	if (rc) return rc;
 	if (gsum && gsum != c.gsum())
 		HIPCHK(hipMemcpyAsync(gsum, c.gsum(), sizeof(double) * tsqr_mi_gram_elems(n), hipMemcpyDeviceToDevice, c.st));
@@ -2404,7 +2401,7 @@ int tsqr_mi_chol_f32(int level, float* r, size_t ldr, const double* gsum, size_t
 	c.rows_global = (double)m;
 	if (gsum && gsum != c.gsum())
 		HIPCHK(hipMemcpyAsync(c.gsum(), gsum, sizeof(double) * tsqr_mi_gram_elems(n), hipMemcpyDeviceToDevice, c.st));
-	int rc = chol_from_g(c, r, ldr, n, level);
+	int rc = chol_from_g(c, SweepOpts{}, r, ldr, n, level);
 	if (rc) return rc;
 	if (!status_out) return 0;                           // asynchronous: read the verdict later with tsqr_mi_chol_status
 	unsigned status = 0;
@@ -2438,7 +2435,7 @@ int tsqr_mi_apply_z_f32(int mode, float* q, size_t ldq, const float* a, size_t l
 	init_ctx(c, wq_v, nullptr, m, n, stream);
 	// under the auto policy a rejected Cholesky (status word != 0) turns a speculatively enqueued apply into a no-op
 	const unsigned* skip = (c.policy == 0) ? c.status_dev(0) : nullptr;
-	return apply_rinv(c, engine, q, ldq, a, lda, nullptr, 0, m, n, /*z_ready=*/true, skip);
+	return apply_rinv(c, SweepOpts{}, nullptr, engine, q, ldq, a, lda, nullptr, 0, m, n, /*z_ready=*/true, skip);
 }
 
 // ---- harness support: the reference's accuracy metrics evaluated on the device in fp64 (src/validation.cu, src/test.cu:147-165) ----
