@@ -382,6 +382,55 @@ inline state_t qr_fp64_wide(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64_wide: ") + tsqr_mi_last_error());
 	return st;
 }
+// Not in the reference: qr_fp64_wide for a matrix whose rows are spread over the ranks of an RCCL communicator, one call per rank
+// (tsqr_mi_qr_f64_dist, include/tsqr_mi.h for the contract): m is THIS rank's block height (1 <= m, m < n allowed), nccl_comm the
+// caller's ncclComm_t -- the caller links RCCL, ncclAllReduce is taken from the global symbol scope.  R is the same on every rank.
+// Returns success_factorization, error_invalid_matrix_size, error_unsupported_mode (n > 1024, or no ncclAllReduce) or error_not_finite.
+template <bool Reorthogonalize>
+struct buffer_fp64_dist {
+	double* dwq;
+	double* dwr;
+	std::size_t total_memory_size;
+
+	buffer_fp64_dist() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
+	~buffer_fp64_dist() { destroy(); }
+	buffer_fp64_dist(const buffer_fp64_dist&) = delete;
+	buffer_fp64_dist& operator=(const buffer_fp64_dist&) = delete;
+
+	void allocate(const std::size_t m_local, const std::size_t n, const int nranks) {
+		if (dwq != nullptr || dwr != nullptr) {
+			throw std::runtime_error("The buffer has been already allocated");
+		}
+		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_dist(m_local, n, nranks);
+		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_dist(m_local, n, nranks);
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
+		total_memory_size = wq_size + wr_size;
+	}
+
+	void destroy() {
+		if (dwq) (void)hipFree(dwq);
+		dwq = nullptr;
+		if (dwr) (void)hipFree(dwr);
+		dwr = nullptr;
+	}
+
+	std::size_t get_device_memory_size() const { return total_memory_size; }
+};
+
+template <bool Reorthogonalize>
+inline state_t qr_fp64_dist(
+		double* const q_ptr, const std::size_t ldq,
+		double* const r_ptr, const std::size_t ldr,
+		double* const a_ptr, const std::size_t lda,
+		const std::size_t m_local, const std::size_t n,
+		buffer_fp64_dist<Reorthogonalize>& bf,
+		void* const nccl_comm, const int nranks,
+		handle_t const stream = nullptr) {
+	const int st = tsqr_mi_qr_f64_dist(Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, a_ptr, lda, m_local, n, bf.dwq, bf.dwr, nccl_comm, nranks, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64_dist: ") + tsqr_mi_last_error());
+	return st;
+}
 }  // namespace qr
 }  // namespace mtk
 

@@ -342,6 +342,42 @@ size_t tsqr_mi_working_r_size_f64_wide(size_t m, size_t n);
 int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
                         size_t m, size_t n, void* wq, void* wr, void* stream);
 
+/*
+ * Row-partitioned double-precision QR (not in the reference): tsqr_mi_qr_f64_wide for a matrix whose rows are spread over the ranks, one
+ * call per rank, 1 <= n <= 1024 (n <= 64 runs the sweeps of tsqr_mi_qr_f64, wider matrices those of tsqr_mi_qr_f64_wide).  Every rank
+ * passes its own row block: m_local may differ between ranks, 1 <= m_local on every rank, and m_local < n is fine.  The GLOBAL row count
+ * must be >= n: that is the caller's contract and is not checked.  A rank that returns early -- 1 for an empty block, say -- leaves the
+ * others waiting in their exchange, so every rank must pass arguments that get past the checks below, or none.
+ * Each sweep of the ladder has ONE exchange, enqueued on `stream` between the Gram reduction and the Cholesky step, with no host wait
+ * that the one-GPU call does not have: the all-reduce (sum, in place) of the Gram matrix and the local row count behind it --
+ * ntri * 256 + 1 <= 2561 doubles for n <= 64, npairs * 4096 + 1 doubles (nb = ceil(n / 64), npairs = nb (nb + 1) / 2; 4.4 MB at n = 1024)
+ * beyond.  Every rank then factors the same bits, and the Cholesky step evaluates the acceptance rule (CholArgs64, tsqr_f64.hip) on the
+ * device from the summed, global row count: the verdicts, hence the number of sweeps and of exchanges, agree on all ranks by
+ * construction, and a NaN anywhere reaches every rank through the sum.  r is bitwise identical on all ranks on return.
+ * For cond(A) <= 1e12 and m_global n <= 2^26, on the stacked matrix:
+ *   ||Q^T Q - I||_F <= 1e-11 max(1, n / 64)  (reorth = 0),  <= 1e-12 max(1, n / 64)  (reorth = 1);  ||A - Q R||_F / ||A||_F <= 1e-13.
+ * Work space: tsqr_mi_working_{q,r}_size_f64_dist(m_local, n, nranks) doubles (never below the sizes of tsqr_mi_qr_f64_wide).
+ * Transport, as for tsqr_mi_qr_f32_dist (the communicator and ncclAllReduce must come from ONE RCCL instance):
+ * tsqr_mi_qr_f64_dist_fn: the caller's ncclComm_t and the address of ncclAllReduce of the library that created it;
+ * tsqr_mi_qr_f64_dist:    a caller that links RCCL: ncclAllReduce from the global symbol scope, as tsqr_mi_qr_f32_dist;
+ * tsqr_mi_qr_f64_dist_cb: a caller-supplied all-reduce (blocking or stream-ordered, in place sum), e.g. torch.distributed.
+ * Returns the states of tsqr_mi_qr_f64_wide: 0, 1 (m_local == 0, n == 0, or a leading dimension below its operand's rows -- but not
+ * n > m_local), 2 (n > 1024, or no all-reduce to call), 3 = TSQR_MI_ERROR_NOT_FINITE (on every rank alike), or -(hipError_t); 1 and 2
+ * come with a tsqr_mi_last_error text and are decided before any HIP call and before any collective.  tsqr_mi_last_sweeps_f64 reports
+ * these entries too.
+ */
+size_t tsqr_mi_working_q_size_f64_dist(size_t m_local, size_t n, int nranks);
+size_t tsqr_mi_working_r_size_f64_dist(size_t m_local, size_t n, int nranks);
+int tsqr_mi_qr_f64_dist(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                        size_t m_local, size_t n, void* wq, void* wr,
+                        void* nccl_comm, int nranks, void* stream);
+int tsqr_mi_qr_f64_dist_fn(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                           size_t m_local, size_t n, void* wq, void* wr,
+                           void* nccl_comm, void* nccl_allreduce_fn, int nranks, void* stream);
+int tsqr_mi_qr_f64_dist_cb(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                           size_t m_local, size_t n, void* wq, void* wr,
+                           tsqr_mi_allreduce_f64_cb allreduce, void* user, int nranks, void* stream);
+
 /* Harness support (reference src/validation.cu:43-127, src/test.cu:147-165): accuracy metrics evaluated on the device in fp64.
  * scratch: n*n + 8 doubles of device memory.  out_host[0..4] = ||Q^T Q - I||_F^2, its diagonal part, its off-diagonal part,
  * ||Q R - A||_F^2, ||A||_F^2 (the last two only when r and a are given).  gram_out_host: optional n*n doubles receiving Q^T Q. */

@@ -1,7 +1,10 @@
 """Speed of the fp64 entries (tsqr_mi_qr_f64, n <= 64, and tsqr_mi_qr_f64_wide, the wide_* cases): median time of blocking calls per
 case, the sweep count, effective TB/s (24 m n bytes per sweep: the Gram pass reads A, the apply pass reads A and writes Q), for the wide
 cases the fp64 rate of one sweep's executed products (2 m n^2, Gram pass and apply pass together), and torch.linalg.qr(float64) on the
-same GPU for 2^20 x 64 and for every wide shape.  Prints one JSON line.  Usage: python tools/f64_speed.py [--calls 50] [--warmup 5]"""
+same GPU for 2^20 x 64 and for every wide shape.  Prints one JSON line.  Usage: python tools/f64_speed.py [--calls 50] [--warmup 5]
+--dist1: instead, the cost of the row-partitioned entry's hook on ONE rank -- tsqr_mi_qr_f64_dist_fn over a one-rank raw RCCL communicator
+against the plain entry on the same operands, calls interleaved in this process, at 2^20 x 64 and 2^18 x 256.  (One rank: the all-reduce
+moves nothing between GPUs; this says nothing about several ranks.)"""
 import argparse
 import json
 import os
@@ -63,15 +66,65 @@ def time_torch_qr(torch, a_rm, reps=3):
     return sorted(ts)[len(ts) // 2] * 1e3
 
 
+def dist1(torch, bq, calls, warmup):
+    import ctypes
+    rccl = ctypes.CDLL("librccl.so")
+
+    class UniqueId(ctypes.Structure):
+        _fields_ = [("internal", ctypes.c_byte * 128)]
+
+    uid = UniqueId()
+    assert rccl.ncclGetUniqueId(ctypes.byref(uid)) == 0
+    comm = ctypes.c_void_p()
+    rccl.ncclCommInitRank.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, UniqueId, ctypes.c_int]
+    assert rccl.ncclCommInitRank(ctypes.byref(comm), 1, uid, 0) == 0
+    allreduce = ctypes.cast(rccl.ncclAllReduce, ctypes.c_void_p)
+    L = bq.lib()
+    out = {"tool": "f64_speed --dist1", "calls": calls, "cases": []}
+    try:
+        for m, n in ((1 << 20, 64), (1 << 18, 256)):
+            a = torch.randn(n, m, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+            q = torch.empty_like(a)
+            r = torch.empty(n, n, dtype=torch.float64, device="cuda")
+            wq = torch.empty(L.tsqr_mi_working_q_size_f64_dist(m, n, 1), dtype=torch.float64, device="cuda")
+            wr = torch.empty(L.tsqr_mi_working_r_size_f64_dist(m, n, 1), dtype=torch.float64, device="cuda")
+            st = torch.cuda.current_stream().cuda_stream
+            head = (0, q.data_ptr(), m, r.data_ptr(), n, a.data_ptr(), m, m, n, wq.data_ptr(), wr.data_ptr())
+            plain = lambda: L.tsqr_mi_qr_f64_wide(*head, st)
+            hooked = lambda: L.tsqr_mi_qr_f64_dist_fn(*head, comm, allreduce, 1, st)
+            ts = {"plain": [], "dist1": []}
+            for i in range(warmup + calls):
+                for name, fn in (("plain", plain), ("dist1", hooked)):
+                    t0 = time.perf_counter()
+                    rc = fn()
+                    dt = time.perf_counter() - t0
+                    assert rc == 0, bq.last_error()
+                    if i >= warmup:
+                        ts[name].append(dt)
+            med = {k: sorted(v)[len(v) // 2] * 1e3 for k, v in ts.items()}
+            lo = {k: min(v) * 1e3 for k, v in ts.items()}
+            out["cases"].append({"m": m, "n": n, "sweeps": L.tsqr_mi_last_sweeps_f64(), "plain_median_ms": med["plain"],
+                                 "dist1_median_ms": med["dist1"], "plain_min_ms": lo["plain"], "dist1_min_ms": lo["dist1"]})
+            del a, q, r, wq, wr
+            torch.cuda.empty_cache()
+    finally:
+        rccl.ncclCommDestroy.argtypes = [ctypes.c_void_p]
+        rccl.ncclCommDestroy(comm)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cases", default="", help="comma-separated case names (default: all)")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch.linalg.qr baseline")
+    ap.add_argument("--dist1", action="store_true", help="time the one-rank row-partitioned call over raw RCCL next to the plain entry")
     args = ap.parse_args()
     import torch
     from tsqr_gpu_amd import blockqr as bq
+    if args.dist1:
+        return dist1(torch, bq, args.calls, args.warmup)
     n = 64
     out = {"tool": "f64_speed", "cases": []}
     gauss = lambda m, seed: torch.randn(m, n, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(seed))

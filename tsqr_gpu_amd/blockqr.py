@@ -53,6 +53,7 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_qr_f32_dist_fn_batch", "tsqr_mi_qr_f32_dist_cb_batch",
     "tsqr_mi_qr_f64", "tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64", "tsqr_mi_last_sweeps_f64",
     "tsqr_mi_qr_f64_wide", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide",
+    "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
 ]
 
 
@@ -185,6 +186,15 @@ def lib():
         getattr(L, name).argtypes = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp]
     L.tsqr_mi_last_sweeps_f64.restype = ci
     L.tsqr_mi_last_sweeps_f64.argtypes = []
+    if hasattr(L, "tsqr_mi_qr_f64_dist_cb"):             # (TSQR_MI_LIB may name an older build for an A/B of the entries both have)
+        for name in ("tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist"):
+            getattr(L, name).restype = sz
+            getattr(L, name).argtypes = [sz, sz, ci]
+        # (reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, <transport>, nranks, stream)
+        f64_dist_head = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp]
+        for name, transport in (("tsqr_mi_qr_f64_dist", [vp]), ("tsqr_mi_qr_f64_dist_fn", [vp, vp]), ("tsqr_mi_qr_f64_dist_cb", [vp, vp])):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = f64_dist_head + transport + [ci, vp]
     _lib = L
     return L
 
@@ -522,8 +532,18 @@ def qr_f64_wide(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=N
     return _qr_f64(_F64_WIDE, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize)
 
 
+def get_working_q_size_f64_dist(m_local, n, nranks):
+    """Doubles of wq for tsqr_mi_qr_f64_dist* (dist.RowPartitionedQRF64 allocates them itself)."""
+    return lib().tsqr_mi_working_q_size_f64_dist(m_local, n, nranks)
+
+
+def get_working_r_size_f64_dist(m_local, n, nranks):
+    """Doubles of wr for tsqr_mi_qr_f64_dist*."""
+    return lib().tsqr_mi_working_r_size_f64_dist(m_local, n, nranks)
+
+
 def last_sweeps_f64():
-    """Sweeps of this thread's last qr_f64 call, plus 100 when it took the shifted path."""
+    """Sweeps of this thread's last qr_f64 / qr_f64_wide / row-partitioned fp64 call, plus 100 when it took the shifted path."""
     return lib().tsqr_mi_last_sweeps_f64()
 
 

@@ -37,16 +37,10 @@ F64Plan f64_plan(size_t m, size_t n) {
 }
 
 // The acceptance rule of a sweep over an m x n matrix (CholArgs64, tsqr_f64.hip, states it and its sources): the bounds on S of a FIRST
-// sweep (later sweeps: max_scond = infinity, never alone) and the coefficient of the shift, s = shift_coef * trace(G)
-struct F64Rule { double shift_coef; float max_scond, alone_max; };
-inline F64Rule f64_rule(size_t m, size_t n, bool first) {
-	F64Rule r{};
-	const double u = 0x1p-53, mn = (double)m * (double)n + (double)n * (double)(n + 1);
-	r.shift_coef = 11.0 * u * mn;
-	r.max_scond = first ? (float)(1.0 / (64.0 * (double)n * u * mn)) : INFINITY;
-	r.alone_max = first ? (float)(1e-12 / (4.0 * (double)n * u)) : 0.0f;
-	return r;
-}
+// sweep (later sweeps: max_scond = infinity, never alone) and the coefficient of the shift, s = shift_coef * trace(G).  The arithmetic is
+// f64_rule_of (tsqr_f64.hip), which the Cholesky kernels of a row-partitioned call evaluate themselves on the all-reduced row count.
+using F64Rule = tsqrmi::F64Rule;
+inline F64Rule f64_rule(size_t m, size_t n, bool first) { return tsqrmi::f64_rule_of((double)m, (int)n, first); }
 
 // the Gram pass of the n <= 64 entry on stream st: gram_f64_kernel<NT> on the plan's grid
 inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramArgs64& ga) {

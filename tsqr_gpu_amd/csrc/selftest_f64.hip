@@ -27,6 +27,15 @@ template <int NT> int selftest_f64_apply(double* q, size_t ldq, const double* a,
 }
 }  // namespace
 
+namespace {
+__global__ __launch_bounds__(64) void f64_rule_probe_kernel(const double* rows, const int* n, const int* first, int count, double* out) {
+	const int i = blockIdx.x * 64 + threadIdx.x;
+	if (i >= count) return;
+	const tsqrmi::F64Rule r = tsqrmi::f64_rule_of(rows[i], n[i], first[i] != 0);
+	out[3 * i] = (double)r.max_scond; out[3 * i + 1] = (double)r.alone_max; out[3 * i + 2] = r.shift_coef;
+}
+}  // namespace
+
 extern "C" {
 
 // out[0..7]: NT, ntri, nch, nwaves, nblocks, doubles of wq, doubles of wr (the partials), F64_GRAM_WAVES.  Host only.
@@ -44,6 +53,15 @@ int tsqr_selftest_f64_rule(size_t m, size_t n, int first, double* out) {
 	const F64Rule r = f64_rule(m, n, first != 0);
 	out[0] = (double)r.max_scond; out[1] = (double)r.alone_max; out[2] = r.shift_coef;
 	return 0;
+}
+
+// The same rule as the DEVICE evaluates it (f64_rule_of inside a kernel: what chol_f64_kernel, cholw_verdict_kernel and wide_shift do in a
+// row-partitioned call, whose row count exists on the device only): case i takes rows[i], n[i], first[i] and leaves out[3 i .. 3 i + 2] =
+// max_scond, alone_max, shift_coef.  All four arrays are device memory.
+int tsqr_selftest_f64_rule_device(const double* rows, const int* n, const int* first, int count, double* out) {
+	if (count <= 0) return -100;
+	hipLaunchKernelGGL(f64_rule_probe_kernel, dim3((unsigned)cdiv((size_t)count, 64)), dim3(64), 0, 0, rows, n, first, count, out);
+	return f64_sync();
 }
 
 // out[0..19]: nb, npairs, ngroups, nslices, cps, nch, bs, o_gs, o_w, o_rw, o_zw, o_ta, o_rc, o_zd, o_sb, o_bst, o_status, wq,

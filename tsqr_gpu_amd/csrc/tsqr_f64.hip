@@ -23,6 +23,22 @@ __global__ __launch_bounds__(256) void gram_f64_kernel(const GramArgs64 a) {
 	gram_body<NT, double>(a, red);
 }
 
+// The three numbers of the acceptance rule (stated at CholArgs64 below) for a sweep over `rows` x n (first: the first sweep of a call).
+// ONE definition for the host (f64_rule, f64_plan.h: a one-GPU call knows its rows) and for the device (a row-partitioned call: only
+// the device sees the all-reduced row count).
+// Both give the same bits: rows n and n (n + 1) are exact integers below 2^53 (rows n <= 2^26 by contract, n <= 1024), so their sum is
+// exact whether or not the compiler contracts it into an FMA; everything after it is a product -- one rounding each, no addition to
+// contract with -- and one IEEE division, correctly rounded on both sides (no fast-math), then one conversion to float.
+struct F64Rule { double shift_coef; float max_scond, alone_max; };
+__host__ __device__ inline F64Rule f64_rule_of(double rows, int n, bool first) {
+	F64Rule r{};
+	const double u = 0x1p-53, mn = rows * (double)n + (double)n * (double)(n + 1);
+	r.shift_coef = 11.0 * u * mn;
+	r.max_scond = first ? (float)(1.0 / (64.0 * (double)n * u * mn)) : INFINITY;
+	r.alone_max = first ? (float)(1e-12 / (4.0 * (double)n * u)) : 0.0f;
+	return r;
+}
+
 // The Cholesky step of the fp64 entry: chol_body16 with fp64 R and Z.  Level 4 of the ladder ("fp64 data"): the rule is stated on the
 // scaled conditioning S = ||D inverse(R)||_F^2 / n (D = diag(sqrt(g_jj)); chol_body16), with u = 2^-53 and rows = m:
 //   accepted for CholeskyQR2   every pivot positive and finite, and  64 n S u (m n + n (n + 1)) <= 1.  Yamamoto, Nakatsukasa, Yanagisawa
@@ -47,20 +63,24 @@ struct CholArgs64 {
 	float max_scond;                     // CholeskyQR2 bound on S (above)
 	float alone_max;                     // one-sweep bound on S (above); 0: never alone
 	int n, NT;
+	const double* rows_dev;              // row-partitioned call: the all-reduced (global) row count behind the summed tiles; the three numbers
+	int first;                           // above are then f64_rule_of(rows_dev[0], n, first) and the arguments are not looked at.  Null: one GPU
 };
 // verdict words: 0 accepted, 2 accepted after the shift, 1 rejected (non-finite input)
 __global__ __launch_bounds__(1024) void chol_f64_kernel(const CholArgs64 a) {
 	auto loadg = [&](int e) { return a.gsum[e]; };
-	chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, a.max_scond, 0.0, 0.0);
+	F64Rule rule{a.shift_coef, a.max_scond, a.alone_max};
+	if (a.rows_dev) rule = f64_rule_of(a.rows_dev[0], a.n, a.first != 0);     // (uniform: every thread reads the same word)
+	chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, rule.max_scond, 0.0, 0.0);
 	__shared__ unsigned again;
 	__syncthreads();
 	if (threadIdx.x == 0) {                              // (thread 0 wrote the verdict itself: program order)
 		again = a.status[0];
-		a.status[3] = (a.status[0] == 0u && __builtin_bit_cast(float, a.status[2]) <= a.alone_max) ? 1u : 0u;
+		a.status[3] = (a.status[0] == 0u && __builtin_bit_cast(float, a.status[2]) <= rule.alone_max) ? 1u : 0u;
 	}
 	__syncthreads();
 	if (again) {
-		chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, INFINITY, a.shift_coef, 0.0);
+		chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, INFINITY, rule.shift_coef, 0.0);
 		__syncthreads();
 		if (threadIdx.x == 0) {
 			if (a.status[0] == 0u) a.status[0] = 2u;

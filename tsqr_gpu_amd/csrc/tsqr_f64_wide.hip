@@ -36,6 +36,9 @@ struct WideF64 {
 	double shift_coef;                   // 11 u (m n + n (n + 1)): s = shift_coef * trace(G), shifted chain only (0 otherwise)
 	float max_scond, alone_max;
 	int n, nb;
+	const double* rows_dev;              // row-partitioned call: the all-reduced (global) row count behind the summed blocks.  The two bounds
+	int first;                           // and the coefficient of the shift are then f64_rule_of(rows_dev[0], n, first) (tsqr_f64.hip); of
+	                                     // shift_coef only "> 0: the shifted chain" is looked at.  Null: one GPU, the arguments hold
 };
 
 __device__ __forceinline__ bool wide_skip(const WideF64& a) { return a.run_if && a.run_if[0] == 0u; }
@@ -48,7 +51,8 @@ __device__ double wide_shift(const WideF64& a) {
 		double tr = 0.0;
 		for (int c = j; c < a.n; c += 64) tr += a.gs[(size_t)wpair(c >> 6, c >> 6) * 4096 + (c & 63) * 65];
 		for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o);
-		if (j == 0) sh = a.shift_coef * tr;
+		// (one expression for every caller; the coefficient of a row-partitioned call is a pure function of one word every kernel reads alike)
+		if (j == 0) sh = (a.rows_dev ? f64_rule_of(a.rows_dev[0], a.n, a.first != 0).shift_coef : a.shift_coef) * tr;
 	}
 	__syncthreads();
 	return sh;
@@ -319,12 +323,14 @@ __global__ __launch_bounds__(64) void cholw_verdict_kernel(const WideF64 a) {
 			for (int I = 0; I <= J; I++) ssum += a.sb[I * a.nb + J];
 		}
 		const float scond = (float)(ssum / (double)a.n);
-		const float max_scond = shifted ? INFINITY : a.max_scond;
+		F64Rule rule{a.shift_coef, a.max_scond, a.alone_max};
+		if (a.rows_dev) rule = f64_rule_of(a.rows_dev[0], a.n, a.first != 0);
+		const float max_scond = shifted ? INFINITY : rule.max_scond;
 		const bool ok = bad == 0u && rm > 0.0f && scond <= max_scond;     // NaN compares false -> rejected
 		a.status[0] = shifted ? (ok ? 2u : 1u) : (ok ? 0u : 1u);
 		a.status[1] = __builtin_bit_cast(unsigned, rm);
 		a.status[2] = __builtin_bit_cast(unsigned, scond);
-		a.status[3] = (!shifted && ok && scond <= a.alone_max) ? 1u : 0u;
+		a.status[3] = (!shifted && ok && scond <= rule.alone_max) ? 1u : 0u;
 	}
 	if (shifted) {
 		volatile unsigned* hs = a.host_status;

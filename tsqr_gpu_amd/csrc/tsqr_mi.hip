@@ -2486,9 +2486,18 @@ constexpr int F64_MAX_SWEEPS = 6;
 thread_local int t_sweeps64 = 0;
 thread_local OwnPinned t_own64;                         // the verdict words of the fp64 entry (slot k & 3 for sweep k)
 
+// The exchange of a row-partitioned sweep (comm active; tsqr_mi_qr_f64_dist*): the summed Gram tiles and the local row count behind
+// them, nelem + 1 doubles, all-reduced in place on the stream between the reduction and the Cholesky step -- no host wait.  Every rank
+// then factors the same bits, and the Cholesky step takes its rule from the summed row count (rows_dev).
+int f64_exchange(const Comm* comm, double* gsum, size_t nelem, hipStream_t st) {
+	if (!comm || !comm->active()) return 0;
+	if (comm->allreduce_f64(gsum, nelem + 1, st)) { t_last_error = "all-reduce of the fp64 Gram tiles failed"; return -1; }
+	return 0;
+}
+
 // Gram pass, reduction and Cholesky step of one sweep over src: R -> r (ldr), Z -> wq[F64_Z], verdict -> status slot `slot`
 int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t ld, size_t m, size_t n, double* r, size_t ldr,
-               bool first, int slot) {
+               bool first, int slot, const Comm* comm = nullptr) {
 	const F64Plan g = f64_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
 	const tsqrmi::GramArgs64 ga{src, ld, m, (int)n, g.nch, g.nwaves, wr};
@@ -2497,6 +2506,7 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
 	const int nelem = g.ntri * 256;
 	launch_reduce1(st, wq + F64_GSUM, wr, g.nblocks, nelem, (double)m);
 	HIPCHK(hipGetLastError());
+	if (const int rc = f64_exchange(comm, wq + F64_GSUM, (size_t)nelem, st)) return rc;
 	tsqrmi::CholArgs64 ca{};
 	ca.r = r; ca.ldr = ldr; ca.z = wq + F64_Z;
 	ca.status = reinterpret_cast<unsigned*>(wq + F64_STATUS) + 4 * slot;
@@ -2505,6 +2515,7 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
 	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64 states the rule and its sources)
 	ca.shift_coef = rule.shift_coef; ca.max_scond = rule.max_scond; ca.alone_max = rule.alone_max;
 	ca.n = (int)n; ca.NT = g.NT;
+	if (comm && comm->active()) { ca.rows_dev = wq + F64_GSUM + nelem; ca.first = first ? 1 : 0; }   // (the rule of the GLOBAL row count, on the device)
 	hipLaunchKernelGGL(tsqrmi::chol_f64_kernel, dim3(1), dim3(1024), 0, st, ca);
 	HIPCHK(hipGetLastError());
 	return 0;
@@ -2527,11 +2538,11 @@ template <int NT> int f64_apply(hipStream_t st, int dev, double* q, size_t ldq, 
 
 // sweep k (0-based): sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R
 int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-              double* wq, double* wr) {
+              double* wq, double* wr, const Comm* comm) {
 	const bool first = k == 0;
 	const double* src = first ? a : q;
 	const size_t lds = first ? lda : ldq;
-	int rc = f64_factor(st, wq, wr, src, lds, m, n, first ? r : wq + F64_R2, first ? ldr : 64, first, k & 3);
+	int rc = f64_factor(st, wq, wr, src, lds, m, n, first ? r : wq + F64_R2, first ? ldr : 64, first, k & 3, comm);
 	if (rc) return rc;
 	const double* z = wq + F64_Z;
 	rc = with_nt((int)(np_of(n) / 16), [&](auto nt) { return f64_apply<decltype(nt)::value>(st, dev, q, ldq, src, lds, m, n, z); });
@@ -2542,13 +2553,13 @@ int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, 
 }
 
 int f64w_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-               double* wq, double* wr);
+               double* wq, double* wr, const Comm* comm);
 
 // The ladder (include/tsqr_mi.h): verdict 0 of sweep 0 with "one sweep suffices" ends a reorth = 0 call, any other accepted first
 // sweep is followed by one more (CholeskyQR2), a shifted sweep by two more (shifted CholeskyQR3), a rejected one ends the call (state 3).
 // wide: the sweeps of tsqr_mi_qr_f64_wide for n > 64 (f64w_sweep); the verdict words and their meaning are the same.
 int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
-                hipStream_t st, bool wide = false) {
+                hipStream_t st, bool wide = false, const Comm* comm = nullptr) {
 	t_sweeps64 = 0;
 	if (!t_own64.get()) { t_last_error = "could not allocate the pinned verdict words"; return -(int)hipErrorOutOfMemory; }
 	volatile unsigned* words = t_own64.host;
@@ -2558,8 +2569,8 @@ int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double
 	bool shifted = false;
 	for (;;) {
 		while (sweeps < need) {
-			const int rc = wide ? f64w_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr)
-			                    : f64_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr);
+			const int rc = wide ? f64w_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm)
+			                    : f64_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm);
 			if (rc) return rc;
 			sweeps++;
 		}
@@ -2572,6 +2583,9 @@ int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double
 				t_last_error = "non-finite input: the Cholesky step was rejected even with the shift";
 				return TSQR_MI_ERROR_NOT_FINITE;
 			}
+			// Row-partitioned call: each rank reads its OWN pinned words.  The ranks factored the same all-reduced bits with deterministic
+			// kernels and a rule taken from the same summed row count, so the words are equal on all ranks and every rank arrives at the
+			// same `need` -- the same number of sweeps, hence of all-reduces -- without a vote.
 			if (v == 2u) { shifted = true; need = std::max(need, checked + 3); }
 			else if (checked == 0 && !(reorth == 0 && w[3] == 1u)) need = std::max(need, 2);
 		}
@@ -2619,7 +2633,7 @@ namespace {
 
 // sweep k (0-based) of the wide entry: sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R
 int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-               double* wq, double* wr) {
+               double* wq, double* wr, const Comm* comm) {
 	const bool first = k == 0;
 	const double* src = first ? a : q;
 	const size_t lds = first ? lda : ldq;
@@ -2631,6 +2645,7 @@ int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double
 	const int nelem = (int)g.bs;
 	launch_reduce1(st, wq + g.o_gs, wr, g.nslices, nelem, (double)m);
 	HIPCHK(hipGetLastError());
+	if (const int rc = f64_exchange(comm, wq + g.o_gs, g.bs, st)) return rc;
 	tsqrmi::WideF64 wa{};
 	wa.gs = wq + g.o_gs; wa.w = wq + g.o_w; wa.rw = wq + g.o_rw; wa.zw = wq + g.o_zw; wa.ta = wq + g.o_ta; wa.zd = wq + g.o_zd;
 	wa.sb = wq + g.o_sb;
@@ -2641,6 +2656,7 @@ int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double
 	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64, tsqr_f64.hip, states the rule)
 	wa.max_scond = rule.max_scond; wa.alone_max = rule.alone_max;
 	wa.n = (int)n; wa.nb = g.nb;
+	if (comm && comm->active()) { wa.rows_dev = wq + g.o_gs + g.bs; wa.first = first ? 1 : 0; }   // (the rule of the GLOBAL row count, on the device)
 	wa.run_if = nullptr; wa.shift_coef = 0.0;
 	int rc = f64w_chain(st, wa);
 	if (rc) return rc;
@@ -2689,6 +2705,48 @@ int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr
 	if (rc) return rc;
 	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
 	                   reinterpret_cast<hipStream_t>(stream), true);
+}
+
+// ---- row-partitioned fp64: one call per rank, the ladder of tsqr_mi_qr_f64_wide with the exchange of f64_exchange in every sweep ----
+size_t tsqr_mi_working_q_size_f64_dist(size_t m_local, size_t n, int /*nranks*/) { return tsqr_mi_working_q_size_f64_wide(m_local, n); }
+size_t tsqr_mi_working_r_size_f64_dist(size_t m_local, size_t n, int /*nranks*/) { return tsqr_mi_working_r_size_f64_wide(m_local, n); }
+
+// every state that does not need the device is decided here, before any HIP call and before any collective
+static int qr_f64_dist(const Comm& comm, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                       size_t m_local, size_t n, void* wq, void* wr, void* stream) {
+	t_sweeps64 = 0;
+	if (m_local == 0 || n == 0 || ldq < m_local || lda < m_local || ldr < n) {
+		t_last_error = "tsqr_mi_qr_f64_dist: m_local >= 1, n >= 1, ldq >= m_local, lda >= m_local and ldr >= n are required";
+		return TSQR_MI_ERROR_INVALID_SIZE;
+	}
+	if (n > F64W_MAX_N) { t_last_error = "tsqr_mi_qr_f64_dist supports n <= 1024"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (!comm.active()) {
+		t_last_error = "tsqr_mi_qr_f64_dist needs an all-reduce: a callback, or an ncclComm_t with the ncclAllReduce entry point of the library that created it";
+		return TSQR_MI_ERROR_UNSUPPORTED;
+	}
+	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	if (rc) return rc;
+	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m_local, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
+	                   reinterpret_cast<hipStream_t>(stream), n > PW, &comm);
+}
+
+int tsqr_mi_qr_f64_dist_cb(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m_local, size_t n,
+                           void* wq, void* wr, tsqr_mi_allreduce_f64_cb allreduce, void* user, int nranks, void* stream) {
+	Comm comm;
+	comm.nranks = nranks; comm.cb_allreduce = allreduce; comm.cb_user = user;
+	return qr_f64_dist(comm, reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, stream);
+}
+int tsqr_mi_qr_f64_dist_fn(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m_local, size_t n,
+                           void* wq, void* wr, void* nccl_comm, void* nccl_allreduce_fn, int nranks, void* stream) {
+	Comm comm;
+	comm.nranks = nranks;
+	if (nccl_comm && nccl_allreduce_fn) { comm.nccl = nccl_comm; comm.nccl_allreduce = reinterpret_cast<nccl_allreduce_t>(nccl_allreduce_fn); }
+	return qr_f64_dist(comm, reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, stream);
+}
+int tsqr_mi_qr_f64_dist(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m_local, size_t n,
+                        void* wq, void* wr, void* nccl_comm, int nranks, void* stream) {
+	// (null when the caller does not link RCCL: state 2 with its text, after the size checks)
+	return tsqr_mi_qr_f64_dist_fn(reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, nccl_comm, rccl_symbol("ncclAllReduce"), nranks, stream);
 }
 
 }  // extern "C"

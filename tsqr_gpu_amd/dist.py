@@ -130,18 +130,14 @@ _ALLREDUCE_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
 _ALLGATHER_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
 
 
-class HipBackend:
-    """The product: one C-ABI call per factorisation (libtsqr_mi.so; raises if the library is missing -- no CPU fallback)."""
+class _ExchangeCallbacks:
+    """The callback transport of a per-rank C call, shared by the fp32 and the fp64 engine: the C side hands back device pointers inside
+    the engine's own buffers (self._buffers: 1-D GPU tensors of any element type); they become tensor views and go to the collectives
+    object (self.coll: TorchCollectives or a double with its methods).  An exception never crosses the C frame: it is kept in
+    self._cb_error for the caller of the C entry to raise."""
 
-    def __init__(self, mode, m_local, n, world, comm=None, collectives=None):
-        self.mode = bq.compute_mode(mode)
-        self.n, self.m_local, self.world = n, m_local, world
-        L = bq.lib()
-        self.wq = torch.empty(max(L.tsqr_mi_working_q_size_dist(m_local, n, world), 1), dtype=torch.float32, device="cuda")
-        self.wr = torch.empty(max(L.tsqr_mi_working_r_size_dist(m_local, n, world), 1), dtype=torch.float32, device="cuda")
-        pc = min(n, 64)                                # (n > 64: 64-column panels; the all-gather is one panel's factors)
-        self.gather = torch.empty(world * pc * pc, dtype=torch.float32, device="cuda")
-        self.comm = comm                               # RcclComm or None
+    def _init_callbacks(self, buffers, collectives):
+        self._buffers = tuple(buffers)
         self.coll = collectives or TorchCollectives()
         self._cb_error = None
         self._ar = _ALLREDUCE_CB(self._allreduce)
@@ -149,13 +145,11 @@ class HipBackend:
 
     # ---- callbacks: device pointers inside our own buffers -> tensor views -> torch.distributed ----
     def _view(self, ptr, count, dtype):
-        for t in (self.wq, self.wr, self.gather):
+        size = 8 if dtype == torch.float64 else 4
+        for t in self._buffers:
             base = t.data_ptr()
-            if base <= ptr < base + 4 * t.numel():
-                off = (ptr - base) // 4
-                if dtype == torch.float64:
-                    return t[off:off + 2 * count].view(torch.float64)
-                return t[off:off + count]
+            if base <= ptr and ptr + size * count <= base + t.element_size() * t.numel():
+                return t.view(torch.uint8)[ptr - base:ptr - base + size * count].view(dtype)
         raise RuntimeError("collective on a pointer outside the engine's buffers")
 
     def _allreduce(self, user, buf, count, stream):
@@ -173,6 +167,21 @@ class HipBackend:
         except Exception as e:
             self._cb_error = e
             return 1
+
+
+class HipBackend(_ExchangeCallbacks):
+    """The product: one C-ABI call per factorisation (libtsqr_mi.so; raises if the library is missing -- no CPU fallback)."""
+
+    def __init__(self, mode, m_local, n, world, comm=None, collectives=None):
+        self.mode = bq.compute_mode(mode)
+        self.n, self.m_local, self.world = n, m_local, world
+        L = bq.lib()
+        self.wq = torch.empty(max(L.tsqr_mi_working_q_size_dist(m_local, n, world), 1), dtype=torch.float32, device="cuda")
+        self.wr = torch.empty(max(L.tsqr_mi_working_r_size_dist(m_local, n, world), 1), dtype=torch.float32, device="cuda")
+        pc = min(n, 64)                                # (n > 64: 64-column panels; the all-gather is one panel's factors)
+        self.gather = torch.empty(world * pc * pc, dtype=torch.float32, device="cuda")
+        self.comm = comm                               # RcclComm or None
+        self._init_callbacks((self.wq, self.wr, self.gather), collectives)
 
     @property
     def last_engine(self):
@@ -268,6 +277,32 @@ class HipBackend:
         return call
 
 
+def _require_rows(group, world, m_local, n):
+    """Collective: raises ValueError on EVERY rank when any rank's block is empty (or n == 0)."""
+    least = min(int(m_local), int(n))
+    if world > 1:
+        on_gpu = dist.get_backend(group) == "nccl"
+        t = torch.tensor([least], dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()) if on_gpu else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
+        least = int(t.item())
+    if least < 1:
+        raise ValueError("row-partitioned QR: every rank needs m_local >= 1 and n >= 1 (at least one rank passed an empty block)")
+
+
+def _raw_comm(comm, group, world):
+    """The transport choice of RowPartitionedQR / RowPartitionedQRF64: an RcclComm (given, or created when asked for or possible), or
+    None for the torch.distributed callbacks."""
+    if isinstance(comm, RcclComm):
+        return comm
+    if dist.is_initialized() and ((comm == "auto" and world > 1) or comm == "rccl"):
+        try:
+            return RcclComm(group)
+        except Exception:
+            if comm == "rccl":
+                raise
+    return None
+
+
 class RowPartitionedQR:
     """mtk::qr::qr for a matrix whose rows are spread over the ranks of `group`.
 
@@ -286,29 +321,13 @@ class RowPartitionedQR:
             self.backend = backend
             self.transport = "test-double"
             return
-        raw = None
-        if isinstance(comm, RcclComm):
-            raw = comm
-        elif dist.is_initialized() and ((comm == "auto" and self.world > 1) or comm == "rccl"):
-            try:
-                raw = RcclComm(group)
-            except Exception:
-                if comm == "rccl":
-                    raise
-                raw = None
+        raw = _raw_comm(comm, group, self.world)
         self.transport = "rccl" if raw is not None else "torch.distributed callbacks"
         self.backend = HipBackend(mode, m_local, n, self.world, comm=raw, collectives=TorchCollectives(group))
 
     def _require_rows(self, m_local):
         """Collective: raises ValueError on EVERY rank when any rank's block is empty (or n == 0)."""
-        least = min(int(m_local), int(self.n))
-        if self.world > 1:
-            on_gpu = dist.get_backend(self.group) == "nccl"
-            t = torch.tensor([least], dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()) if on_gpu else "cpu")
-            dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
-            least = int(t.item())
-        if least < 1:
-            raise ValueError("row-partitioned QR: every rank needs m_local >= 1 and n >= 1 (at least one rank passed an empty block)")
+        _require_rows(self.group, self.world, m_local, self.n)
 
     def qr(self, q, ldq, r, a, lda, reorthogonalize=False, m_local=None):
         """q, a: column-major m_local x n blocks (tensors; q may alias a only with reorthogonalize... never for the first sweep);
@@ -356,3 +375,70 @@ class RowPartitionedQR:
     @property
     def last_engine(self):
         return getattr(self.backend, "last_engine", 0)
+
+
+class RowPartitionedQRF64(_ExchangeCallbacks):
+    """Double-precision QR (1 <= n <= 1024) of a matrix whose rows are spread over the ranks of `group`: one tsqr_mi_qr_f64_dist_{fn,cb}
+    call per rank (include/tsqr_mi.h), the ladder of qr_f64_wide with one all-reduce of the Gram matrix and the row count per sweep.
+    m_local: the tallest block this rank will pass (it sizes the work space); 1 <= m_local, m_local < n is fine as long as the ranks
+    hold n rows between them.  comm: as RowPartitionedQR ("auto", "rccl", "callbacks" or an RcclComm)."""
+
+    def __init__(self, m_local, n, group=None, comm="auto"):
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.n, self.m_local = n, m_local
+        _require_rows(group, self.world, m_local, n)      # (collective: every rank raises together)
+        self.comm = _raw_comm(comm, group, self.world)
+        self.transport = "rccl" if self.comm is not None else "torch.distributed callbacks"
+        L = bq.lib()
+        self.wq = torch.empty(max(L.tsqr_mi_working_q_size_f64_dist(m_local, n, self.world), 1), dtype=torch.float64, device="cuda")
+        self.wr = torch.empty(max(L.tsqr_mi_working_r_size_f64_dist(m_local, n, self.world), 1), dtype=torch.float64, device="cuda")
+        self._init_callbacks((self.wq, self.wr), TorchCollectives(group))
+        self._sweeps = 0
+
+    def _check_operands(self, q, ldq, r, a, lda, m_local):
+        """Before anything is handed to C, which cannot see an allocation: dtype, device, ld >= rows, numel >= (n - 1) ld + rows."""
+        n = self.n
+        for name, t, ld, rows in (("q", q, ldq, m_local), ("r", r, n, n), ("a", a, lda, m_local)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise TypeError("RowPartitionedQRF64: %s must be a float64 tensor, got %s" % (name, getattr(t, "dtype", type(t).__name__)))
+            if not t.is_cuda:
+                raise TypeError("RowPartitionedQRF64: %s is not a GPU tensor" % name)
+            if ld < rows:
+                raise ValueError("RowPartitionedQRF64: the leading dimension %d of %s is below its %d rows" % (ld, name, rows))
+            need = (n - 1) * ld + rows
+            if t.numel() < need:
+                raise ValueError("RowPartitionedQRF64: %s holds %d elements, %d x %d with ld %d needs %d" % (name, t.numel(), rows, n, ld, need))
+        L = bq.lib()
+        if (L.tsqr_mi_working_q_size_f64_dist(m_local, n, self.world) > self.wq.numel() or
+                L.tsqr_mi_working_r_size_f64_dist(m_local, n, self.world) > self.wr.numel()):
+            raise ValueError("row block of %d rows needs larger work buffers than were allocated for %d rows: construct "
+                             "RowPartitionedQRF64 with the largest block height" % (m_local, self.m_local))
+
+    def qr(self, q, ldq, r, a, lda, reorthogonalize=False, m_local=None):
+        """q, a: column-major m_local x n float64 blocks on the GPU (q may be a itself with ldq == lda: in place); r: n x n, ld n,
+        identical bits on every rank on return.  Blocking, collective.  Returns the state of tsqr_mi_qr_f64_dist (0, 1, 2 or 3: the
+        same on every rank).  The operand checks raise on this rank alone -- before any collective, so the other ranks would wait:
+        a caller that cannot rule them out must agree on them first."""
+        m_local = self.m_local if m_local is None else m_local
+        self._check_operands(q, ldq, r, a, lda, m_local)
+        st = torch.cuda.current_stream().cuda_stream   # the callbacks issue torch work on the current stream: it must be this one
+        L = bq.lib()
+        head = (int(bool(reorthogonalize)), q.data_ptr(), ldq, r.data_ptr(), self.n, a.data_ptr(), lda, m_local, self.n,
+                self.wq.data_ptr(), self.wr.data_ptr())
+        self._cb_error = None
+        if self.comm is not None:
+            rc = L.tsqr_mi_qr_f64_dist_fn(*head, self.comm.comm, self.comm.allreduce_fn, self.world, st)
+        else:
+            rc = L.tsqr_mi_qr_f64_dist_cb(*head, self._ar, None, self.world, st)
+        self._sweeps = L.tsqr_mi_last_sweeps_f64()
+        if self._cb_error is not None:
+            raise self._cb_error
+        if rc < 0:
+            raise RuntimeError("tsqr_mi_qr_f64_dist failed: %s" % bq.last_error())
+        return rc
+
+    @property
+    def last_sweeps(self):
+        """Sweeps of the last qr() of this object, plus 100 when it took the shifted path (tsqr_mi_last_sweeps_f64)."""
+        return self._sweeps
