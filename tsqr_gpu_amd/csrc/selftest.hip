@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void apply_stamp_kernel(const tsqrmi::ApplyArg
 }
 extern "C" int tsqr_selftest_apply_balance(float* q, const float* a, size_t ld, size_t m, const float* z, int nwg, unsigned long long* stamps, int warm,
                                            int s0, int s1, int s2, int s3, int even_share) {
-	constexpr size_t lds = sizeof(float) * 64 * (64 + 4) + (size_t)3 * 6 * 512 * 2;
+	constexpr size_t lds = tsqrmi::ApplyGeom<1, 4, false, 64>::lds_bytes(false);   // (apply_stamp_kernel's instance)
 	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&apply_stamp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 	tsqrmi::ApplyArgs aa{};
 	aa.a = a; aa.lda = ld; aa.q = q; aa.ldq = ld; aa.m = m; aa.n = 64; aa.z = z;

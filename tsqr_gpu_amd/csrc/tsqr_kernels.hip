@@ -2011,6 +2011,92 @@ struct ApplyArgs {
 	                                    // A/B -- the second sweep then starts with the blocks the cache has already dropped)
 };
 
+// The geometry of one apply instance: every size and index map that the kernel body (apply_wg_body), the host launchers and the test
+// library share.  Plain constexpr C++: one definition on both sides of the launch, so the dynamic-LDS size cannot drift from the layout.
+template <int ENGINE_, int NT_, bool UPD_, int ROWS_, int NW_ = 4>
+struct ApplyGeom {
+	static constexpr int ENGINE = ENGINE_, NT = NT_, ROWS = ROWS_, NW = NW_;
+	static constexpr bool UPD = UPD_;
+	static constexpr int THREADS = 64 * NW;
+	static constexpr int NP = 16 * NT;
+	static constexpr int NTRI = (NT * (NT + 1)) / 2;
+	static constexpr int RS = ROWS + 4;                         // column stride of As (floats)
+	static constexpr int LPC = ROWS / 4, CPI = 64 / LPC;        // lanes per column, columns per load instruction
+	static constexpr int NI = NP / (NW * CPI);                  // load instructions per wave and block
+	static constexpr int SL = ROWS / (16 * NW);                 // 16-row slabs per wave
+	static constexpr int ZS = NP + 16;
+	// fp32-MFMA engine, triangular 128 x 128 Z: only the part on and right of the diagonal tiles is kept (row k holds the columns
+	// j >= 16 (k / 16)), 40 KiB instead of 72 -- two workgroups then share a CU.  The row stride of a 16-row group is its length padded
+	// to 16 or 48 mod 64 floats, so that the four rows a B operand touches (k = 4t + q) fall on different banks.
+	static constexpr bool ZTRI = (ENGINE == 0 && NT == 8 && !UPD);
+	__host__ __device__ __forceinline__ static constexpr int ztri_stride(int g) { return g == 0 ? 144 : (g <= 2 ? 112 : (g <= 4 ? 80 : (g <= 6 ? 48 : 16))); }
+	__host__ __device__ __forceinline__ static constexpr int ztri_base(int g) { int o = 0; for (int i = 0; i < g; i++) o += 16 * ztri_stride(i); return o; }
+	static constexpr int KT = (NP + 31) / 32;
+	// blocks (kt, ct) of the MFMA-operand image of Z: for a triangular 64 x 64 Z the two blocks (1,0), (1,1) are zero and
+	// are not stored -- 18.4 KB instead of 24.6 KB, which lets three workgroups share a CU's LDS
+	static constexpr bool COMPACT = (!UPD && (NT == 4 || NT == 8));
+	static constexpr int NB = COMPACT ? KT * NT - KT * (KT - 1) : KT * NT;      // triangular: row kt keeps the blocks ct >= 2 kt
+	__host__ __device__ __forceinline__ static constexpr int zblk(int kt, int ct) { return COMPACT ? kt * NT - kt * (kt - 1) + ct - 2 * kt : kt * NT + ct; }
+	__host__ __device__ __forceinline__ static constexpr int zblk_kt(int b) { int kt = 0; while (COMPACT && kt + 1 < KT && b >= (kt + 1) * NT - (kt + 1) * kt) kt++; return COMPACT ? kt : b / NT; }
+	__host__ __device__ __forceinline__ static constexpr int zblk_ct(int b, int kt) { return COMPACT ? b - (kt * NT - kt * (kt - 1)) + 2 * kt : b % NT; }   // (kt = zblk_kt(b))
+	__host__ __device__ __forceinline__ static constexpr int swz(int col) { return ((col >> 3) & 1) << 4; }
+	// dynamic LDS: the block As, behind it Z (ENGINE 0: floats, whole or triangular; 1: three bf16 operand images; 2: one fp16 image)
+	static constexpr size_t block_bytes() { return sizeof(float) * NP * RS; }
+	static constexpr size_t z_bytes() {
+		return ENGINE == 0 ? sizeof(float) * (ZTRI ? ztri_base(NT) : NP * ZS) : (size_t)(ENGINE == 2 ? 1 : 3) * NB * 512 * 2;
+	}
+	static constexpr size_t lds_bytes(bool gramq) {          // GRAMQ: the final workgroup reduction (wg_sum4_store) aliases the block
+		const size_t lds = block_bytes() + z_bytes(), red = sizeof(double) * 2 * NTRI * 256;
+		return gramq && red > lds ? red : lds;
+	}
+};
+// today's sizes: a change of the layout is a deliberate edit of these
+static_assert(ApplyGeom<1, 4, false, 64>::lds_bytes(false) == 35840 && ApplyGeom<1, 4, false, 64>::NB == 6, "apply_wg_kernel<1, 4, false, 64>");
+static_assert(ApplyGeom<0, 4, false, 128>::lds_bytes(false) == 54272, "apply_wg_kernel<0, 4, false, 128>");
+static_assert(ApplyGeom<1, 8, false, 128, 8>::lds_bytes(false) == 129024 && ApplyGeom<1, 8, false, 128, 8>::NB == 20, "apply_wide_kernel<1>");
+static_assert(ApplyGeom<2, 8, false, 128, 8>::lds_bytes(false) == 88064, "apply_wide_kernel<2>");
+static_assert(ApplyGeom<0, 8, false, 64>::lds_bytes(false) == 75776 && ApplyGeom<0, 8, false, 64>::z_bytes() == 10240 * sizeof(float), "apply_wide_f32_kernel");
+
+// The fused Gram accumulation of apply_wg_body (GRAMQ), wave wv, lane (c, q), after the wave has written its result rows to As.
+// Gram tiles of this wave's freshly written rows (ROWS/4 rows = ROWS/128 K-steps of 32): lane (c,q) reads logical rows
+// 8q..8q+7 of column 16t+c (two 16-byte reads; the XOR swizzle keeps 8-row groups contiguous), one MFMA chain from zero per
+// K-step, added to fp64 totals -- exactly gram_bf16_kernel's arithmetic on the values that are about to be stored
+template <class G>
+__device__ __forceinline__ void gramq_accumulate(f64x4 (&gtot)[G::NTRI], const float* As, const int wv, const int c, const int q) {
+	constexpr int NT = G::NT, NTRI = G::NTRI;
+#pragma unroll
+	for (int ks = 0; ks < G::ROWS / 128; ks++) {
+		const int rbk = wv * (G::ROWS / 4) + 32 * ks + 8 * q;
+		bf16x8 oh[NT], om[NT], ol[NT];
+#pragma unroll
+		for (int tt = 0; tt < NT; tt++) {
+			const int col = 16 * tt + c;
+			split3_operand(*reinterpret_cast<const f32x4*>(&As[col * G::RS + (rbk ^ G::swz(col))]),
+			               *reinterpret_cast<const f32x4*>(&As[col * G::RS + ((rbk + 4) ^ G::swz(col))]), oh[tt], om[tt], ol[tt]);
+		}
+		f32x4 gacc[NTRI];
+#pragma unroll
+		for (int tt = 0; tt < NTRI; tt++) gacc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+		for (int pass = 3; pass < 9; pass++) {       // (split_a: the six products, smallest first)
+			int idx = 0;
+#pragma unroll
+			for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+				for (int tj = ti; tj < NT; tj++) {
+					gacc[idx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(split_a(pass, oh[ti], om[ti], ol[ti]), split_b(pass, oh[tj], om[tj], ol[tj]),
+					                                                    gacc[idx], 0, 0, 0);
+					idx++;
+				}
+		}
+#pragma unroll
+		for (int tt = 0; tt < NTRI; tt++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) gtot[tt][r] += (double)gacc[tt][r];
+	}
+}
+
+
 // ---------------------------------------------------------------------------------------------
 // apply_wg_kernel: the product Q = A * Z organised per WORKGROUP for the DRAM access pattern.
 // Measured (round 1, tools/pattern_bench*.py in git history, 2^20 x 64, lda = 2^20): a wave that touches 64 columns x 256 B per chunk copies at
@@ -2035,36 +2121,19 @@ template <int ENGINE, int NT, bool UPD, int ROWS, bool GRAMQ, int NW = 4, class 
 __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 	static_assert(!GRAMQ || NW == 4, "the fused Gram accumulation is written for four waves");
 	static_assert(sizeof(IO) == 4 || (!UPD && !GRAMQ), "fp16 I/O: the plain product only");
-	constexpr int NP = 16 * NT;
-	constexpr int RS = ROWS + 4;                         // column stride of As (floats)
-	constexpr int LPC = ROWS / 4, CPI = 64 / LPC;        // lanes per column, columns per load instruction
-	constexpr int NI = NP / (NW * CPI);                   // load instructions per wave and block
-	constexpr int SL = ROWS / (16 * NW);                       // 16-row slabs per wave
-	constexpr int ZS = NP + 16;
-	// fp32-MFMA engine, triangular 128 x 128 Z: only the part on and right of the diagonal tiles is kept (row k holds the columns
-	// j >= 16 (k / 16)), 40 KiB instead of 72 -- two workgroups then share a CU.  The row stride of a 16-row group is its length padded
-	// to 16 or 48 mod 64 floats, so that the four rows a B operand touches (k = 4t + q) fall on different banks.
-	constexpr bool ZTRI = (ENGINE == 0 && NT == 8 && !UPD);
-	auto ztri_stride = [](int g) { return g == 0 ? 144 : (g <= 2 ? 112 : (g <= 4 ? 80 : (g <= 6 ? 48 : 16))); };
-	auto ztri_base = [&](int g) { int o = 0; for (int i = 0; i < g; i++) o += 16 * ztri_stride(i); return o; };
-	constexpr int KT = (NP + 31) / 32;
-	// blocks (kt, ct) of the MFMA-operand image of Z: for a triangular 64 x 64 Z the two blocks (1,0), (1,1) are zero and
-	// are not stored -- 18.4 KB instead of 24.6 KB, which lets three workgroups share a CU's LDS
-	constexpr bool COMPACT = (!UPD && (NT == 4 || NT == 8));
-	constexpr int NB = COMPACT ? KT * NT - KT * (KT - 1) : KT * NT;      // triangular: row kt keeps the blocks ct >= 2 kt
-	auto zblk = [](int kt, int ct) { return COMPACT ? kt * NT - kt * (kt - 1) + ct - 2 * kt : kt * NT + ct; };
-	auto zblk_kt = [](int b) { int kt = 0; while (COMPACT && kt + 1 < KT && b >= (kt + 1) * NT - (kt + 1) * kt) kt++; return COMPACT ? kt : b / NT; };
+	using G = ApplyGeom<ENGINE, NT, UPD, ROWS, NW>;
+	constexpr int NP = G::NP, RS = G::RS, CPI = G::CPI, NI = G::NI, SL = G::SL, ZS = G::ZS, KT = G::KT, NB = G::NB, NTRI = G::NTRI;
+	constexpr bool ZTRI = G::ZTRI;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	float* As = reinterpret_cast<float*>(smem);
-	char* zbase = smem + sizeof(float) * NP * RS;
+	char* zbase = smem + G::block_bytes();
 	const int lane = threadIdx.x & 63;
 	const int wv = threadIdx.x >> 6;
 	const int c = lane & 15, q = lane >> 4;
-	const int lcol = lane / LPC, lrow = 4 * (lane % LPC);
+	const int lcol = lane / G::LPC, lrow = 4 * (lane % G::LPC);
 
 	const int nblk = a.nchunks, nwg = a.nwaves;
 	// (block order does not matter to the Infinity Cache: tools/seq_bench.py; blk() below)
-	auto swz = [](int col) { return ((col >> 3) & 1) << 4; };
 	auto load_block = [&](f32x4 (&v)[NI], const auto* base, size_t ld, int ncols, int b) {
 		using T = std::remove_cv_t<std::remove_pointer_t<decltype(base)>>;
 		const size_t row = (size_t)b * ROWS + lrow;
@@ -2091,7 +2160,6 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 	};
 	const IO* a_in = reinterpret_cast<const IO*>(a.a);
 
-	constexpr int NTRI = (NT * (NT + 1)) / 2;
 	f64x4 gtot[GRAMQ ? NTRI : 1];
 	if constexpr (GRAMQ) {
 #pragma unroll
@@ -2164,7 +2232,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 			const int k = idx % NP, j = idx / NP;
 			if constexpr (ZTRI) {
 				const int g = k >> 4;
-				if (j >= 16 * g) Zs[ztri_base(g) + (k & 15) * ztri_stride(g) + (j - 16 * g)] = zv0[u];
+				if (j >= 16 * g) Zs[G::ztri_base(g) + (k & 15) * G::ztri_stride(g) + (j - 16 * g)] = zv0[u];
 			} else {
 				Zs[k * ZS + j] = zv0[u];
 			}
@@ -2179,7 +2247,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 		for (int u = 0; u < ZE2; u++) {                      // (loads first, all in flight: see the bf16 engine below)
 			const int idx = threadIdx.x + u * 64 * NW;
 			const int jj = idx & 7, l = (idx >> 3) & 63, b = idx >> 9;
-			const int kt = zblk_kt(b), ct = COMPACT ? b - (kt * NT - kt * (kt - 1)) + 2 * kt : b % NT;
+			const int kt = G::zblk_kt(b), ct = G::zblk_ct(b, kt);
 			const int k = 32 * kt + 8 * (l >> 4) + jj, j = 16 * ct + (l & 15);
 			zv2[u] = a.z[(size_t)j * NP + min(k, NP - 1)];
 			if (k >= NP) zv2[u] = 0.0f;
@@ -2197,7 +2265,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 		for (int u = 0; u < ZE; u++) {
 			const int idx = threadIdx.x + u * 64 * NW;
 			const int jj = idx & 7, l = (idx >> 3) & 63, b = idx >> 9;
-			const int kt = zblk_kt(b), ct = COMPACT ? b - (kt * NT - kt * (kt - 1)) + 2 * kt : b % NT;
+			const int kt = G::zblk_kt(b), ct = G::zblk_ct(b, kt);
 			const int k = 32 * kt + 8 * (l >> 4) + jj, j = 16 * ct + (l & 15);
 			zv[u] = a.z[(size_t)j * NP + min(k, NP - 1)];
 			if (k >= NP) zv[u] = 0.0f;
@@ -2218,7 +2286,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 #pragma unroll
 		for (int k = 0; k < NI; k++) {
 			const int col = (wv + NW * k) * CPI + lcol;
-			*reinterpret_cast<f32x4*>(&As[col * RS + (lrow ^ swz(col))]) = v[k];
+			*reinterpret_cast<f32x4*>(&As[col * RS + (lrow ^ G::swz(col))]) = v[k];
 		}
 		__syncthreads();                                 // (also orders the Z image on the first pass)
 		if constexpr (DEEP) {
@@ -2243,12 +2311,12 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 				// LDS read (one read per product otherwise: 96 instead of 32 cycles per product)
 				auto fetch = [&](int t, float& av, float (&bv)[NT]) {
 					const int k = 4 * t + q;
-					av = As[k * RS + ((rb + c) ^ swz(k))];
+					av = As[k * RS + ((rb + c) ^ G::swz(k))];
 #pragma unroll
 					for (int ct = 0; ct < NT; ct++) {
 						bv[ct] = 0.0f;
 						if (UPD || 4 * t <= 16 * ct + 15) {
-							if constexpr (ZTRI) bv[ct] = Zs[ztri_base(t / 4) + (4 * (t % 4) + q) * ztri_stride(t / 4) + 16 * (ct - t / 4) + c];
+							if constexpr (ZTRI) bv[ct] = Zs[G::ztri_base(t / 4) + (4 * (t % 4) + q) * G::ztri_stride(t / 4) + 16 * (ct - t / 4) + c];
 							else bv[ct] = Zs[k * ZS + 16 * ct + c];
 						}
 					}
@@ -2281,14 +2349,14 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 #pragma unroll
 					for (int e = 0; e < 8; e++) {
 						const int k0 = 32 * kt + 8 * q + e;
-						ah[kt][e] = (_Float16)((k0 < NP) ? As[k0 * RS + ((rb + c) ^ swz(k0))] : 0.0f);
+						ah[kt][e] = (_Float16)((k0 < NP) ? As[k0 * RS + ((rb + c) ^ G::swz(k0))] : 0.0f);
 					}
 #pragma unroll
 				for (int kt = 0; kt < KT; kt++)
 #pragma unroll
 					for (int ct = 0; ct < NT; ct++) {
 						if (UPD || 32 * kt <= 16 * ct + 15) {         // triangular Z: block (kt, ct) is zero when all its k > all its j
-							const f16x8 bh = *reinterpret_cast<const f16x8*>(&Zh[(zblk(kt, ct) * 64 + lane) * 8]);
+							const f16x8 bh = *reinterpret_cast<const f16x8*>(&Zh[(G::zblk(kt, ct) * 64 + lane) * 8]);
 							acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[kt], bh, acc[ct], 0, 0, 0);
 						}
 					}
@@ -2304,7 +2372,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 #pragma unroll
 						for (int e = 0; e < 8; e++) {
 							const int k0 = 32 * kt + 8 * q + e;
-							x[8 * kt + e] = (k0 < NP) ? As[k0 * RS + ((rb + c) ^ swz(k0))] : 0.0f;
+							x[8 * kt + e] = (k0 < NP) ? As[k0 * RS + ((rb + c) ^ G::swz(k0))] : 0.0f;
 						}
 					split3_pairs<4 * KT>(x, hh, mm, ll);
 #pragma unroll
@@ -2317,7 +2385,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 				auto pair = [&](auto KTc, auto CTc, auto KTd, auto CTd) {
 					constexpr int k0 = decltype(KTc)::value, c0 = decltype(CTc)::value;
 					constexpr int k1 = decltype(KTd)::value, c1 = decltype(CTd)::value;
-					const int o0 = (zblk(k0, c0) * 64 + lane) * 8, o1 = (zblk(k1, c1) * 64 + lane) * 8;
+					const int o0 = (G::zblk(k0, c0) * 64 + lane) * 8, o1 = (G::zblk(k1, c1) * 64 + lane) * 8;
 					const bf16x8 bh0 = *reinterpret_cast<const bf16x8*>(&Zb[0 * PS + o0]);
 					const bf16x8 bm0 = *reinterpret_cast<const bf16x8*>(&Zb[1 * PS + o0]);
 					const bf16x8 bl0 = *reinterpret_cast<const bf16x8*>(&Zb[2 * PS + o0]);
@@ -2369,44 +2437,10 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 #pragma unroll
 			for (int ct = 0; ct < NT; ct++) {
 				const int col = 16 * ct + c;
-				*reinterpret_cast<f32x4*>(&As[col * RS + ((rb + 4 * q) ^ swz(col))]) = acc[ct];
+				*reinterpret_cast<f32x4*>(&As[col * RS + ((rb + 4 * q) ^ G::swz(col))]) = acc[ct];
 			}
 		}
-		if constexpr (GRAMQ) {
-			// Gram tiles of this wave's freshly written rows (ROWS/4 rows = ROWS/128 K-steps of 32): lane (c,q) reads logical rows
-			// 8q..8q+7 of column 16t+c (two 16-byte reads; the XOR swizzle keeps 8-row groups contiguous), one MFMA chain from zero per
-			// K-step, added to fp64 totals -- exactly gram_bf16_kernel's arithmetic on the values that are about to be stored
-#pragma unroll
-			for (int ks = 0; ks < ROWS / 128; ks++) {
-				const int rbk = wv * (ROWS / 4) + 32 * ks + 8 * q;
-				bf16x8 oh[NT], om[NT], ol[NT];
-#pragma unroll
-				for (int t = 0; t < NT; t++) {
-					const int col = 16 * t + c;
-					split3_operand(*reinterpret_cast<const f32x4*>(&As[col * RS + (rbk ^ swz(col))]),
-					               *reinterpret_cast<const f32x4*>(&As[col * RS + ((rbk + 4) ^ swz(col))]), oh[t], om[t], ol[t]);
-				}
-				f32x4 gacc[NTRI];
-#pragma unroll
-				for (int t = 0; t < NTRI; t++) gacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-				for (int pass = 3; pass < 9; pass++) {       // (split_a: the six products, smallest first)
-					int idx = 0;
-#pragma unroll
-					for (int ti = 0; ti < NT; ti++)
-#pragma unroll
-						for (int tj = ti; tj < NT; tj++) {
-							gacc[idx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(split_a(pass, oh[ti], om[ti], ol[ti]), split_b(pass, oh[tj], om[tj], ol[tj]),
-							                                                    gacc[idx], 0, 0, 0);
-							idx++;
-						}
-				}
-#pragma unroll
-				for (int t = 0; t < NTRI; t++)
-#pragma unroll
-					for (int r = 0; r < 4; r++) gtot[t][r] += (double)gacc[t][r];
-			}
-		}
+		if constexpr (GRAMQ) gramq_accumulate<G>(gtot, As, wv, c, q);
 		__syncthreads();
 		{
 			const size_t row = (size_t)b * ROWS + lrow;
@@ -2415,7 +2449,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 			for (int k = 0; k < NI; k++) {
 				const int col = (wv + NW * k) * CPI + lcol;
 				if (col < nout) {
-					f32x4 x = *reinterpret_cast<const f32x4*>(&As[col * RS + (lrow ^ swz(col))]);
+					f32x4 x = *reinterpret_cast<const f32x4*>(&As[col * RS + (lrow ^ G::swz(col))]);
 					if constexpr (UPD) x += cin[k];
 					if constexpr (sizeof(IO) == 2) {
 						_Float16* dh = reinterpret_cast<_Float16*>(a.q) + (size_t)col * a.ldq + row;

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -621,95 +622,110 @@ int chol_from_g(Ctx& c, const SweepOpts& o, float* r, size_t ldr, size_t n, int 
 	return 0;
 }
 
-// apply_wg_kernel launcher: args.nchunks = row blocks of ROWS, args.nwaves = workgroups (persistent grid); GRAMQ: their number -> *gramq_nparts
+// The launcher of the apply family (KERNEL: the entry; G: its tsqrmi::ApplyGeom): the dynamic-LDS attribute, once per device and instance; the
+// persistent grid -- as many workgroups as are resident on the 256 CUs at once, CAP per CU at the most (QUERY: and no more than the
+// runtime's occupancy figure) -- or grid.wgs of them, split over grid.gy panels and never more than grid.max_wgs; a.nchunks = row blocks
+// of G::ROWS, a.nwaves = workgroups.  pre(a, per_cu, lds, gy) sees the sized grid before the launch; true: the pass has run, no launch.
+struct ApplyGrid { int wgs = 0; unsigned gy = 1; int max_wgs = INT_MAX; };
+template <auto KERNEL, class G, bool GRAMQ, int CAP, bool QUERY, class Pre>
+int launch_apply(Ctx& c, tsqrmi::ApplyArgs a, const ApplyGrid& grid, Pre&& pre) {
+	constexpr size_t lds = G::lds_bytes(GRAMQ);
+	static DevOnce attr;                                 // (per template instance)
+	static std::atomic<int> per_cu_cache[MAX_DEV];
+	if (attr.need(c.dev)) {
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+		int nb = CAP;
+		if constexpr (QUERY) {
+			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(KERNEL), G::THREADS, lds) != hipSuccess || nb < 1) {
+				(void)hipGetLastError(); nb = 2;
+			}
+		}
+		per_cu_cache[c.dev].store(std::min(nb, CAP));
+		attr.done(c.dev);
+	}
+	const int per_cu = per_cu_cache[c.dev].load();
+	const size_t nblk = cdiv(a.m, (size_t)G::ROWS);
+	const size_t want = grid.wgs > 0 ? (size_t)grid.wgs : (size_t)256 * per_cu;
+	a.nchunks = (int)nblk;
+	a.nwaves = std::min((int)std::min<size_t>(nblk, std::max<size_t>(1, want / grid.gy)), grid.max_wgs);   // (the resident workgroups split over the trailing panels)
+	a.cpw = 0;
+	if (pre(a, per_cu, lds, grid.gy)) return 0;
+	hipLaunchKernelGGL(KERNEL, dim3(a.nwaves, grid.gy), dim3(G::THREADS), lds, c.st, a);
+	return 0;
+}
+inline bool apply_no_pre(tsqrmi::ApplyArgs&, int, size_t, unsigned) { return false; }
+
+// Four workgroups per CU on the whole chip: uneven shares by XCD parity and by dispatch round (apply_wg_body; round 3, on every box
+// looked at THEN: the pass ends at 78 us instead of 84).  Round 4: on five boxes in a row the same shares COST 5-6 % of the call
+// (blocking 194.9-198.9 us against 186.1-188.1 with equal shares, chained 170.3-173.2 against 159.4-161.1; three interleaved runs,
+// profiles/r04_experiment_log.md) -- the XCD asymmetry they answer is a property of the box's state, not of the chip.  So the
+// choice is MEASURED once per process and device (and per side of the cache size), on the first large out-of-place pass: the two
+// candidates (shares by XCD parity and round / equal) run the pass itself in turn under HIP events, four times each (Q = A Z is the
+// same whoever computes a block: the last run leaves the result), ~0.7 ms once; the uneven shares are taken only when they are 1 %
+// faster.  TSQR_MI_APPLY_SHARES=0 / 1 / 2 pins equal / both / by round only.
+// Sets a's shares; true: this was the measurement, the pass has run.
+template <auto KERNEL> bool choose_block_shares(Ctx& c, tsqrmi::ApplyArgs& a, int per_cu, size_t lds, unsigned gy) {
+	if (a.nwaves != 1024 || per_cu != 4) return false;
+	static const int pinned = env_int("TSQR_MI_APPLY_SHARES", -1);
+	static std::atomic<int> chosen[MAX_DEV][2];      // 0 not measured yet, 1 both, 2 rounds only, 3 equal; [1]: a matrix beyond the Infinity Cache
+	auto set_mode = [](tsqrmi::ApplyArgs& x, int mode) {
+		x.share[0] = x.share[1] = x.share[2] = x.share[3] = 0; x.even_share = 0;
+		if (mode == 1 || mode == 2) { x.share[0] = 18; x.share[1] = 17; x.share[2] = 15; x.share[3] = 14; x.even_share = (mode == 1) ? 69 : 64; }
+	};
+	const double bytes = (double)a.m * (double)a.n * sizeof(float);
+	const int cls = bytes > 256.0 * 1048576.0 ? 1 : 0;
+	int mode = pinned == 0 ? 3 : (pinned == 1 ? 1 : (pinned == 2 ? 2 : chosen[c.dev][cls].load()));
+	const bool big = bytes >= 128.0 * 1048576.0;
+	if (mode == 0 && big && reinterpret_cast<const void*>(a.q) != reinterpret_cast<const void*>(a.a) && !t_prof.on) {
+		constexpr int REPS = 4;                          // interleaved: uneven, equal, uneven, equal, ...
+		hipEvent_t ev[2 * REPS + 1];
+		bool ok = true;
+		for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+		if (ok) {
+			for (int i = 0; i < 2 * REPS; i++) {
+				tsqrmi::ApplyArgs x = a;
+				set_mode(x, (i & 1) ? 3 : 1);
+				(void)hipEventRecord(ev[i], c.st);
+				hipLaunchKernelGGL(KERNEL, dim3(a.nwaves, gy), dim3(256), lds, c.st, x);
+			}
+			(void)hipEventRecord(ev[2 * REPS], c.st);
+			ok = hipEventSynchronize(ev[2 * REPS]) == hipSuccess;
+			float t[2] = {0.f, 0.f};
+			for (int i = 0; i < 2 * REPS && ok; i++) { float ms = 0.f; ok = hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess; t[i & 1] += ms; }
+			// (a speculative pass that skipped itself -- rejected Gram matrix -- measures nothing: ask again next time)
+			if (ok && t[0] > 0.01f * REPS && t[1] > 0.01f * REPS)
+				chosen[c.dev][cls].store(t[0] < 0.99f * t[1] ? 1 : 3);   // equal shares unless the uneven ones are (1 %) faster: 3 % on the boxes they were tuned on, 5-10 % SLOWER elsewhere
+		}
+		for (auto& e : ev) (void)hipEventDestroy(e);
+		(void)hipGetLastError();
+		return true;                                     // (the pass has run)
+	}
+	set_mode(a, mode == 0 ? 3 : mode);
+	return false;
+}
+
+// apply_wg_kernel launcher; GRAMQ: the number of workgroups (one partial each) -> *gramq_nparts
 template <int E, int NT, bool UPD, int ROWS, bool GRAMQ> constexpr auto apply_wg_entry() {
 	if constexpr (GRAMQ) return &tsqrmi::apply_wg_gramq_kernel<E, NT, UPD, ROWS>;
 	else return &tsqrmi::apply_wg_kernel<E, NT, UPD, ROWS>;
 }
-template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_apply_wg(Ctx& c, const SweepOpts& o, int* gramq_nparts, tsqrmi::ApplyArgs a) {
+template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_apply_wg(Ctx& c, const SweepOpts& o, int* gramq_nparts, const tsqrmi::ApplyArgs& a) {
 	constexpr auto kernel = apply_wg_entry<E, NT, UPD, ROWS, GRAMQ>();
-	constexpr int NP = 16 * NT, KT = (NP + 31) / 32;
-	constexpr int NB = (!UPD && NT == 4) ? 6 : KT * NT;  // operand blocks of Z kept in LDS (apply_wg_kernel: COMPACT)
-	size_t lds = sizeof(float) * NP * (ROWS + 4) +
-	             (E == 0 ? sizeof(float) * NP * (NP + 16) : (size_t)(E == 2 ? 1 : 3) * NB * 512 * 2);
-	if (GRAMQ) lds = std::max(lds, sizeof(double) * 2 * (NT * (NT + 1) / 2) * 256);   // the final workgroup reduction aliases the block
-	static DevOnce attr;                                 // (per template instance)
-	static std::atomic<int> per_cu_cache[MAX_DEV];
-	if (attr.need(c.dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kernel), 256, lds) != hipSuccess || nb < 1) {
-			(void)hipGetLastError(); nb = 2;
+	// persistent grid: as many workgroups as are resident on the 256 CUs at once (LDS / register bound: 2 or 3 per CU);
+	// measured: the fp32-MFMA engine is slower with three per CU (132 vs 112 us)
+	constexpr int CAP = ROWS == 64 ? 4 : (E == 0 ? 2 : 3);
+	ApplyGrid grid;
+	grid.wgs = g_set.apply_wgs.load();
+	if (UPD && a.multi_cols > 0) grid.gy = (unsigned)cdiv((size_t)a.multi_cols, PW);
+	if (GRAMQ) grid.max_wgs = o.gramq_cap;               // one partial per workgroup: never more than the buffer holds
+	return launch_apply<kernel, tsqrmi::ApplyGeom<E, NT, UPD, ROWS>, GRAMQ, CAP, true>(c, a, grid, [&](tsqrmi::ApplyArgs& x, int per_cu, size_t lds, unsigned gy) {
+		if constexpr (GRAMQ) {
+			x.gpart = o.gramq_part;
+			if (gramq_nparts) *gramq_nparts = x.nwaves;
 		}
-		// persistent grid: as many workgroups as are resident on the 256 CUs at once (LDS / register bound: 2 or 3 per CU);
-		// measured: the fp32-MFMA engine is slower with three per CU (132 vs 112 us)
-		per_cu_cache[c.dev].store(std::min(nb, ROWS == 64 ? 4 : (E == 0 ? 2 : 3)));
-		attr.done(c.dev);
-	}
-	const size_t nblk = cdiv(a.m, (size_t)ROWS);
-	a.nchunks = (int)nblk;
-	const int wgs = g_set.apply_wgs.load();
-	size_t want = wgs > 0 ? (size_t)wgs : (size_t)256 * per_cu_cache[c.dev].load();
-	unsigned gy = 1;
-	if constexpr (UPD) {
-		if (a.multi_cols > 0) { gy = (unsigned)cdiv((size_t)a.multi_cols, PW); want = std::max<size_t>(1, want / gy); }   // (the resident workgroups split over the trailing panels)
-	}
-	a.nwaves = (int)std::min<size_t>(nblk, want);
-	a.cpw = 0;
-	if constexpr (GRAMQ) {
-		a.nwaves = std::min(a.nwaves, o.gramq_cap);      // one partial per workgroup: never more than the buffer holds
-		a.gpart = o.gramq_part;
-		if (gramq_nparts) *gramq_nparts = a.nwaves;
-	}
-	if constexpr (!UPD && !GRAMQ && ROWS == 64) {
-		// Four workgroups per CU on the whole chip: uneven shares by XCD parity and by dispatch round (apply_wg_body; round 3, on every box
-		// looked at THEN: the pass ends at 78 us instead of 84).  Round 4: on five boxes in a row the same shares COST 5-6 % of the call
-		// (blocking 194.9-198.9 us against 186.1-188.1 with equal shares, chained 170.3-173.2 against 159.4-161.1; three interleaved runs,
-		// profiles/r04_experiment_log.md) -- the XCD asymmetry they answer is a property of the box's state, not of the chip.  So the
-		// choice is MEASURED once per process and device (and per side of the cache size), on the first large out-of-place pass: the two
-		// candidates (shares by XCD parity and round / equal) run the pass itself in turn under HIP events, four times each (Q = A Z is the
-		// same whoever computes a block: the last run leaves the result), ~0.7 ms once; the uneven shares are taken only when they are 1 %
-		// faster.  TSQR_MI_APPLY_SHARES=0 / 1 / 2 pins equal / both / by round only.
-		if (a.nwaves == 1024 && per_cu_cache[c.dev].load() == 4) {
-			static const int pinned = env_int("TSQR_MI_APPLY_SHARES", -1);
-			static std::atomic<int> chosen[MAX_DEV][2];      // 0 not measured yet, 1 both, 2 rounds only, 3 equal; [1]: a matrix beyond the Infinity Cache
-			auto set_mode = [](tsqrmi::ApplyArgs& x, int mode) {
-				x.share[0] = x.share[1] = x.share[2] = x.share[3] = 0; x.even_share = 0;
-				if (mode == 1 || mode == 2) { x.share[0] = 18; x.share[1] = 17; x.share[2] = 15; x.share[3] = 14; x.even_share = (mode == 1) ? 69 : 64; }
-			};
-			const double bytes = (double)a.m * (double)a.n * sizeof(float);
-			const int cls = bytes > 256.0 * 1048576.0 ? 1 : 0;
-			int mode = pinned == 0 ? 3 : (pinned == 1 ? 1 : (pinned == 2 ? 2 : chosen[c.dev][cls].load()));
-			const bool big = bytes >= 128.0 * 1048576.0;
-			if (mode == 0 && big && reinterpret_cast<const void*>(a.q) != reinterpret_cast<const void*>(a.a) && !t_prof.on) {
-				constexpr int REPS = 4;                          // interleaved: uneven, equal, uneven, equal, ...
-				hipEvent_t ev[2 * REPS + 1];
-				bool ok = true;
-				for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-				if (ok) {
-					for (int i = 0; i < 2 * REPS; i++) {
-						tsqrmi::ApplyArgs x = a;
-						set_mode(x, (i & 1) ? 3 : 1);
-						(void)hipEventRecord(ev[i], c.st);
-						hipLaunchKernelGGL(kernel, dim3(a.nwaves, gy), dim3(256), lds, c.st, x);
-					}
-					(void)hipEventRecord(ev[2 * REPS], c.st);
-					ok = hipEventSynchronize(ev[2 * REPS]) == hipSuccess;
-					float t[2] = {0.f, 0.f};
-					for (int i = 0; i < 2 * REPS && ok; i++) { float ms = 0.f; ok = hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess; t[i & 1] += ms; }
-					// (a speculative pass that skipped itself -- rejected Gram matrix -- measures nothing: ask again next time)
-					if (ok && t[0] > 0.01f * REPS && t[1] > 0.01f * REPS)
-						chosen[c.dev][cls].store(t[0] < 0.99f * t[1] ? 1 : 3);   // equal shares unless the uneven ones are (1 %) faster: 3 % on the boxes they were tuned on, 5-10 % SLOWER elsewhere
-				}
-				for (auto& e : ev) (void)hipEventDestroy(e);
-				(void)hipGetLastError();
-				return 0;                                    // (the pass has run)
-			}
-			set_mode(a, mode == 0 ? 3 : mode);
-		}
-	}
-	hipLaunchKernelGGL(kernel, dim3(a.nwaves, gy), dim3(256), lds, c.st, a);
-	return 0;
+		if constexpr (!UPD && !GRAMQ && ROWS == 64) return choose_block_shares<kernel>(c, x, per_cu, lds, gy);
+		else return false;
+	});
 }
 template <int E, int NT, bool UPD> int launch_apply_any(Ctx& c, const SweepOpts& o, int* gramq_nparts, const tsqrmi::ApplyArgs& a) {
 	if constexpr (!UPD && E != 0) {                      // (the fp32-MFMA engine's fused variant spills and loses: 0.29 vs 0.22 ms per apply)
@@ -723,29 +739,9 @@ template <int E, int NT, bool UPD> int launch_apply_any(Ctx& c, const SweepOpts&
 }
 // fp16 I/O modes: the plain product with halves at both ends -- bf16x3 engine 1 (fp16_notc) or single-fp16-product engine 2
 // (fp16_tc_nocor); 64- / 128-row blocks as in the fp32 call, two blocks in flight
-template <int E, int NT> int launch_apply_h(Ctx& c, tsqrmi::ApplyArgs a) {
+template <int E, int NT> int launch_apply_h(Ctx& c, const tsqrmi::ApplyArgs& a) {
 	constexpr int ROWS = (E == 1) ? 64 : 128;           // (measured: the bf16x3 engine at 128-row blocks 90 us against 59 at 64)
-	constexpr auto kernel = &tsqrmi::apply_wg_h_kernel<E, NT, ROWS>;
-	constexpr int NP = 16 * NT, KT = (NP + 31) / 32;
-	constexpr int NB = (NT == 4) ? 6 : KT * NT;
-	const size_t lds = sizeof(float) * NP * (ROWS + 4) + (E == 0 ? sizeof(float) * NP * (NP + 16) : (size_t)(E == 2 ? 1 : 3) * NB * 512 * 2);
-	static DevOnce attr;
-	static std::atomic<int> per_cu_cache[MAX_DEV];
-	if (attr.need(c.dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kernel), 256, lds) != hipSuccess || nb < 1) {
-			(void)hipGetLastError(); nb = 2;
-		}
-		per_cu_cache[c.dev].store(std::min(nb, ROWS == 64 ? 4 : 3));
-		attr.done(c.dev);
-	}
-	const size_t nblk = cdiv(a.m, (size_t)ROWS);
-	a.nchunks = (int)nblk;
-	a.nwaves = (int)std::min<size_t>(nblk, (size_t)256 * per_cu_cache[c.dev].load());
-	a.cpw = 0;
-	hipLaunchKernelGGL(kernel, dim3(a.nwaves), dim3(256), lds, c.st, a);
-	return 0;
+	return launch_apply<&tsqrmi::apply_wg_h_kernel<E, NT, ROWS>, tsqrmi::ApplyGeom<E, NT, false, ROWS>, false, (ROWS == 64 ? 4 : 3), true>(c, a, ApplyGrid{}, apply_no_pre);
 }
 template <int E> int dispatch_apply_h(Ctx& c, int NT, const tsqrmi::ApplyArgs& a) {
 	return with_nt(NT, [&](auto nt) { return launch_apply_h<E, decltype(nt)::value>(c, a); });
@@ -1011,26 +1007,11 @@ int sweep(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, int r_engin
 // slot o.slot (and its pinned alias), the apply pass skips itself on rejection, A is untouched (q == a is allowed: every workgroup
 // has its block in LDS before it writes).  r receives the full n x n factor.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int E> int launch_apply_wide(Ctx& c, tsqrmi::ApplyArgs a) {
+template <int E> int launch_apply_wide(Ctx& c, const tsqrmi::ApplyArgs& a) {
 	// bf16x3 / fp16 engines: eight waves on 128-row blocks, one workgroup per CU; fp32-MFMA engine: four waves on 64-row blocks with
-	// the compact triangular Z (40 KiB), two workgroups per CU
-	constexpr bool F32 = (E == 0);
-	constexpr int ROWS = F32 ? 64 : 128, THREADS = F32 ? 256 : 512, PER_CU = F32 ? 2 : 1;
-	constexpr size_t lds = sizeof(float) * 128 * (ROWS + 4) + (F32 ? sizeof(float) * 10240 : (size_t)(E == 2 ? 1 : 3) * 20 * 512 * 2);
-	const void* kernel;
-	if constexpr (F32) kernel = reinterpret_cast<const void*>(&tsqrmi::apply_wide_f32_kernel);
-	else kernel = reinterpret_cast<const void*>(&tsqrmi::apply_wide_kernel<E>);
-	static DevOnce attr;
-	if (attr.need(c.dev)) {
-		HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		attr.done(c.dev);
-	}
-	const size_t nblk = cdiv(a.m, (size_t)ROWS);
-	a.nchunks = (int)nblk;
-	a.nwaves = (int)std::min<size_t>(nblk, (size_t)256 * PER_CU);
-	if constexpr (F32) hipLaunchKernelGGL(tsqrmi::apply_wide_f32_kernel, dim3(a.nwaves), dim3(THREADS), lds, c.st, a);
-	else hipLaunchKernelGGL(tsqrmi::apply_wide_kernel<E>, dim3(a.nwaves), dim3(THREADS), lds, c.st, a);
-	return 0;
+	// the compact triangular Z (40 KiB), two workgroups per CU (fixed: the occupancy is not asked for)
+	if constexpr (E == 0) return launch_apply<&tsqrmi::apply_wide_f32_kernel, tsqrmi::ApplyGeom<0, 8, false, 64, 4>, false, 2, false>(c, a, ApplyGrid{}, apply_no_pre);
+	else return launch_apply<&tsqrmi::apply_wide_kernel<E>, tsqrmi::ApplyGeom<E, 8, false, 128, 8>, false, 1, false>(c, a, ApplyGrid{}, apply_no_pre);
 }
 // the one-panel path's arguments, shared by the blocking call (sweep_wide) and the stream of 128-column calls (chained128); verdict and
 // skip word: status slot o.slot
