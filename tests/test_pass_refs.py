@@ -192,3 +192,140 @@ def test_local_r_bounds():
     r = np.linalg.qr(a.astype(np.float64), mode="r").astype(np.float32).astype(np.float64)
     d = r.T @ r - a.astype(np.float64).T @ a.astype(np.float64)
     assert np.linalg.norm(d) <= pr.local_r_backward_bound(a)             # rounding R to fp32 alone is far inside it
+
+
+# =========================================================================================================================================
+# The one-panel path (64 < n <= 128)
+# =========================================================================================================================================
+@pytest.mark.parametrize("n", [65, 80, 97, 113, 127, 128])
+def test_wide_tile_unpack_inverts_pack(n):
+    rng = np.random.default_rng(n)
+    g = rng.standard_normal((n, n))
+    g = g + g.T
+    v = pr.pack_wide_tiles(g, n)
+    assert v.shape == (36 * 256,)
+    want = np.zeros((128, 128))
+    want[:n, :n] = g
+    back = pr.unpack_wide_tiles(v)
+    assert np.array_equal(back, want)
+    assert np.array_equal(pr.pack_wide_tiles(back[:n, :n], n), v)
+
+
+def test_wide_tile_order_is_the_kernels():
+    """[G11: 10][G22: 10][G12: 16 row-major]; the first ten tiles are pack_tiles' NT = 4 array of G11 (a chol_body16 input), the next ten
+    that of G22; the diagonal element (c, c) of diagonal tile d sits where chol_wide_kernel reads it"""
+    assert [pr.wide_tile(t, t) for t in range(8)] == [0, 4, 7, 9, 10, 14, 17, 19]
+    assert pr.wide_tile(0, 4) == 20 and pr.wide_tile(3, 7) == 35 and pr.wide_tile(1, 6) == 26
+    assert sorted(pr.wide_tile(i, j) for i in range(8) for j in range(i, 8)) == list(range(36))
+    g = np.arange(128.0 * 128).reshape(128, 128)
+    g = g + g.T
+    v = pr.pack_wide_tiles(g, 128)
+    assert np.array_equal(v[:2560], pr.pack_tiles(g[:64, :64], 64, True))
+    assert np.array_equal(v[2560:5120], pr.pack_tiles(g[64:, 64:], 64, True))
+    for blk in (0, 1):
+        for j in range(64):
+            d, cc = j >> 4, j & 15
+            e = (2560 if blk else 0) + pr._tri4(d, d) * 256 + (cc & 3) * 64 + 16 * (cc >> 2) + cc
+            assert v[e] == g[64 * blk + j, 64 * blk + j]
+    e = 5120 + (2 * 4 + 1) * 256 + 3 * 64 + 37                               # G12 tile (2, 5), reg 3, lane 37: row 4 * 2 + 3, column 5
+    assert v[e] == g[32 + 11, 64 + 16 + 5]
+
+
+@pytest.mark.parametrize("n,split", pr.WIDE_CHOL_CASES + [(n, s) for n in pr.WIDE_APPLY_N for s in pr.WIDE_APPLY_SPLITS if s < n])
+def test_exact_wide_pair_is_an_exact_inverse_with_a_closed_form_verdict(n, split):
+    rng = np.random.default_rng(n + split)
+    r, z, g, b = pr.exact_wide_pair(rng, n, split)
+    assert np.array_equal(r @ z, np.eye(n)) and np.array_equal(r.T @ r, g)
+    assert np.array_equal(r.astype(np.float32), r) and np.array_equal(z.astype(np.float32), z)
+    assert np.max(np.abs(g)) * n < 2.0 ** 53
+    from tests import pass_refs_f64 as p64
+    if np.finfo(np.longdouble).eps < 2.0 ** -60:
+        s_ref, ratio_ref = p64.scond_ref(g)
+        ratio, s = pr.exact_wide_verdict(b, n)
+        assert abs(s_ref - s) <= 1e-12 * s and abs(ratio_ref - ratio) <= 1e-12 * ratio
+        assert ratio > 2.0 ** -5
+    zw = pr.zw_of(z, n).reshape(128, 128)
+    assert np.array_equal(zw[:n, :n].T, z) and np.all(zw[n:] == 0) and np.all(zw[:, n:] == 0)
+    # the model of the intended arithmetic reproduces R and Z exactly on this data
+    rm, zm = pr.model_chol_wide(g, n)
+    assert np.array_equal(rm, r) and np.array_equal(zm, z)
+
+
+def test_wide_budgets_hold_for_the_gpu_shapes():
+    for m in pr.WIDE_GRAM_M + [337]:
+        chain, total = pr.gram_exact_budget(511, m)
+        assert chain <= 24 and total <= 53
+    for split in pr.WIDE_APPLY_SPLITS:
+        assert pr.apply_wide_exact_budget(63, 2, split, 3) <= 24
+    assert pr.wide_scond_threshold(1000) == 4.0 and pr.wide_scond_threshold(1 << 20) == float(np.float32(0.12) * np.float32(1024.0))
+    assert pr.wide_scond_threshold(1 << 30) == 128.0
+
+
+@pytest.mark.parametrize("n,cond", pr.WIDE_CHOL_GENERAL)
+def test_chol_wide_bounds_hold_for_fp64_and_fail_for_fp32_shortcuts(n, cond):
+    """the bound against a longdouble factorisation holds for the NumPy model of the intended arithmetic (all products in fp64) and is
+    missed by a Schur complement or a Z12 accumulated in fp32 -- by more than a factor of 4 at every case (measured: 8 .. 800, printed;
+    of the order of n at cond(A) = 2 and 4).  Only at cond(A) <= 2 does the fp64 term stay far below the ulp term (asserted: below 0.05
+    ulp32 on the entries that are not tiny); at cond(A) = 10 and 30 the bound is several ulps wide on the smaller entries and what it still
+    guarantees is this separation from the fp32 shortcuts.  The cases are those of the GPU test, pass_refs.WIDE_CHOL_GENERAL: cond(A)
+    2 .. 30, the conditioning chol_wide_bounds covers (its docstring says why not 1e3)."""
+    from tests import pass_refs_f64 as p64
+    p64.require_longdouble()
+    rng = np.random.default_rng(int(cond) + n)
+    a = pr.well_conditioned(rng, 4 * n, n, cond).astype(np.float64)
+    g = pr.unpack_wide_tiles(pr.pack_wide_tiles(a.T @ a, n))[:n, :n]
+    r = p64.chol_ld(g)
+    z = p64.trinv_ld(r)
+    r64, z64 = np.asarray(r, np.float64), np.asarray(z, np.float64)
+    br, bz = pr.chol_wide_bounds(r64, z64, n)
+    up = np.triu(np.ones((n, n), bool))
+    big = up & (np.abs(r64) > 1e-3 * np.max(np.abs(r64)))
+    if cond <= 2.0:
+        assert np.max((br - 0.5 * pr.ulp32(r64))[big] / pr.ulp32(r64)[big]) < 0.05       # the fp64 term: far below the ulp term
+    worst = {}
+    for name, kw in (("fp64", {}), ("schur32", {"schur32": True}), ("z12_32", {"z12_32": True})):
+        rm, zm = pr.model_chol_wide(g, n, **kw)
+        er = np.abs(rm.astype(np.longdouble) - r).astype(np.float64)
+        ez = np.abs(zm.astype(np.longdouble) - z).astype(np.float64)
+        worst[name] = (float(np.max(er[up] / br[up])), float(np.max(ez[up] / bz[up])))
+    print("chol wide model n=%d cond=%g: max(err / bound) on (R, Z) fp64 %s, fp32 Schur %s, fp32 Z12 %s"
+          % (n, cond, *("(%.3g, %.3g)" % worst[k] for k in ("fp64", "schur32", "z12_32"))))
+    assert worst["fp64"][0] <= 1.0 and worst["fp64"][1] <= 1.0, worst
+    assert worst["schur32"][0] > 4.0, worst                                    # R22 (and Z22, Z12) carry the fp32 Schur error
+    assert worst["z12_32"][1] > 4.0 and worst["z12_32"][0] <= 1.0, worst       # only Z12 is touched
+
+
+def test_coupling_and_half_budgets_hold_for_the_gpu_shapes():
+    """cross_kernel with the default plan (cpw = 1 up to 2048 chunks: a workgroup sums 256 rows in fp32) and with three waves asked for at
+    4097 rows (cpw = 22: one workgroup sums all 4097 rows in fp32, still below 2^24 with |k| <= 63 -- 4228 rows would not be); half operands"""
+    for m in pr.CROSS_M:
+        wg, total = pr.cross_exact_budget(63, m, 256)
+        assert wg <= 24 and total <= 53
+    assert pr.cross_exact_budget(63, 4097, 4 * 22 * 64)[0] <= 24 and pr.cross_exact_budget(63, 4228, 4 * 22 * 64)[0] > 24
+    for m in pr.HALF_GRAM_M:
+        sig, chain, total, big = pr.half_exact_budget(511, (-3, 3), m)
+        assert sig <= 11 and chain <= 24 and total <= 53 and big <= 65504
+    assert pr.half_exact_budget(2047, (0, 0), 64)[1] > 24                      # eleven-bit integers overrun a 64-row chain
+    h = pr.exact_halves(np.random.default_rng(0), 127, 33)
+    assert h.dtype == np.float16 and np.max(np.abs(h.astype(np.float64))) <= 511 * 8
+
+
+def test_cross_isolated_bound_sees_a_dropped_product():
+    """NumPy emulation of one isolated product per entry: the exact product rounded to fp32 lies within the bound; with the mid x mid term of
+    the bf16 split dropped (about 2^-16 relative) it does not"""
+    rng = np.random.default_rng(3)
+    x = pr.isolated_rows(rng, 256, 64)
+    y = np.zeros((256, 17), np.float32)
+    y[np.any(x != 0, axis=1)] = pr.full_mantissa(rng, (4, 17), 6)
+    exact = x.astype(np.float64).T @ y.astype(np.float64)
+    bound = pr.cross_isolated_bound(x, y, 256, 1)
+
+    def mid(v):
+        v = v.astype(np.float64)
+        hi = (v.astype(np.float32).view(np.uint32) & 0xffff0000).view(np.float32).astype(np.float64)
+        r = v - hi
+        return (r.astype(np.float32).view(np.uint32) & 0xffff0000).view(np.float32).astype(np.float64)
+    ok = np.abs(exact.astype(np.float32).astype(np.float64) - exact)
+    assert np.all(ok <= bound)
+    dropped = np.abs(mid(x).T @ mid(y))
+    assert np.max(dropped / np.maximum(bound, 1e-300)) > 4.0

@@ -8,12 +8,14 @@
 #include "tsqr_f64.hip"
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
+#include "f32_plan.h"
 #include "launch_util.h"
 
 namespace {
 inline int fail(hipError_t e, const char*) { return -(int)e; }     // (HIPCHK of launch_util.h: the entries return minus the HIP error)
 }  // namespace
 #include "selftest_f64.hip"
+#include "selftest_f32.hip"
 
 namespace {
 using namespace tsqrmi;

@@ -37,6 +37,7 @@
 #include "tsqr_f64.hip"
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
+#include "f32_plan.h"
 #include "launch_util.h"
 #include "validate.hip"
 
@@ -50,13 +51,13 @@ int env_int(const char* name, int dflt) { const char* e = getenv(name); return e
 struct Settings {
 	std::atomic<int> policy{0};          // 0 auto, 1 Householder, 2 Gram without check/fallback
 	std::atomic<int> gram_level{2};      // first Gram level tried: 2 bf16-split (then fp64), 1 fp64 only
-	std::atomic<int> level0_waves{2048}, tree_cpw{4}, gram_waves{2048};
+	std::atomic<int> level0_waves{2048}, tree_cpw{4}, gram_waves{GRAM_WAVES_DEFAULT};
 	std::atomic<int> wide{1};            // 64 < n <= 128: one Cholesky-QR panel of up to 128 columns first (policy 5 turns it off)
 	std::atomic<int> apply_wgs{0};       // workgroups of the apply pass; 0: as many as are resident at once (tsqr_mi_set_tuning2)
 	std::atomic<int> loop_depth{3};      // *_loop entries: 1 blocking calls, 2 two calls in flight, 3 also the chained schedule (tsqr_mi_set_loop_depth)
 	// the two environment switches that are left (read once at load): the floor of the bf16-split level's bound on the scaled
 	// conditioning S, and a diagnostic print of every Cholesky verdict
-	const float bf16_scond_floor = (float)env_int("TSQR_MI_BF16_MAX_SCOND", 4);
+	const float bf16_scond_floor = (float)env_int("TSQR_MI_BF16_MAX_SCOND", BF16_SCOND_FLOOR_DEFAULT);
 	// chained schedules over DIFFERENT matrices: taken when one matrix is at most this many MiB.  The Gram pass of matrix i + 1 runs
 	// between the Gram pass and the apply pass of matrix i; both fit the 256 MiB Infinity Cache only up to ~half of it each -- beyond
 	// that the apply pass of matrix i finds its A evicted and streams it from HBM again (measured at 2^20 x 64, 256 MiB a matrix:
@@ -138,9 +139,8 @@ int blk_kernel_attrs(int dev) {
 int wide_kernel_attrs(int dev) {
 	static DevOnce attr;
 	if (attr.need(dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GW_LDS_BYTES));
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_wide_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GWC_LDS_BYTES));
+		const int rc = wide_gram_attrs();                // (f32_plan.h)
+		if (rc) return rc;
 		attr.done(dev);
 	}
 	return 0;
@@ -193,37 +193,15 @@ Plan make_plan(size_t m, size_t n) {
 	return p;
 }
 
-// Gram engine geometry: waves / workgroups of the Gram kernels and the size of their per-workgroup partials (in floats)
-struct GramPlan { int nch, cpw, nwaves, nblocks, ntri; size_t part_floats; };
-GramPlan gram_plan(size_t m, size_t n) {
-	GramPlan g{};
-	const size_t NT = np_of(n) / 16;
-	g.nch = (int)cdiv(m, 64);
-	g.cpw = (int)std::max<size_t>(1, cdiv((size_t)g.nch, (size_t)g_set.gram_waves.load()));
-	g.nwaves = (int)cdiv((size_t)g.nch, (size_t)g.cpw);
-	g.nblocks = (g.nwaves + 3) / 4;
-	g.ntri = (int)(NT * (NT + 1) / 2);
-	g.part_floats = (size_t)g.nblocks * g.ntri * 256 * 2;
-	return g;
-}
-
-// Coupling partials (cross_kernel: 16 tiles x 256 doubles per workgroup).  A launch covers as many trailing panels as the work space holds
-// workgroup partials for -- every panel with the full workgroup count of one panel pair, so the grouping of the sums (and with it every bit
-// of S) is that of rounds 1-3: up to CROSS_SLOT_CAP slots (32 MiB), never fewer than one panel's.
-constexpr size_t CROSS_SLOT_CAP = 1024;
-size_t cross_slots(size_t m, size_t n) {
-	if (n <= PW) return 0;
-	const size_t nb = (size_t)gram_plan(m, PW).nblocks, ntr = cdiv(n, PW) - 1;
-	return std::max(nb, std::min(ntr * nb, CROSS_SLOT_CAP));
-}
+// Gram engine geometry and the coupling partials (GramPlan, gram_plan_of, cross_slots_of, cross_group: f32_plan.h -- shared with the test
+// library), with the process's setting of the wave count
+GramPlan gram_plan(size_t m, size_t n) { return gram_plan_of(m, n, g_set.gram_waves.load()); }
+size_t cross_slots(size_t m, size_t n) { return cross_slots_of(n, gram_plan(m, PW).nblocks); }
 // extra work space of the one-panel path for 64 < n <= 128 (offsets in floats from WqLayout::wide; the doubles first, 16-byte aligned):
 // [summed tiles 36*256 + row count (+pad)] | [Z 128 x 128 fp32][Z22 fp32 4096]
 constexpr size_t WIDE_G_DOUBLES = 36 * 256 + 8;
 constexpr size_t WIDE_OFF_ZW = 2 * WIDE_G_DOUBLES, WIDE_OFF_ZF2 = WIDE_OFF_ZW + 128 * 128, WIDE_FLOATS = WIDE_OFF_ZF2 + 4096;
-constexpr int WIDE_MAX_WGS = 255;                       // gram_wide_kernel: one eight-wave workgroup per CU -- on 255 of the 256 CUs: in a stream of calls the
-                                                        // last CU holds the factorisation of the call before (gram_wide_chain_kernel), and the partials must
-                                                        // be those of the blocking call
-inline size_t wide_part_floats(size_t m) { return (std::min<size_t>((m + 63) / 64, WIDE_MAX_WGS) + 1) * 36 * 256 * 2; }
+// (WIDE_MAX_WGS, wide_part_floats and the split of the Gram pass over its two kernel forms: f32_plan.h -- shared with the test library)
 
 // layout of wq (floats): [stack_b][Z: 4096][S: 4096][R1 copy: n*n][R2: n*n][r3, r4, r5, r6: 4096 each][summed tiles + row count][status]
 // (the summed tiles + row count take GSUM_DOUBLES: f64_plan.h)
@@ -625,30 +603,22 @@ int chol_from_g(Ctx& c, const SweepOpts& o, float* r, size_t ldr, size_t n, int 
 // The launcher of the apply family (KERNEL: the entry; G: its tsqrmi::ApplyGeom): the dynamic-LDS attribute, once per device and instance; the
 // persistent grid -- as many workgroups as are resident on the 256 CUs at once, CAP per CU at the most (QUERY: and no more than the
 // runtime's occupancy figure) -- or grid.wgs of them, split over grid.gy panels and never more than grid.max_wgs; a.nchunks = row blocks
-// of G::ROWS, a.nwaves = workgroups.  pre(a, per_cu, lds, gy) sees the sized grid before the launch; true: the pass has run, no launch.
-struct ApplyGrid { int wgs = 0; unsigned gy = 1; int max_wgs = INT_MAX; };
+// of G::ROWS, a.nwaves = workgroups (ApplyGrid, apply_instance_setup, apply_grid_fill: f32_plan.h -- shared with the test library).
+// pre(a, per_cu, lds, gy) sees the sized grid before the launch; true: the pass has run, no launch.
 template <auto KERNEL, class G, bool GRAMQ, int CAP, bool QUERY, class Pre>
 int launch_apply(Ctx& c, tsqrmi::ApplyArgs a, const ApplyGrid& grid, Pre&& pre) {
 	constexpr size_t lds = G::lds_bytes(GRAMQ);
 	static DevOnce attr;                                 // (per template instance)
 	static std::atomic<int> per_cu_cache[MAX_DEV];
 	if (attr.need(c.dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 		int nb = CAP;
-		if constexpr (QUERY) {
-			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(KERNEL), G::THREADS, lds) != hipSuccess || nb < 1) {
-				(void)hipGetLastError(); nb = 2;
-			}
-		}
-		per_cu_cache[c.dev].store(std::min(nb, CAP));
+		const int rc = apply_instance_setup<KERNEL, G, GRAMQ, CAP, QUERY>(&nb);
+		if (rc) return rc;
+		per_cu_cache[c.dev].store(nb);
 		attr.done(c.dev);
 	}
 	const int per_cu = per_cu_cache[c.dev].load();
-	const size_t nblk = cdiv(a.m, (size_t)G::ROWS);
-	const size_t want = grid.wgs > 0 ? (size_t)grid.wgs : (size_t)256 * per_cu;
-	a.nchunks = (int)nblk;
-	a.nwaves = std::min((int)std::min<size_t>(nblk, std::max<size_t>(1, want / grid.gy)), grid.max_wgs);   // (the resident workgroups split over the trailing panels)
-	a.cpw = 0;
+	apply_grid_fill<G>(a, grid, per_cu);
 	if (pre(a, per_cu, lds, grid.gy)) return 0;
 	hipLaunchKernelGGL(KERNEL, dim3(a.nwaves, grid.gy), dim3(G::THREADS), lds, c.st, a);
 	return 0;
@@ -713,10 +683,10 @@ template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_appl
 	constexpr auto kernel = apply_wg_entry<E, NT, UPD, ROWS, GRAMQ>();
 	// persistent grid: as many workgroups as are resident on the 256 CUs at once (LDS / register bound: 2 or 3 per CU);
 	// measured: the fp32-MFMA engine is slower with three per CU (132 vs 112 us)
-	constexpr int CAP = ROWS == 64 ? 4 : (E == 0 ? 2 : 3);
+	constexpr int CAP = apply_wg_cap<E, ROWS>();         // (f32_plan.h)
 	ApplyGrid grid;
 	grid.wgs = g_set.apply_wgs.load();
-	if (UPD && a.multi_cols > 0) grid.gy = (unsigned)cdiv((size_t)a.multi_cols, PW);
+	if (UPD) grid.gy = UpdApply<E>::gy(a.multi_cols);
 	if (GRAMQ) grid.max_wgs = o.gramq_cap;               // one partial per workgroup: never more than the buffer holds
 	return launch_apply<kernel, tsqrmi::ApplyGeom<E, NT, UPD, ROWS>, GRAMQ, CAP, true>(c, a, grid, [&](tsqrmi::ApplyArgs& x, int per_cu, size_t lds, unsigned gy) {
 		if constexpr (GRAMQ) {
@@ -734,14 +704,13 @@ template <int E, int NT, bool UPD> int launch_apply_any(Ctx& c, const SweepOpts&
 	// block height per engine (measured, profiles/r02_experiment_log.md): the bf16x3 engine streams best with 64-row blocks, four
 	// workgroups per CU and two blocks in flight (88 vs 92 us at 2^20 x 64); the exact-fp32 and fp16 engines and the coupling
 	// update (UPD) use 128-row blocks
-	if constexpr (!UPD && E == 1) return launch_apply_wg<E, NT, UPD, 64>(c, o, gramq_nparts, a);
-	else return launch_apply_wg<E, NT, UPD, 128>(c, o, gramq_nparts, a);
+	return launch_apply_wg<E, NT, UPD, apply_wg_rows<E, UPD>()>(c, o, gramq_nparts, a);
 }
 // fp16 I/O modes: the plain product with halves at both ends -- bf16x3 engine 1 (fp16_notc) or single-fp16-product engine 2
 // (fp16_tc_nocor); 64- / 128-row blocks as in the fp32 call, two blocks in flight
 template <int E, int NT> int launch_apply_h(Ctx& c, const tsqrmi::ApplyArgs& a) {
-	constexpr int ROWS = (E == 1) ? 64 : 128;           // (measured: the bf16x3 engine at 128-row blocks 90 us against 59 at 64)
-	return launch_apply<&tsqrmi::apply_wg_h_kernel<E, NT, ROWS>, tsqrmi::ApplyGeom<E, NT, false, ROWS>, false, (ROWS == 64 ? 4 : 3), true>(c, a, ApplyGrid{}, apply_no_pre);
+	using H = HalfApply<E, NT>;                          // (the instance table: f32_plan.h)
+	return launch_apply<H::kernel(), typename H::G, false, H::CAP, H::QUERY>(c, a, ApplyGrid{}, apply_no_pre);
 }
 template <int E> int dispatch_apply_h(Ctx& c, int NT, const tsqrmi::ApplyArgs& a) {
 	return with_nt(NT, [&](auto nt) { return launch_apply_h<E, decltype(nt)::value>(c, a); });
@@ -970,24 +939,18 @@ int sweep(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, int r_engin
 		double* gm = reinterpret_cast<double*>(c.wq + c.L.gmulti);
 		float* sm = c.wq + c.L.smulti;
 		float* rblk = r + T0 * ldr + Pc;                 // R(Pc : Pc + 64, T0 : n)
-		const size_t grp = std::max<size_t>(1, c.cross_slots / (size_t)g.nblocks);
+		const size_t grp = cross_group(c.cross_slots, g.nblocks);
 		for (size_t j0 = 0; j0 < ntr; j0 += grp) {
 			const unsigned gy = (unsigned)std::min(grp, ntr - j0);
-			const int cols = (int)(ntc - PW * j0);       // columns from trailing panel j0 on
-			tsqrmi::CrossArgs ca{};
-			ca.x = q + Pc * ldq; ca.ldx = ldq; ca.y = a + (T0 + PW * j0) * lda; ca.ldy = lda; ca.m = m; ca.ny = std::min((int)PW, cols); ca.ny_total = cols;
-			ca.nchunks = g.nch; ca.cpw = g.cpw; ca.nwaves = g.nwaves; ca.part = reinterpret_cast<double*>(c.wr);
-			hipLaunchKernelGGL(tsqrmi::cross_kernel, dim3(g.nblocks, gy), dim3(256), 0, c.st, ca);
 			// one GPU: the reduction writes -S_j (operand of the update) and the block row of R itself; row-partitioned: the sums only
-			const bool fin = !c.comm.active();
-			hipLaunchKernelGGL(tsqrmi::cross_reduce_multi_kernel, dim3(256, gy), dim3(256), 0, c.st, gm + j0 * (size_t)tsqrmi::CROSS_GSTRIDE, ca.part, g.nblocks,
-			                   (double)m, fin ? rblk + j0 * PW * ldr : (float*)nullptr, ldr, fin ? sm + j0 * 4096 : (float*)nullptr, cols);
+			// (cross_group_launch: f32_plan.h -- shared with the test library)
+			cross_group_launch(c.st, g, q + Pc * ldq, ldq, a + T0 * lda, lda, m, ntc, j0, gy, reinterpret_cast<double*>(c.wr), gm, !c.comm.active(), rblk, ldr, sm);
 			HIPCHK(hipGetLastError());
 		}
 		if (c.comm.active()) {
 			// ONE all-reduce for the whole block row (every rank holds the same S afterwards: the same R, the same update)
 			if (c.comm.allreduce_f64(gm, ntr * (size_t)tsqrmi::CROSS_GSTRIDE, c.st)) { t_last_error = "all-reduce of the coupling tiles failed"; return -1; }
-			hipLaunchKernelGGL(tsqrmi::cross_finish_kernel, dim3(16, (unsigned)ntr), dim3(256), 0, c.st, rblk, ldr, sm, gm, 0, (int)ntc);
+			cross_finish_launch(c.st, rblk, ldr, sm, gm, ntc);
 			HIPCHK(hipGetLastError());
 		}
 		tsqrmi::ApplyArgs ua{};
@@ -1008,10 +971,8 @@ int sweep(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, int r_engin
 // has its block in LDS before it writes).  r receives the full n x n factor.
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int E> int launch_apply_wide(Ctx& c, const tsqrmi::ApplyArgs& a) {
-	// bf16x3 / fp16 engines: eight waves on 128-row blocks, one workgroup per CU; fp32-MFMA engine: four waves on 64-row blocks with
-	// the compact triangular Z (40 KiB), two workgroups per CU (fixed: the occupancy is not asked for)
-	if constexpr (E == 0) return launch_apply<&tsqrmi::apply_wide_f32_kernel, tsqrmi::ApplyGeom<0, 8, false, 64, 4>, false, 2, false>(c, a, ApplyGrid{}, apply_no_pre);
-	else return launch_apply<&tsqrmi::apply_wide_kernel<E>, tsqrmi::ApplyGeom<E, 8, false, 128, 8>, false, 1, false>(c, a, ApplyGrid{}, apply_no_pre);
+	using W = WideApply<E>;                              // (the instance table: f32_plan.h)
+	return launch_apply<W::kernel(), typename W::G, false, W::CAP, W::QUERY>(c, a, ApplyGrid{}, apply_no_pre);
 }
 // the one-panel path's arguments, shared by the blocking call (sweep_wide) and the stream of 128-column calls (chained128); verdict and
 // skip word: status slot o.slot
@@ -1030,12 +991,10 @@ tsqrmi::GramWideArgs gram_wide_args(Ctx& c, const float* a, size_t lda, size_t m
 // chol(G11) -> Schur complement -> chol(G22') -> Z12 + verdict: one workgroup, one launch (chol_wide_kernel)
 tsqrmi::CholWideArgs chol_wide_args(const Ctx& c, const SweepOpts& o, float* r, size_t ldr, size_t m, size_t n) {
 	const WideWs w = wide_ws(c);
-	tsqrmi::CholWideArgs wa{};
-	wa.gsum = w.gsum; wa.r = r; wa.ldr = ldr; wa.n = (int)n; wa.zf1 = c.wq + c.L.z; wa.zf2 = w.zf2; wa.zw = w.zw;
-	wa.st1 = c.status_dev(2); wa.st2 = c.status_dev(3); wa.status = c.status_dev(o.slot);
+	tsqrmi::CholWideArgs wa = chol_wide_wiring(w.gsum, r, ldr, m, n, c.wq + c.L.z, w.zf2, w.zw, c.status_dev(2), c.status_dev(3), g_set.bf16_scond_floor);
+	wa.status = c.status_dev(o.slot);
 	wa.host_status = c.hsig.dev ? c.hsig.dev + 4 * o.slot : nullptr;
 	wa.prev_status = o.prev_slot >= 0 ? c.status_dev(o.prev_slot) : nullptr;
-	wa.rows = (double)m; wa.scond_floor = g_set.bf16_scond_floor;
 	return wa;
 }
 // Q = A * inverse(R) of the one-panel path; skips itself when the verdict in o.slot rejects
@@ -1052,10 +1011,10 @@ int apply_wide(Ctx& c, const SweepOpts& o, int engine, float* q, size_t ldq, con
 	return 0;
 }
 int sweep_wide(Ctx& c, const SweepOpts& o, int engine, float* q, size_t ldq, float* r, size_t ldr, const float* a, size_t lda, size_t m, size_t n) {
-	// full 64-row blocks of a 128-column matrix go to the fast form of the Gram kernel, whatever is left (ragged last rows, or the
-	// whole matrix when n < 128) to the general form; both write per-workgroup partials, one after the other
-	const size_t nfull = (n == 2 * PW && lda <= ((size_t)1 << 23)) ? m / 64 : 0, nrest = cdiv(m, 64) - nfull;   // (fast form: 32-bit buffer offsets)
-	const int wgs_fast = (int)std::min<size_t>(nfull, WIDE_MAX_WGS), wgs_rest = (int)std::min<size_t>(nrest, WIDE_MAX_WGS);
+	// the fast form of the Gram kernel for the full 64-row blocks of a 128-column matrix, the general form for the rest (wide_gram_plan)
+	const WideGramPlan wp = wide_gram_plan(m, n, lda);
+	const size_t nfull = wp.nfull, nrest = wp.nrest;
+	const int wgs_fast = wp.wgs_fast, wgs_rest = wp.wgs_rest;
 	const int rca = wide_kernel_attrs(c.dev);
 	if (rca) return rca;
 	{
