@@ -335,6 +335,52 @@ inline state_t qr_fp64(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
+
+// Not in the reference: the R factor of qr_fp64 alone, Q never formed (tsqr_mi_r_f64, include/tsqr_mi.h for the contract): a is read
+// only, no m x n work space.  Returns the states of qr_fp64.
+template <bool Reorthogonalize>
+struct buffer_fp64_r {
+	double* dwq;
+	double* dwr;
+	std::size_t total_memory_size;
+
+	buffer_fp64_r() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
+	~buffer_fp64_r() { destroy(); }
+	buffer_fp64_r(const buffer_fp64_r&) = delete;
+	buffer_fp64_r& operator=(const buffer_fp64_r&) = delete;
+
+	void allocate(const std::size_t m, const std::size_t n) {
+		if (dwq != nullptr || dwr != nullptr) {
+			throw std::runtime_error("The buffer has been already allocated");
+		}
+		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_r(m, n);
+		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_r(m, n);
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
+		total_memory_size = wq_size + wr_size;
+	}
+
+	void destroy() {
+		if (dwq) (void)hipFree(dwq);
+		dwq = nullptr;
+		if (dwr) (void)hipFree(dwr);
+		dwr = nullptr;
+	}
+
+	std::size_t get_device_memory_size() const { return total_memory_size; }
+};
+
+template <bool Reorthogonalize>
+inline state_t r_fp64(
+		double* const r_ptr, const std::size_t ldr,
+		const double* const a_ptr, const std::size_t lda,
+		const std::size_t m, const std::size_t n,
+		buffer_fp64_r<Reorthogonalize>& bf,
+		handle_t const stream = nullptr) {
+	const int st = tsqr_mi_r_f64(Reorthogonalize ? 1 : 0, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::r_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
 // Not in the reference: double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide, include/tsqr_mi.h for the
 // contract): qr_fp64 itself for n <= 64, whole-matrix CholeskyQR sweeps with the same ladder beyond.  Returns success_factorization,
 // error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.

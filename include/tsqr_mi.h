@@ -324,6 +324,29 @@ int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, dou
 int tsqr_mi_last_sweeps_f64(void);
 
 /*
+ * The R factor alone, in double precision (not in the reference): tsqr_mi_qr_f64's R without ever forming Q, for callers that need only
+ * R (semi-normal equations, preconditioning, singular values, an R that is reduced further).  r (n x n, ldr) and a (m x n, lda) hold
+ * doubles, column-major, device memory; 1 <= n <= 64, n <= m.  Blocking: returns when its work on `stream` has finished.  A is never
+ * written; r must not overlap A.  R: the full n x n block, exact zeros below the diagonal, a positive diagonal.  Bitwise deterministic
+ * (fixed launch plans, fixed reduction tree).  Work space: wq of tsqr_mi_working_q_size_f64_r(m, n) doubles (independent of m), wr of
+ * tsqr_mi_working_r_size_f64_r(m, n) doubles (the larger of the two Gram plans' partials); there is no m x n buffer.
+ * The ladder, the verdicts and the acceptance rule are tsqr_mi_qr_f64's (CholArgs64 in tsqr_f64.hip).  Sweep 1 is that entry's first
+ * Gram pass and Cholesky step on A -- one read of A, and for a call that ends there R is bitwise tsqr_mi_qr_f64's.  Every further
+ * sweep reads A once more and writes nothing of size m: it takes the Gram matrix of A Z, Z the product of the inverses of all sweeps so
+ * far, forming each 16-row block of A Z in registers (gramq_f64_kernel), and multiplies R on the left.
+ *   reorth = 0  one sweep when the device's estimate allows it, else two; shifted CholeskyQR3 (three sweeps) on a rejected Gram matrix
+ *   reorth = 1  at least two sweeps
+ * For cond(A) <= 1e12: ||(A inverse(R))^T (A inverse(R)) - I||_F is within a small factor of Householder QR's R on the same A (DESIGN.md
+ * section 9 has the measured factors), ||R^T R - A^T A||_F / ||A^T A||_F <= 1e-13.
+ * Returns 0, 1 (n > m, m == 0, n == 0, lda < m or ldr < n), 2 (n > 64; tsqr_mi_last_error says so), 3 = TSQR_MI_ERROR_NOT_FINITE, or
+ * -(hipError_t).  Sizes are checked before any HIP call.  tsqr_mi_last_sweeps_f64 reports this entry too.
+ */
+size_t tsqr_mi_working_q_size_f64_r(size_t m, size_t n);
+size_t tsqr_mi_working_r_size_f64_r(size_t m, size_t n);
+int tsqr_mi_r_f64(int reorth, double* r, size_t ldr, const double* a, size_t lda,
+                  size_t m, size_t n, void* wq, void* wr, void* stream);
+
+/*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
  * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
  * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column

@@ -4,7 +4,11 @@ cases the fp64 rate of one sweep's executed products (2 m n^2, Gram pass and app
 same GPU for 2^20 x 64 and for every wide shape.  Prints one JSON line.  Usage: python tools/f64_speed.py [--calls 50] [--warmup 5]
 --dist1: instead, the cost of the row-partitioned entry's hook on ONE rank -- tsqr_mi_qr_f64_dist_fn over a one-rank raw RCCL communicator
 against the plain entry on the same operands, calls interleaved in this process, at 2^20 x 64 and 2^18 x 256.  (One rank: the all-reduce
-moves nothing between GPUs; this says nothing about several ranks.)"""
+moves nothing between GPUs; this says nothing about several ranks.)
+--r-only: instead, the R-only entry (tsqr_mi_r_f64) next to tsqr_mi_qr_f64 on the same operands in this process, at 2^20, 2^16 and
+2^23 rows x 64: Gaussian with reorth = 0 and 1, and cond 1e12.  Per case the median of --calls blocking calls of each entry, the sweep
+counts, the ratio r_only / full and whether the one-sweep R is bitwise the full call's.  Writes nothing itself: redirect the JSON line
+(profiles/fp64_r_speed.json)."""
 import argparse
 import json
 import os
@@ -66,6 +70,48 @@ def time_torch_qr(torch, a_rm, reps=3):
     return sorted(ts)[len(ts) // 2] * 1e3
 
 
+def r_only(torch, bq, calls, warmup):
+    n = 64
+    out = {"tool": "f64_speed --r-only", "calls": calls, "warmup": warmup, "cases": []}
+
+    def timed(call):
+        for _ in range(warmup):
+            assert call() == 0, bq.last_error()
+        ts = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            st = call()                                     # (blocking: returns when the stream has drained)
+            ts.append(time.perf_counter() - t0)
+            assert st == 0
+        ts.sort()
+        return ts[len(ts) // 2] * 1e3, ts[0] * 1e3, bq.last_sweeps_f64()
+
+    for lg in (20, 16, 23):
+        m = 1 << lg
+        gauss = lambda: torch.randn(m, n, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(lg))
+        for name, make, reorth in (("gauss_2p%d_r0" % lg, gauss, 0), ("gauss_2p%d_r1" % lg, gauss, 1),
+                                   ("cond1e12_2p%d_r0" % lg, lambda: cond_matrix(torch, m, n, 1e12, lg), 0)):
+            a = make().T.contiguous()                       # (n, m): column-major m x n
+            q = torch.empty_like(a)
+            r_full = torch.empty(n, n, dtype=torch.float64, device="cuda")
+            r_only_ = torch.empty(n, n, dtype=torch.float64, device="cuda")
+            bf, bfr = bq.buffer_f64(reorth), bq.buffer_f64_r(reorth)
+            bf.allocate(m, n)
+            bfr.allocate(m, n)
+            full = timed(lambda: bq.qr_f64(q, m, r_full, n, a, m, m, n, bf))
+            ronly = timed(lambda: bq.r_f64(r_only_, n, a, m, m, n, bfr))
+            dr = (torch.linalg.norm(r_only_ - r_full) / torch.linalg.norm(r_full)).item()
+            out["cases"].append({"case": name, "m": m, "n": n, "reorth": reorth,
+                                 "full_median_ms": full[0], "full_min_ms": full[1], "full_sweeps": full[2],
+                                 "r_only_median_ms": ronly[0], "r_only_min_ms": ronly[1], "r_only_sweeps": ronly[2],
+                                 "ratio_r_only_over_full": ronly[0] / full[0], "r_bitwise_equal": bool(torch.equal(r_only_, r_full)),
+                                 "r_rel_diff": dr, "work_bytes_full": bf.get_device_memory_size() + 8 * q.numel(),
+                                 "work_bytes_r_only": bfr.get_device_memory_size()})
+            del a, q, bf, bfr
+            torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def dist1(torch, bq, calls, warmup):
     import ctypes
     rccl = ctypes.CDLL("librccl.so")
@@ -119,12 +165,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cases", default="", help="comma-separated case names (default: all)")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch.linalg.qr baseline")
+    ap.add_argument("--r-only", action="store_true", help="time tsqr_mi_r_f64 next to tsqr_mi_qr_f64 on the same operands")
     ap.add_argument("--dist1", action="store_true", help="time the one-rank row-partitioned call over raw RCCL next to the plain entry")
     args = ap.parse_args()
     import torch
     from tsqr_gpu_amd import blockqr as bq
     if args.dist1:
         return dist1(torch, bq, args.calls, args.warmup)
+    if args.r_only:
+        return r_only(torch, bq, args.calls, args.warmup)
     n = 64
     out = {"tool": "f64_speed", "cases": []}
     gauss = lambda m, seed: torch.randn(m, n, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(seed))

@@ -54,6 +54,7 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_qr_f64", "tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64", "tsqr_mi_last_sweeps_f64",
     "tsqr_mi_qr_f64_wide", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide",
     "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
+    "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
 ]
 
 
@@ -195,6 +196,12 @@ def lib():
         for name, transport in (("tsqr_mi_qr_f64_dist", [vp]), ("tsqr_mi_qr_f64_dist_fn", [vp, vp]), ("tsqr_mi_qr_f64_dist_cb", [vp, vp])):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = f64_dist_head + transport + [ci, vp]
+    if hasattr(L, "tsqr_mi_r_f64"):                      # (as above: an older build has no R-only entry)
+        for name in ("tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r"):
+            getattr(L, name).restype = sz
+            getattr(L, name).argtypes = [sz, sz]
+        L.tsqr_mi_r_f64.restype = ci
+        L.tsqr_mi_r_f64.argtypes = [ci, vp, sz, vp, sz, sz, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -461,23 +468,32 @@ class buffer_f64:
         return 0 if self.dwq is None else 8 * (self.dwq.numel() + self.dwr.numel())
 
 
-def check_f64_operands(m, n, ldq, ldr, lda, q, r, a):
-    """The size and overlap rules of qr_f64 on (address, elements) pairs: ld >= rows, room for (n - 1) ld + rows doubles, q either
-    the very operand a (same address and ld: in place) or apart from it, r apart from both.  Raises ValueError."""
-    ops = (("q", q, ldq, m), ("r", r, ldr, n), ("a", a, lda, m))
+def _f64_spans(who, n, ops):
+    """ld >= rows and room for (n - 1) ld + rows doubles for every (name, (address, elements), ld, rows) of ops; returns the byte span
+    of each operand.  Raises ValueError."""
     span = {}
     for name, (addr, numel), ld, rows in ops:
         if ld < rows:
-            raise ValueError("qr_f64: ld%s = %d is smaller than the %d rows of %s" % (name, ld, rows, name))
+            raise ValueError("%s: ld%s = %d is smaller than the %d rows of %s" % (who, name, ld, rows, name))
         need = (n - 1) * ld + rows
         if numel < need:
-            raise ValueError("qr_f64: %s holds %d elements, an operand of %d x %d with ld %d needs %d" % (name, numel, rows, n, ld, need))
+            raise ValueError("%s: %s holds %d elements, an operand of %d x %d with ld %d needs %d" % (who, name, numel, rows, n, ld, need))
         span[name] = (addr, addr + 8 * need)
-    apart = lambda x, y: span[x][1] <= span[y][0] or span[y][1] <= span[x][0]
-    if not (q[0] == a[0] and ldq == lda) and not apart("q", "a"):
+    return span
+
+
+def _apart(span, x, y):
+    return span[x][1] <= span[y][0] or span[y][1] <= span[x][0]
+
+
+def check_f64_operands(m, n, ldq, ldr, lda, q, r, a):
+    """The size and overlap rules of qr_f64 on (address, elements) pairs: ld >= rows, room for (n - 1) ld + rows doubles, q either
+    the very operand a (same address and ld: in place) or apart from it, r apart from both.  Raises ValueError."""
+    span = _f64_spans("qr_f64", n, (("q", q, ldq, m), ("r", r, ldr, n), ("a", a, lda, m)))
+    if not (q[0] == a[0] and ldq == lda) and not _apart(span, "q", "a"):
         raise ValueError("qr_f64: q overlaps a without being a (in place needs q == a and ldq == lda)")
     for other in ("q", "a"):
-        if not apart("r", other):
+        if not _apart(span, "r", other):
             raise ValueError("qr_f64: r overlaps %s" % other)
 
 
@@ -532,6 +548,50 @@ def qr_f64_wide(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=N
     return _qr_f64(_F64_WIDE, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize)
 
 
+class buffer_f64_r(buffer_f64):
+    """Work space of r_f64 (tsqr_mi_working_{q,r}_size_f64_r doubles on the GPU: no m x n part); reorthogonalize as in buffer_f64."""
+    _entry = ("r_f64", 64, "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r")
+
+
+def check_f64_r_operands(m, n, ldr, lda, r, a):
+    """check_f64_operands' rules for the two operands of r_f64: ld >= rows, room for (n - 1) ld + rows doubles, r apart from a."""
+    span = _f64_spans("r_f64", n, (("r", r, ldr, n), ("a", a, lda, m)))
+    if not _apart(span, "r", "a"):
+        raise ValueError("r_f64: r overlaps a")
+
+
+def r_f64(r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
+    """The R factor of qr_f64 alone, Q never formed (tsqr_mi_r_f64), 1 <= n <= 64, n <= m: r and a are float64 GPU tensors holding
+    column-major data (only data_ptr and numel are used); a is read only.  bf is a buffer_f64_r.  Blocking; returns the state: 0,
+    error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite.  Operands are checked before anything is launched:
+    TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a leading dimension below the rows, or r overlapping a.
+    last_sweeps_f64() tells how many sweeps the call took."""
+    import torch
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    for opname, t in (("r", r), ("a", a)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError("r_f64: %s must be a float64 tensor, got %s" % (opname, getattr(t, "dtype", type(t).__name__)))
+    for opname, t in (("r", r), ("a", a)):
+        if not t.is_cuda:
+            raise TypeError("r_f64: %s is not a GPU tensor" % opname)
+    if n > m or m == 0 or n == 0:
+        return error_invalid_matrix_size
+    L = lib()
+    if n > 64:
+        return L.tsqr_mi_r_f64(int(reorth), None, ldr, None, lda, m, n, None, None, None)
+    check_f64_r_operands(m, n, ldr, lda, (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
+    if bf.dwq is None:
+        raise RuntimeError("r_f64: the buffer is not allocated")
+    if bf.dwq.numel() < L.tsqr_mi_working_q_size_f64_r(m, n) or bf.dwr.numel() < L.tsqr_mi_working_r_size_f64_r(m, n):
+        raise ValueError("r_f64: the buffer was allocated for a smaller matrix")
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    st = L.tsqr_mi_r_f64(int(reorth), r.data_ptr(), ldr, a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("tsqr_mi_r_f64 failed: %s" % last_error())
+    return st
+
+
 def get_working_q_size_f64_dist(m_local, n, nranks):
     """Doubles of wq for tsqr_mi_qr_f64_dist* (dist.RowPartitionedQRF64 allocates them itself)."""
     return lib().tsqr_mi_working_q_size_f64_dist(m_local, n, nranks)
@@ -543,7 +603,7 @@ def get_working_r_size_f64_dist(m_local, n, nranks):
 
 
 def last_sweeps_f64():
-    """Sweeps of this thread's last qr_f64 / qr_f64_wide / row-partitioned fp64 call, plus 100 when it took the shifted path."""
+    """Sweeps of this thread's last qr_f64 / qr_f64_wide / r_f64 / row-partitioned fp64 call, plus 100 when it took the shifted path."""
     return lib().tsqr_mi_last_sweeps_f64()
 
 

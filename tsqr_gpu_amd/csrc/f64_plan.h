@@ -59,6 +59,36 @@ template <int NT> int f64_apply_resident(int dev) {
 // ... but no more than one wave per 32-row block
 inline size_t f64_apply_wgs(size_t nblocks, size_t resident) { return std::max<size_t>(1, std::min(cdiv(nblocks, 4), resident)); }
 
+// ---- tsqr_mi_r_f64 (n <= 64, R only) ---------------------------------------------------------------------------------------------------
+// Sweep 0 is the Gram pass above; sweeps k >= 1 run gramq_f64_kernel on 16-row tiles of A.  Like F64_GRAM_WAVES the wave count is a fixed
+// function of (m, n) -- no occupancy query, no setting -- so that the reduction tree, the bits of R and the size of wr are the same everywhere.
+constexpr int F64R_GRAMQ_WAVES = 2048;
+// wq (doubles): [the F64_WQ layout (the sweep's Z, the sweep's R, summed tiles, status words)][Z_acc: the product of the inverses so far: 4096]
+constexpr size_t F64R_ZACC = F64_WQ, F64R_WQ = F64R_ZACC + 4096;
+
+struct F64RPlan { int NT, ntri, ntiles, nwaves, nblocks; };
+inline F64RPlan f64r_plan(size_t m, size_t n) {
+	F64RPlan g{};
+	g.NT = (int)(np_of(n) / 16);
+	g.ntri = g.NT * (g.NT + 1) / 2;
+	g.ntiles = (int)cdiv(m, 16);
+	const size_t tpw = std::max<size_t>(1, cdiv((size_t)g.ntiles, F64R_GRAMQ_WAVES));
+	g.nwaves = (int)cdiv((size_t)g.ntiles, tpw);
+	g.nblocks = (g.nwaves + 3) / 4;
+	return g;
+}
+// doubles of wr: the larger of the two Gram plans' partials
+inline size_t f64r_wr_doubles(size_t m, size_t n) {
+	const F64Plan g0 = f64_plan(m, n);
+	const F64RPlan g1 = f64r_plan(m, n);
+	return (size_t)std::max(g0.nblocks, g1.nblocks) * g0.ntri * 256;
+}
+
+// the Gram pass of sweeps k >= 1 of the R-only entry on stream st: gramq_f64_kernel<NT> on the plan's grid
+inline void f64r_gramq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::GramQArgs64& ga) {
+	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gramq_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
+}
+
 // ---- tsqr_mi_qr_f64_wide (64 < n <= 1024) ----------------------------------------------------------------------------------------------
 constexpr size_t F64W_MAX_N = 1024;
 constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m

@@ -119,6 +119,39 @@ int tsqr_selftest_f64_rmul(double* r, size_t ldr, const double* r2, int n) {
 	return f64_sync();
 }
 
+// ---- n <= 64, R only (tsqr_mi_r_f64) ------------------------------------------------------------------------------------------------------
+// out[0..7]: NT, ntri, ntiles, nwaves, nblocks, doubles of wq, doubles of wr (the larger of the two Gram plans' partials),
+// F64R_GRAMQ_WAVES.  Host only.
+int tsqr_selftest_f64r_plan(size_t m, size_t n, long long* out) {
+	if (m == 0 || n == 0 || n > PW) return -100;
+	const F64RPlan g = f64r_plan(m, n);
+	out[0] = g.NT; out[1] = g.ntri; out[2] = g.ntiles; out[3] = g.nwaves; out[4] = g.nblocks;
+	out[5] = (long long)F64R_WQ; out[6] = (long long)f64r_wr_doubles(m, n); out[7] = F64R_GRAMQ_WAVES;
+	return 0;
+}
+
+// gramq_f64_kernel + reduction: gsum[ntri * 256 + 1] = the tiles of (a z)^T (a z) and the row count behind them; z: NP x NP (ld NP).
+// nwaves > 0 overrides the plan's wave count; part holds part_cap doubles.
+int tsqr_selftest_f64_gramq(double* gsum, const double* a, size_t lda, size_t m, int n, const double* z, double* part, size_t part_cap,
+                            int nwaves) {
+	if (m == 0 || n <= 0 || n > (int)PW || lda < m) return -100;
+	F64RPlan g = f64r_plan(m, (size_t)n);
+	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
+	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
+	const tsqrmi::GramQArgs64 ga{a, lda, m, n, g.ntiles, g.nwaves, z, part};
+	f64r_gramq_launch(0, g, ga);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
+	return f64_sync();
+}
+
+// zmul_f64_kernel: z <- z zk (both NP x NP with ld NP, NP = 16 ceil(n / 16)), in place
+int tsqr_selftest_f64_zmul(double* z, const double* zk, int n) {
+	if (n <= 0 || n > (int)PW) return -100;
+	hipLaunchKernelGGL(tsqrmi::zmul_f64_kernel, dim3(1), dim3(1024), 0, 0, z, zk, n, (int)np_of((size_t)n));
+	return f64_sync();
+}
+
 // ---- 64 < n <= 1024 ---------------------------------------------------------------------------------------------------------------------
 // Gram pass + reduction: gs[bs + 1] in the block store's layout.  cps > 0 overrides the chunks per slice; part holds part_cap doubles.
 int tsqr_selftest_f64w_gram(double* gs, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, size_t cps) {

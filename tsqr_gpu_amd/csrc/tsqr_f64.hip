@@ -6,6 +6,9 @@
 //                       once with the shift of Fukaya et al.
 //   apply_f64_kernel  : Q = A Z on v_mfma_f64_16x16x4_f64, Z upper triangular (its zero blocks are skipped), in place allowed
 //   rmul_f64_kernel   : R <- R2 R on v_mfma_f64_16x16x4_f64, in place
+// and of the R-only entry (tsqr_mi_r_f64), whose sweeps after the first stream A and never store Q:
+//   gramq_f64_kernel  : per-workgroup partials of (A Z)^T (A Z), each 16-row block of A Z formed and consumed in registers
+//   zmul_f64_kernel   : Z <- Z Zk, the inverse of all sweeps so far, in place
 #include <hip/hip_runtime.h>
 
 namespace tsqrmi {
@@ -176,6 +179,106 @@ __global__ __launch_bounds__(1024) void rmul_f64_kernel(double* r, size_t ldr, c
 	for (int reg = 0; reg < 4; reg++) {
 		const int i = 16 * ti + lq + 4 * reg, j = 16 * tj + li;
 		if (i < n && j < n) r[(size_t)j * ldr + i] = (i <= j) ? c[reg] : 0.0;
+	}
+}
+
+// ---- the R-only entry (tsqr_mi_r_f64): sweeps after the first never store Q --------------------------------------------------------
+struct GramQArgs64 {
+	const double* a; size_t lda; size_t m; int n;
+	int ntiles; int nwaves;              // 16-row tiles of A; waves that take tiles (wave w: tiles w, w + nwaves, ...)
+	const double* z;                     // NP x NP (ld NP) upper triangular, zero padded: chol_f64_kernel's Z or a product of such
+	double* part;                        // [gridDim.x][NTRI][256], gram_f64_kernel's partials
+};
+
+// Per-workgroup partials of (A Z)^T (A Z) without storing A Z.  A wave takes 16-row tiles of A.  apply_f64_kernel's register contents
+// (zop: lane (li, lq) holds Z[4 kb + lq][16 jt + li]; av: lane (li, lq) holds A[row0 + li][4 kb + lq]) with the MFMA operands SWAPPED:
+// D[r][j] = sum_k A[row0 + r][k] Z[k][16 jt + j], so the C/D layout (col = lane & 15, row = (lane >> 4) + 4 reg) leaves
+// Q[row0 + lq + 4 reg][16 jt + li] in register reg of lane (li, lq) -- the operand form of the Gram MFMA (gram_body: sixteen lanes hold
+// sixteen COLUMNS of one row, the lane quarter picks the row of the K-step).  Register reg of tiles ti and tj then feed
+// G(ti, tj) += Q_reg(ti)^T Q_reg(tj) directly: K-step reg sums the rows row0 + 4 reg + {0, 1, 2, 3} -- both operands come from the same
+// lane and register, so they name the same row.  No LDS transpose, no store; output tile jt needs k < 16 (jt + 1) only, as in the apply
+// pass.  Rows >= m and columns >= n enter as zeros.  The partials leave in gram_f64_kernel's layout (wg_sum4_store).
+template <int NT>
+__global__ __launch_bounds__(256) void gramq_f64_kernel(const GramQArgs64 a) {
+	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1), NTRI = (NT * (NT + 1)) / 2;
+	__shared__ double red[2 * NTRI * 256];
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
+	const int gw = blockIdx.x * 4 + wv;
+	f64x4 acc[NTRI];
+#pragma unroll
+	for (int t = 0; t < NTRI; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+	if (gw < a.nwaves) {
+		double zop[NZ];
+		static_for<0, NT>([&](auto jt_) {
+			constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+#pragma unroll
+			for (int kb = 0; kb < 4 * (jt + 1); kb++) zop[base + kb] = a.z[(size_t)(16 * jt + li) * NP + 4 * kb + lq];
+		});
+		// av of the tile after this one is loaded before this one's products are issued (one wave per SIMD: nothing else hides the loads);
+		// a tile beyond the last reads nothing and leaves zeros
+		auto load_tile = [&](double (&av)[KB], int tile) {
+			const size_t row = (size_t)tile * 16 + li;
+			const bool live = tile < a.ntiles && row < a.m;
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) {
+				const int col = 4 * kb + lq;
+				av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+			}
+		};
+		double av[KB], nx[KB];
+		load_tile(av, gw);
+		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
+			load_tile(nx, tile + a.nwaves);
+			f64x4 qt[NT];
+			static_for<0, NT>([&](auto jt_) {
+				constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+				for (int kb = 0; kb < 4 * (jt + 1); kb++)
+					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zop[base + kb], qt[jt], 0, 0, 0);
+			});
+#pragma unroll
+			for (int reg = 0; reg < 4; reg++) {
+				int idx = 0;
+#pragma unroll
+				for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+					for (int tj = ti; tj < NT; tj++) {
+						acc[idx] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], qt[tj][reg], acc[idx], 0, 0, 0);
+						idx++;
+					}
+			}
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
+		}
+	}
+	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NTRI * 256, wv, lane);
+}
+
+// Z <- Z Zk (both NP x NP with ld NP, upper triangular, zero padded; n <= 64), in place: rmul_f64_kernel's scheme on the layout of
+// chol_f64_kernel's Z.  The whole NP x NP block is written (zeros below the diagonal and beyond n).  Every thread has read its entries
+// before the barrier that precedes the first store.
+__global__ __launch_bounds__(1024) void zmul_f64_kernel(double* z, const double* __restrict__ zk, int n, int NP) {
+	__shared__ double A2[64 * 65], A1[64 * 65];          // A2[i * 65 + k] = Z[i][k], A1[k * 65 + j] = Zk[k][j]; zero outside the upper triangles
+	const int t = threadIdx.x;
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		const bool in = i <= j && j < n;
+		A2[i * 65 + j] = in ? z[(size_t)j * NP + i] : 0.0;
+		A1[i * 65 + j] = in ? zk[(size_t)j * NP + i] : 0.0;
+	}
+	__syncthreads();
+	const int w = t >> 6, l = t & 63, ti = w >> 2, tj = w & 3, li = l & 15, lq = l >> 4;
+	f64x4 c = f64x4{0.0, 0.0, 0.0, 0.0};                // c[reg] = (Z Zk)[16 ti + lq + 4 reg][16 tj + li]
+	if (ti <= tj) {
+		for (int ks = 4 * ti; ks < 4 * (tj + 1); ks++)
+			c = __builtin_amdgcn_mfma_f64_16x16x4f64(A2[(16 * ti + li) * 65 + 4 * ks + lq], A1[(4 * ks + lq) * 65 + 16 * tj + li], c, 0, 0, 0);
+	}
+#pragma unroll
+	for (int reg = 0; reg < 4; reg++) {
+		const int i = 16 * ti + lq + 4 * reg, j = 16 * tj + li;
+		if (i < NP && j < NP) z[(size_t)j * NP + i] = (i <= j) ? c[reg] : 0.0;
 	}
 }
 

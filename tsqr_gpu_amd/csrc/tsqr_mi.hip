@@ -2435,6 +2435,24 @@ int f64_exchange(const Comm* comm, double* gsum, size_t nelem, hipStream_t st) {
 	return 0;
 }
 
+// The Cholesky step on the summed tiles in wq[F64_GSUM] with the rule of an m x n sweep: R -> r (ldr), Z -> wq[F64_Z], verdict -> status
+// slot `slot`
+int f64_chol(hipStream_t st, double* wq, size_t m, size_t n, double* r, size_t ldr, bool first, int slot, const Comm* comm) {
+	const int NT = (int)(np_of(n) / 16), nelem = NT * (NT + 1) / 2 * 256;
+	tsqrmi::CholArgs64 ca{};
+	ca.r = r; ca.ldr = ldr; ca.z = wq + F64_Z;
+	ca.status = reinterpret_cast<unsigned*>(wq + F64_STATUS) + 4 * slot;
+	ca.host_status = t_own64.dev + 4 * slot;
+	ca.gsum = wq + F64_GSUM;
+	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64 states the rule and its sources)
+	ca.shift_coef = rule.shift_coef; ca.max_scond = rule.max_scond; ca.alone_max = rule.alone_max;
+	ca.n = (int)n; ca.NT = NT;
+	if (comm && comm->active()) { ca.rows_dev = wq + F64_GSUM + nelem; ca.first = first ? 1 : 0; }   // (the rule of the GLOBAL row count, on the device)
+	hipLaunchKernelGGL(tsqrmi::chol_f64_kernel, dim3(1), dim3(1024), 0, st, ca);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
 // Gram pass, reduction and Cholesky step of one sweep over src: R -> r (ldr), Z -> wq[F64_Z], verdict -> status slot `slot`
 int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t ld, size_t m, size_t n, double* r, size_t ldr,
                bool first, int slot, const Comm* comm = nullptr) {
@@ -2447,18 +2465,7 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
 	launch_reduce1(st, wq + F64_GSUM, wr, g.nblocks, nelem, (double)m);
 	HIPCHK(hipGetLastError());
 	if (const int rc = f64_exchange(comm, wq + F64_GSUM, (size_t)nelem, st)) return rc;
-	tsqrmi::CholArgs64 ca{};
-	ca.r = r; ca.ldr = ldr; ca.z = wq + F64_Z;
-	ca.status = reinterpret_cast<unsigned*>(wq + F64_STATUS) + 4 * slot;
-	ca.host_status = t_own64.dev + 4 * slot;
-	ca.gsum = wq + F64_GSUM;
-	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64 states the rule and its sources)
-	ca.shift_coef = rule.shift_coef; ca.max_scond = rule.max_scond; ca.alone_max = rule.alone_max;
-	ca.n = (int)n; ca.NT = g.NT;
-	if (comm && comm->active()) { ca.rows_dev = wq + F64_GSUM + nelem; ca.first = first ? 1 : 0; }   // (the rule of the GLOBAL row count, on the device)
-	hipLaunchKernelGGL(tsqrmi::chol_f64_kernel, dim3(1), dim3(1024), 0, st, ca);
-	HIPCHK(hipGetLastError());
-	return 0;
+	return f64_chol(st, wq, m, n, r, ldr, first, slot, comm);
 }
 
 // Q = A Z on a persistent grid: as many workgroups as are resident at once, each wave striding over 32-row blocks
@@ -2497,20 +2504,17 @@ int f64w_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r,
 
 // The ladder (include/tsqr_mi.h): verdict 0 of sweep 0 with "one sweep suffices" ends a reorth = 0 call, any other accepted first
 // sweep is followed by one more (CholeskyQR2), a shifted sweep by two more (shifted CholeskyQR3), a rejected one ends the call (state 3).
-// wide: the sweeps of tsqr_mi_qr_f64_wide for n > 64 (f64w_sweep); the verdict words and their meaning are the same.
-int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
-                hipStream_t st, bool wide = false, const Comm* comm = nullptr) {
+template <class Sweep>                                   // sweep(k): enqueue sweep k (0-based) on st; non-zero ends the call with that state
+int f64_ladder(int reorth, hipStream_t st, Sweep sweep) {
 	t_sweeps64 = 0;
 	if (!t_own64.get()) { t_last_error = "could not allocate the pinned verdict words"; return -(int)hipErrorOutOfMemory; }
 	volatile unsigned* words = t_own64.host;
 	for (int i = 0; i < 16; i++) words[i] = 1u;          // (a sweep that never reported reads as rejected)
-	const int dev = cur_device();
 	int sweeps = 0, need = reorth ? 2 : 1, checked = 0;
 	bool shifted = false;
 	for (;;) {
 		while (sweeps < need) {
-			const int rc = wide ? f64w_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm)
-			                    : f64_sweep(st, dev, sweeps, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm);
+			const int rc = sweep(sweeps);
 			if (rc) return rc;
 			sweeps++;
 		}
@@ -2536,9 +2540,61 @@ int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double
 	return TSQR_MI_SUCCESS;
 }
 
+// wide: the sweeps of tsqr_mi_qr_f64_wide for n > 64 (f64w_sweep); the verdict words and their meaning are the same.
+int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
+                hipStream_t st, bool wide = false, const Comm* comm = nullptr) {
+	const int dev = cur_device();
+	return f64_ladder(reorth, st, [&](int k) {
+		return wide ? f64w_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm)
+		            : f64_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm);
+	});
+}
+
+// Sweep k (0-based) of the R-only entry.  Sweep 0 is f64_factor on A: R_1 -> r, Z_1 -> wq[F64_Z].  Sweep k >= 1 never forms Q: first
+// Z_acc = Z_1 ... Z_k (sweep 1: a copy of Z_1; later: Z_acc <- Z_acc Z_k, with the Z_k that sweep k - 1 left in wq[F64_Z]), then the Gram
+// matrix of A Z_acc straight from A (gramq_f64_kernel), the reduction, the Cholesky step of a later sweep (R_(k+1) -> wq[F64_R2],
+// Z_(k+1) -> wq[F64_Z]) and r <- R_(k+1) r.
+int f64r_sweep(hipStream_t st, int k, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, double* wq, double* wr) {
+	if (k == 0) return f64_factor(st, wq, wr, a, lda, m, n, r, ldr, true, 0);
+	const size_t NP = np_of(n);
+	double* zacc = wq + F64R_ZACC;
+	if (k == 1) HIPCHK(hipMemcpyAsync(zacc, wq + F64_Z, NP * NP * sizeof(double), hipMemcpyDeviceToDevice, st));
+	else hipLaunchKernelGGL(tsqrmi::zmul_f64_kernel, dim3(1), dim3(1024), 0, st, zacc, (const double*)(wq + F64_Z), (int)n, (int)NP);
+	HIPCHK(hipGetLastError());
+	const F64RPlan g = f64r_plan(m, n);
+	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	const tsqrmi::GramQArgs64 ga{a, lda, m, (int)n, g.ntiles, g.nwaves, zacc, wr};
+	f64r_gramq_launch(st, g, ga);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(st, wq + F64_GSUM, wr, g.nblocks, g.ntri * 256, (double)m);
+	HIPCHK(hipGetLastError());
+	if (const int rc = f64_chol(st, wq, m, n, wq + F64_R2, 64, false, k & 3, nullptr)) return rc;
+	hipLaunchKernelGGL(tsqrmi::rmul_f64_kernel, dim3(1), dim3(1024), 0, st, r, ldr, wq + F64_R2, (int)n);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// the ladder of qr_f64_core (f64_ladder) on the sweeps of f64r_sweep
+int r_f64_core(int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, hipStream_t st) {
+	return f64_ladder(reorth, st, [&](int k) { return f64r_sweep(st, k, r, ldr, a, lda, m, n, wq, wr); });
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t tsqr_mi_working_q_size_f64_r(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : F64R_WQ; }
+size_t tsqr_mi_working_r_size_f64_r(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : f64r_wr_doubles(m, std::min(n, PW)); }
+
+int tsqr_mi_r_f64(int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, void* wq, void* wr, void* stream) {
+	t_sweeps64 = 0;
+	if (n > m || m == 0 || n == 0 || lda < m || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > PW) { t_last_error = "tsqr_mi_r_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	if (rc) return rc;
+	return r_f64_core(reorth, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
+	                  reinterpret_cast<hipStream_t>(stream));
+}
 
 size_t tsqr_mi_working_q_size_f64(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : F64_WQ; }
 size_t tsqr_mi_working_r_size_f64(size_t m, size_t n) {
