@@ -43,7 +43,14 @@ enum tsqr_mi_compute_mode {
 #define TSQR_MI_SUCCESS               0   /* success_factorization */
 #define TSQR_MI_ERROR_INVALID_SIZE    1   /* error_invalid_matrix_size: n > m, m == 0 or n == 0 */
 #define TSQR_MI_ERROR_UNSUPPORTED     2   /* new: compute_mode without a gfx950 implementation */
-#define TSQR_MI_ERROR_NOT_FINITE      3   /* new, tsqr_mi_qr_f64 only: A holds an Inf or NaN (or A^T A overflows); Q and R are undefined */
+#define TSQR_MI_ERROR_NOT_FINITE      3   /* new, the fp64 entries only: no factorisation inside the bands could be formed; Q and R are undefined.  A holds
+                                           * an Inf or NaN; or A^T A leaves the normal fp64 range -- an entry overflows (a column norm of 2^512 or more), or
+                                           * a squared column norm lies below 2^-1022 (a column norm below 2^-511, a zero matrix included); or A is rank
+                                           * deficient in a way the shift cannot repair (an exactly zero column among non-zero ones: every sweep is shifted
+                                           * again and the ladder ends at its cap).  On every rank alike for the row-partitioned entries.  Supported range of
+                                           * column norms (the range is judged on the column norms of the sweep's input, the diagonal of its Gram matrix):
+                                           * [2^-511, 2^512), and ||A||_F < 2^512 for input that takes the shifted path (its trace).  Inside
+                                           * it, scaling the columns by powers of two changes no bit of Q (tests/test_gpu_f64_scale.py) */
 /* negative return values: -(hipError_t) of the failing runtime call */
 
 int tsqr_mi_version(void);

@@ -242,6 +242,36 @@ def test_chol_verdicts_thresholds_and_shift(st):
     assert v == 0 and one == 0
 
 
+def floor_matrix(n, target):
+    """SPD G = R^T R (longdouble, rounded to fp64) whose LAST pivot ratio r_nn^2 / g_nn is `target`, every other one that of a
+    well-conditioned matrix: R is the factor of spd(n, 3) with its last diagonal entry set from r_nn^2 = target c / (1 - target),
+    c the squared norm of the rest of the last column"""
+    g0, _ = p64.spd(n, 3.0, 1)
+    r = p64.chol_ld(g0)
+    c = np.sum(r[:n - 1, n - 1] ** 2)
+    r[n - 1, n - 1] = np.sqrt(LD(target) * c / (LD(1) - LD(target)))
+    return np.asarray(r.T @ r, np.float64)                 # (longdouble product, symmetric term by term, rounded once)
+
+
+@pytest.mark.parametrize("n", [64, 17])
+def test_chol_pivot_floor_of_every_plain_factorisation(st, n):
+    """F64_MIN_PIVOT_RATIO = 2^-40 (CholArgs64): a later sweep (first = 0, no bound on S) whose smallest pivot ratio is 1.5 times above
+    the floor is accepted, one 1.5 times below it is factored shifted -- at the smallest and the largest row count alike: the floor does
+    not depend on the shape.  (The kernel's pivot carries about n u / ratio = 1 % of rounding at the floor: the margin 1.5 is a
+    condition.)  The ratios are checked in longdouble first."""
+    floor = 2.0 ** -40
+    for factor, want in ((1.5, 0), (1.0 / 1.5, 2)):
+        g = floor_matrix(n, factor * floor)
+        ratio_ref = p64.scond_ref(g)[1]
+        assert abs(ratio_ref - factor * floor) <= 0.02 * factor * floor, (ratio_ref, factor * floor)
+        for m in (4096, 1 << 23):
+            v, ratio, _, one = chol_narrow(st, g, n, m=m, first=0)[2]
+            print("n %d m %d: pivot ratio %.3g (longdouble %.3g, floor %.3g): verdict %d" % (n, m, ratio, ratio_ref, floor, v))
+            assert v == want and one == 0, (n, m, factor, v)
+            if want == 0:
+                assert abs(ratio - ratio_ref) <= 0.05 * ratio_ref
+
+
 def apply_narrow(st, a, z, ld_pad, offset, wgs=0, in_place=False):
     L, torch = st
     m, n = a.shape

@@ -53,9 +53,33 @@ __host__ __device__ inline F64Rule f64_rule_of(double rows, int n, bool first) {
 //   rejected                   otherwise: the same launch factors G + s I, s = 11 (m n + n (n + 1)) u trace(G) (Fukaya, Kannan,
 //                              Nakatsukasa, Yamamoto and Yanagisawa, "Shifted Cholesky QR for computing the QR factorization of
 //                              ill-conditioned matrices", SISC 42 (2020)), accepted whenever every pivot is positive: two more sweeps
-//                              follow (shifted CholeskyQR3).  Rejected even so: non-finite input.
-// Sweeps after the first pass alone_max = max_scond = infinity: their input is Q of a sweep before, and only a breakdown sends them
-// to the shift.
+//                              follow (shifted CholeskyQR3).  Rejected even so: non-finite input, or a Gram matrix outside the normal range.
+//   the range                  both factorisations also require every diagonal entry of the matrix they factor (G, or G + s I) to be a NORMAL
+//                              fp64 number (F64_MIN_DIAG = 2^-1022; chol_body16's min_diag).  Below it the entries of G are subnormal: they
+//                              carry an absolute error of 2^-1075 instead of a relative one, nothing in the rule sees that, and the call
+//                              returned 0 with ||Q^T Q - I||_F beyond the header's band (2^-520 times a 4097 x 64 Gaussian matrix: 1.8e-11
+//                              after one sweep).  With g_jj >= 2^-1022 a product that underflows costs at most 2^-1075 <= u g_jj, one
+//                              more rounding error of the size the rule already budgets per term.  An overflowing G needs no rule of its
+//                              own: Inf and NaN fail every comparison of the verdict.
+//   the pivot floor            the plain factorisation of EVERY sweep also requires the smallest pivot ratio r_jj^2 / g_jj -- the squared sine of
+//                              the angle between column j and the columns before it -- to exceed F64_MIN_PIVOT_RATIO = 2^-40, the bound this
+//                              library already uses for "beyond fp64 Cholesky" (chol_body16, the fp64 Gram level of the fp32 ladder); it
+//                              does not depend on the shape.  A pivot is a difference g_jj - sum r_kj^2 of j + 1 rounded terms, each
+//                              carrying the rounding of its Gram entries: one that small next to g_jj is mostly rounding error.
+//                              Why it is needed: with exactly dependent columns in A, Q of the shifted sweep is rank deficient up to
+//                              rounding and the pivot of the dependent column in the next sweep is noise (ratios of 1e-16 .. 5e-15 in a
+//                              numpy model of the ladder on the cases of tests/test_gpu_f64_scale.py).  Negative noise was always
+//                              shifted again; positive noise was accepted, R of that sweep had a condition number near 1 / u and
+//                              Q <- Q inverse(R) lost ||A - Q R||_F / ||A||_F = 6e-10.  A first sweep does not notice the floor:
+//                              S >= 1 / (n ratio), so its bound on S already implies ratio >= 64 u (m n + n (n + 1)), and that
+//                              exceeds 2^-40 from m n = 128 up.  Later sweeps of in-contract input
+//                              meet it only at the far end: the sweep after the shift on cond(A) = 1e12 has ratios around 1e-12 .. 1e-14
+//                              and may be shifted once more (profiles/fp64_scale_tests.md has the sweep counts measured at 2^20 and
+//                              2^23 rows); cond(A) <= 1e10 stays where it was.
+// Sweeps after the first pass alone_max = max_scond = infinity: their input is Q of a sweep before, and only a breakdown or a pivot
+// under the floor sends them to the shift.
+constexpr float F64_MIN_PIVOT_RATIO = 0x1p-40f;
+constexpr double F64_MIN_DIAG = 0x1p-1022;              // the smallest normal fp64 number
 struct CholArgs64 {
 	double* r; size_t ldr;               // R out: n x n, full block written (zeros below the diagonal)
 	double* z;                           // Z = inverse(R) out: NP x NP column-major (ld NP), zero padded
@@ -74,7 +98,7 @@ __global__ __launch_bounds__(1024) void chol_f64_kernel(const CholArgs64 a) {
 	auto loadg = [&](int e) { return a.gsum[e]; };
 	F64Rule rule{a.shift_coef, a.max_scond, a.alone_max};
 	if (a.rows_dev) rule = f64_rule_of(a.rows_dev[0], a.n, a.first != 0);     // (uniform: every thread reads the same word)
-	chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, rule.max_scond, 0.0, 0.0);
+	chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, F64_MIN_PIVOT_RATIO, rule.max_scond, 0.0, F64_MIN_DIAG);
 	__shared__ unsigned again;
 	__syncthreads();
 	if (threadIdx.x == 0) {                              // (thread 0 wrote the verdict itself: program order)
@@ -83,7 +107,7 @@ __global__ __launch_bounds__(1024) void chol_f64_kernel(const CholArgs64 a) {
 	}
 	__syncthreads();
 	if (again) {
-		chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, INFINITY, rule.shift_coef, 0.0);
+		chol_body16(a.r, a.ldr, a.z, a.status, nullptr, loadg, a.n, a.NT, 0, 0.0f, INFINITY, rule.shift_coef, F64_MIN_DIAG);
 		__syncthreads();
 		if (threadIdx.x == 0) {
 			if (a.status[0] == 0u) a.status[0] = 2u;

@@ -234,7 +234,10 @@ __global__ __launch_bounds__(1024) void cholw_row_kernel(const WideF64 a, int k)
 		if (t == 0) a.sb[I * a.nb + k] = s;
 		return;
 	}
-	// block k: Z_kk into the block store (zero padded), R_kk's padding zeroed, the S term and the smallest pivot ratio r_jj^2 / g_jj
+	// block k: Z_kk into the block store (zero padded), R_kk's padding zeroed, the S term and the smallest pivot ratio r_jj^2 / g_jj.
+	// A diagonal entry of the factored matrix (G, or G + s I in the shifted chain) below the normal range counts as a ratio of zero
+	// (F64_MIN_DIAG, CholArgs64: the rule of the narrow entry, taken here on the ORIGINAL diagonal like the rest of the verdict).
+	const double shift = (a.shift_coef > 0.0) ? wide_shift(a) : 0.0;     // (the whole workgroup has this role: the barrier inside is uniform)
 	const double* gd = a.gs + (size_t)wpair(k, k) * 4096;
 	double* zo = a.zw + (size_t)wpair(k, k) * 4096;
 	double* ro = a.rw + (size_t)wpair(k, k) * 4096;
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(1024) void cholw_row_kernel(const WideF64 a, int k)
 		if (r >= nk || c >= nk) ro[e] = 0.0;
 		if (r < nk && c < nk) {
 			s = fma(gd[r * 65] * z, z, s);
-			if (r == c) ratio = fminf(ratio, (float)(1.0 / (gd[r * 65] * z * z)));
+			if (r == c) ratio = fminf(ratio, (gd[r * 65] + shift >= F64_MIN_DIAG) ? (float)(1.0 / (gd[r * 65] * z * z)) : 0.0f);
 		}
 	}
 	for (int o = 32; o > 0; o >>= 1) ratio = fminf(ratio, __shfl_xor(ratio, o));
@@ -306,7 +309,7 @@ __global__ __launch_bounds__(1024) void cholw_update_kernel(const WideF64 a, int
 }
 
 // The verdict over all n columns (CholArgs64's rule, tsqr_f64.hip): every block's pivots positive and finite, the smallest pivot ratio
-// r_jj^2 / g_jj > 0, and S = ||D Z||_F^2 / n (D = diag(sqrt(g_jj)) of the ORIGINAL G, the Z blocks' terms added in pair order) against the
+// r_jj^2 / g_jj above F64_MIN_PIVOT_RATIO (plain chain; > 0 in the shifted one), and S = ||D Z||_F^2 / n (D = diag(sqrt(g_jj)) of the ORIGINAL G, the Z blocks' terms added in pair order) against the
 // CholeskyQR2 bound.  Plain chain: words [0] 0 / 1, [3] one sweep suffices.  Shifted chain (run_if set): when the plain verdict was 0 it
 // changes nothing; otherwise 2 (accepted after the shift) or 1 (non-finite input), [3] = 0.  The shifted chain's launch is the last of
 // the sweep's Cholesky step and always copies the four words to the pinned host words.
@@ -326,7 +329,8 @@ __global__ __launch_bounds__(64) void cholw_verdict_kernel(const WideF64 a) {
 		F64Rule rule{a.shift_coef, a.max_scond, a.alone_max};
 		if (a.rows_dev) rule = f64_rule_of(a.rows_dev[0], a.n, a.first != 0);
 		const float max_scond = shifted ? INFINITY : rule.max_scond;
-		const bool ok = bad == 0u && rm > 0.0f && scond <= max_scond;     // NaN compares false -> rejected
+		const float min_ratio = shifted ? 0.0f : F64_MIN_PIVOT_RATIO;
+		const bool ok = bad == 0u && rm > min_ratio && scond <= max_scond;     // NaN compares false -> rejected
 		a.status[0] = shifted ? (ok ? 2u : 1u) : (ok ? 0u : 1u);
 		a.status[1] = __builtin_bit_cast(unsigned, rm);
 		a.status[2] = __builtin_bit_cast(unsigned, scond);

@@ -2510,7 +2510,7 @@ int f64_ladder(int reorth, hipStream_t st, Sweep sweep) {
 	if (!t_own64.get()) { t_last_error = "could not allocate the pinned verdict words"; return -(int)hipErrorOutOfMemory; }
 	volatile unsigned* words = t_own64.host;
 	for (int i = 0; i < 16; i++) words[i] = 1u;          // (a sweep that never reported reads as rejected)
-	int sweeps = 0, need = reorth ? 2 : 1, checked = 0;
+	int sweeps = 0, need = reorth ? 2 : 1, checked = 0, last_shift = -1;
 	bool shifted = false;
 	for (;;) {
 		while (sweeps < need) {
@@ -2524,19 +2524,26 @@ int f64_ladder(int reorth, hipStream_t st, Sweep sweep) {
 			const unsigned v = w[0];
 			if (v == 1u) {
 				t_sweeps64 = checked + 1 + (shifted ? 100 : 0);
-				t_last_error = "non-finite input: the Cholesky step was rejected even with the shift";
+				t_last_error = "the Cholesky step was rejected even with the shift: Inf or NaN in A, or a column norm outside [2^-511, 2^512)";
 				return TSQR_MI_ERROR_NOT_FINITE;
 			}
 			// Row-partitioned call: each rank reads its OWN pinned words.  The ranks factored the same all-reduced bits with deterministic
 			// kernels and a rule taken from the same summed row count, so the words are equal on all ranks and every rank arrives at the
 			// same `need` -- the same number of sweeps, hence of all-reduces -- without a vote.
-			if (v == 2u) { shifted = true; need = std::max(need, checked + 3); }
+			if (v == 2u) { shifted = true; last_shift = checked; need = std::max(need, checked + 3); }
 			else if (checked == 0 && !(reorth == 0 && w[3] == 1u)) need = std::max(need, 2);
 		}
 		need = std::min(need, F64_MAX_SWEEPS);
 		if (sweeps >= need) break;
 	}
 	t_sweeps64 = sweeps + (shifted ? 100 : 0);
+	// A shifted sweep leaves Q orthonormal only to about s / sigma_min^2; the two plain sweeps behind it are what the bands rest on.  When
+	// the cap ends the ladder before they ran -- every sweep of a matrix with an exactly zero column is shifted again: the column stays
+	// zero -- Q is not inside the bands (measured 1.2e-7 on the OTHER columns of a 4097 x 64 matrix), and the call says so.
+	if (shifted && sweeps < last_shift + 3) {
+		t_last_error = "rank-deficient input: the ladder ended before two plain sweeps had followed the last shifted one";
+		return TSQR_MI_ERROR_NOT_FINITE;
+	}
 	return TSQR_MI_SUCCESS;
 }
 
