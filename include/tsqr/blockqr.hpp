@@ -381,6 +381,57 @@ inline state_t r_fp64(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::r_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
+
+// Not in the reference: X = argmin ||A X - B||_F and the R of r_fp64, on the R-only factorisation (tsqr_mi_lstsq_f64, include/tsqr_mi.h
+// for the contract and the accuracy statement): a and b are read only, no work space of size m.  Returns the states of r_fp64;
+// error_unsupported_mode also for nrhs > 16 or refine outside 0 .. 4.
+template <bool Reorthogonalize>
+struct buffer_fp64_lstsq {
+	double* dwq;
+	double* dwr;
+	std::size_t total_memory_size;
+
+	buffer_fp64_lstsq() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
+	~buffer_fp64_lstsq() { destroy(); }
+	buffer_fp64_lstsq(const buffer_fp64_lstsq&) = delete;
+	buffer_fp64_lstsq& operator=(const buffer_fp64_lstsq&) = delete;
+
+	void allocate(const std::size_t m, const std::size_t n, const std::size_t nrhs) {
+		if (dwq != nullptr || dwr != nullptr) {
+			throw std::runtime_error("The buffer has been already allocated");
+		}
+		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs);
+		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_lstsq(m, n, nrhs);
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
+		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
+		total_memory_size = wq_size + wr_size;
+	}
+
+	void destroy() {
+		if (dwq) (void)hipFree(dwq);
+		dwq = nullptr;
+		if (dwr) (void)hipFree(dwr);
+		dwr = nullptr;
+	}
+
+	std::size_t get_device_memory_size() const { return total_memory_size; }
+};
+
+template <bool Reorthogonalize>
+inline state_t lstsq_fp64(
+		double* const x_ptr, const std::size_t ldx,
+		double* const r_ptr, const std::size_t ldr,
+		const double* const a_ptr, const std::size_t lda,
+		const double* const b_ptr, const std::size_t ldb,
+		const std::size_t m, const std::size_t n, const std::size_t nrhs,
+		buffer_fp64_lstsq<Reorthogonalize>& bf,
+		const int refine = 1,
+		handle_t const stream = nullptr) {
+	const int st = tsqr_mi_lstsq_f64(Reorthogonalize ? 1 : 0, refine, x_ptr, ldx, r_ptr, ldr, a_ptr, lda, b_ptr, ldb, m, n, nrhs,
+	                                 bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::lstsq_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
 // Not in the reference: double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide, include/tsqr_mi.h for the
 // contract): qr_fp64 itself for n <= 64, whole-matrix CholeskyQR sweeps with the same ladder beyond.  Returns success_factorization,
 // error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.

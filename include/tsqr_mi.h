@@ -354,6 +354,37 @@ int tsqr_mi_r_f64(int reorth, double* r, size_t ldr, const double* a, size_t lda
                   size_t m, size_t n, void* wq, void* wr, void* stream);
 
 /*
+ * Least squares in double precision on the R-only factorisation (not in the reference): X = argmin ||A X - B||_F and R of tsqr_mi_r_f64.
+ * x (n x nrhs, ldx), r (n x n, ldr), a (m x n, lda), b (m x nrhs, ldb) hold doubles, column-major, device memory; 1 <= n <= 64, n <= m,
+ * 1 <= nrhs <= 16, 0 <= refine <= 4.  Blocking.  A and B are never written; x and r must not overlap A, B or each other.  Nothing of
+ * size m is stored: wq of tsqr_mi_working_q_size_f64_lstsq doubles (independent of m), wr of tsqr_mi_working_r_size_f64_lstsq doubles.
+ * Bitwise deterministic (the launch plan is a fixed function of (m, n); fixed reduction tree).
+ * Method -- corrected semi-normal equations carried out in Q-space: the ladder of tsqr_mi_r_f64 (reorth as there; R is bitwise that
+ * entry's), Z = inverse(R) as the product of the sweeps' inverses, then refine + 1 passes that each read A and B once:
+ *   X_0 = Z (Q~^T B),   X <- X + Z (Q~^T (B - A X)),   Q~ = A Z formed 16 rows at a time in registers, never stored
+ * (lsq_f64_kernel).  The ladder waits on the host as tsqr_mi_r_f64 does; the passes behind it are enqueued back to
+ * back with one wait at the end.
+ * Accuracy: each correction pass contracts the error of X by a factor of order cond(A)^2 u, so the method is NOT a substitute for
+ * Householder QR beyond cond(A) of about 1e7.  Claimed for cond(A) <= 1e6 and refine >= 1: ||X - X*||_F / ||X*||_F within a small
+ * factor of LAPACK's fp64 least-squares solve on the same data (DESIGN.md section 9 and profiles/fp64_lstsq_accuracy.md have the
+ * measured factors: at most 0.69 over Gaussian and cond 1 .. 1e6 matrices).  For larger cond(A) the call still returns 0 while the
+ * ladder accepts A; what follows is measured (4096 x 64, 16 right-hand sides, B = A X*, error of refine = 0 / 1 / 2, LAPACK's), not a bound:
+ *   cond 1e7: 7.4e-5 / 1.6e-11 / 1.3e-11, 2.7e-11;  cond 1e8: 8.3e-3 / 1.3e-10 / 1.2e-10, 1.9e-10;  cond 1e10: 1e2 / 8.0e-7 / 8.7e-9, 1.6e-8
+ * -- at 1e10 X_0 has no correct digit and refine = 1 is 50 times worse than LAPACK.  refine = 0 returns X_0, whose error grows like
+ * cond(A)^2 u when the residual is small.
+ * Non-finite B: B enters the residual through a matrix product with an identity operand, so ONE Inf or NaN in row i of B makes row i of
+ * the residual non-finite for all right-hand sides, hence every column of X; the call returns 0.  Non-finite A is the ladder's state 3.
+ * Returns 0; 1 (m, n or nrhs == 0, n > m, lda < m, ldb < m, ldr < n or ldx < n); 2 (n > 64, nrhs > 16, refine outside 0 .. 4;
+ * tsqr_mi_last_error says which); 3 = TSQR_MI_ERROR_NOT_FINITE from the ladder (rank-deficient or non-finite A; x is undefined); or
+ * -(hipError_t).  Sizes are checked before any HIP call.  tsqr_mi_last_sweeps_f64 reports this entry's ladder too.
+ */
+size_t tsqr_mi_working_q_size_f64_lstsq(size_t m, size_t n, size_t nrhs);
+size_t tsqr_mi_working_r_size_f64_lstsq(size_t m, size_t n, size_t nrhs);
+int tsqr_mi_lstsq_f64(int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr,
+                      const double* a, size_t lda, const double* b, size_t ldb,
+                      size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
+
+/*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
  * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
  * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column

@@ -8,9 +8,13 @@ moves nothing between GPUs; this says nothing about several ranks.)
 --r-only: instead, the R-only entry (tsqr_mi_r_f64) next to tsqr_mi_qr_f64 on the same operands in this process, at 2^20, 2^16 and
 2^23 rows x 64: Gaussian with reorth = 0 and 1, and cond 1e12.  Per case the median of --calls blocking calls of each entry, the sweep
 counts, the ratio r_only / full and whether the one-sweep R is bitwise the full call's.  Writes nothing itself: redirect the JSON line
-(profiles/fp64_r_speed.json)."""
+(profiles/fp64_r_speed.json).
+--lstsq: instead, the least-squares entry (tsqr_mi_lstsq_f64, reorth = 0) with refine 0 and 1, tsqr_mi_r_f64 alone and
+torch.linalg.lstsq(float64) on the same Gaussian operands in this process, at 2^16, 2^20 and 2^23 rows x 64 with 1 and 16 right-hand
+sides: the median of --calls blocking calls each (torch at 2^23 rows: of five).  Redirect the JSON line (profiles/fp64_lstsq_speed.json)."""
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -112,6 +116,81 @@ def r_only(torch, bq, calls, warmup):
     print(json.dumps(out))
 
 
+def lstsq(torch, bq, calls, warmup):
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    n = 64
+    out = {"tool": "f64_speed --lstsq", "calls": calls, "warmup": warmup, "cases": []}
+
+    def timed(call):
+        for _ in range(warmup):
+            assert call() == 0, bq.last_error()
+        ts = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            st = call()                                     # (blocking: returns when the stream has drained)
+            ts.append(time.perf_counter() - t0)
+            assert st == 0
+        ts.sort()
+        return ts[len(ts) // 2] * 1e3, ts[0] * 1e3
+
+    for lg in (16, 20, 23):
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg)
+        a = torch.randn(n, m, dtype=torch.float64, device="cuda", generator=g)      # (n, m): column-major m x n
+        r = torch.empty(n, n, dtype=torch.float64, device="cuda")
+        bfr = bq.buffer_f64_r(False)
+        bfr.allocate(m, n)
+        ronly = timed(lambda: bq.r_f64(r, n, a, m, m, n, bfr))
+        r_sweeps = bq.last_sweeps_f64()
+        for nrhs in (1, 16):
+            b = torch.randn(nrhs, m, dtype=torch.float64, device="cuda", generator=g)
+            x = torch.empty(nrhs, n, dtype=torch.float64, device="cuda")
+            wq = torch.empty(L.tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device="cuda")
+            wr = torch.empty(L.tsqr_mi_working_r_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device="cuda")
+            st = torch.cuda.current_stream().cuda_stream
+            case = {"m": m, "n": n, "nrhs": nrhs, "r_only_median_ms": ronly[0], "r_only_min_ms": ronly[1], "r_only_sweeps": r_sweeps,
+                    "work_bytes": 8 * (wq.numel() + wr.numel())}
+            for refine in (0, 1):
+                t = timed(lambda: L.tsqr_mi_lstsq_f64(0, refine, vp(x.data_ptr()), n, vp(r.data_ptr()), n, vp(a.data_ptr()), m,
+                                                      vp(b.data_ptr()), m, m, n, nrhs, vp(wq.data_ptr()), vp(wr.data_ptr()), vp(st)))
+                case["lstsq_refine%d_median_ms" % refine], case["lstsq_refine%d_min_ms" % refine] = t
+                case["lstsq_sweeps"] = bq.last_sweeps_f64()
+            case["ms_per_pass"] = case["lstsq_refine1_median_ms"] - case["lstsq_refine0_median_ms"]
+            am, bm = a.T, b.T                               # torch's driver on the same operands (it copies what it overwrites)
+
+            def torch_call():
+                torch.linalg.lstsq(am, bm)
+                torch.cuda.synchronize()
+                return 0
+            tt = timed(torch_call) if lg < 23 else (None, None)
+            if lg == 23:                                    # (five calls: the library's solve takes long at this size)
+                torch_call()
+                ts = []
+                for _ in range(5):
+                    t0 = time.perf_counter()
+                    torch_call()
+                    ts.append(time.perf_counter() - t0)
+                ts.sort()
+                tt = (ts[2] * 1e3, ts[0] * 1e3)
+            case["torch_lstsq_median_ms"], case["torch_lstsq_min_ms"] = tt
+            xt = torch.linalg.lstsq(am, bm).solution
+            # ||A^T (B - A X)||_F / (||A||_F ||B||_F) in fp64 on the GPU, for the entry's X (refine = 1) and for torch's
+            nres = lambda xs: (torch.linalg.norm(am.T @ (bm - am @ xs)) / (torch.linalg.norm(am) * torch.linalg.norm(bm))).item()
+            case["normal_residual_lstsq"], case["normal_residual_torch"] = nres(x.T), nres(xt)
+            case["rel_diff_to_torch"] = (torch.linalg.norm(x.T - xt) / torch.linalg.norm(xt)).item()
+            case["norm_x_lstsq"], case["norm_x_torch"] = torch.linalg.norm(x).item(), torch.linalg.norm(xt).item()
+            for k, v in case.items():                       # (torch's solution at 2^23 rows came back non-finite: null in the JSON line)
+                if isinstance(v, float) and not math.isfinite(v):
+                    case[k] = None
+            out["cases"].append(case)
+            del b, x, wq, wr, xt
+        del a, r, bfr
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def dist1(torch, bq, calls, warmup):
     import ctypes
     rccl = ctypes.CDLL("librccl.so")
@@ -166,6 +245,7 @@ def main():
     ap.add_argument("--cases", default="", help="comma-separated case names (default: all)")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch.linalg.qr baseline")
     ap.add_argument("--r-only", action="store_true", help="time tsqr_mi_r_f64 next to tsqr_mi_qr_f64 on the same operands")
+    ap.add_argument("--lstsq", action="store_true", help="time tsqr_mi_lstsq_f64 next to tsqr_mi_r_f64 and torch.linalg.lstsq")
     ap.add_argument("--dist1", action="store_true", help="time the one-rank row-partitioned call over raw RCCL next to the plain entry")
     args = ap.parse_args()
     import torch
@@ -174,6 +254,8 @@ def main():
         return dist1(torch, bq, args.calls, args.warmup)
     if args.r_only:
         return r_only(torch, bq, args.calls, args.warmup)
+    if args.lstsq:
+        return lstsq(torch, bq, args.calls, args.warmup)
     n = 64
     out = {"tool": "f64_speed", "cases": []}
     gauss = lambda m, seed: torch.randn(m, n, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(seed))

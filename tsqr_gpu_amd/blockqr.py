@@ -55,6 +55,7 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_qr_f64_wide", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide",
     "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
     "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
+    "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
 ]
 
 
@@ -202,6 +203,12 @@ def lib():
             getattr(L, name).argtypes = [sz, sz]
         L.tsqr_mi_r_f64.restype = ci
         L.tsqr_mi_r_f64.argtypes = [ci, vp, sz, vp, sz, sz, sz, vp, vp, vp]
+    if hasattr(L, "tsqr_mi_lstsq_f64"):                  # (as above: an older build has no least-squares entry)
+        for name in ("tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq"):
+            getattr(L, name).restype = sz
+            getattr(L, name).argtypes = [sz, sz, sz]
+        L.tsqr_mi_lstsq_f64.restype = ci
+        L.tsqr_mi_lstsq_f64.argtypes = [ci, ci, vp, sz, vp, sz, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -592,6 +599,70 @@ def r_f64(r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
     return st
 
 
+class LstsqError(RuntimeError):
+    """lstsq_f64 ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
+
+    def __init__(self, state, text):
+        RuntimeError.__init__(self, text)
+        self.state = state
+
+
+def _colmajor_f64(t):
+    """(tensor whose storage holds t column-major, its leading dimension): t itself when its columns are already contiguous (stride 1
+    down a column, at least the row count between columns), a column-major copy otherwise -- the operand of the call is never written"""
+    rows, cols = t.shape
+    if t.stride(0) == 1 and (cols == 1 or t.stride(1) >= max(rows, 1)):
+        return t, (t.stride(1) if cols > 1 else max(rows, 1))
+    return t.t().contiguous().t(), max(rows, 1)
+
+
+def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
+    """X = argmin ||a X - b||_F in double precision (tsqr_mi_lstsq_f64: include/tsqr_mi.h has the method and the accuracy statement;
+    claimed for cond(a) <= 1e6, not a substitute for Householder QR beyond cond(a) of about 1e7).  a: m x n float64 GPU tensor,
+    1 <= n <= 64, n <= m; b: m x nrhs (or m) float64 GPU tensor, nrhs <= 16; any strides -- an operand whose columns are contiguous is
+    used where it lies, any other is copied once; neither is written.  reorth: the R-only ladder's argument (r_f64); refine: correction
+    passes, 0 .. 4.  Blocking.  Returns (x, r): x n x nrhs (n when b is one-dimensional), r the n x n upper-triangular factor, bitwise
+    r_f64's on the same a.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for shapes that do not fit together, LstsqError
+    (.state) when the C entry returns a state other than 0: sizes it does not support, or error_not_finite from the ladder (Inf or NaN
+    in a, or a rank-deficient a).  last_sweeps_f64() tells how many sweeps the ladder took."""
+    import torch
+    for opname, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError("lstsq_f64: %s must be a float64 tensor, got %s" % (opname, getattr(t, "dtype", type(t).__name__)))
+    for opname, t in (("a", a), ("b", b)):
+        if not t.is_cuda:
+            raise TypeError("lstsq_f64: %s is not a GPU tensor" % opname)
+    if a.dim() != 2 or b.dim() not in (1, 2) or b.shape[0] != a.shape[0]:
+        raise ValueError("lstsq_f64: a must be m x n and b m x nrhs (or m), got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    vector = b.dim() == 1
+    b2 = b.unsqueeze(1) if vector else b
+    m, n = a.shape
+    nrhs = b2.shape[1]
+    L = lib()
+    z = ctypes.c_void_p(0)
+    if m == 0 or n == 0 or nrhs == 0 or n > m or n > 64 or nrhs > 16 or not 0 <= int(refine) <= 4:
+        st = L.tsqr_mi_lstsq_f64(int(bool(reorth)), int(refine), z, max(n, 1), z, max(n, 1), z, max(m, 1), z, max(m, 1), m, n, nrhs, z, z, z)
+        raise LstsqError(st, "lstsq_f64: state %d for a %d x %d, nrhs %d, refine %d%s"
+                         % (st, m, n, nrhs, int(refine), (": " + last_error()) if st == error_unsupported_mode else ""))
+    ac, lda = _colmajor_f64(a)
+    bc, ldb = _colmajor_f64(b2)
+    x = torch.empty((nrhs, n), dtype=torch.float64, device=a.device)
+    r = torch.empty((n, n), dtype=torch.float64, device=a.device)
+    wq = torch.empty(L.tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device=a.device)
+    wr = torch.empty(L.tsqr_mi_working_r_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        st = L.tsqr_mi_lstsq_f64(int(bool(reorth)), int(refine), x.data_ptr(), n, r.data_ptr(), n, ac.data_ptr(), lda, bc.data_ptr(), ldb,
+                                 m, n, nrhs, wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("tsqr_mi_lstsq_f64 failed: %s" % last_error())
+    if st:
+        raise LstsqError(st, "lstsq_f64: state %d: %s" % (st, last_error()))
+    x = x.t()
+    return (x[:, 0] if vector else x), r.t()
+
+
 def get_working_q_size_f64_dist(m_local, n, nranks):
     """Doubles of wq for tsqr_mi_qr_f64_dist* (dist.RowPartitionedQRF64 allocates them itself)."""
     return lib().tsqr_mi_working_q_size_f64_dist(m_local, n, nranks)
@@ -603,7 +674,7 @@ def get_working_r_size_f64_dist(m_local, n, nranks):
 
 
 def last_sweeps_f64():
-    """Sweeps of this thread's last qr_f64 / qr_f64_wide / r_f64 / row-partitioned fp64 call, plus 100 when it took the shifted path."""
+    """Sweeps of this thread's last qr_f64 / qr_f64_wide / r_f64 / lstsq_f64 / row-partitioned fp64 call, plus 100 when it took the shifted path."""
     return lib().tsqr_mi_last_sweeps_f64()
 
 

@@ -89,6 +89,20 @@ inline void f64r_gramq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::G
 	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gramq_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
 }
 
+// ---- tsqr_mi_lstsq_f64 (n <= 64, nrhs <= 16) -------------------------------------------------------------------------------------------
+// The ladder is the R-only entry's; every pass behind it runs lsq_f64_kernel on f64r_plan's grid, tiles and waves -- a fixed function of
+// (m, n), the same for every nrhs -- so the reduction tree and the bits of X are the same everywhere.  A partial is NT tiles of 256 doubles,
+// never more than the ntri tiles of a Gram partial: wr is the R-only entry's.
+constexpr size_t F64L_MAX_NRHS = 16;
+constexpr int F64L_MAX_REFINE = 4;
+// wq (doubles): [the F64R_WQ layout][X, NP x 16 (ld NP): 1024][summed D: 4 tiles of 256 + the row-count word of the reduction]
+constexpr size_t F64L_X = F64R_WQ, F64L_D = F64L_X + 1024, F64L_WQ = F64L_D + 1024 + 8;
+
+// one pass of the least-squares entry on stream st: lsq_f64_kernel<NT> on the R-only plan's grid
+inline void f64r_lsq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::LsqArgs64& la) {
+	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::lsq_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, la); });
+}
+
 // ---- tsqr_mi_qr_f64_wide (64 < n <= 1024) ----------------------------------------------------------------------------------------------
 constexpr size_t F64W_MAX_N = 1024;
 constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m

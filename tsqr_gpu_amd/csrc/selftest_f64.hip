@@ -152,6 +152,29 @@ int tsqr_selftest_f64_zmul(double* z, const double* zk, int n) {
 	return f64_sync();
 }
 
+// ---- n <= 64, least squares (tsqr_mi_lstsq_f64) ---------------------------------------------------------------------------------------------
+// lsq_f64_kernel + reduction, one pass: dsum[NT * 256 + 1] = the tiles of (a z)^T (b - a x) and the row count behind them; z: NP x NP
+// (ld NP), x: NP x 16 (ld NP) or null = zero.  nwaves > 0 overrides the plan's wave count; part holds part_cap doubles.
+int tsqr_selftest_f64_lsq(double* dsum, const double* a, size_t lda, const double* b, size_t ldb, size_t m, int n, int nrhs,
+                          const double* z, const double* x, double* part, size_t part_cap, int nwaves) {
+	if (m == 0 || n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || lda < m || ldb < m) return -100;
+	F64RPlan g = f64r_plan(m, (size_t)n);
+	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
+	if (g.nblocks <= 0 || (size_t)g.nblocks * g.NT * 256 > part_cap) return -100;
+	const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, n, nrhs, g.ntiles, g.nwaves, z, x, part};
+	f64r_lsq_launch(0, g, la);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, dsum, part, g.nblocks, g.NT * 256, (double)m);
+	return f64_sync();
+}
+
+// lsq_update_f64_kernel: xw (NP x 16, ld NP) <- xw + z d (first: xw taken as zero), and x (n x nrhs, ldx) too when last
+int tsqr_selftest_f64_lsq_update(double* xw, double* x, size_t ldx, const double* z, const double* d, int n, int nrhs, int first, int last) {
+	if (n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || ldx < (size_t)n) return -100;
+	hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel, dim3(1), dim3(1024), 0, 0, xw, x, ldx, z, d, n, (int)np_of((size_t)n), nrhs, first, last);
+	return f64_sync();
+}
+
 // ---- 64 < n <= 1024 ---------------------------------------------------------------------------------------------------------------------
 // Gram pass + reduction: gs[bs + 1] in the block store's layout.  cps > 0 overrides the chunks per slice; part holds part_cap doubles.
 int tsqr_selftest_f64w_gram(double* gs, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, size_t cps) {

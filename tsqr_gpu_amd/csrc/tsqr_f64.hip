@@ -9,6 +9,9 @@
 // and of the R-only entry (tsqr_mi_r_f64), whose sweeps after the first stream A and never store Q:
 //   gramq_f64_kernel  : per-workgroup partials of (A Z)^T (A Z), each 16-row block of A Z formed and consumed in registers
 //   zmul_f64_kernel   : Z <- Z Zk, the inverse of all sweeps so far, in place
+// and of the least-squares entry (tsqr_mi_lstsq_f64), whose passes behind that ladder stream A and B and store nothing of size m:
+//   lsq_f64_kernel        : per-workgroup partials of (A Z)^T (B - A X), each 16-row block of A Z and of the residual held in registers
+//   lsq_update_f64_kernel : X <- X + Z D on one workgroup
 #include <hip/hip_runtime.h>
 
 namespace tsqrmi {
@@ -304,6 +307,120 @@ __global__ __launch_bounds__(1024) void zmul_f64_kernel(double* z, const double*
 		const int i = 16 * ti + lq + 4 * reg, j = 16 * tj + li;
 		if (i < NP && j < NP) z[(size_t)j * NP + i] = (i <= j) ? c[reg] : 0.0;
 	}
+}
+
+// ---- the least-squares entry (tsqr_mi_lstsq_f64): passes over A and B behind the R-only ladder ----------------------------------------
+struct LsqArgs64 {
+	const double* a; size_t lda;
+	const double* b; size_t ldb;         // m x nrhs right-hand sides
+	size_t m; int n; int nrhs;
+	int ntiles; int nwaves;              // 16-row tiles of A and B; waves that take tiles (wave w: tiles w, w + nwaves, ...)
+	const double* z;                     // NP x NP (ld NP) upper triangular, zero padded: the inverse of R
+	const double* x;                     // n x 16 (ld NP) current solution; may be null = zero
+	double* part;                        // [gridDim.x][NT][256]: tile ti of a partial holds rows 16 ti .. 16 ti + 15 of D
+};
+
+// Per-workgroup partials of D = (A Z)^T (B - A X), NP x 16, without storing A Z or the residual.  The tile loop, the loads of av, the
+// prefetch and zop are gramq_f64_kernel's.  Per 16-row tile:
+//   1  qt[jt] = A_tile Z, gramq_f64_kernel's first stage: register reg of lane (li, lq) holds Q~[row0 + lq + 4 reg][16 jt + li].
+//   2  rt = B_tile - A_tile X in the same C/D layout: register reg of lane (li, lq) holds the residual of row row0 + lq + 4 reg and
+//      right-hand side li.  B enters through four k-blocks against an identity operand built on the fly (lane (li, lq) of k-block kb holds
+//      [4 kb + lq == li]): B is then loaded exactly like A -- lane (li, lq) holds B[row0 + li][4 kb + lq], whole 128-byte column segments,
+//      the same bounds logic, prefetched with the next tile of A -- where the C/D layout itself would take four loads of sixteen 32-byte
+//      pieces each.  The price is 4 MFMAs of 76 at NT = 4, and that 0 * B[row][j] enters every right-hand side of that row: ONE non-finite
+//      entry of B makes row `row` of the residual non-finite for ALL right-hand sides, hence every column of X (include/tsqr_mi.h says
+//      so).  For finite B the four k-blocks give B exactly (b * 1 + zeros).  Then 4 NT k-blocks of av against xop, lane (li, lq) of
+//      k-block kb holding -X[4 kb + lq][li] (x null: -0).
+//   3  acc[ti] += qt[ti][reg]^T rt[reg] for reg 0 .. 3: the Gram MFMA of gramq_f64_kernel with rt as its second operand -- both come from
+//      the same lane and register, so they name the same row.  Register reg of lane (li, lq) of acc[ti] holds D[16 ti + lq + 4 reg][li].
+// Rows >= m, columns >= n and right-hand sides >= nrhs enter as zeros.  A partial is NT tiles of 256 doubles (wg_sum4_store).
+template <int NT>
+__global__ __launch_bounds__(256) void lsq_f64_kernel(const LsqArgs64 a) {
+	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1);
+	__shared__ double red[2 * NT * 256];
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
+	const int gw = blockIdx.x * 4 + wv;
+	f64x4 acc[NT];
+#pragma unroll
+	for (int t = 0; t < NT; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+	if (gw < a.nwaves) {
+		double zop[NZ], xop[KB], idop[4];
+		static_for<0, NT>([&](auto jt_) {
+			constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+#pragma unroll
+			for (int kb = 0; kb < 4 * (jt + 1); kb++) zop[base + kb] = a.z[(size_t)(16 * jt + li) * NP + 4 * kb + lq];
+		});
+#pragma unroll
+		for (int kb = 0; kb < KB; kb++) {
+			const int row = 4 * kb + lq;
+			xop[kb] = -((a.x && row < a.n && li < a.nrhs) ? a.x[(size_t)li * NP + row] : 0.0);
+		}
+#pragma unroll
+		for (int kb = 0; kb < 4; kb++) idop[kb] = (4 * kb + lq == li) ? 1.0 : 0.0;
+		// a tile beyond the last reads nothing and leaves zeros (gramq_f64_kernel's load_tile, and the same for the tile of B)
+		auto load_tile = [&](double (&av)[KB], double (&bv)[4], int tile) {
+			const size_t row = (size_t)tile * 16 + li;
+			const bool live = tile < a.ntiles && row < a.m;
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) {
+				const int col = 4 * kb + lq;
+				av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+			}
+#pragma unroll
+			for (int kb = 0; kb < 4; kb++) {
+				const int col = 4 * kb + lq;
+				bv[kb] = (live && col < a.nrhs) ? a.b[(size_t)col * a.ldb + row] : 0.0;
+			}
+		};
+		double av[KB], nx[KB], bv[4], nb[4];
+		load_tile(av, bv, gw);
+		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
+			load_tile(nx, nb, tile + a.nwaves);
+			f64x4 qt[NT];
+			static_for<0, NT>([&](auto jt_) {
+				constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+				for (int kb = 0; kb < 4 * (jt + 1); kb++)
+					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zop[base + kb], qt[jt], 0, 0, 0);
+			});
+			f64x4 rt = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+			for (int kb = 0; kb < 4; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[kb], idop[kb], rt, 0, 0, 0);
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], xop[kb], rt, 0, 0, 0);
+#pragma unroll
+			for (int reg = 0; reg < 4; reg++)
+#pragma unroll
+				for (int ti = 0; ti < NT; ti++)
+					acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], rt[reg], acc[ti], 0, 0, 0);
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
+#pragma unroll
+			for (int kb = 0; kb < 4; kb++) bv[kb] = nb[kb];
+		}
+	}
+	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NT * 256, wv, lane);
+}
+
+// X <- X + Z D on one workgroup (n <= 64 rows by 16 right-hand sides: not on the hot path, plain fp64).  xw: the work copy, NP x 16
+// (ld NP), wholly written -- zeros in rows >= n and right-hand sides >= nrhs; first: X is taken as zero and xw is not read.  d: the summed
+// partials of lsq_f64_kernel, D[k][j] at ((k >> 4) * 4 + ((k & 15) >> 2)) * 64 + (k & 3) * 16 + j.  Z upper triangular: row i sums
+// k = i .. n - 1, in that order, one fused multiply-add each, so the bits do not depend on how the compiler contracts.  last: the result
+// also goes to the caller's x (n x nrhs, ldx).  Thread (i, j) reads and writes no entry of X but its own.
+__global__ __launch_bounds__(1024) void lsq_update_f64_kernel(double* xw, double* x, size_t ldx, const double* __restrict__ z,
+                                                              const double* __restrict__ d, int n, int NP, int nrhs, int first, int last) {
+	const int i = threadIdx.x & 63, j = threadIdx.x >> 6;
+	if (i >= NP) return;
+	double v = 0.0;
+	if (i < n && j < nrhs) {
+		double s = 0.0;
+		for (int k = i; k < n; k++)
+			s = __builtin_fma(z[(size_t)k * NP + i], d[((k >> 4) * 4 + ((k & 15) >> 2)) * 64 + (k & 3) * 16 + j], s);
+		v = (first ? 0.0 : xw[(size_t)j * NP + i]) + s;
+		if (last) x[(size_t)j * ldx + i] = v;
+	}
+	xw[(size_t)j * NP + i] = v;
 }
 
 }  // namespace tsqrmi

@@ -2586,9 +2586,55 @@ int r_f64_core(int reorth, double* r, size_t ldr, const double* a, size_t lda, s
 	return f64_ladder(reorth, st, [&](int k) { return f64r_sweep(st, k, r, ldr, a, lda, m, n, wq, wr); });
 }
 
+// The least-squares entry behind the R-only ladder (corrected semi-normal equations carried out in Q-space; include/tsqr_mi.h).  The
+// ladder's last sweep s left Z_1 ... Z_(s-1) in wq[F64R_ZACC] (nothing for s = 1) and Z_s in wq[F64_Z]: one copy or one zmul_f64_kernel
+// completes Z = inverse(R).  Then refine + 1 passes, each lsq_f64_kernel (D = (A Z)^T (B - A X), X null the first time), the reduction
+// and X <- X + Z D, enqueued back to back; one wait at the end.
+int lstsq_f64_core(int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
+                   const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, double* wq, double* wr, hipStream_t st) {
+	if (const int rc = r_f64_core(reorth, r, ldr, a, lda, m, n, wq, wr, st)) return rc;
+	const size_t NP = np_of(n);
+	double *zacc = wq + F64R_ZACC, *xw = wq + F64L_X, *dsum = wq + F64L_D;
+	if (t_sweeps64 % 100 == 1) HIPCHK(hipMemcpyAsync(zacc, wq + F64_Z, NP * NP * sizeof(double), hipMemcpyDeviceToDevice, st));
+	else hipLaunchKernelGGL(tsqrmi::zmul_f64_kernel, dim3(1), dim3(1024), 0, st, zacc, (const double*)(wq + F64_Z), (int)n, (int)NP);
+	HIPCHK(hipGetLastError());
+	const F64RPlan g = f64r_plan(m, n);
+	if (g.nblocks <= 0) { t_last_error = "fp64 least-squares pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	for (int p = 0; p <= refine; p++) {
+		const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, (int)n, (int)nrhs, g.ntiles, g.nwaves, zacc, p == 0 ? nullptr : xw, wr};
+		f64r_lsq_launch(st, g, la);
+		HIPCHK(hipGetLastError());
+		launch_reduce1(st, dsum, wr, g.nblocks, g.NT * 256, (double)m);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel, dim3(1), dim3(1024), 0, st, xw, x, ldx, (const double*)zacc, (const double*)dsum,
+		                   (int)n, (int)NP, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	return TSQR_MI_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t tsqr_mi_working_q_size_f64_lstsq(size_t m, size_t n, size_t nrhs) { return (m == 0 || n == 0 || nrhs == 0) ? 0 : F64L_WQ; }
+size_t tsqr_mi_working_r_size_f64_lstsq(size_t m, size_t n, size_t nrhs) {
+	return (m == 0 || n == 0 || nrhs == 0) ? 0 : f64r_wr_doubles(m, std::min(n, PW));
+}
+
+int tsqr_mi_lstsq_f64(int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
+                      const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream) {
+	t_sweeps64 = 0;
+	if (n > m || m == 0 || n == 0 || nrhs == 0 || lda < m || ldb < m || ldr < n || ldx < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > PW) { t_last_error = "tsqr_mi_lstsq_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (nrhs > F64L_MAX_NRHS) { t_last_error = "tsqr_mi_lstsq_f64 supports nrhs <= 16"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (refine < 0 || refine > F64L_MAX_REFINE) { t_last_error = "tsqr_mi_lstsq_f64 supports 0 <= refine <= 4"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	if (rc) return rc;
+	return lstsq_f64_core(reorth, refine, x, ldx, r, ldr, a, lda, b, ldb, m, n, nrhs, reinterpret_cast<double*>(wq),
+	                      reinterpret_cast<double*>(wr), reinterpret_cast<hipStream_t>(stream));
+}
 
 size_t tsqr_mi_working_q_size_f64_r(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : F64R_WQ; }
 size_t tsqr_mi_working_r_size_f64_r(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : f64r_wr_doubles(m, std::min(n, PW)); }
