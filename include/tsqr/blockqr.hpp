@@ -370,14 +370,21 @@ struct buffer_fp64_r {
 	std::size_t get_device_memory_size() const { return total_memory_size; }
 };
 
+// layout_t: how a (and, for lstsq_fp64, b) is stored.  row_major: element (i, j) at ptr[i * ld + j], ld >= the column count, read where it
+// lies (tsqr_mi_r_f64_lay / tsqr_mi_lstsq_f64_lay); r and x stay column-major and have the bits of the column-major call on the same matrix.
+using layout_t = int;
+const layout_t col_major = TSQR_MI_COL_MAJOR;
+const layout_t row_major = TSQR_MI_ROW_MAJOR;
+
 template <bool Reorthogonalize>
 inline state_t r_fp64(
 		double* const r_ptr, const std::size_t ldr,
 		const double* const a_ptr, const std::size_t lda,
 		const std::size_t m, const std::size_t n,
 		buffer_fp64_r<Reorthogonalize>& bf,
-		handle_t const stream = nullptr) {
-	const int st = tsqr_mi_r_f64(Reorthogonalize ? 1 : 0, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major) {
+	const int st = tsqr_mi_r_f64_lay(a_layout, Reorthogonalize ? 1 : 0, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::r_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
@@ -426,9 +433,10 @@ inline state_t lstsq_fp64(
 		const std::size_t m, const std::size_t n, const std::size_t nrhs,
 		buffer_fp64_lstsq<Reorthogonalize>& bf,
 		const int refine = 1,
-		handle_t const stream = nullptr) {
-	const int st = tsqr_mi_lstsq_f64(Reorthogonalize ? 1 : 0, refine, x_ptr, ldx, r_ptr, ldr, a_ptr, lda, b_ptr, ldb, m, n, nrhs,
-	                                 bf.dwq, bf.dwr, stream);
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major, const layout_t b_layout = col_major) {
+	const int st = tsqr_mi_lstsq_f64_lay(a_layout, b_layout, Reorthogonalize ? 1 : 0, refine, x_ptr, ldx, r_ptr, ldr, a_ptr, lda, b_ptr, ldb,
+	                                     m, n, nrhs, bf.dwq, bf.dwr, stream);
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::lstsq_fp64: ") + tsqr_mi_last_error());
 	return st;
 }

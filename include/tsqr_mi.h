@@ -385,6 +385,31 @@ int tsqr_mi_lstsq_f64(int reorth, int refine, double* x, size_t ldx, double* r, 
                       size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
 
 /*
+ * tsqr_mi_r_f64 and tsqr_mi_lstsq_f64 on operands that are read where they lie in either layout (not in the reference).  a_layout and
+ * b_layout are TSQR_MI_COL_MAJOR (element (i, j) at a[i + j * lda], lda >= m: the entries above) or TSQR_MI_ROW_MAJOR (element (i, j)
+ * at a[i * lda + j], lda >= n; for B b[i * ldb + j], ldb >= nrhs -- a contiguous C or torch array of shape (m, n)).  R and X are
+ * column-major as above; the work space is that of tsqr_mi_working_{q,r}_size_f64_r and ..._f64_lstsq.  No copy of A or B is made and
+ * nothing between n and lda (nrhs and ldb) or behind row m is read.
+ * Bit-for-bit relation: the row-major kernels put the values of A and B into the registers the column-major kernels hold them in, on the
+ * same launch plans, so R, X, the state and tsqr_mi_last_sweeps_f64 are BITWISE those of tsqr_mi_r_f64 / tsqr_mi_lstsq_f64 on a
+ * column-major copy of the same matrices.  With every layout TSQR_MI_COL_MAJOR the calls ARE those entries (which call these).  The
+ * accuracy statements, the ladder and the non-finite rules above hold unchanged.
+ * Measured on one MI355X (profiles/fp64_rowmajor_speed.json, median of 50 blocking calls, ms; row-major / column-major / a transposing
+ * copy of the operands followed by the column-major call): tsqr_mi_lstsq_f64_lay, refine 1, 16 right-hand sides, 2^20 x 64
+ * 0.748 / 0.700 / 2.31, 2^23 x 64 4.67 / 4.37 / 20.4; tsqr_mi_r_f64_lay 2^20 x 64 0.187 / 0.165 / 1.46 (one sweep), 0.475 / 0.466 / 1.75
+ * (reorth = 1).  The one-sweep call is 13 .. 23 % slower row-major (narrower loads in the first Gram pass); later sweeps are level.
+ * Returns what those entries return; 1 also for a layout other than 0 or 1, and for a row-major operand with lda < n or ldb < nrhs
+ * (not lda < m).  Arguments are checked before any HIP call.
+ */
+#define TSQR_MI_COL_MAJOR 0
+#define TSQR_MI_ROW_MAJOR 1
+int tsqr_mi_r_f64_lay(int a_layout, int reorth, double* r, size_t ldr, const double* a, size_t lda,
+                      size_t m, size_t n, void* wq, void* wr, void* stream);
+int tsqr_mi_lstsq_f64_lay(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr,
+                          const double* a, size_t lda, const double* b, size_t ldb,
+                          size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
+
+/*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
  * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
  * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column

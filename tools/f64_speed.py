@@ -11,7 +11,14 @@ counts, the ratio r_only / full and whether the one-sweep R is bitwise the full 
 (profiles/fp64_r_speed.json).
 --lstsq: instead, the least-squares entry (tsqr_mi_lstsq_f64, reorth = 0) with refine 0 and 1, tsqr_mi_r_f64 alone and
 torch.linalg.lstsq(float64) on the same Gaussian operands in this process, at 2^16, 2^20 and 2^23 rows x 64 with 1 and 16 right-hand
-sides: the median of --calls blocking calls each (torch at 2^23 rows: of five).  Redirect the JSON line (profiles/fp64_lstsq_speed.json)."""
+sides: the median of --calls blocking calls each (torch at 2^23 rows: of five).  Redirect the JSON line (profiles/fp64_lstsq_speed.json).
+--row-major: instead, the layout entries (tsqr_mi_r_f64_lay with reorth 0 and 1, tsqr_mi_lstsq_f64_lay with refine 1 and 16 right-hand
+sides) at 2^16, 2^20 and 2^23 rows x 64 and 2^20 x 16, Gaussian, three arms interleaved call by call in this process: (i) the layout
+entry on row-major operands, (ii) the column-major entry on operands transposed beforehand, (iii) the transposing copy of each operand
+(t().contiguous().t(), allocation included: what lstsq_f64 did to a contiguous tensor before the layout entries) followed by the
+column-major entry.  Arm (ii) runs three times per round: the max / min of its three medians is the spread a ratio has to be read
+against.  Per arm the median of --calls blocking calls; the ratios i / ii and i / iii; whether R and X of (i) are bitwise those of (ii).
+Redirect the JSON line (profiles/fp64_rowmajor_speed.json)."""
 import argparse
 import json
 import math
@@ -191,6 +198,72 @@ def lstsq(torch, bq, calls, warmup):
     print(json.dumps(out))
 
 
+def row_major(torch, bq, calls, warmup):
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    out = {"tool": "f64_speed --row-major", "calls": calls, "warmup": warmup, "cases": []}
+    for lg, n in ((16, 64), (20, 64), (23, 64), (20, 16)):
+        m, nrhs = 1 << lg, 16
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a_rm = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g)        # row-major m x n
+        b_rm = torch.randn(m, nrhs, dtype=torch.float64, device="cuda", generator=g)
+        a_cm, b_cm = a_rm.t().contiguous(), b_rm.t().contiguous()                          # (n, m): column-major m x n
+        x = [torch.empty(nrhs, n, dtype=torch.float64, device="cuda") for _ in range(2)]
+        r = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(2)]
+        wq = torch.empty(L.tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device="cuda")
+        wr = torch.empty(L.tsqr_mi_working_r_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device="cuda")
+        st = vp(torch.cuda.current_stream().cuda_stream)
+        work = (vp(wq.data_ptr()), vp(wr.data_ptr()), st)
+
+        def r_call(lay, a, lda, reorth, k):
+            return L.tsqr_mi_r_f64_lay(lay, reorth, vp(r[k].data_ptr()), n, vp(a.data_ptr()), lda, m, n, *work)
+
+        def l_call(lay, a, lda, b, ldb, k):
+            return L.tsqr_mi_lstsq_f64_lay(lay, lay, 0, 1, vp(x[k].data_ptr()), n, vp(r[k].data_ptr()), n, vp(a.data_ptr()), lda,
+                                           vp(b.data_ptr()), ldb, m, n, nrhs, *work)
+
+        def copy_then(call, with_b):
+            a_c = a_rm.t().contiguous()                     # (the copy is enqueued on the stream of the call behind it)
+            b_c = b_rm.t().contiguous() if with_b else None
+            return call(a_c, b_c)
+
+        kinds = [("r_f64_reorth0", lambda lay, a, lda, b, ldb, k: r_call(lay, a, lda, 0, k), False),
+                 ("r_f64_reorth1", lambda lay, a, lda, b, ldb, k: r_call(lay, a, lda, 1, k), False),
+                 ("lstsq_f64_refine1_nrhs16", l_call, True)]
+        for kind, call, with_b in kinds:
+            ii = lambda: call(0, a_cm, m, b_cm, m, 1)
+            arms = [("i_row_major", lambda: call(1, a_rm, n, b_rm, nrhs, 0)), ("ii_col_major", ii),
+                    ("iii_copy_then_col_major", lambda: copy_then(lambda ac, bc: call(0, ac, m, bc if with_b else b_cm, m, 1), with_b)),
+                    ("ii_col_major_again", ii), ("ii_col_major_third", ii)]
+            ts = {name: [] for name, _ in arms}
+            for i in range(warmup + calls):
+                for name, fn in arms:
+                    t0 = time.perf_counter()
+                    rc = fn()                               # (blocking: returns when the stream has drained)
+                    dt = time.perf_counter() - t0
+                    assert rc == 0, bq.last_error()
+                    if i >= warmup:
+                        ts[name].append(dt)
+            med = {k: sorted(v)[len(v) // 2] * 1e3 for k, v in ts.items()}
+            ii_meds = [med["ii_col_major"], med["ii_col_major_again"], med["ii_col_major_third"]]
+            arms[0][1]()
+            arms[1][1]()
+            case = {"m": m, "n": n, "call": kind, "sweeps": bq.last_sweeps_f64(),
+                    "i_row_major_median_ms": med["i_row_major"], "ii_col_major_median_ms": sorted(ii_meds)[1],
+                    "iii_copy_then_col_major_median_ms": med["iii_copy_then_col_major"],
+                    "ii_medians_ms": ii_meds, "ii_spread_max_over_min": max(ii_meds) / min(ii_meds),
+                    "ratio_i_over_ii": med["i_row_major"] / sorted(ii_meds)[1],
+                    "ratio_i_over_iii": med["i_row_major"] / med["iii_copy_then_col_major"],
+                    "i_not_slower_than_iii": bool(med["i_row_major"] <= med["iii_copy_then_col_major"]),
+                    "r_bitwise_equal": bool(torch.equal(r[0], r[1])),
+                    "x_bitwise_equal": bool(torch.equal(x[0], x[1])) if with_b else None}
+            out["cases"].append(case)
+        del a_rm, b_rm, a_cm, b_cm, x, r, wq, wr
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def dist1(torch, bq, calls, warmup):
     import ctypes
     rccl = ctypes.CDLL("librccl.so")
@@ -246,6 +319,7 @@ def main():
     ap.add_argument("--no-torch", action="store_true", help="skip the torch.linalg.qr baseline")
     ap.add_argument("--r-only", action="store_true", help="time tsqr_mi_r_f64 next to tsqr_mi_qr_f64 on the same operands")
     ap.add_argument("--lstsq", action="store_true", help="time tsqr_mi_lstsq_f64 next to tsqr_mi_r_f64 and torch.linalg.lstsq")
+    ap.add_argument("--row-major", action="store_true", help="time the layout entries on row-major operands next to the column-major entries")
     ap.add_argument("--dist1", action="store_true", help="time the one-rank row-partitioned call over raw RCCL next to the plain entry")
     args = ap.parse_args()
     import torch
@@ -256,6 +330,8 @@ def main():
         return r_only(torch, bq, args.calls, args.warmup)
     if args.lstsq:
         return lstsq(torch, bq, args.calls, args.warmup)
+    if args.row_major:
+        return row_major(torch, bq, args.calls, args.warmup)
     n = 64
     out = {"tool": "f64_speed", "cases": []}
     gauss = lambda m, seed: torch.randn(m, n, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(seed))

@@ -56,7 +56,10 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
     "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
     "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
+    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay",
 ]
+
+COL_MAJOR, ROW_MAJOR = 0, 1              # TSQR_MI_COL_MAJOR, TSQR_MI_ROW_MAJOR: the layout arguments of the *_lay entries
 
 
 class Ticket(ctypes.Structure):
@@ -209,6 +212,11 @@ def lib():
             getattr(L, name).argtypes = [sz, sz, sz]
         L.tsqr_mi_lstsq_f64.restype = ci
         L.tsqr_mi_lstsq_f64.argtypes = [ci, ci, vp, sz, vp, sz, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]
+    if hasattr(L, "tsqr_mi_r_f64_lay"):                  # (as above: an older build reads column-major operands only)
+        L.tsqr_mi_r_f64_lay.restype = ci
+        L.tsqr_mi_r_f64_lay.argtypes = [ci] + L.tsqr_mi_r_f64.argtypes
+        L.tsqr_mi_lstsq_f64_lay.restype = ci
+        L.tsqr_mi_lstsq_f64_lay.argtypes = [ci, ci] + L.tsqr_mi_lstsq_f64.argtypes
     _lib = L
     return L
 
@@ -560,16 +568,23 @@ class buffer_f64_r(buffer_f64):
     _entry = ("r_f64", 64, "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r")
 
 
-def check_f64_r_operands(m, n, ldr, lda, r, a):
-    """check_f64_operands' rules for the two operands of r_f64: ld >= rows, room for (n - 1) ld + rows doubles, r apart from a."""
-    span = _f64_spans("r_f64", n, (("r", r, ldr, n), ("a", a, lda, m)))
+def check_f64_r_operands(m, n, ldr, lda, r, a, row_major=False):
+    """check_f64_operands' rules for the two operands of r_f64: ld >= rows, room for (n - 1) ld + rows doubles, r apart from a.
+    row_major: a is row-major -- lda >= n and room for (m - 1) lda + n doubles, the span r has to stay clear of."""
+    if row_major:
+        span = _f64_spans("r_f64", n, (("r", r, ldr, n),))
+        span.update(_f64_spans("r_f64", m, (("a", a, lda, n),)))     # (the transposed view: m "columns" of n contiguous elements)
+    else:
+        span = _f64_spans("r_f64", n, (("r", r, ldr, n), ("a", a, lda, m)))
     if not _apart(span, "r", "a"):
         raise ValueError("r_f64: r overlaps a")
 
 
-def r_f64(r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
+def r_f64(r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False):
     """The R factor of qr_f64 alone, Q never formed (tsqr_mi_r_f64), 1 <= n <= 64, n <= m: r and a are float64 GPU tensors holding
-    column-major data (only data_ptr and numel are used); a is read only.  bf is a buffer_f64_r.  Blocking; returns the state: 0,
+    column-major data (only data_ptr and numel are used); a is read only.  row_major=True (tsqr_mi_r_f64_lay): a holds ROW-major data,
+    element (i, j) at i * lda + j with lda >= n -- a contiguous (m, n) tensor with lda = n -- read where it lies; r stays column-major and
+    has the bits of the column-major call on the same matrix.  bf is a buffer_f64_r.  Blocking; returns the state: 0,
     error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite.  Operands are checked before anything is launched:
     TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a leading dimension below the rows, or r overlapping a.
     last_sweeps_f64() tells how many sweeps the call took."""
@@ -584,16 +599,18 @@ def r_f64(r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
     if n > m or m == 0 or n == 0:
         return error_invalid_matrix_size
     L = lib()
+    layout = ROW_MAJOR if row_major else COL_MAJOR
     if n > 64:
-        return L.tsqr_mi_r_f64(int(reorth), None, ldr, None, lda, m, n, None, None, None)
-    check_f64_r_operands(m, n, ldr, lda, (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
+        return L.tsqr_mi_r_f64_lay(layout, int(reorth), None, ldr, None, lda, m, n, None, None, None)
+    check_f64_r_operands(m, n, ldr, lda, (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()), row_major=bool(row_major))
     if bf.dwq is None:
         raise RuntimeError("r_f64: the buffer is not allocated")
     if bf.dwq.numel() < L.tsqr_mi_working_q_size_f64_r(m, n) or bf.dwr.numel() < L.tsqr_mi_working_r_size_f64_r(m, n):
         raise ValueError("r_f64: the buffer was allocated for a smaller matrix")
     if stream is None:
         stream = torch.cuda.current_stream()
-    st = L.tsqr_mi_r_f64(int(reorth), r.data_ptr(), ldr, a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
+    st = L.tsqr_mi_r_f64_lay(layout, int(reorth), r.data_ptr(), ldr, a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr(),
+                             stream.cuda_stream)
     if st < 0:
         raise RuntimeError("tsqr_mi_r_f64 failed: %s" % last_error())
     return st
@@ -616,11 +633,26 @@ def _colmajor_f64(t):
     return t.t().contiguous().t(), max(rows, 1)
 
 
+def _operand_f64(t):
+    """(tensor, leading dimension, layout) under which lstsq_f64 hands the two-dimensional t to tsqr_mi_lstsq_f64_lay.  Used where it
+    lies: columns contiguous (_colmajor_f64's rule: COL_MAJOR), rows contiguous (stride(1) == 1 and stride(0) >= cols: ROW_MAJOR), or a
+    single column (any stride(0) >= 1: ROW_MAJOR with that stride).  Any other operand: _colmajor_f64's copy."""
+    rows, cols = t.shape
+    if t.stride(0) == 1 and (cols == 1 or t.stride(1) >= max(rows, 1)):
+        return _colmajor_f64(t) + (COL_MAJOR,)
+    if (t.stride(1) == 1 or cols == 1) and t.stride(0) >= max(cols, 1):
+        return t, t.stride(0), ROW_MAJOR
+    return _colmajor_f64(t) + (COL_MAJOR,)
+
+
 def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
     """X = argmin ||a X - b||_F in double precision (tsqr_mi_lstsq_f64: include/tsqr_mi.h has the method and the accuracy statement;
     claimed for cond(a) <= 1e6, not a substitute for Householder QR beyond cond(a) of about 1e7).  a: m x n float64 GPU tensor,
-    1 <= n <= 64, n <= m; b: m x nrhs (or m) float64 GPU tensor, nrhs <= 16; any strides -- an operand whose columns are contiguous is
-    used where it lies, any other is copied once; neither is written.  reorth: the R-only ladder's argument (r_f64); refine: correction
+    1 <= n <= 64, n <= m; b: m x nrhs (or m) float64 GPU tensor, nrhs <= 16; any strides; neither is written.  An operand is read where
+    it lies, without a copy, when its columns are contiguous (stride(0) == 1, stride(1) >= m), when its rows are contiguous
+    (stride(1) == 1, stride(0) >= its column count: every contiguous torch tensor), or when it has a single column; any other operand
+    (a[:, ::2], an expanded or overlapping view) is copied once into column-major storage.  The result has the same bits whichever way
+    the operand is stored.  reorth: the R-only ladder's argument (r_f64); refine: correction
     passes, 0 .. 4.  Blocking.  Returns (x, r): x n x nrhs (n when b is one-dimensional), r the n x n upper-triangular factor, bitwise
     r_f64's on the same a.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for shapes that do not fit together, LstsqError
     (.state) when the C entry returns a state other than 0: sizes it does not support, or error_not_finite from the ladder (Inf or NaN
@@ -644,8 +676,8 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
         st = L.tsqr_mi_lstsq_f64(int(bool(reorth)), int(refine), z, max(n, 1), z, max(n, 1), z, max(m, 1), z, max(m, 1), m, n, nrhs, z, z, z)
         raise LstsqError(st, "lstsq_f64: state %d for a %d x %d, nrhs %d, refine %d%s"
                          % (st, m, n, nrhs, int(refine), (": " + last_error()) if st == error_unsupported_mode else ""))
-    ac, lda = _colmajor_f64(a)
-    bc, ldb = _colmajor_f64(b2)
+    ac, lda, a_layout = _operand_f64(a)
+    bc, ldb, b_layout = _operand_f64(b2)
     x = torch.empty((nrhs, n), dtype=torch.float64, device=a.device)
     r = torch.empty((n, n), dtype=torch.float64, device=a.device)
     wq = torch.empty(L.tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device=a.device)
@@ -653,8 +685,8 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
     with torch.cuda.device(a.device):
         if stream is None:
             stream = torch.cuda.current_stream()
-        st = L.tsqr_mi_lstsq_f64(int(bool(reorth)), int(refine), x.data_ptr(), n, r.data_ptr(), n, ac.data_ptr(), lda, bc.data_ptr(), ldb,
-                                 m, n, nrhs, wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
+        st = L.tsqr_mi_lstsq_f64_lay(a_layout, b_layout, int(bool(reorth)), int(refine), x.data_ptr(), n, r.data_ptr(), n, ac.data_ptr(), lda,
+                                     bc.data_ptr(), ldb, m, n, nrhs, wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
     if st < 0:
         raise RuntimeError("tsqr_mi_lstsq_f64 failed: %s" % last_error())
     if st:

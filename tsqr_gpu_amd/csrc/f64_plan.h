@@ -103,6 +103,28 @@ inline void f64r_lsq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::Lsq
 	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::lsq_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, la); });
 }
 
+// ---- row-major operands (tsqr_mi_r_f64_lay, tsqr_mi_lstsq_f64_lay) -----------------------------------------------------------------------
+// The plans, grids and partials above; only the kernel differs.  Layout values: TSQR_MI_COL_MAJOR = 0, TSQR_MI_ROW_MAJOR = 1
+// (include/tsqr_mi.h); ga.lda / la.lda / la.ldb are row strides for a row-major operand.
+inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramArgs64& ga, int a_layout) {
+	if (!a_layout) return f64_gram_launch(st, g, ga);
+	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gram_f64_rm_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
+}
+inline void f64r_gramq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::GramQArgs64& ga, int a_layout) {
+	if (!a_layout) return f64r_gramq_launch(st, g, ga);
+	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gramq_f64_rm_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
+}
+inline void f64r_lsq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::LsqArgs64& la, int a_layout, int b_layout) {
+	if (!a_layout && !b_layout) return f64r_lsq_launch(st, g, la);
+	with_nt(g.NT, [&](auto nt) {
+		constexpr int NT = decltype(nt)::value;
+		auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(g.nblocks), dim3(256), 0, st, la); };
+		if (a_layout && b_layout) go(tsqrmi::lsq_f64_lay_kernel<NT, true, true>);
+		else if (a_layout) go(tsqrmi::lsq_f64_lay_kernel<NT, true, false>);
+		else go(tsqrmi::lsq_f64_lay_kernel<NT, false, true>);
+	});
+}
+
 // ---- tsqr_mi_qr_f64_wide (64 < n <= 1024) ----------------------------------------------------------------------------------------------
 constexpr size_t F64W_MAX_N = 1024;
 constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m

@@ -168,6 +168,53 @@ int tsqr_selftest_f64_lsq(double* dsum, const double* a, size_t lda, const doubl
 	return f64_sync();
 }
 
+// ---- n <= 64, row-major operands (tsqr_mi_r_f64_lay, tsqr_mi_lstsq_f64_lay) -------------------------------------------------------------
+// tsqr_selftest_f64_gram / _gramq / _lsq with a layout per operand (0 column-major: those very entries; 1 row-major, the leading dimension
+// is then the row stride: lda >= n, ldb >= nrhs), through the launchers the product uses (f64_plan.h).  The same nwaves override, so the
+// partials in `part` can be compared one by one with the column-major run's.
+int tsqr_selftest_f64_gram_lay(int a_layout, double* gsum, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, int nwaves) {
+	if (a_layout != 0 && a_layout != 1) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || lda < (a_layout ? (size_t)n : m)) return -100;
+	F64Plan g = f64_plan(m, (size_t)n);
+	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
+	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
+	const tsqrmi::GramArgs64 ga{a, lda, m, n, g.nch, g.nwaves, part};
+	f64_gram_launch(0, g, ga, a_layout);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
+	return f64_sync();
+}
+
+int tsqr_selftest_f64_gramq_lay(int a_layout, double* gsum, const double* a, size_t lda, size_t m, int n, const double* z, double* part,
+                                size_t part_cap, int nwaves) {
+	if (a_layout != 0 && a_layout != 1) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || lda < (a_layout ? (size_t)n : m)) return -100;
+	F64RPlan g = f64r_plan(m, (size_t)n);
+	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
+	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
+	const tsqrmi::GramQArgs64 ga{a, lda, m, n, g.ntiles, g.nwaves, z, part};
+	f64r_gramq_launch(0, g, ga, a_layout);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
+	return f64_sync();
+}
+
+int tsqr_selftest_f64_lsq_lay(int a_layout, int b_layout, double* dsum, const double* a, size_t lda, const double* b, size_t ldb, size_t m,
+                              int n, int nrhs, const double* z, const double* x, double* part, size_t part_cap, int nwaves) {
+	if ((a_layout != 0 && a_layout != 1) || (b_layout != 0 && b_layout != 1)) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || lda < (a_layout ? (size_t)n : m) ||
+	    ldb < (b_layout ? (size_t)nrhs : m))
+		return -100;
+	F64RPlan g = f64r_plan(m, (size_t)n);
+	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
+	if (g.nblocks <= 0 || (size_t)g.nblocks * g.NT * 256 > part_cap) return -100;
+	const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, n, nrhs, g.ntiles, g.nwaves, z, x, part};
+	f64r_lsq_launch(0, g, la, a_layout, b_layout);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, dsum, part, g.nblocks, g.NT * 256, (double)m);
+	return f64_sync();
+}
+
 // lsq_update_f64_kernel: xw (NP x 16, ld NP) <- xw + z d (first: xw taken as zero), and x (n x nrhs, ldx) too when last
 int tsqr_selftest_f64_lsq_update(double* xw, double* x, size_t ldx, const double* z, const double* d, int n, int nrhs, int first, int last) {
 	if (n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || ldx < (size_t)n) return -100;

@@ -28,6 +28,13 @@ __global__ __launch_bounds__(256) void gram_f64_kernel(const GramArgs64 a) {
 	__shared__ double red[2 * NTRI * 256];
 	gram_body<NT, double>(a, red);
 }
+// the same pass on a row-major A (a.lda: the row stride, >= n): load_chunk_f64_rm fills the registers load_chunk_f64 fills
+template <int NT>
+__global__ __launch_bounds__(256) void gram_f64_rm_kernel(const GramArgs64 a) {
+	constexpr int NTRI = (NT * (NT + 1)) / 2;
+	__shared__ double red[2 * NTRI * 256];
+	gram_body<NT, double, true>(a, red);
+}
 
 // The three numbers of the acceptance rule (stated at CholArgs64 below) for a sweep over `rows` x n (first: the first sweep of a call).
 // ONE definition for the host (f64_rule, f64_plan.h: a one-GPU call knows its rows) and for the device (a row-partitioned call: only
@@ -421,6 +428,153 @@ __global__ __launch_bounds__(1024) void lsq_update_f64_kernel(double* xw, double
 		if (last) x[(size_t)j * ldx + i] = v;
 	}
 	xw[(size_t)j * NP + i] = v;
+}
+
+// ---- row-major A and B (tsqr_mi_r_f64_lay, tsqr_mi_lstsq_f64_lay) ---------------------------------------------------------------------
+// Element (i, j) of a row-major operand lies at s[i * ld + j], ld >= the column count.  The kernels below are gramq_f64_kernel and
+// lsq_f64_kernel with another address for the same register: at every MFMA lane (li, lq) of k-block kb holds S[row0 + li][4 kb + lq], as
+// there, so every partial -- and behind the unchanged reduction R, X and the sweep count -- has the bits of the column-major kernel on
+// the transposed copy.  (Sweep 0: gram_f64_rm_kernel above.)
+
+// v[kb] = S[row][4 kb + lq] for kb < KB from a row-major S; zero where the row is not live or the column is >= n (neither is read).
+// The direct address: one load instruction reads sixteen 32-byte pieces, one per row, and the four k-blocks 4 g .. 4 g + 3 together use
+// every byte of the 128-byte lines they touch.  Measured against wide loads with a 4 x 4 exchange between the four lane quarters
+// (v_permlane32_swap, v_permlane16_swap), which was slower: DESIGN.md section 9 has both figures.
+template <int KB>
+__device__ __forceinline__ void load_rows_rm(double (&v)[KB], const double* __restrict__ s, size_t ld, size_t row, bool live, int n, int lq) {
+#pragma unroll
+	for (int kb = 0; kb < KB; kb++) {
+		const int col = 4 * kb + lq;
+		v[kb] = (live && col < n) ? s[row * ld + col] : 0.0;
+	}
+}
+
+// gramq_f64_kernel on a row-major A (a.lda: the row stride): its text but for load_tile
+template <int NT>
+__global__ __launch_bounds__(256) void gramq_f64_rm_kernel(const GramQArgs64 a) {
+	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1), NTRI = (NT * (NT + 1)) / 2;
+	__shared__ double red[2 * NTRI * 256];
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
+	const int gw = blockIdx.x * 4 + wv;
+	f64x4 acc[NTRI];
+#pragma unroll
+	for (int t = 0; t < NTRI; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+	if (gw < a.nwaves) {
+		double zop[NZ];
+		static_for<0, NT>([&](auto jt_) {
+			constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+#pragma unroll
+			for (int kb = 0; kb < 4 * (jt + 1); kb++) zop[base + kb] = a.z[(size_t)(16 * jt + li) * NP + 4 * kb + lq];
+		});
+		auto load_tile = [&](double (&av)[KB], int tile) {
+			const size_t row = (size_t)tile * 16 + li;
+			load_rows_rm<KB>(av, a.a, a.lda, row, tile < a.ntiles && row < a.m, a.n, lq);
+		};
+		double av[KB], nx[KB];
+		load_tile(av, gw);
+		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
+			load_tile(nx, tile + a.nwaves);
+			f64x4 qt[NT];
+			static_for<0, NT>([&](auto jt_) {
+				constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+				for (int kb = 0; kb < 4 * (jt + 1); kb++)
+					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zop[base + kb], qt[jt], 0, 0, 0);
+			});
+#pragma unroll
+			for (int reg = 0; reg < 4; reg++) {
+				int idx = 0;
+#pragma unroll
+				for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+					for (int tj = ti; tj < NT; tj++) {
+						acc[idx] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], qt[tj][reg], acc[idx], 0, 0, 0);
+						idx++;
+					}
+			}
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
+		}
+	}
+	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NTRI * 256, wv, lane);
+}
+
+// lsq_f64_kernel with A row-major (AROW; a.lda: the row stride), B row-major (BROW; a.ldb: the row stride) or both: its text but for
+// load_tile.  A row-major B still enters through the identity k-blocks: the products, and the rule that one non-finite entry of B spoils
+// its row, stay those of lsq_f64_kernel.
+template <int NT, bool AROW, bool BROW>
+__global__ __launch_bounds__(256) void lsq_f64_lay_kernel(const LsqArgs64 a) {
+	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1);
+	__shared__ double red[2 * NT * 256];
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
+	const int gw = blockIdx.x * 4 + wv;
+	f64x4 acc[NT];
+#pragma unroll
+	for (int t = 0; t < NT; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+	if (gw < a.nwaves) {
+		double zop[NZ], xop[KB], idop[4];
+		static_for<0, NT>([&](auto jt_) {
+			constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+#pragma unroll
+			for (int kb = 0; kb < 4 * (jt + 1); kb++) zop[base + kb] = a.z[(size_t)(16 * jt + li) * NP + 4 * kb + lq];
+		});
+#pragma unroll
+		for (int kb = 0; kb < KB; kb++) {
+			const int row = 4 * kb + lq;
+			xop[kb] = -((a.x && row < a.n && li < a.nrhs) ? a.x[(size_t)li * NP + row] : 0.0);
+		}
+#pragma unroll
+		for (int kb = 0; kb < 4; kb++) idop[kb] = (4 * kb + lq == li) ? 1.0 : 0.0;
+		auto load_tile = [&](double (&av)[KB], double (&bv)[4], int tile) {
+			const size_t row = (size_t)tile * 16 + li;
+			const bool live = tile < a.ntiles && row < a.m;
+			if constexpr (AROW) load_rows_rm<KB>(av, a.a, a.lda, row, live, a.n, lq);
+			else {
+#pragma unroll
+				for (int kb = 0; kb < KB; kb++) {
+					const int col = 4 * kb + lq;
+					av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+				}
+			}
+			if constexpr (BROW) load_rows_rm<4>(bv, a.b, a.ldb, row, live, a.nrhs, lq);
+			else {
+#pragma unroll
+				for (int kb = 0; kb < 4; kb++) {
+					const int col = 4 * kb + lq;
+					bv[kb] = (live && col < a.nrhs) ? a.b[(size_t)col * a.ldb + row] : 0.0;
+				}
+			}
+		};
+		double av[KB], nx[KB], bv[4], nb[4];
+		load_tile(av, bv, gw);
+		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
+			load_tile(nx, nb, tile + a.nwaves);
+			f64x4 qt[NT];
+			static_for<0, NT>([&](auto jt_) {
+				constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
+				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+				for (int kb = 0; kb < 4 * (jt + 1); kb++)
+					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zop[base + kb], qt[jt], 0, 0, 0);
+			});
+			f64x4 rt = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+			for (int kb = 0; kb < 4; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[kb], idop[kb], rt, 0, 0, 0);
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], xop[kb], rt, 0, 0, 0);
+#pragma unroll
+			for (int reg = 0; reg < 4; reg++)
+#pragma unroll
+				for (int ti = 0; ti < NT; ti++)
+					acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], rt[reg], acc[ti], 0, 0, 0);
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
+#pragma unroll
+			for (int kb = 0; kb < 4; kb++) bv[kb] = nb[kb];
+		}
+	}
+	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NT * 256, wv, lane);
 }
 
 }  // namespace tsqrmi

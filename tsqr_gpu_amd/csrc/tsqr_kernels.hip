@@ -130,6 +130,32 @@ __device__ __forceinline__ void load_chunk_f64(double (&p)[NT][16], const double
 	}
 }
 
+// load_chunk_f64 from a ROW-major source (element (i, j) at src[i * ld + j], ld >= n): the same registers -- lane 16 q + c holds rows
+// 16 rt + 4 q + i of column 16 ct + c in p[ct][4 rt + i] -- so every product of gram_body is the column-major one.  One load instruction
+// reads sixteen consecutive columns (128 bytes) of four rows; rows >= m and columns >= n are not read and enter as zeros.
+template <int NT>
+__device__ __forceinline__ void load_chunk_f64_rm(double (&p)[NT][16], const double* __restrict__ src, size_t ld, size_t row0, size_t m, int n,
+                                                  int c, int q) {
+	const bool full = (row0 + 64 <= m);
+#pragma unroll
+	for (int ct = 0; ct < NT; ct++) {
+		const int col = 16 * ct + c;
+		if (col < n) {
+			const double* base = src + (row0 + 4 * q) * ld + col;
+#pragma unroll
+			for (int rt = 0; rt < 4; rt++)
+#pragma unroll
+				for (int i = 0; i < 4; i++) {
+					const size_t row = row0 + 16 * rt + 4 * q + i;
+					p[ct][4 * rt + i] = (full || row < m) ? base[(size_t)(16 * rt + i) * ld] : 0.0;
+				}
+		} else {
+#pragma unroll
+			for (int r = 0; r < 16; r++) p[ct][r] = 0.0;
+		}
+	}
+}
+
 // ---- bf16 split helpers (shared by the fold, Gram and apply kernels) ----
 __device__ __forceinline__ unsigned f2bf(float x) {    // round-to-nearest-even bf16 bits (finite inputs)
 	const unsigned u = __builtin_bit_cast(unsigned, x);
@@ -748,7 +774,7 @@ __device__ __forceinline__ void announce_previous_call(unsigned* word, unsigned 
 }
 
 // The body of gram_kernel (GramArgs: fp32 data, widened on the way to the MFMA) and of gram_f64_kernel (GramArgs64, tsqr_f64.hip).
-template <int NT, class T, class ARGS>                  // T: the element type of a.a
+template <int NT, class T, bool ROW_MAJOR = false, class ARGS>   // T: the element type of a.a; ROW_MAJOR (fp64 only): a.a is row-major, a.lda its row stride
 __device__ __forceinline__ void gram_body(const ARGS& a, double* red) {
 	constexpr int NTRI = (NT * (NT + 1)) / 2;
 	const int lane = threadIdx.x & 63;
@@ -762,6 +788,7 @@ __device__ __forceinline__ void gram_body(const ARGS& a, double* red) {
 		T p[NT][16];
 		for (int ch = gw; ch < a.nchunks; ch += a.nwaves) {      // interleaved: consecutive chunks go to consecutive waves
 			if constexpr (std::is_same_v<T, float>) load_chunk<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
+			else if constexpr (ROW_MAJOR) load_chunk_f64_rm<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
 			else load_chunk_f64<NT>(p, a.a, a.lda, (size_t)ch * 64, a.m, a.n, c, q);
 #pragma unroll
 			for (int rho = 0; rho < 16; rho++) {

@@ -2454,12 +2454,13 @@ int f64_chol(hipStream_t st, double* wq, size_t m, size_t n, double* r, size_t l
 }
 
 // Gram pass, reduction and Cholesky step of one sweep over src: R -> r (ldr), Z -> wq[F64_Z], verdict -> status slot `slot`
+// (layout: TSQR_MI_ROW_MAJOR when src is row-major with row stride ld -- the R-only and least-squares entries)
 int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t ld, size_t m, size_t n, double* r, size_t ldr,
-               bool first, int slot, const Comm* comm = nullptr) {
+               bool first, int slot, const Comm* comm = nullptr, int layout = TSQR_MI_COL_MAJOR) {
 	const F64Plan g = f64_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
 	const tsqrmi::GramArgs64 ga{src, ld, m, (int)n, g.nch, g.nwaves, wr};
-	f64_gram_launch(st, g, ga);
+	f64_gram_launch(st, g, ga, layout);
 	HIPCHK(hipGetLastError());
 	const int nelem = g.ntri * 256;
 	launch_reduce1(st, wq + F64_GSUM, wr, g.nblocks, nelem, (double)m);
@@ -2560,9 +2561,10 @@ int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double
 // Sweep k (0-based) of the R-only entry.  Sweep 0 is f64_factor on A: R_1 -> r, Z_1 -> wq[F64_Z].  Sweep k >= 1 never forms Q: first
 // Z_acc = Z_1 ... Z_k (sweep 1: a copy of Z_1; later: Z_acc <- Z_acc Z_k, with the Z_k that sweep k - 1 left in wq[F64_Z]), then the Gram
 // matrix of A Z_acc straight from A (gramq_f64_kernel), the reduction, the Cholesky step of a later sweep (R_(k+1) -> wq[F64_R2],
-// Z_(k+1) -> wq[F64_Z]) and r <- R_(k+1) r.
-int f64r_sweep(hipStream_t st, int k, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, double* wq, double* wr) {
-	if (k == 0) return f64_factor(st, wq, wr, a, lda, m, n, r, ldr, true, 0);
+// Z_(k+1) -> wq[F64_Z]) and r <- R_(k+1) r.  a_layout: TSQR_MI_ROW_MAJOR picks the row-major form of the two kernels that read A; every
+// other launch is the same.
+int f64r_sweep(hipStream_t st, int k, double* r, size_t ldr, int a_layout, const double* a, size_t lda, size_t m, size_t n, double* wq, double* wr) {
+	if (k == 0) return f64_factor(st, wq, wr, a, lda, m, n, r, ldr, true, 0, nullptr, a_layout);
 	const size_t NP = np_of(n);
 	double* zacc = wq + F64R_ZACC;
 	if (k == 1) HIPCHK(hipMemcpyAsync(zacc, wq + F64_Z, NP * NP * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -2571,7 +2573,7 @@ int f64r_sweep(hipStream_t st, int k, double* r, size_t ldr, const double* a, si
 	const F64RPlan g = f64r_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
 	const tsqrmi::GramQArgs64 ga{a, lda, m, (int)n, g.ntiles, g.nwaves, zacc, wr};
-	f64r_gramq_launch(st, g, ga);
+	f64r_gramq_launch(st, g, ga, a_layout);
 	HIPCHK(hipGetLastError());
 	launch_reduce1(st, wq + F64_GSUM, wr, g.nblocks, g.ntri * 256, (double)m);
 	HIPCHK(hipGetLastError());
@@ -2582,17 +2584,17 @@ int f64r_sweep(hipStream_t st, int k, double* r, size_t ldr, const double* a, si
 }
 
 // the ladder of qr_f64_core (f64_ladder) on the sweeps of f64r_sweep
-int r_f64_core(int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, hipStream_t st) {
-	return f64_ladder(reorth, st, [&](int k) { return f64r_sweep(st, k, r, ldr, a, lda, m, n, wq, wr); });
+int r_f64_core(int a_layout, int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, hipStream_t st) {
+	return f64_ladder(reorth, st, [&](int k) { return f64r_sweep(st, k, r, ldr, a_layout, a, lda, m, n, wq, wr); });
 }
 
 // The least-squares entry behind the R-only ladder (corrected semi-normal equations carried out in Q-space; include/tsqr_mi.h).  The
 // ladder's last sweep s left Z_1 ... Z_(s-1) in wq[F64R_ZACC] (nothing for s = 1) and Z_s in wq[F64_Z]: one copy or one zmul_f64_kernel
 // completes Z = inverse(R).  Then refine + 1 passes, each lsq_f64_kernel (D = (A Z)^T (B - A X), X null the first time), the reduction
 // and X <- X + Z D, enqueued back to back; one wait at the end.
-int lstsq_f64_core(int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
+int lstsq_f64_core(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
                    const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, double* wq, double* wr, hipStream_t st) {
-	if (const int rc = r_f64_core(reorth, r, ldr, a, lda, m, n, wq, wr, st)) return rc;
+	if (const int rc = r_f64_core(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, st)) return rc;
 	const size_t NP = np_of(n);
 	double *zacc = wq + F64R_ZACC, *xw = wq + F64L_X, *dsum = wq + F64L_D;
 	if (t_sweeps64 % 100 == 1) HIPCHK(hipMemcpyAsync(zacc, wq + F64_Z, NP * NP * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -2602,7 +2604,7 @@ int lstsq_f64_core(int reorth, int refine, double* x, size_t ldx, double* r, siz
 	if (g.nblocks <= 0) { t_last_error = "fp64 least-squares pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
 	for (int p = 0; p <= refine; p++) {
 		const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, (int)n, (int)nrhs, g.ntiles, g.nwaves, zacc, p == 0 ? nullptr : xw, wr};
-		f64r_lsq_launch(st, g, la);
+		f64r_lsq_launch(st, g, la, a_layout, b_layout);
 		HIPCHK(hipGetLastError());
 		launch_reduce1(st, dsum, wr, g.nblocks, g.NT * 256, (double)m);
 		HIPCHK(hipGetLastError());
@@ -2623,30 +2625,48 @@ size_t tsqr_mi_working_r_size_f64_lstsq(size_t m, size_t n, size_t nrhs) {
 	return (m == 0 || n == 0 || nrhs == 0) ? 0 : f64r_wr_doubles(m, std::min(n, PW));
 }
 
-int tsqr_mi_lstsq_f64(int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
-                      const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream) {
+// rows of storage between the leading-dimension steps of an operand with `rows` rows and `cols` columns in the given layout
+static bool f64_layout_ok(int layout) { return layout == TSQR_MI_COL_MAJOR || layout == TSQR_MI_ROW_MAJOR; }
+static size_t f64_min_ld(int layout, size_t rows, size_t cols) { return layout == TSQR_MI_ROW_MAJOR ? cols : rows; }
+
+int tsqr_mi_lstsq_f64_lay(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr,
+                          const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
+                          void* wq, void* wr, void* stream) {
 	t_sweeps64 = 0;
-	if (n > m || m == 0 || n == 0 || nrhs == 0 || lda < m || ldb < m || ldr < n || ldx < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (!f64_layout_ok(a_layout) || !f64_layout_ok(b_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > m || m == 0 || n == 0 || nrhs == 0 || lda < f64_min_ld(a_layout, m, n) || ldb < f64_min_ld(b_layout, m, nrhs) || ldr < n || ldx < n)
+		return TSQR_MI_ERROR_INVALID_SIZE;
 	if (n > PW) { t_last_error = "tsqr_mi_lstsq_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
 	if (nrhs > F64L_MAX_NRHS) { t_last_error = "tsqr_mi_lstsq_f64 supports nrhs <= 16"; return TSQR_MI_ERROR_UNSUPPORTED; }
 	if (refine < 0 || refine > F64L_MAX_REFINE) { t_last_error = "tsqr_mi_lstsq_f64 supports 0 <= refine <= 4"; return TSQR_MI_ERROR_UNSUPPORTED; }
 	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	if (rc) return rc;
-	return lstsq_f64_core(reorth, refine, x, ldx, r, ldr, a, lda, b, ldb, m, n, nrhs, reinterpret_cast<double*>(wq),
+	return lstsq_f64_core(a_layout, b_layout, reorth, refine, x, ldx, r, ldr, a, lda, b, ldb, m, n, nrhs, reinterpret_cast<double*>(wq),
 	                      reinterpret_cast<double*>(wr), reinterpret_cast<hipStream_t>(stream));
+}
+
+int tsqr_mi_lstsq_f64(int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
+                      const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream) {
+	return tsqr_mi_lstsq_f64_lay(TSQR_MI_COL_MAJOR, TSQR_MI_COL_MAJOR, reorth, refine, x, ldx, r, ldr, a, lda, b, ldb, m, n, nrhs, wq, wr, stream);
 }
 
 size_t tsqr_mi_working_q_size_f64_r(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : F64R_WQ; }
 size_t tsqr_mi_working_r_size_f64_r(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : f64r_wr_doubles(m, std::min(n, PW)); }
 
-int tsqr_mi_r_f64(int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, void* wq, void* wr, void* stream) {
+int tsqr_mi_r_f64_lay(int a_layout, int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n,
+                      void* wq, void* wr, void* stream) {
 	t_sweeps64 = 0;
-	if (n > m || m == 0 || n == 0 || lda < m || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (!f64_layout_ok(a_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > m || m == 0 || n == 0 || lda < f64_min_ld(a_layout, m, n) || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
 	if (n > PW) { t_last_error = "tsqr_mi_r_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
 	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	if (rc) return rc;
-	return r_f64_core(reorth, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
+	return r_f64_core(a_layout, reorth, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
 	                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int tsqr_mi_r_f64(int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n, void* wq, void* wr, void* stream) {
+	return tsqr_mi_r_f64_lay(TSQR_MI_COL_MAJOR, reorth, r, ldr, a, lda, m, n, wq, wr, stream);
 }
 
 size_t tsqr_mi_working_q_size_f64(size_t m, size_t n) { return (m == 0 || n == 0) ? 0 : F64_WQ; }
