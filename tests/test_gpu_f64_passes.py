@@ -1,7 +1,7 @@
 """Each pass of the fp64 entries on its own, through the test library's tsqr_selftest_f64_* entries (tsqr_gpu_amd/csrc/selftest_f64.hip:
 the product's kernels launched with the product's plan, f64_plan.h), against exact data bit for bit or extended-precision references:
 
-  n <= 64       gram_f64_kernel + gram_reduce1_kernel, chol_f64_kernel, apply_f64_kernel<NT>, rmul_f64_kernel
+  n <= 64       gram_f64_kernel + gram_reduce1_kernel, chol_f64_kernel, apply_f64_kernel<NT>, trimul_f64_kernel
   64 < n <= 1024 gram_wide_f64_kernel + reduction, the blocked Cholesky chain (plain, shifted, both as the product enqueues them),
                 apply_wide_f64_kernel, rcopy_wide_f64_kernel, rsave_ + rmul_wide_f64_kernel
 

@@ -1,4 +1,4 @@
-"""The row-major forms of the three streaming fp64 kernels (gram_f64_rm_kernel, gramq_f64_rm_kernel, lsq_f64_lay_kernel), pass by pass,
+"""The row-major forms of the three streaming fp64 kernels (gram_f64_kernel, gramq_f64_kernel and lsq_f64_kernel with their AROW / BROW flags set), pass by pass,
 through the test library's tsqr_selftest_f64_{gram,gramq,lsq}_lay: EVERY workgroup partial of the row-major kernel equals, bit for bit,
 the partial of the column-major kernel on the transposed copy of the same matrix -- the statement of include/tsqr_mi.h that the entry-level
 equality rests on.  The data are Gaussian (nothing has to be exact: both runs form the same products in the same order).  The padding

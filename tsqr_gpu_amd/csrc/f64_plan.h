@@ -24,17 +24,21 @@ constexpr int F64_GRAM_WAVES = 2048;                    // fixed (not tsqr_mi_se
 // wq (doubles): [Z: 4096][R of the sweep: 4096][summed tiles + row count][status words: 4 slots x 4 words]
 constexpr size_t F64_Z = 0, F64_R2 = 4096, F64_GSUM = 8192, F64_STATUS = F64_GSUM + GSUM_DOUBLES, F64_WQ = F64_STATUS + 8;
 
-struct F64Plan { int NT, ntri, nch, nwaves, nblocks; };
-F64Plan f64_plan(size_t m, size_t n) {
+// The partition of a streaming pass over the m rows: nunits units of `unit_rows` rows dealt to nwaves waves (at most wave_cap, and no
+// wave without a unit), four waves to a workgroup.  ntri: the tiles of a Gram partial.
+struct F64Plan { int NT, ntri, nunits, nwaves, nblocks; };
+inline F64Plan f64_plan_of(size_t m, size_t n, size_t unit_rows, int wave_cap) {
 	F64Plan g{};
 	g.NT = (int)(np_of(n) / 16);
 	g.ntri = g.NT * (g.NT + 1) / 2;
-	g.nch = (int)cdiv(m, 64);
-	const size_t cpw = std::max<size_t>(1, cdiv((size_t)g.nch, F64_GRAM_WAVES));
-	g.nwaves = (int)cdiv((size_t)g.nch, cpw);
+	g.nunits = (int)cdiv(m, unit_rows);
+	const size_t upw = std::max<size_t>(1, cdiv((size_t)g.nunits, (size_t)wave_cap));
+	g.nwaves = (int)cdiv((size_t)g.nunits, upw);
 	g.nblocks = (g.nwaves + 3) / 4;
 	return g;
 }
+// the Gram pass (sweep 0 of every n <= 64 entry, every sweep of tsqr_mi_qr_f64): 64-row chunks
+inline F64Plan f64_plan(size_t m, size_t n) { return f64_plan_of(m, n, 64, F64_GRAM_WAVES); }
 
 // The acceptance rule of a sweep over an m x n matrix (CholArgs64, tsqr_f64.hip, states it and its sources): the bounds on S of a FIRST
 // sweep (later sweeps: max_scond = infinity, never alone) and the coefficient of the shift, s = shift_coef * trace(G).  The arithmetic is
@@ -42,9 +46,17 @@ F64Plan f64_plan(size_t m, size_t n) {
 using F64Rule = tsqrmi::F64Rule;
 inline F64Rule f64_rule(size_t m, size_t n, bool first) { return tsqrmi::f64_rule_of((double)m, (int)n, first); }
 
-// the Gram pass of the n <= 64 entry on stream st: gram_f64_kernel<NT> on the plan's grid
-inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramArgs64& ga) {
-	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gram_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
+// The launchers of the three passes that read A (and B) take a layout per operand: TSQR_MI_COL_MAJOR = 0, TSQR_MI_ROW_MAJOR = 1
+// (include/tsqr_mi.h); ga.lda / la.lda / la.ldb are row strides for a row-major operand.  The plans, grids and partials do not depend on
+// it; only the kernel's template flag does.
+
+// the Gram pass of the n <= 64 entry on stream st: gram_f64_kernel<NT, AROW> on the plan's grid
+inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramArgs64& ga, int a_layout = 0) {
+	with_nt(g.NT, [&](auto nt) {
+		with_layout(a_layout, [&](auto ar) {
+			hipLaunchKernelGGL((tsqrmi::gram_f64_kernel<decltype(nt)::value, decltype(ar)::value>), dim3(g.nblocks), dim3(256), 0, st, ga);
+		});
+	});
 }
 
 // the apply pass of the n <= 64 entry runs on a persistent grid: the workgroups resident at once on device dev ...
@@ -59,6 +71,16 @@ template <int NT> int f64_apply_resident(int dev) {
 // ... but no more than one wave per 32-row block
 inline size_t f64_apply_wgs(size_t nblocks, size_t resident) { return std::max<size_t>(1, std::min(cdiv(nblocks, 4), resident)); }
 
+// the two uses of trimul_f64_kernel on stream st, both in place: r (n x n, ldr) <- r2 r with r2 packed with ld 64 (the destination is the
+// right factor), and z <- z zk, both NP x NP with ld NP (the destination is the left factor; the whole block is written)
+inline void f64_rmul_launch(hipStream_t st, double* r, size_t ldr, const double* r2, int n) {
+	hipLaunchKernelGGL(tsqrmi::trimul_f64_kernel, dim3(1), dim3(1024), 0, st, r, ldr, r2, (size_t)64, (const double*)r, ldr, n, n);
+}
+inline void f64r_zmul_launch(hipStream_t st, double* z, const double* zk, int n) {
+	const size_t NP = np_of((size_t)n);
+	hipLaunchKernelGGL(tsqrmi::trimul_f64_kernel, dim3(1), dim3(1024), 0, st, z, NP, (const double*)z, NP, zk, NP, n, (int)NP);
+}
+
 // ---- tsqr_mi_r_f64 (n <= 64, R only) ---------------------------------------------------------------------------------------------------
 // Sweep 0 is the Gram pass above; sweeps k >= 1 run gramq_f64_kernel on 16-row tiles of A.  Like F64_GRAM_WAVES the wave count is a fixed
 // function of (m, n) -- no occupancy query, no setting -- so that the reduction tree, the bits of R and the size of wr are the same everywhere.
@@ -66,27 +88,20 @@ constexpr int F64R_GRAMQ_WAVES = 2048;
 // wq (doubles): [the F64_WQ layout (the sweep's Z, the sweep's R, summed tiles, status words)][Z_acc: the product of the inverses so far: 4096]
 constexpr size_t F64R_ZACC = F64_WQ, F64R_WQ = F64R_ZACC + 4096;
 
-struct F64RPlan { int NT, ntri, ntiles, nwaves, nblocks; };
-inline F64RPlan f64r_plan(size_t m, size_t n) {
-	F64RPlan g{};
-	g.NT = (int)(np_of(n) / 16);
-	g.ntri = g.NT * (g.NT + 1) / 2;
-	g.ntiles = (int)cdiv(m, 16);
-	const size_t tpw = std::max<size_t>(1, cdiv((size_t)g.ntiles, F64R_GRAMQ_WAVES));
-	g.nwaves = (int)cdiv((size_t)g.ntiles, tpw);
-	g.nblocks = (g.nwaves + 3) / 4;
-	return g;
-}
+inline F64Plan f64r_plan(size_t m, size_t n) { return f64_plan_of(m, n, 16, F64R_GRAMQ_WAVES); }   // 16-row tiles
 // doubles of wr: the larger of the two Gram plans' partials
 inline size_t f64r_wr_doubles(size_t m, size_t n) {
-	const F64Plan g0 = f64_plan(m, n);
-	const F64RPlan g1 = f64r_plan(m, n);
+	const F64Plan g0 = f64_plan(m, n), g1 = f64r_plan(m, n);
 	return (size_t)std::max(g0.nblocks, g1.nblocks) * g0.ntri * 256;
 }
 
-// the Gram pass of sweeps k >= 1 of the R-only entry on stream st: gramq_f64_kernel<NT> on the plan's grid
-inline void f64r_gramq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::GramQArgs64& ga) {
-	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gramq_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
+// the Gram pass of sweeps k >= 1 of the R-only entry on stream st: gramq_f64_kernel<NT, AROW> on the plan's grid
+inline void f64r_gramq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramQArgs64& ga, int a_layout = 0) {
+	with_nt(g.NT, [&](auto nt) {
+		with_layout(a_layout, [&](auto ar) {
+			hipLaunchKernelGGL((tsqrmi::gramq_f64_kernel<decltype(nt)::value, decltype(ar)::value>), dim3(g.nblocks), dim3(256), 0, st, ga);
+		});
+	});
 }
 
 // ---- tsqr_mi_lstsq_f64 (n <= 64, nrhs <= 16) -------------------------------------------------------------------------------------------
@@ -98,30 +113,15 @@ constexpr int F64L_MAX_REFINE = 4;
 // wq (doubles): [the F64R_WQ layout][X, NP x 16 (ld NP): 1024][summed D: 4 tiles of 256 + the row-count word of the reduction]
 constexpr size_t F64L_X = F64R_WQ, F64L_D = F64L_X + 1024, F64L_WQ = F64L_D + 1024 + 8;
 
-// one pass of the least-squares entry on stream st: lsq_f64_kernel<NT> on the R-only plan's grid
-inline void f64r_lsq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::LsqArgs64& la) {
-	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::lsq_f64_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, la); });
-}
-
-// ---- row-major operands (tsqr_mi_r_f64_lay, tsqr_mi_lstsq_f64_lay) -----------------------------------------------------------------------
-// The plans, grids and partials above; only the kernel differs.  Layout values: TSQR_MI_COL_MAJOR = 0, TSQR_MI_ROW_MAJOR = 1
-// (include/tsqr_mi.h); ga.lda / la.lda / la.ldb are row strides for a row-major operand.
-inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramArgs64& ga, int a_layout) {
-	if (!a_layout) return f64_gram_launch(st, g, ga);
-	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gram_f64_rm_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
-}
-inline void f64r_gramq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::GramQArgs64& ga, int a_layout) {
-	if (!a_layout) return f64r_gramq_launch(st, g, ga);
-	with_nt(g.NT, [&](auto nt) { hipLaunchKernelGGL(tsqrmi::gramq_f64_rm_kernel<decltype(nt)::value>, dim3(g.nblocks), dim3(256), 0, st, ga); });
-}
-inline void f64r_lsq_launch(hipStream_t st, const F64RPlan& g, const tsqrmi::LsqArgs64& la, int a_layout, int b_layout) {
-	if (!a_layout && !b_layout) return f64r_lsq_launch(st, g, la);
+// one pass of the least-squares entry on stream st: lsq_f64_kernel<NT, AROW, BROW> on the R-only plan's grid
+inline void f64r_lsq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::LsqArgs64& la, int a_layout = 0, int b_layout = 0) {
 	with_nt(g.NT, [&](auto nt) {
-		constexpr int NT = decltype(nt)::value;
-		auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(g.nblocks), dim3(256), 0, st, la); };
-		if (a_layout && b_layout) go(tsqrmi::lsq_f64_lay_kernel<NT, true, true>);
-		else if (a_layout) go(tsqrmi::lsq_f64_lay_kernel<NT, true, false>);
-		else go(tsqrmi::lsq_f64_lay_kernel<NT, false, true>);
+		with_layout(a_layout, [&](auto ar) {
+			with_layout(b_layout, [&](auto br) {
+				hipLaunchKernelGGL((tsqrmi::lsq_f64_kernel<decltype(nt)::value, decltype(ar)::value, decltype(br)::value>), dim3(g.nblocks),
+				                   dim3(256), 0, st, la);
+			});
+		});
 	});
 }
 

@@ -1,5 +1,5 @@
 // launch_util.h -- the pieces of host launch code that every schedule of tsqr_mi.hip and the test library share: the dispatch on the tile
-// count NT and on the MFMA engine, the launch of gram_reduce1_kernel and the spin-then-poll wait on a pinned word.  ONE definition each,
+// count NT, on an operand's layout and on the MFMA engine, the launch of gram_reduce1_kernel and the spin-then-poll wait on a pinned word.  ONE definition each,
 // compiled into libtsqr_mi.so (tsqr_mi.hip) and into libtsqr_selftest.so (selftest.hip).  Nothing here knows the per-call context.
 // Included after tsqr_kernels.hip (f64_plan.h includes it).  The including file defines fail(): what a function returns, through HIPCHK,
 // when a HIP call did not succeed.
@@ -21,6 +21,9 @@ template <class F> inline auto with_nt(int NT, F&& f) {
 		default: return f(std::integral_constant<int, 4>{});
 	}
 }
+
+// f(std::bool_constant<ROW>{}) for the layout of an operand: 0 column-major (false), any other value row-major (true)
+template <class F> inline auto with_layout(int layout, F&& f) { return layout ? f(std::true_type{}) : f(std::false_type{}); }
 
 // f(std::integral_constant<int, E>{}) for the MFMA engine of the apply pass: 0 fp32, 1 bf16x3 (any other value: 2, single fp16 product)
 template <class F> inline auto with_engine(int engine, F&& f) {

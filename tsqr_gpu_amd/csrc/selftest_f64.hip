@@ -27,6 +27,14 @@ template <int NT> int selftest_f64_apply(double* q, size_t ldq, const double* a,
 }
 }  // namespace
 
+// the nwaves override of the Gram, gramq and lsq entries (0: the plan's); false when `part` has no room for the partials of `tiles` tiles
+namespace {
+inline bool f64_override(F64Plan& g, int nwaves, int tiles, size_t part_cap) {
+	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
+	return g.nblocks > 0 && (size_t)g.nblocks * tiles * 256 <= part_cap;
+}
+}  // namespace
+
 namespace {
 __global__ __launch_bounds__(64) void f64_rule_probe_kernel(const double* rows, const int* n, const int* first, int count, double* out) {
 	const int i = blockIdx.x * 64 + threadIdx.x;
@@ -42,7 +50,7 @@ extern "C" {
 int tsqr_selftest_f64_plan(size_t m, size_t n, long long* out) {
 	if (m == 0 || n == 0 || n > PW) return -100;
 	const F64Plan g = f64_plan(m, n);
-	out[0] = g.NT; out[1] = g.ntri; out[2] = g.nch; out[3] = g.nwaves; out[4] = g.nblocks;
+	out[0] = g.NT; out[1] = g.ntri; out[2] = g.nunits; out[3] = g.nwaves; out[4] = g.nblocks;
 	out[5] = (long long)F64_WQ; out[6] = (long long)g.nblocks * g.ntri * 256; out[7] = F64_GRAM_WAVES;
 	return 0;
 }
@@ -78,19 +86,24 @@ int tsqr_selftest_f64w_plan(size_t m, size_t n, long long* out) {
 }
 
 // ---- n <= 64 --------------------------------------------------------------------------------------------------------------------------
-// Gram pass + reduction: gsum[ntri * 256 + 1] (the row count behind the tiles).  nwaves > 0 overrides the plan's wave count;
-// part holds part_cap doubles.
-int tsqr_selftest_f64_gram(double* gsum, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, int nwaves) {
-	if (m == 0 || n <= 0 || n > (int)PW || lda < m) return -100;
+// The Gram, gramq and lsq entries come in two forms: _lay takes a layout per operand (0 column-major; 1 row-major, the leading dimension
+// is then the row stride: lda >= n, ldb >= nrhs) and goes through the launchers the product uses (f64_plan.h); the plain entry is _lay
+// at layout 0.  nwaves > 0 overrides the plan's wave count -- the same partition for every layout, so the partials in `part` (part_cap
+// doubles) can be compared one by one.
+// Gram pass + reduction: gsum[ntri * 256 + 1] (the row count behind the tiles).
+int tsqr_selftest_f64_gram_lay(int a_layout, double* gsum, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, int nwaves) {
+	if (a_layout != 0 && a_layout != 1) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || lda < (a_layout ? (size_t)n : m)) return -100;
 	F64Plan g = f64_plan(m, (size_t)n);
-	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
-	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
-	const tsqrmi::GramArgs64 ga{a, lda, m, n, g.nch, g.nwaves, part};
-	f64_gram_launch(0, g, ga);
+	if (!f64_override(g, nwaves, g.ntri, part_cap)) return -100;
+	const tsqrmi::GramArgs64 ga{a, lda, m, n, g.nunits, g.nwaves, part};
+	f64_gram_launch(0, g, ga, a_layout);
 	HIPCHK(hipGetLastError());
-	const int nelem = g.ntri * 256;
-	launch_reduce1(0, gsum, part, g.nblocks, nelem, (double)m);
+	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
 	return f64_sync();
+}
+int tsqr_selftest_f64_gram(double* gsum, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, int nwaves) {
+	return tsqr_selftest_f64_gram_lay(0, gsum, a, lda, m, n, part, part_cap, nwaves);
 }
 
 // chol_f64_kernel with the thresholds and the shift of an m x n first sweep (first = 1) or of a later one (0): r (n x n, ldr),
@@ -112,10 +125,10 @@ int tsqr_selftest_f64_apply(double* q, size_t ldq, const double* a, size_t lda, 
 	return with_nt((int)(np_of((size_t)n) / 16), [&](auto nt) { return selftest_f64_apply<decltype(nt)::value>(q, ldq, a, lda, m, n, z, wgs); });
 }
 
-// rmul_f64_kernel: r <- r2 r (r2 packed with ld 64), in place
+// trimul_f64_kernel as f64_sweep launches it: r <- r2 r (r2 packed with ld 64), in place
 int tsqr_selftest_f64_rmul(double* r, size_t ldr, const double* r2, int n) {
 	if (n <= 0 || n > (int)PW || ldr < (size_t)n) return -100;
-	hipLaunchKernelGGL(tsqrmi::rmul_f64_kernel, dim3(1), dim3(1024), 0, 0, r, ldr, r2, n);
+	f64_rmul_launch(0, r, ldr, r2, n);
 	return f64_sync();
 }
 
@@ -124,95 +137,57 @@ int tsqr_selftest_f64_rmul(double* r, size_t ldr, const double* r2, int n) {
 // F64R_GRAMQ_WAVES.  Host only.
 int tsqr_selftest_f64r_plan(size_t m, size_t n, long long* out) {
 	if (m == 0 || n == 0 || n > PW) return -100;
-	const F64RPlan g = f64r_plan(m, n);
-	out[0] = g.NT; out[1] = g.ntri; out[2] = g.ntiles; out[3] = g.nwaves; out[4] = g.nblocks;
+	const F64Plan g = f64r_plan(m, n);
+	out[0] = g.NT; out[1] = g.ntri; out[2] = g.nunits; out[3] = g.nwaves; out[4] = g.nblocks;
 	out[5] = (long long)F64R_WQ; out[6] = (long long)f64r_wr_doubles(m, n); out[7] = F64R_GRAMQ_WAVES;
 	return 0;
 }
 
 // gramq_f64_kernel + reduction: gsum[ntri * 256 + 1] = the tiles of (a z)^T (a z) and the row count behind them; z: NP x NP (ld NP).
-// nwaves > 0 overrides the plan's wave count; part holds part_cap doubles.
-int tsqr_selftest_f64_gramq(double* gsum, const double* a, size_t lda, size_t m, int n, const double* z, double* part, size_t part_cap,
-                            int nwaves) {
-	if (m == 0 || n <= 0 || n > (int)PW || lda < m) return -100;
-	F64RPlan g = f64r_plan(m, (size_t)n);
-	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
-	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
-	const tsqrmi::GramQArgs64 ga{a, lda, m, n, g.ntiles, g.nwaves, z, part};
-	f64r_gramq_launch(0, g, ga);
-	HIPCHK(hipGetLastError());
-	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
-	return f64_sync();
-}
-
-// zmul_f64_kernel: z <- z zk (both NP x NP with ld NP, NP = 16 ceil(n / 16)), in place
-int tsqr_selftest_f64_zmul(double* z, const double* zk, int n) {
-	if (n <= 0 || n > (int)PW) return -100;
-	hipLaunchKernelGGL(tsqrmi::zmul_f64_kernel, dim3(1), dim3(1024), 0, 0, z, zk, n, (int)np_of((size_t)n));
-	return f64_sync();
-}
-
-// ---- n <= 64, least squares (tsqr_mi_lstsq_f64) ---------------------------------------------------------------------------------------------
-// lsq_f64_kernel + reduction, one pass: dsum[NT * 256 + 1] = the tiles of (a z)^T (b - a x) and the row count behind them; z: NP x NP
-// (ld NP), x: NP x 16 (ld NP) or null = zero.  nwaves > 0 overrides the plan's wave count; part holds part_cap doubles.
-int tsqr_selftest_f64_lsq(double* dsum, const double* a, size_t lda, const double* b, size_t ldb, size_t m, int n, int nrhs,
-                          const double* z, const double* x, double* part, size_t part_cap, int nwaves) {
-	if (m == 0 || n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || lda < m || ldb < m) return -100;
-	F64RPlan g = f64r_plan(m, (size_t)n);
-	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
-	if (g.nblocks <= 0 || (size_t)g.nblocks * g.NT * 256 > part_cap) return -100;
-	const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, n, nrhs, g.ntiles, g.nwaves, z, x, part};
-	f64r_lsq_launch(0, g, la);
-	HIPCHK(hipGetLastError());
-	launch_reduce1(0, dsum, part, g.nblocks, g.NT * 256, (double)m);
-	return f64_sync();
-}
-
-// ---- n <= 64, row-major operands (tsqr_mi_r_f64_lay, tsqr_mi_lstsq_f64_lay) -------------------------------------------------------------
-// tsqr_selftest_f64_gram / _gramq / _lsq with a layout per operand (0 column-major: those very entries; 1 row-major, the leading dimension
-// is then the row stride: lda >= n, ldb >= nrhs), through the launchers the product uses (f64_plan.h).  The same nwaves override, so the
-// partials in `part` can be compared one by one with the column-major run's.
-int tsqr_selftest_f64_gram_lay(int a_layout, double* gsum, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, int nwaves) {
-	if (a_layout != 0 && a_layout != 1) return -100;
-	if (m == 0 || n <= 0 || n > (int)PW || lda < (a_layout ? (size_t)n : m)) return -100;
-	F64Plan g = f64_plan(m, (size_t)n);
-	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
-	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
-	const tsqrmi::GramArgs64 ga{a, lda, m, n, g.nch, g.nwaves, part};
-	f64_gram_launch(0, g, ga, a_layout);
-	HIPCHK(hipGetLastError());
-	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
-	return f64_sync();
-}
-
 int tsqr_selftest_f64_gramq_lay(int a_layout, double* gsum, const double* a, size_t lda, size_t m, int n, const double* z, double* part,
                                 size_t part_cap, int nwaves) {
 	if (a_layout != 0 && a_layout != 1) return -100;
 	if (m == 0 || n <= 0 || n > (int)PW || lda < (a_layout ? (size_t)n : m)) return -100;
-	F64RPlan g = f64r_plan(m, (size_t)n);
-	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
-	if (g.nblocks <= 0 || (size_t)g.nblocks * g.ntri * 256 > part_cap) return -100;
-	const tsqrmi::GramQArgs64 ga{a, lda, m, n, g.ntiles, g.nwaves, z, part};
+	F64Plan g = f64r_plan(m, (size_t)n);
+	if (!f64_override(g, nwaves, g.ntri, part_cap)) return -100;
+	const tsqrmi::GramQArgs64 ga{a, lda, m, n, g.nunits, g.nwaves, z, part};
 	f64r_gramq_launch(0, g, ga, a_layout);
 	HIPCHK(hipGetLastError());
 	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
 	return f64_sync();
 }
+int tsqr_selftest_f64_gramq(double* gsum, const double* a, size_t lda, size_t m, int n, const double* z, double* part, size_t part_cap,
+                            int nwaves) {
+	return tsqr_selftest_f64_gramq_lay(0, gsum, a, lda, m, n, z, part, part_cap, nwaves);
+}
 
+// trimul_f64_kernel as f64r_zacc launches it: z <- z zk (both NP x NP with ld NP, NP = 16 ceil(n / 16)), in place
+int tsqr_selftest_f64_zmul(double* z, const double* zk, int n) {
+	if (n <= 0 || n > (int)PW) return -100;
+	f64r_zmul_launch(0, z, zk, n);
+	return f64_sync();
+}
+
+// ---- n <= 64, least squares (tsqr_mi_lstsq_f64) ---------------------------------------------------------------------------------------------
+// lsq_f64_kernel + reduction, one pass: dsum[NT * 256 + 1] = the tiles of (a z)^T (b - a x) and the row count behind them; z: NP x NP
+// (ld NP), x: NP x 16 (ld NP) or null = zero.
 int tsqr_selftest_f64_lsq_lay(int a_layout, int b_layout, double* dsum, const double* a, size_t lda, const double* b, size_t ldb, size_t m,
                               int n, int nrhs, const double* z, const double* x, double* part, size_t part_cap, int nwaves) {
 	if ((a_layout != 0 && a_layout != 1) || (b_layout != 0 && b_layout != 1)) return -100;
 	if (m == 0 || n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || lda < (a_layout ? (size_t)n : m) ||
 	    ldb < (b_layout ? (size_t)nrhs : m))
 		return -100;
-	F64RPlan g = f64r_plan(m, (size_t)n);
-	if (nwaves > 0) { g.nwaves = nwaves; g.nblocks = (nwaves + 3) / 4; }
-	if (g.nblocks <= 0 || (size_t)g.nblocks * g.NT * 256 > part_cap) return -100;
-	const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, n, nrhs, g.ntiles, g.nwaves, z, x, part};
+	F64Plan g = f64r_plan(m, (size_t)n);
+	if (!f64_override(g, nwaves, g.NT, part_cap)) return -100;
+	const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, n, nrhs, g.nunits, g.nwaves, z, x, part};
 	f64r_lsq_launch(0, g, la, a_layout, b_layout);
 	HIPCHK(hipGetLastError());
 	launch_reduce1(0, dsum, part, g.nblocks, g.NT * 256, (double)m);
 	return f64_sync();
+}
+int tsqr_selftest_f64_lsq(double* dsum, const double* a, size_t lda, const double* b, size_t ldb, size_t m, int n, int nrhs,
+                          const double* z, const double* x, double* part, size_t part_cap, int nwaves) {
+	return tsqr_selftest_f64_lsq_lay(0, 0, dsum, a, lda, b, ldb, m, n, nrhs, z, x, part, part_cap, nwaves);
 }
 
 // lsq_update_f64_kernel: xw (NP x 16, ld NP) <- xw + z d (first: xw taken as zero), and x (n x nrhs, ldx) too when last

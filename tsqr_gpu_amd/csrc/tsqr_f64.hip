@@ -5,13 +5,18 @@
 //   chol_f64_kernel   : G -> R, Z = inverse(R) in fp64, the fp64 acceptance rule (CholArgs64), a rejected matrix factored again at
 //                       once with the shift of Fukaya et al.
 //   apply_f64_kernel  : Q = A Z on v_mfma_f64_16x16x4_f64, Z upper triangular (its zero blocks are skipped), in place allowed
-//   rmul_f64_kernel   : R <- R2 R on v_mfma_f64_16x16x4_f64, in place
+//   trimul_f64_kernel : D = L R of two upper triangular factors on v_mfma_f64_16x16x4_f64, in place: R <- R2 R
 // and of the R-only entry (tsqr_mi_r_f64), whose sweeps after the first stream A and never store Q:
 //   gramq_f64_kernel  : per-workgroup partials of (A Z)^T (A Z), each 16-row block of A Z formed and consumed in registers
-//   zmul_f64_kernel   : Z <- Z Zk, the inverse of all sweeps so far, in place
+//   trimul_f64_kernel : Z <- Z Zk, the inverse of all sweeps so far, in place
 // and of the least-squares entry (tsqr_mi_lstsq_f64), whose passes behind that ladder stream A and B and store nothing of size m:
 //   lsq_f64_kernel        : per-workgroup partials of (A Z)^T (B - A X), each 16-row block of A Z and of the residual held in registers
 //   lsq_update_f64_kernel : X <- X + Z D on one workgroup
+// The three passes that read A (and B) take the layout of each operand as a template flag (AROW, BROW: tsqr_mi_r_f64_lay,
+// tsqr_mi_lstsq_f64_lay).  Element (i, j) of a row-major operand lies at s[i * ld + j], ld >= the column count.  A row-major kernel is the
+// column-major one with another address for the same register: at every MFMA lane (li, lq) of k-block kb holds S[row0 + li][4 kb + lq]
+// in both, so every partial -- and behind the unchanged reduction R, X and the sweep count -- has the bits of the column-major kernel on
+// the transposed copy.
 #include <hip/hip_runtime.h>
 
 namespace tsqrmi {
@@ -22,18 +27,12 @@ struct GramArgs64 {
 	double* part;                        // [gridDim.x][NTRI][256], the order of gram_kernel's partials
 };
 
-template <int NT>
+// AROW: A is row-major (a.lda: the row stride, >= n): load_chunk_f64_rm fills the registers load_chunk_f64 fills
+template <int NT, bool AROW>
 __global__ __launch_bounds__(256) void gram_f64_kernel(const GramArgs64 a) {
 	constexpr int NTRI = (NT * (NT + 1)) / 2;
 	__shared__ double red[2 * NTRI * 256];
-	gram_body<NT, double>(a, red);
-}
-// the same pass on a row-major A (a.lda: the row stride, >= n): load_chunk_f64_rm fills the registers load_chunk_f64 fills
-template <int NT>
-__global__ __launch_bounds__(256) void gram_f64_rm_kernel(const GramArgs64 a) {
-	constexpr int NTRI = (NT * (NT + 1)) / 2;
-	__shared__ double red[2 * NTRI * 256];
-	gram_body<NT, double, true>(a, red);
+	gram_body<NT, double, AROW>(a, red);
 }
 
 // The three numbers of the acceptance rule (stated at CholArgs64 below) for a sweep over `rows` x n (first: the first sweep of a call).
@@ -189,22 +188,26 @@ __global__ __launch_bounds__(256) void apply_f64_kernel(double* q, size_t ldq, c
 	}
 }
 
-// R <- R2 R (n x n upper triangular, n <= 64; R2 packed with ld 64), in place: one workgroup of sixteen waves stages both factors
-// in LDS, wave w forms the 16 x 16 tile (w >> 2, w & 3) over the k range in which both are non-zero (rmul64_kernel's scheme with
-// fp64 I/O).  Every thread has read its entries before the barrier that precedes the first store.
-__global__ __launch_bounds__(1024) void rmul_f64_kernel(double* r, size_t ldr, const double* __restrict__ r2, int n) {
-	__shared__ double A2[64 * 65], A1[64 * 65];          // A2[i * 65 + k] = R2[i][k], A1[k * 65 + j] = R[k][j]; zero outside the upper triangles
+// D = L R, the product of two n x n upper triangular factors (n <= 64; column-major with ldl, ldr), written as the leading ext x ext block
+// of d (ldd; zeros below the diagonal and beyond n), in place: d may be either factor.  Its two uses:
+//   R <- R2 R   d = R, the right factor (its ld); L = R2 packed with ld 64; ext = n
+//   Z <- Z Zk   d = Z, the left factor; both NP x NP with ld NP, zero padded, the layout of chol_f64_kernel's Z; ext = NP, the whole block
+// One workgroup of sixteen waves stages both factors in LDS, wave w forms the 16 x 16 tile (w >> 2, w & 3) over the k range in which both
+// are non-zero (rmul64_kernel's scheme with fp64 I/O).  Every thread has read its entries before the barrier that precedes the first store.
+__global__ __launch_bounds__(1024) void trimul_f64_kernel(double* d, size_t ldd, const double* l, size_t ldl, const double* r, size_t ldr,
+                                                          int n, int ext) {
+	__shared__ double A2[64 * 65], A1[64 * 65];          // A2[i * 65 + k] = L[i][k], A1[k * 65 + j] = R[k][j]; zero outside the upper triangles
 	const int t = threadIdx.x;
 #pragma unroll
 	for (int u = 0; u < 4; u++) {
 		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
 		const bool in = i <= j && j < n;
-		A2[i * 65 + j] = in ? r2[(size_t)j * 64 + i] : 0.0;
+		A2[i * 65 + j] = in ? l[(size_t)j * ldl + i] : 0.0;
 		A1[i * 65 + j] = in ? r[(size_t)j * ldr + i] : 0.0;
 	}
 	__syncthreads();
-	const int w = t >> 6, l = t & 63, ti = w >> 2, tj = w & 3, li = l & 15, lq = l >> 4;
-	f64x4 c = f64x4{0.0, 0.0, 0.0, 0.0};                // c[reg] = (R2 R)[16 ti + lq + 4 reg][16 tj + li]
+	const int w = t >> 6, ln = t & 63, ti = w >> 2, tj = w & 3, li = ln & 15, lq = ln >> 4;
+	f64x4 c = f64x4{0.0, 0.0, 0.0, 0.0};                // c[reg] = (L R)[16 ti + lq + 4 reg][16 tj + li]
 	if (ti <= tj) {
 		for (int ks = 4 * ti; ks < 4 * (tj + 1); ks++)
 			c = __builtin_amdgcn_mfma_f64_16x16x4f64(A2[(16 * ti + li) * 65 + 4 * ks + lq], A1[(4 * ks + lq) * 65 + 16 * tj + li], c, 0, 0, 0);
@@ -212,7 +215,21 @@ __global__ __launch_bounds__(1024) void rmul_f64_kernel(double* r, size_t ldr, c
 #pragma unroll
 	for (int reg = 0; reg < 4; reg++) {
 		const int i = 16 * ti + lq + 4 * reg, j = 16 * tj + li;
-		if (i < n && j < n) r[(size_t)j * ldr + i] = (i <= j) ? c[reg] : 0.0;
+		if (i < ext && j < ext) d[(size_t)j * ldd + i] = (i <= j) ? c[reg] : 0.0;
+	}
+}
+
+// v[kb] = S[row][4 kb + lq] for kb < KB from a ROW-major S (ld: the row stride), the registers the column-major loops of gramq_f64_kernel
+// and lsq_f64_kernel fill; zero where the row is not live or the column is >= n (neither is read).
+// The direct address: one load instruction reads sixteen 32-byte pieces, one per row, and the four k-blocks 4 g .. 4 g + 3 together use
+// every byte of the 128-byte lines they touch.  Measured against wide loads with a 4 x 4 exchange between the four lane quarters
+// (v_permlane32_swap, v_permlane16_swap), which was slower: DESIGN.md section 9 has both figures.
+template <int KB>
+__device__ __forceinline__ void load_rows_rm(double (&v)[KB], const double* __restrict__ s, size_t ld, size_t row, bool live, int n, int lq) {
+#pragma unroll
+	for (int kb = 0; kb < KB; kb++) {
+		const int col = 4 * kb + lq;
+		v[kb] = (live && col < n) ? s[row * ld + col] : 0.0;
 	}
 }
 
@@ -232,7 +249,8 @@ struct GramQArgs64 {
 // G(ti, tj) += Q_reg(ti)^T Q_reg(tj) directly: K-step reg sums the rows row0 + 4 reg + {0, 1, 2, 3} -- both operands come from the same
 // lane and register, so they name the same row.  No LDS transpose, no store; output tile jt needs k < 16 (jt + 1) only, as in the apply
 // pass.  Rows >= m and columns >= n enter as zeros.  The partials leave in gram_f64_kernel's layout (wg_sum4_store).
-template <int NT>
+// AROW: A is row-major (a.lda: the row stride).
+template <int NT, bool AROW>
 __global__ __launch_bounds__(256) void gramq_f64_kernel(const GramQArgs64 a) {
 	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1), NTRI = (NT * (NT + 1)) / 2;
 	__shared__ double red[2 * NTRI * 256];
@@ -253,10 +271,13 @@ __global__ __launch_bounds__(256) void gramq_f64_kernel(const GramQArgs64 a) {
 		auto load_tile = [&](double (&av)[KB], int tile) {
 			const size_t row = (size_t)tile * 16 + li;
 			const bool live = tile < a.ntiles && row < a.m;
+			if constexpr (AROW) load_rows_rm<KB>(av, a.a, a.lda, row, live, a.n, lq);
+			else {
 #pragma unroll
-			for (int kb = 0; kb < KB; kb++) {
-				const int col = 4 * kb + lq;
-				av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+				for (int kb = 0; kb < KB; kb++) {
+					const int col = 4 * kb + lq;
+					av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+				}
 			}
 		};
 		double av[KB], nx[KB];
@@ -289,33 +310,6 @@ __global__ __launch_bounds__(256) void gramq_f64_kernel(const GramQArgs64 a) {
 	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NTRI * 256, wv, lane);
 }
 
-// Z <- Z Zk (both NP x NP with ld NP, upper triangular, zero padded; n <= 64), in place: rmul_f64_kernel's scheme on the layout of
-// chol_f64_kernel's Z.  The whole NP x NP block is written (zeros below the diagonal and beyond n).  Every thread has read its entries
-// before the barrier that precedes the first store.
-__global__ __launch_bounds__(1024) void zmul_f64_kernel(double* z, const double* __restrict__ zk, int n, int NP) {
-	__shared__ double A2[64 * 65], A1[64 * 65];          // A2[i * 65 + k] = Z[i][k], A1[k * 65 + j] = Zk[k][j]; zero outside the upper triangles
-	const int t = threadIdx.x;
-#pragma unroll
-	for (int u = 0; u < 4; u++) {
-		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
-		const bool in = i <= j && j < n;
-		A2[i * 65 + j] = in ? z[(size_t)j * NP + i] : 0.0;
-		A1[i * 65 + j] = in ? zk[(size_t)j * NP + i] : 0.0;
-	}
-	__syncthreads();
-	const int w = t >> 6, l = t & 63, ti = w >> 2, tj = w & 3, li = l & 15, lq = l >> 4;
-	f64x4 c = f64x4{0.0, 0.0, 0.0, 0.0};                // c[reg] = (Z Zk)[16 ti + lq + 4 reg][16 tj + li]
-	if (ti <= tj) {
-		for (int ks = 4 * ti; ks < 4 * (tj + 1); ks++)
-			c = __builtin_amdgcn_mfma_f64_16x16x4f64(A2[(16 * ti + li) * 65 + 4 * ks + lq], A1[(4 * ks + lq) * 65 + 16 * tj + li], c, 0, 0, 0);
-	}
-#pragma unroll
-	for (int reg = 0; reg < 4; reg++) {
-		const int i = 16 * ti + lq + 4 * reg, j = 16 * tj + li;
-		if (i < NP && j < NP) z[(size_t)j * NP + i] = (i <= j) ? c[reg] : 0.0;
-	}
-}
-
 // ---- the least-squares entry (tsqr_mi_lstsq_f64): passes over A and B behind the R-only ladder ----------------------------------------
 struct LsqArgs64 {
 	const double* a; size_t lda;
@@ -341,7 +335,9 @@ struct LsqArgs64 {
 //   3  acc[ti] += qt[ti][reg]^T rt[reg] for reg 0 .. 3: the Gram MFMA of gramq_f64_kernel with rt as its second operand -- both come from
 //      the same lane and register, so they name the same row.  Register reg of lane (li, lq) of acc[ti] holds D[16 ti + lq + 4 reg][li].
 // Rows >= m, columns >= n and right-hand sides >= nrhs enter as zeros.  A partial is NT tiles of 256 doubles (wg_sum4_store).
-template <int NT>
+// AROW: A is row-major (a.lda: the row stride); BROW: B is row-major (a.ldb: the row stride).  A row-major B still enters through the
+// identity k-blocks: the products, and the rule that one non-finite entry of B spoils its row, do not depend on the layout.
+template <int NT, bool AROW, bool BROW>
 __global__ __launch_bounds__(256) void lsq_f64_kernel(const LsqArgs64 a) {
 	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1);
 	__shared__ double red[2 * NT * 256];
@@ -368,15 +364,21 @@ __global__ __launch_bounds__(256) void lsq_f64_kernel(const LsqArgs64 a) {
 		auto load_tile = [&](double (&av)[KB], double (&bv)[4], int tile) {
 			const size_t row = (size_t)tile * 16 + li;
 			const bool live = tile < a.ntiles && row < a.m;
+			if constexpr (AROW) load_rows_rm<KB>(av, a.a, a.lda, row, live, a.n, lq);
+			else {
 #pragma unroll
-			for (int kb = 0; kb < KB; kb++) {
-				const int col = 4 * kb + lq;
-				av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+				for (int kb = 0; kb < KB; kb++) {
+					const int col = 4 * kb + lq;
+					av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+				}
 			}
+			if constexpr (BROW) load_rows_rm<4>(bv, a.b, a.ldb, row, live, a.nrhs, lq);
+			else {
 #pragma unroll
-			for (int kb = 0; kb < 4; kb++) {
-				const int col = 4 * kb + lq;
-				bv[kb] = (live && col < a.nrhs) ? a.b[(size_t)col * a.ldb + row] : 0.0;
+				for (int kb = 0; kb < 4; kb++) {
+					const int col = 4 * kb + lq;
+					bv[kb] = (live && col < a.nrhs) ? a.b[(size_t)col * a.ldb + row] : 0.0;
+				}
 			}
 		};
 		double av[KB], nx[KB], bv[4], nb[4];
@@ -428,153 +430,6 @@ __global__ __launch_bounds__(1024) void lsq_update_f64_kernel(double* xw, double
 		if (last) x[(size_t)j * ldx + i] = v;
 	}
 	xw[(size_t)j * NP + i] = v;
-}
-
-// ---- row-major A and B (tsqr_mi_r_f64_lay, tsqr_mi_lstsq_f64_lay) ---------------------------------------------------------------------
-// Element (i, j) of a row-major operand lies at s[i * ld + j], ld >= the column count.  The kernels below are gramq_f64_kernel and
-// lsq_f64_kernel with another address for the same register: at every MFMA lane (li, lq) of k-block kb holds S[row0 + li][4 kb + lq], as
-// there, so every partial -- and behind the unchanged reduction R, X and the sweep count -- has the bits of the column-major kernel on
-// the transposed copy.  (Sweep 0: gram_f64_rm_kernel above.)
-
-// v[kb] = S[row][4 kb + lq] for kb < KB from a row-major S; zero where the row is not live or the column is >= n (neither is read).
-// The direct address: one load instruction reads sixteen 32-byte pieces, one per row, and the four k-blocks 4 g .. 4 g + 3 together use
-// every byte of the 128-byte lines they touch.  Measured against wide loads with a 4 x 4 exchange between the four lane quarters
-// (v_permlane32_swap, v_permlane16_swap), which was slower: DESIGN.md section 9 has both figures.
-template <int KB>
-__device__ __forceinline__ void load_rows_rm(double (&v)[KB], const double* __restrict__ s, size_t ld, size_t row, bool live, int n, int lq) {
-#pragma unroll
-	for (int kb = 0; kb < KB; kb++) {
-		const int col = 4 * kb + lq;
-		v[kb] = (live && col < n) ? s[row * ld + col] : 0.0;
-	}
-}
-
-// gramq_f64_kernel on a row-major A (a.lda: the row stride): its text but for load_tile
-template <int NT>
-__global__ __launch_bounds__(256) void gramq_f64_rm_kernel(const GramQArgs64 a) {
-	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1), NTRI = (NT * (NT + 1)) / 2;
-	__shared__ double red[2 * NTRI * 256];
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
-	const int gw = blockIdx.x * 4 + wv;
-	f64x4 acc[NTRI];
-#pragma unroll
-	for (int t = 0; t < NTRI; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-	if (gw < a.nwaves) {
-		double zop[NZ];
-		static_for<0, NT>([&](auto jt_) {
-			constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
-#pragma unroll
-			for (int kb = 0; kb < 4 * (jt + 1); kb++) zop[base + kb] = a.z[(size_t)(16 * jt + li) * NP + 4 * kb + lq];
-		});
-		auto load_tile = [&](double (&av)[KB], int tile) {
-			const size_t row = (size_t)tile * 16 + li;
-			load_rows_rm<KB>(av, a.a, a.lda, row, tile < a.ntiles && row < a.m, a.n, lq);
-		};
-		double av[KB], nx[KB];
-		load_tile(av, gw);
-		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
-			load_tile(nx, tile + a.nwaves);
-			f64x4 qt[NT];
-			static_for<0, NT>([&](auto jt_) {
-				constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
-				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-				for (int kb = 0; kb < 4 * (jt + 1); kb++)
-					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zop[base + kb], qt[jt], 0, 0, 0);
-			});
-#pragma unroll
-			for (int reg = 0; reg < 4; reg++) {
-				int idx = 0;
-#pragma unroll
-				for (int ti = 0; ti < NT; ti++)
-#pragma unroll
-					for (int tj = ti; tj < NT; tj++) {
-						acc[idx] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], qt[tj][reg], acc[idx], 0, 0, 0);
-						idx++;
-					}
-			}
-#pragma unroll
-			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
-		}
-	}
-	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NTRI * 256, wv, lane);
-}
-
-// lsq_f64_kernel with A row-major (AROW; a.lda: the row stride), B row-major (BROW; a.ldb: the row stride) or both: its text but for
-// load_tile.  A row-major B still enters through the identity k-blocks: the products, and the rule that one non-finite entry of B spoils
-// its row, stay those of lsq_f64_kernel.
-template <int NT, bool AROW, bool BROW>
-__global__ __launch_bounds__(256) void lsq_f64_lay_kernel(const LsqArgs64 a) {
-	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1);
-	__shared__ double red[2 * NT * 256];
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
-	const int gw = blockIdx.x * 4 + wv;
-	f64x4 acc[NT];
-#pragma unroll
-	for (int t = 0; t < NT; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-	if (gw < a.nwaves) {
-		double zop[NZ], xop[KB], idop[4];
-		static_for<0, NT>([&](auto jt_) {
-			constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
-#pragma unroll
-			for (int kb = 0; kb < 4 * (jt + 1); kb++) zop[base + kb] = a.z[(size_t)(16 * jt + li) * NP + 4 * kb + lq];
-		});
-#pragma unroll
-		for (int kb = 0; kb < KB; kb++) {
-			const int row = 4 * kb + lq;
-			xop[kb] = -((a.x && row < a.n && li < a.nrhs) ? a.x[(size_t)li * NP + row] : 0.0);
-		}
-#pragma unroll
-		for (int kb = 0; kb < 4; kb++) idop[kb] = (4 * kb + lq == li) ? 1.0 : 0.0;
-		auto load_tile = [&](double (&av)[KB], double (&bv)[4], int tile) {
-			const size_t row = (size_t)tile * 16 + li;
-			const bool live = tile < a.ntiles && row < a.m;
-			if constexpr (AROW) load_rows_rm<KB>(av, a.a, a.lda, row, live, a.n, lq);
-			else {
-#pragma unroll
-				for (int kb = 0; kb < KB; kb++) {
-					const int col = 4 * kb + lq;
-					av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
-				}
-			}
-			if constexpr (BROW) load_rows_rm<4>(bv, a.b, a.ldb, row, live, a.nrhs, lq);
-			else {
-#pragma unroll
-				for (int kb = 0; kb < 4; kb++) {
-					const int col = 4 * kb + lq;
-					bv[kb] = (live && col < a.nrhs) ? a.b[(size_t)col * a.ldb + row] : 0.0;
-				}
-			}
-		};
-		double av[KB], nx[KB], bv[4], nb[4];
-		load_tile(av, bv, gw);
-		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
-			load_tile(nx, nb, tile + a.nwaves);
-			f64x4 qt[NT];
-			static_for<0, NT>([&](auto jt_) {
-				constexpr int jt = decltype(jt_)::value, base = 2 * jt * (jt + 1);
-				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-				for (int kb = 0; kb < 4 * (jt + 1); kb++)
-					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zop[base + kb], qt[jt], 0, 0, 0);
-			});
-			f64x4 rt = f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-			for (int kb = 0; kb < 4; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[kb], idop[kb], rt, 0, 0, 0);
-#pragma unroll
-			for (int kb = 0; kb < KB; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], xop[kb], rt, 0, 0, 0);
-#pragma unroll
-			for (int reg = 0; reg < 4; reg++)
-#pragma unroll
-				for (int ti = 0; ti < NT; ti++)
-					acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], rt[reg], acc[ti], 0, 0, 0);
-#pragma unroll
-			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
-#pragma unroll
-			for (int kb = 0; kb < 4; kb++) bv[kb] = nb[kb];
-		}
-	}
-	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NT * 256, wv, lane);
 }
 
 }  // namespace tsqrmi

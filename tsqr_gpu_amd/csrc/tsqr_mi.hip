@@ -2459,7 +2459,7 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
                bool first, int slot, const Comm* comm = nullptr, int layout = TSQR_MI_COL_MAJOR) {
 	const F64Plan g = f64_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
-	const tsqrmi::GramArgs64 ga{src, ld, m, (int)n, g.nch, g.nwaves, wr};
+	const tsqrmi::GramArgs64 ga{src, ld, m, (int)n, g.nunits, g.nwaves, wr};
 	f64_gram_launch(st, g, ga, layout);
 	HIPCHK(hipGetLastError());
 	const int nelem = g.ntri * 256;
@@ -2495,7 +2495,7 @@ int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, 
 	const double* z = wq + F64_Z;
 	rc = with_nt((int)(np_of(n) / 16), [&](auto nt) { return f64_apply<decltype(nt)::value>(st, dev, q, ldq, src, lds, m, n, z); });
 	if (rc || first) return rc;
-	hipLaunchKernelGGL(tsqrmi::rmul_f64_kernel, dim3(1), dim3(1024), 0, st, r, ldr, wq + F64_R2, (int)n);
+	f64_rmul_launch(st, r, ldr, wq + F64_R2, (int)n);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -2558,6 +2558,15 @@ int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double
 	});
 }
 
+// Z_acc = Z_1 ... Z_k, the inverse of R after k sweeps, from Z_k in wq[F64_Z]: a copy for k = 1, else Z_acc <- Z_acc Z_k (trimul_f64_kernel)
+int f64r_zacc(hipStream_t st, int k, double* wq, size_t n) {
+	const size_t NP = np_of(n);
+	if (k == 1) HIPCHK(hipMemcpyAsync(wq + F64R_ZACC, wq + F64_Z, NP * NP * sizeof(double), hipMemcpyDeviceToDevice, st));
+	else f64r_zmul_launch(st, wq + F64R_ZACC, wq + F64_Z, (int)n);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
 // Sweep k (0-based) of the R-only entry.  Sweep 0 is f64_factor on A: R_1 -> r, Z_1 -> wq[F64_Z].  Sweep k >= 1 never forms Q: first
 // Z_acc = Z_1 ... Z_k (sweep 1: a copy of Z_1; later: Z_acc <- Z_acc Z_k, with the Z_k that sweep k - 1 left in wq[F64_Z]), then the Gram
 // matrix of A Z_acc straight from A (gramq_f64_kernel), the reduction, the Cholesky step of a later sweep (R_(k+1) -> wq[F64_R2],
@@ -2565,20 +2574,17 @@ int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double
 // other launch is the same.
 int f64r_sweep(hipStream_t st, int k, double* r, size_t ldr, int a_layout, const double* a, size_t lda, size_t m, size_t n, double* wq, double* wr) {
 	if (k == 0) return f64_factor(st, wq, wr, a, lda, m, n, r, ldr, true, 0, nullptr, a_layout);
-	const size_t NP = np_of(n);
 	double* zacc = wq + F64R_ZACC;
-	if (k == 1) HIPCHK(hipMemcpyAsync(zacc, wq + F64_Z, NP * NP * sizeof(double), hipMemcpyDeviceToDevice, st));
-	else hipLaunchKernelGGL(tsqrmi::zmul_f64_kernel, dim3(1), dim3(1024), 0, st, zacc, (const double*)(wq + F64_Z), (int)n, (int)NP);
-	HIPCHK(hipGetLastError());
-	const F64RPlan g = f64r_plan(m, n);
+	if (const int rc = f64r_zacc(st, k, wq, n)) return rc;
+	const F64Plan g = f64r_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
-	const tsqrmi::GramQArgs64 ga{a, lda, m, (int)n, g.ntiles, g.nwaves, zacc, wr};
+	const tsqrmi::GramQArgs64 ga{a, lda, m, (int)n, g.nunits, g.nwaves, zacc, wr};
 	f64r_gramq_launch(st, g, ga, a_layout);
 	HIPCHK(hipGetLastError());
 	launch_reduce1(st, wq + F64_GSUM, wr, g.nblocks, g.ntri * 256, (double)m);
 	HIPCHK(hipGetLastError());
 	if (const int rc = f64_chol(st, wq, m, n, wq + F64_R2, 64, false, k & 3, nullptr)) return rc;
-	hipLaunchKernelGGL(tsqrmi::rmul_f64_kernel, dim3(1), dim3(1024), 0, st, r, ldr, wq + F64_R2, (int)n);
+	f64_rmul_launch(st, r, ldr, wq + F64_R2, (int)n);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -2589,21 +2595,19 @@ int r_f64_core(int a_layout, int reorth, double* r, size_t ldr, const double* a,
 }
 
 // The least-squares entry behind the R-only ladder (corrected semi-normal equations carried out in Q-space; include/tsqr_mi.h).  The
-// ladder's last sweep s left Z_1 ... Z_(s-1) in wq[F64R_ZACC] (nothing for s = 1) and Z_s in wq[F64_Z]: one copy or one zmul_f64_kernel
-// completes Z = inverse(R).  Then refine + 1 passes, each lsq_f64_kernel (D = (A Z)^T (B - A X), X null the first time), the reduction
+// ladder's last sweep s left Z_1 ... Z_(s-1) in wq[F64R_ZACC] (nothing for s = 1) and Z_s in wq[F64_Z]: one copy or one product
+// (f64r_zacc) completes Z = inverse(R).  Then refine + 1 passes, each lsq_f64_kernel (D = (A Z)^T (B - A X), X null the first time), the reduction
 // and X <- X + Z D, enqueued back to back; one wait at the end.
 int lstsq_f64_core(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
                    const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, double* wq, double* wr, hipStream_t st) {
 	if (const int rc = r_f64_core(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, st)) return rc;
 	const size_t NP = np_of(n);
 	double *zacc = wq + F64R_ZACC, *xw = wq + F64L_X, *dsum = wq + F64L_D;
-	if (t_sweeps64 % 100 == 1) HIPCHK(hipMemcpyAsync(zacc, wq + F64_Z, NP * NP * sizeof(double), hipMemcpyDeviceToDevice, st));
-	else hipLaunchKernelGGL(tsqrmi::zmul_f64_kernel, dim3(1), dim3(1024), 0, st, zacc, (const double*)(wq + F64_Z), (int)n, (int)NP);
-	HIPCHK(hipGetLastError());
-	const F64RPlan g = f64r_plan(m, n);
+	if (const int rc = f64r_zacc(st, t_sweeps64 % 100, wq, n)) return rc;
+	const F64Plan g = f64r_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 least-squares pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
 	for (int p = 0; p <= refine; p++) {
-		const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, (int)n, (int)nrhs, g.ntiles, g.nwaves, zacc, p == 0 ? nullptr : xw, wr};
+		const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, (int)n, (int)nrhs, g.nunits, g.nwaves, zacc, p == 0 ? nullptr : xw, wr};
 		f64r_lsq_launch(st, g, la, a_layout, b_layout);
 		HIPCHK(hipGetLastError());
 		launch_reduce1(st, dsum, wr, g.nblocks, g.NT * 256, (double)m);
