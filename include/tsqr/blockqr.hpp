@@ -323,6 +323,14 @@ struct buffer_fp64 {
 	std::size_t get_device_memory_size() const { return total_memory_size; }
 };
 
+// layout_t: how a (for qr_fp64 also q, for lstsq_fp64 also b) is stored.  row_major: element (i, j) at ptr[i * ld + j], ld >= the column
+// count, read (q: written) where it lies (tsqr_mi_qr_f64_lay / tsqr_mi_r_f64_lay / tsqr_mi_lstsq_f64_lay); r and x stay column-major, and
+// every result has the bits of the column-major call on the same matrix.
+using layout_t = int;
+const layout_t col_major = TSQR_MI_COL_MAJOR;
+const layout_t row_major = TSQR_MI_ROW_MAJOR;
+
+// a_layout, q_layout: the layouts of a and of q (they need not agree; in place, q_ptr == a_ptr, needs equal layouts and ldq == lda)
 template <bool Reorthogonalize>
 inline state_t qr_fp64(
 		double* const q_ptr, const std::size_t ldq,
@@ -330,8 +338,9 @@ inline state_t qr_fp64(
 		double* const a_ptr, const std::size_t lda,
 		const std::size_t m, const std::size_t n,
 		buffer_fp64<Reorthogonalize>& bf,
-		handle_t const stream = nullptr) {
-	const int st = tsqr_mi_qr_f64(Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major, const layout_t q_layout = col_major) {
+	const int st = tsqr_mi_qr_f64_lay(a_layout, q_layout, Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
@@ -369,12 +378,6 @@ struct buffer_fp64_r {
 
 	std::size_t get_device_memory_size() const { return total_memory_size; }
 };
-
-// layout_t: how a (and, for lstsq_fp64, b) is stored.  row_major: element (i, j) at ptr[i * ld + j], ld >= the column count, read where it
-// lies (tsqr_mi_r_f64_lay / tsqr_mi_lstsq_f64_lay); r and x stay column-major and have the bits of the column-major call on the same matrix.
-using layout_t = int;
-const layout_t col_major = TSQR_MI_COL_MAJOR;
-const layout_t row_major = TSQR_MI_ROW_MAJOR;
 
 template <bool Reorthogonalize>
 inline state_t r_fp64(

@@ -410,6 +410,29 @@ int tsqr_mi_lstsq_f64_lay(int a_layout, int b_layout, int reorth, int refine, do
                           size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
 
 /*
+ * tsqr_mi_qr_f64 on operands in either layout (not in the reference): a_layout is how A is stored, q_layout how Q is written, each
+ * TSQR_MI_COL_MAJOR (element (i, j) at p[i + j * ld], ld >= m) or TSQR_MI_ROW_MAJOR (element (i, j) at p[i * ld + j], ld >= n -- a
+ * contiguous C or torch array of shape (m, n)); the two need not agree.  R is column-major as above.  The work space is that of
+ * tsqr_mi_working_{q,r}_size_f64.  No copy of A or Q is made; nothing between n and the leading dimension of a row-major operand, or
+ * behind row m, is read or written.  1 <= n <= 64, n <= m.
+ * Sweep 1 reads A in a_layout (the Gram pass, then the apply pass, which writes Q in q_layout); later sweeps read and write Q in
+ * q_layout, in place (gram_f64_kernel and apply_f64_kernel with their layout flags, tsqr_f64.hip).
+ * Bit-for-bit relation: the row-major kernels put the values of A into the registers the column-major kernels hold them in, on the same
+ * launch plans, and a row-major Q is formed by the same products summed in the same order (the MFMA operands swapped: apply_f64_kernel),
+ * so Q -- read as a matrix --, R, the state and tsqr_mi_last_sweeps_f64 are BITWISE those of tsqr_mi_qr_f64 on a column-major copy of
+ * the same matrix, for all four layout pairs.  With both layouts TSQR_MI_COL_MAJOR the call IS tsqr_mi_qr_f64 (which calls this one).
+ * The accuracy bands, the ladder and the non-finite rules of tsqr_mi_qr_f64 hold unchanged.  In place as there: q == a is allowed with
+ * a_layout == q_layout and ldq == lda; Q and R must not overlap A otherwise, nor each other.
+ * Column-major only: the wide entry (tsqr_mi_qr_f64_wide beyond n = 64) and the row-partitioned entries (tsqr_mi_qr_f64_dist*) below
+ * take no layout.
+ * Returns what tsqr_mi_qr_f64 returns; 1 also for a layout other than 0 or 1, for a row-major operand with a leading dimension below
+ * n (not below m), and for q == a with different layouts or ldq != lda; 2 for n > 64 (tsqr_mi_last_error says so).  Arguments are
+ * checked before any HIP call.
+ */
+int tsqr_mi_qr_f64_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                       size_t m, size_t n, void* wq, void* wr, void* stream);
+
+/*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
  * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
  * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column

@@ -18,7 +18,11 @@ entry on row-major operands, (ii) the column-major entry on operands transposed 
 (t().contiguous().t(), allocation included: what lstsq_f64 did to a contiguous tensor before the layout entries) followed by the
 column-major entry.  Arm (ii) runs three times per round: the max / min of its three medians is the spread a ratio has to be read
 against.  Per arm the median of --calls blocking calls; the ratios i / ii and i / iii; whether R and X of (i) are bitwise those of (ii).
-Redirect the JSON line (profiles/fp64_rowmajor_speed.json)."""
+Redirect the JSON line (profiles/fp64_rowmajor_speed.json).
+--qr-row-major: instead, the full QR's layout entry (tsqr_mi_qr_f64_lay, reorth 0 and 1) at the shapes and under the protocol of
+--row-major: (i) the layout entry on row-major A and Q, (ii) tsqr_mi_qr_f64 on operands transposed beforehand, (iii) the transposing
+copy of A (t().contiguous().t()), tsqr_mi_qr_f64 and a transposing copy of Q back into row-major storage, waited for.  Asserts that Q
+and R of (i) are bitwise those of (ii) in every case.  Redirect the JSON line (profiles/fp64_qr_rowmajor_speed.json)."""
 import argparse
 import json
 import math
@@ -264,6 +268,68 @@ def row_major(torch, bq, calls, warmup):
     print(json.dumps(out))
 
 
+def qr_row_major(torch, bq, calls, warmup):
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    out = {"tool": "f64_speed --qr-row-major", "calls": calls, "warmup": warmup, "cases": []}
+    for lg, n in ((16, 64), (20, 64), (23, 64), (20, 16)):
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a_rm = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g)        # row-major m x n
+        a_cm = a_rm.t().contiguous()                                                       # (n, m): column-major m x n
+        q_rm, q_cm = torch.empty_like(a_rm), torch.empty_like(a_cm)
+        r = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(2)]
+        wq = torch.empty(L.tsqr_mi_working_q_size_f64(m, n), dtype=torch.float64, device="cuda")
+        wr = torch.empty(L.tsqr_mi_working_r_size_f64(m, n), dtype=torch.float64, device="cuda")
+        work = (vp(wq.data_ptr()), vp(wr.data_ptr()), vp(torch.cuda.current_stream().cuda_stream))
+
+        def call(lay, q, a, ld, reorth, k):
+            return L.tsqr_mi_qr_f64_lay(lay, lay, reorth, vp(q.data_ptr()), ld, vp(r[k].data_ptr()), n, vp(a.data_ptr()), ld, m, n, *work)
+
+        def copy_in_out(reorth):
+            a_c = a_rm.t().contiguous()                     # (the copy is enqueued on the stream of the call behind it)
+            rc = call(0, q_cm, a_c, m, reorth, 1)
+            q_out = q_cm.t().contiguous()                   # Q back in the caller's layout
+            torch.cuda.synchronize()
+            del q_out
+            return rc
+
+        for reorth in (0, 1):
+            ii = lambda: call(0, q_cm, a_cm, m, reorth, 1)
+            arms = [("i_row_major", lambda: call(1, q_rm, a_rm, n, reorth, 0)), ("ii_col_major", ii),
+                    ("iii_copy_in_col_major_copy_out", lambda: copy_in_out(reorth)),
+                    ("ii_col_major_again", ii), ("ii_col_major_third", ii)]
+            ts = {name: [] for name, _ in arms}
+            for i in range(warmup + calls):
+                for name, fn in arms:
+                    t0 = time.perf_counter()
+                    rc = fn()                               # (blocking: returns when the stream has drained)
+                    dt = time.perf_counter() - t0
+                    assert rc == 0, bq.last_error()
+                    if i >= warmup:
+                        ts[name].append(dt)
+            med = {k: sorted(v)[len(v) // 2] * 1e3 for k, v in ts.items()}
+            ii_meds = [med["ii_col_major"], med["ii_col_major_again"], med["ii_col_major_third"]]
+            arms[1][1]()
+            sweeps_ii = bq.last_sweeps_f64()
+            arms[0][1]()
+            sweeps_i = bq.last_sweeps_f64()
+            q_equal, r_equal = bool(torch.equal(q_rm, q_cm.t())), bool(torch.equal(r[0], r[1]))
+            assert q_equal and r_equal and sweeps_i == sweeps_ii, (m, n, reorth, q_equal, r_equal, sweeps_i, sweeps_ii)
+            out["cases"].append({"m": m, "n": n, "call": "qr_f64_reorth%d" % reorth, "sweeps": sweeps_i,
+                                 "i_row_major_median_ms": med["i_row_major"], "ii_col_major_median_ms": sorted(ii_meds)[1],
+                                 "iii_copy_in_col_major_copy_out_median_ms": med["iii_copy_in_col_major_copy_out"],
+                                 "ii_medians_ms": ii_meds, "ii_spread_max_over_min": max(ii_meds) / min(ii_meds),
+                                 "ratio_i_over_ii": med["i_row_major"] / sorted(ii_meds)[1],
+                                 "ratio_i_over_iii": med["i_row_major"] / med["iii_copy_in_col_major_copy_out"],
+                                 "i_faster_than_iii": bool(med["i_row_major"] < med["iii_copy_in_col_major_copy_out"]),
+                                 "q_bitwise_equal": q_equal, "r_bitwise_equal": r_equal})
+        del a_rm, a_cm, q_rm, q_cm, r, wq, wr
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def dist1(torch, bq, calls, warmup):
     import ctypes
     rccl = ctypes.CDLL("librccl.so")
@@ -320,6 +386,7 @@ def main():
     ap.add_argument("--r-only", action="store_true", help="time tsqr_mi_r_f64 next to tsqr_mi_qr_f64 on the same operands")
     ap.add_argument("--lstsq", action="store_true", help="time tsqr_mi_lstsq_f64 next to tsqr_mi_r_f64 and torch.linalg.lstsq")
     ap.add_argument("--row-major", action="store_true", help="time the layout entries on row-major operands next to the column-major entries")
+    ap.add_argument("--qr-row-major", action="store_true", help="time tsqr_mi_qr_f64_lay on row-major A and Q next to tsqr_mi_qr_f64")
     ap.add_argument("--dist1", action="store_true", help="time the one-rank row-partitioned call over raw RCCL next to the plain entry")
     args = ap.parse_args()
     import torch
@@ -332,6 +399,8 @@ def main():
         return lstsq(torch, bq, args.calls, args.warmup)
     if args.row_major:
         return row_major(torch, bq, args.calls, args.warmup)
+    if args.qr_row_major:
+        return qr_row_major(torch, bq, args.calls, args.warmup)
     n = 64
     out = {"tool": "f64_speed", "cases": []}
     gauss = lambda m, seed: torch.randn(m, n, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(seed))

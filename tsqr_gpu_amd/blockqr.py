@@ -56,7 +56,7 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
     "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
     "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
-    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay",
+    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay",
 ]
 
 COL_MAJOR, ROW_MAJOR = 0, 1              # TSQR_MI_COL_MAJOR, TSQR_MI_ROW_MAJOR: the layout arguments of the *_lay entries
@@ -217,6 +217,9 @@ def lib():
         L.tsqr_mi_r_f64_lay.argtypes = [ci] + L.tsqr_mi_r_f64.argtypes
         L.tsqr_mi_lstsq_f64_lay.restype = ci
         L.tsqr_mi_lstsq_f64_lay.argtypes = [ci, ci] + L.tsqr_mi_lstsq_f64.argtypes
+    if hasattr(L, "tsqr_mi_qr_f64_lay"):                 # (as above: an older build factors column-major operands only)
+        L.tsqr_mi_qr_f64_lay.restype = ci
+        L.tsqr_mi_qr_f64_lay.argtypes = [ci, ci] + L.tsqr_mi_qr_f64.argtypes
     _lib = L
     return L
 
@@ -501,10 +504,15 @@ def _apart(span, x, y):
     return span[x][1] <= span[y][0] or span[y][1] <= span[x][0]
 
 
-def check_f64_operands(m, n, ldq, ldr, lda, q, r, a):
+def check_f64_operands(m, n, ldq, ldr, lda, q, r, a, row_major=False):
     """The size and overlap rules of qr_f64 on (address, elements) pairs: ld >= rows, room for (n - 1) ld + rows doubles, q either
-    the very operand a (same address and ld: in place) or apart from it, r apart from both.  Raises ValueError."""
-    span = _f64_spans("qr_f64", n, (("q", q, ldq, m), ("r", r, ldr, n), ("a", a, lda, m)))
+    the very operand a (same address and ld: in place) or apart from it, r apart from both.  row_major: q and a are row-major --
+    ld >= n and room for (m - 1) ld + n doubles each (check_f64_r_operands' rule); r stays column-major.  Raises ValueError."""
+    if row_major:
+        span = _f64_spans("qr_f64", n, (("r", r, ldr, n),))
+        span.update(_f64_spans("qr_f64", m, (("q", q, ldq, n), ("a", a, lda, n))))   # (the transposed view: m "columns" of n contiguous elements)
+    else:
+        span = _f64_spans("qr_f64", n, (("q", q, ldq, m), ("r", r, ldr, n), ("a", a, lda, m)))
     if not (q[0] == a[0] and ldq == lda) and not _apart(span, "q", "a"):
         raise ValueError("qr_f64: q overlaps a without being a (in place needs q == a and ldq == lda)")
     for other in ("q", "a"):
@@ -512,10 +520,16 @@ def check_f64_operands(m, n, ldq, ldr, lda, q, r, a):
             raise ValueError("qr_f64: r overlaps %s" % other)
 
 
-def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize):
-    """The body of qr_f64 (entry _F64) and qr_f64_wide (_F64_WIDE)."""
+def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize, row_major=False):
+    """The body of qr_f64 (entry _F64) and qr_f64_wide (_F64_WIDE).  row_major (qr_f64 only): tsqr_mi_qr_f64_lay with q and a row-major."""
     import torch
     name, nmax, qr_fn, wq_fn, wr_fn = entry
+    if row_major:
+        lay_fn = getattr(lib(), qr_fn + "_lay")
+        qr_fn = qr_fn + "_lay"
+        call = lambda *args: lay_fn(ROW_MAJOR, ROW_MAJOR, *args)
+    else:
+        call = getattr(lib(), qr_fn)
     reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
     for opname, t in (("q", q), ("r", r), ("a", a)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
@@ -526,8 +540,9 @@ def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize):
     if n > m or m == 0 or n == 0:
         return error_invalid_matrix_size
     if n > nmax:
-        return getattr(lib(), qr_fn)(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
-    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()))
+        return call(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
+    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()),
+                       row_major=bool(row_major))
     if bf.dwq is None:
         raise RuntimeError("%s: the buffer is not allocated" % name)
     L = lib()
@@ -535,20 +550,24 @@ def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize):
         raise ValueError("%s: the buffer was allocated for a smaller matrix" % name)
     if stream is None:
         stream = torch.cuda.current_stream()
-    st = getattr(L, qr_fn)(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
-                           bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
+    st = call(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
+              bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
     if st < 0:
         raise RuntimeError("%s failed: %s" % (qr_fn, last_error()))
     return st
 
 
-def qr_f64(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
+def qr_f64(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False):
     """Double-precision tall-skinny QR (tsqr_mi_qr_f64), 1 <= n <= 64, n <= m: q, r, a are float64 GPU tensors holding column-major
-    data (only data_ptr and numel are used); q may be a itself (in place, ldq == lda).  Blocking; returns the state: 0,
+    data (only data_ptr and numel are used); q may be a itself (in place, ldq == lda).  row_major=True (tsqr_mi_qr_f64_lay): q and a
+    hold ROW-major data, element (i, j) at i * ld + j with ld >= n -- a contiguous (m, n) tensor with ld = n -- read and written where
+    they lie; r stays column-major, and q, r, the state and the sweep count have the bits of the column-major call on the same matrix.
+    Blocking; returns the state: 0,
     error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite.  Operands are checked before anything is launched:
-    TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a leading dimension below the rows, or overlapping
-    operands.  last_sweeps_f64() tells how many sweeps the call took."""
-    return _qr_f64(_F64, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize)
+    TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a leading dimension below the rows (row-major: below
+    the columns), or overlapping operands.  last_sweeps_f64() tells how many sweeps the call took.  qr_f64_tensor is the same
+    factorisation on a two-dimensional tensor with any strides."""
+    return _qr_f64(_F64, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize, row_major)
 
 
 class buffer_f64_wide(buffer_f64):
@@ -693,6 +712,61 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
         raise LstsqError(st, "lstsq_f64: state %d: %s" % (st, last_error()))
     x = x.t()
     return (x[:, 0] if vector else x), r.t()
+
+
+class QrError(RuntimeError):
+    """qr_f64_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
+
+    def __init__(self, state, text):
+        RuntimeError.__init__(self, text)
+        self.state = state
+
+
+def qr_f64_tensor(a, reorth=False, overwrite_a=False, stream=None):
+    """(q, r) of the double-precision tall-skinny QR (tsqr_mi_qr_f64_lay: include/tsqr_mi.h has the method and the accuracy bands) of a
+    two-dimensional float64 GPU tensor a, m x n with 1 <= n <= 64, n <= m, any strides.  a is read where it lies, without a copy, when
+    its columns are contiguous, when its rows are contiguous (every contiguous torch tensor) or when it has a single column
+    (_operand_f64's rule, as for lstsq_f64); any other a (a[:, ::2], an expanded view) is copied once into column-major storage.
+    q has a's shape, row-major for a row-major a and with column-major strides for a column-major one; r is the n x n upper-triangular
+    factor.  For the same matrix q and r have the same bits whichever way a is stored.  overwrite_a=True: when a is used where it lies,
+    q IS a (the factorisation runs in place); otherwise a is never written.  reorth: CholeskyQR2 at least (qr_f64).  The work space is
+    allocated per call.  Blocking.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for a tensor that is not
+    two-dimensional, QrError (.state) when the C entry returns a state other than 0: sizes it does not support (n > m, an empty a:
+    error_invalid_matrix_size; n > 64: error_unsupported_mode) or error_not_finite from the ladder (Inf or NaN in a, or a
+    rank-deficient a).  last_sweeps_f64() tells how many sweeps the call took."""
+    import torch
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
+        raise TypeError("qr_f64_tensor: a must be a float64 tensor, got %s" % getattr(a, "dtype", type(a).__name__))
+    if not a.is_cuda:
+        raise TypeError("qr_f64_tensor: a is not a GPU tensor")
+    if a.dim() != 2:
+        raise ValueError("qr_f64_tensor: a must be m x n, got %s" % (tuple(a.shape),))
+    m, n = a.shape
+    L = lib()
+    z = ctypes.c_void_p(0)
+    if m == 0 or n == 0 or n > m or n > 64:
+        st = L.tsqr_mi_qr_f64_lay(COL_MAJOR, COL_MAJOR, int(bool(reorth)), z, max(m, 1), z, max(n, 1), z, max(m, 1), m, n, z, z, z)
+        raise QrError(st, "qr_f64_tensor: state %d for a %d x %d%s" % (st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
+    ac, lda, layout = _operand_f64(a)
+    if overwrite_a and ac.data_ptr() == a.data_ptr():
+        q, ldq = a, lda                                    # (in place: the same layout and leading dimension)
+    elif layout == ROW_MAJOR:
+        q, ldq = torch.empty((m, n), dtype=torch.float64, device=a.device), n
+    else:
+        q, ldq = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+    r = torch.empty((n, n), dtype=torch.float64, device=a.device)
+    wq = torch.empty(L.tsqr_mi_working_q_size_f64(m, n), dtype=torch.float64, device=a.device)
+    wr = torch.empty(L.tsqr_mi_working_r_size_f64(m, n), dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        st = L.tsqr_mi_qr_f64_lay(layout, layout, int(bool(reorth)), q.data_ptr(), ldq, r.data_ptr(), n, ac.data_ptr(), lda, m, n,
+                                  wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("tsqr_mi_qr_f64_lay failed: %s" % last_error())
+    if st:
+        raise QrError(st, "qr_f64_tensor: state %d: %s" % (st, last_error()))
+    return q, r.t()
 
 
 def get_working_q_size_f64_dist(m_local, n, nranks):

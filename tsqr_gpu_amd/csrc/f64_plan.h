@@ -59,10 +59,11 @@ inline void f64_gram_launch(hipStream_t st, const F64Plan& g, const tsqrmi::Gram
 	});
 }
 
-// the apply pass of the n <= 64 entry runs on a persistent grid: the workgroups resident at once on device dev ...
-template <int NT> int f64_apply_resident(int dev) {
+// the apply pass of the n <= 64 entry runs on a persistent grid: the workgroups of the instantiation that is launched (AROW, QROW: the
+// layouts of the operand read and of the operand written, tsqr_mi_qr_f64_lay) resident at once on device dev ...
+template <int NT, bool AROW = false, bool QROW = false> int f64_apply_resident(int dev) {
 	int nb = 0, cus = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tsqrmi::apply_f64_kernel<NT>), 256, 0) != hipSuccess || nb < 1) {
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tsqrmi::apply_f64_kernel<NT, AROW, QROW>), 256, 0) != hipSuccess || nb < 1) {
 		(void)hipGetLastError(); nb = 1;
 	}
 	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
@@ -70,6 +71,12 @@ template <int NT> int f64_apply_resident(int dev) {
 }
 // ... but no more than one wave per 32-row block
 inline size_t f64_apply_wgs(size_t nblocks, size_t resident) { return std::max<size_t>(1, std::min(cdiv(nblocks, 4), resident)); }
+// f(nt, arow, qrow) for the instantiation apply_f64_kernel<NT, AROW, QROW> of n columns and the two layouts
+template <class F> inline auto with_apply(size_t n, int a_layout, int q_layout, F&& f) {
+	return with_nt((int)(np_of(n) / 16), [&](auto nt) {
+		return with_layout(a_layout, [&](auto ar) { return with_layout(q_layout, [&](auto qr) { return f(nt, ar, qr); }); });
+	});
+}
 
 // the two uses of trimul_f64_kernel on stream st, both in place: r (n x n, ldr) <- r2 r with r2 packed with ld 64 (the destination is the
 // right factor), and z <- z zk, both NP x NP with ld NP (the destination is the left factor; the whole block is written)

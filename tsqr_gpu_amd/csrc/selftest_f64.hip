@@ -12,17 +12,19 @@ inline int f64_sync() {
 }
 }  // namespace
 
-// apply_f64_kernel<NT>: q = a z (z: NP x NP).  wgs > 0 overrides the grid; 0: the resident workgroups, as f64_apply takes them
+// apply_f64_kernel<NT, AROW, QROW>: q = a z (z: NP x NP).  wgs > 0 overrides the grid; 0: the resident workgroups of that instantiation,
+// as f64_apply takes them
 namespace {
-template <int NT> int selftest_f64_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* z, int wgs_over) {
+template <int NT, bool AROW, bool QROW>
+int selftest_f64_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* z, int wgs_over) {
 	const size_t nblocks = cdiv(m, 32);
 	size_t wgs = (size_t)wgs_over;
 	if (wgs_over <= 0) {
 		int dev = 0;
 		(void)hipGetDevice(&dev);
-		wgs = f64_apply_wgs(nblocks, (size_t)f64_apply_resident<NT>(dev));
+		wgs = f64_apply_wgs(nblocks, (size_t)f64_apply_resident<NT, AROW, QROW>(dev));
 	}
-	hipLaunchKernelGGL(tsqrmi::apply_f64_kernel<NT>, dim3((unsigned)wgs), dim3(256), 0, 0, q, ldq, a, lda, m, n, z, nblocks);
+	hipLaunchKernelGGL((tsqrmi::apply_f64_kernel<NT, AROW, QROW>), dim3((unsigned)wgs), dim3(256), 0, 0, q, ldq, a, lda, m, n, z, nblocks);
 	return f64_sync();
 }
 }  // namespace
@@ -120,9 +122,20 @@ int tsqr_selftest_f64_chol(double* r, size_t ldr, double* z, unsigned* status, u
 	return f64_sync();
 }
 
+// The apply pass in two forms, like the Gram entries above: _lay takes the layout of the operand read and of the operand written (1:
+// row-major, the leading dimension is then the row stride, >= n); the plain entry is _lay at layouts 0.  q == a (in place) needs equal
+// layouts and leading dimensions.
+int tsqr_selftest_f64_apply_lay(int a_layout, int q_layout, double* q, size_t ldq, const double* a, size_t lda, size_t m, int n,
+                                const double* z, int wgs) {
+	if ((a_layout != 0 && a_layout != 1) || (q_layout != 0 && q_layout != 1)) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || lda < (a_layout ? (size_t)n : m) || ldq < (q_layout ? (size_t)n : m) || wgs > 65535) return -100;
+	if (q == a && (a_layout != q_layout || ldq != lda)) return -100;
+	return with_apply((size_t)n, a_layout, q_layout, [&](auto nt, auto ar, auto qr) {
+		return selftest_f64_apply<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(q, ldq, a, lda, m, n, z, wgs);
+	});
+}
 int tsqr_selftest_f64_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* z, int wgs) {
-	if (m == 0 || n <= 0 || n > (int)PW || lda < m || ldq < m || wgs > 65535) return -100;
-	return with_nt((int)(np_of((size_t)n) / 16), [&](auto nt) { return selftest_f64_apply<decltype(nt)::value>(q, ldq, a, lda, m, n, z, wgs); });
+	return tsqr_selftest_f64_apply_lay(0, 0, q, ldq, a, lda, m, n, z, wgs);
 }
 
 // trimul_f64_kernel as f64_sweep launches it: r <- r2 r (r2 packed with ld 64), in place

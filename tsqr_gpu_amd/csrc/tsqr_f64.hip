@@ -12,11 +12,12 @@
 // and of the least-squares entry (tsqr_mi_lstsq_f64), whose passes behind that ladder stream A and B and store nothing of size m:
 //   lsq_f64_kernel        : per-workgroup partials of (A Z)^T (B - A X), each 16-row block of A Z and of the residual held in registers
 //   lsq_update_f64_kernel : X <- X + Z D on one workgroup
-// The three passes that read A (and B) take the layout of each operand as a template flag (AROW, BROW: tsqr_mi_r_f64_lay,
-// tsqr_mi_lstsq_f64_lay).  Element (i, j) of a row-major operand lies at s[i * ld + j], ld >= the column count.  A row-major kernel is the
-// column-major one with another address for the same register: at every MFMA lane (li, lq) of k-block kb holds S[row0 + li][4 kb + lq]
-// in both, so every partial -- and behind the unchanged reduction R, X and the sweep count -- has the bits of the column-major kernel on
-// the transposed copy.
+// The four passes that read A (and B) take the layout of each operand as a template flag (AROW, BROW: tsqr_mi_r_f64_lay,
+// tsqr_mi_lstsq_f64_lay, tsqr_mi_qr_f64_lay).  Element (i, j) of a row-major operand lies at s[i * ld + j], ld >= the column count.  A
+// row-major kernel is the column-major one with another address for the same register: at every MFMA lane (li, lq) of k-block kb holds
+// S[row0 + li][4 kb + lq] in both, so every partial -- and behind the unchanged reduction R, X and the sweep count -- has the bits of the
+// column-major kernel on the transposed copy.  The apply pass also takes the layout of the operand it WRITES (QROW, tsqr_mi_qr_f64_lay):
+// that one swaps the MFMA operands, which changes no bit either (apply_f64_kernel says why).
 #include <hip/hip_runtime.h>
 
 namespace tsqrmi {
@@ -132,14 +133,38 @@ __global__ __launch_bounds__(1024) void chol_f64_kernel(const CholArgs64 a) {
 	}
 }
 
-// Q = A Z, Z (ld NP) upper triangular.  Each wave owns 32-row blocks (two 16-row tiles; a persistent grid strides over them) and
-// computes Q^T tile by tile: D[j][r] = sum_k Z[k][j] A[r][k] -- MFMA operand A is Z^T (lane (li, lq) holds Z[4 kb + lq][16 jt + li]),
-// operand B is A^T (lane (li, lq) holds A[row0 + li][4 kb + lq]), so the C/D layout (col = lane & 15, row = (lane >> 4) + 4 reg)
-// puts sixteen consecutive ROWS of one column of Q in sixteen lanes: every load and store moves whole 128-byte column segments.
+// v[kb] = S[row][4 kb + lq] for kb < KB from a ROW-major S (ld: the row stride), the registers the column-major loops of apply_f64_kernel,
+// gramq_f64_kernel and lsq_f64_kernel fill; zero where the row is not live or the column is >= n (neither is read).
+// The direct address: one load instruction reads sixteen 32-byte pieces, one per row, and the four k-blocks 4 g .. 4 g + 3 together use
+// every byte of the 128-byte lines they touch.  Measured against wide loads with a 4 x 4 exchange between the four lane quarters
+// (v_permlane32_swap, v_permlane16_swap), which was slower: DESIGN.md section 9 has both figures.
+template <int KB>
+__device__ __forceinline__ void load_rows_rm(double (&v)[KB], const double* __restrict__ s, size_t ld, size_t row, bool live, int n, int lq) {
+#pragma unroll
+	for (int kb = 0; kb < KB; kb++) {
+		const int col = 4 * kb + lq;
+		v[kb] = (live && col < n) ? s[row * ld + col] : 0.0;
+	}
+}
+
+// Q = A Z, Z (ld NP) upper triangular.  Each wave owns 32-row blocks (two 16-row tiles; a persistent grid strides over them).  Both
+// register sets are the same for every layout: zop, lane (li, lq) holds Z[4 kb + lq][16 jt + li]; av, lane (li, lq) holds
+// A[row0 + li][4 kb + lq].  AROW: A is row-major (lda: the row stride, >= n) -- load_rows_rm fills the registers the column-major loop
+// fills.  QROW: Q is row-major (ldq: the row stride, >= n).  The layout of Q picks the ORDER of the MFMA operands, so that every store
+// moves whole 128-byte segments:
+//   column-major Q  D[j][r] = sum_k Z[k][j] A[r][k]: operand A is Z^T, operand B is A^T, and the C/D layout (col = lane & 15,
+//                   row = (lane >> 4) + 4 reg) puts sixteen consecutive ROWS of one column of Q in sixteen lanes;
+//   row-major Q     D[r][j] = sum_k A[r][k] Z[k][j], the operands swapped (gramq_f64_kernel's first stage): register reg of lane
+//                   (li, lq) holds Q[row0 + lq + 4 reg][16 jt + li], sixteen consecutive COLUMNS of one row in sixteen lanes, and one
+//                   store instruction writes four 128-byte row segments.
+// Either order forms, for every entry of Q, the accumulator plus the same four products k = 0 .. 3 of the same k-block -- the swap
+// transposes the tile and exchanges the factors of each product, and IEEE multiplication is commutative -- so Q has the same bits for
+// all four layout pairs (tests/test_gpu_f64_apply_rowmajor_passes.py compares them on the device).
 // Output tile jt needs k < 16 (jt + 1) only: 2 NT (NT + 1) k-blocks of Z instead of 4 NT^2, held in registers for the whole kernel.
-// In place (q == a, ldq == lda) is safe: a wave reads all n columns of its rows before it writes any of them (every stored column
-// block depends on the loads of its own columns), and no two waves share a row.
-template <int NT>
+// In place (q == a, the same layout, ldq == lda) is safe: a wave reads all n columns of its rows before it writes any of them (every
+// stored block depends on the loads of its own rows and columns), no two waves share a row, and rows of a row-major operand with
+// ld >= n do not overlap.  Nothing at a row >= m or at a column between n and the leading dimension is read or written.
+template <int NT, bool AROW, bool QROW>
 __global__ __launch_bounds__(256) void apply_f64_kernel(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n,
                                                         const double* __restrict__ z, size_t nblocks) {
 	constexpr int NP = 16 * NT, KB = 4 * NT, NZ = 2 * NT * (NT + 1);
@@ -157,10 +182,13 @@ __global__ __launch_bounds__(256) void apply_f64_kernel(double* q, size_t ldq, c
 #pragma unroll
 		for (int rt = 0; rt < 2; rt++) {
 			const size_t row = row0 + 16 * rt + li;
+			if constexpr (AROW) load_rows_rm<KB>(av[rt], a, lda, row, row < m, n, lq);
+			else {
 #pragma unroll
-			for (int kb = 0; kb < KB; kb++) {
-				const int col = 4 * kb + lq;
-				av[rt][kb] = (row < m && col < n) ? a[(size_t)col * lda + row] : 0.0;
+				for (int kb = 0; kb < KB; kb++) {
+					const int col = 4 * kb + lq;
+					av[rt][kb] = (row < m && col < n) ? a[(size_t)col * lda + row] : 0.0;
+				}
 			}
 		}
 		f64x4 acc[2][NT];
@@ -170,19 +198,27 @@ __global__ __launch_bounds__(256) void apply_f64_kernel(double* q, size_t ldq, c
 			for (int rt = 0; rt < 2; rt++) {
 				acc[rt][jt] = f64x4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-				for (int kb = 0; kb < 4 * (jt + 1); kb++)
-					acc[rt][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(zop[base + kb], av[rt][kb], acc[rt][jt], 0, 0, 0);
+				for (int kb = 0; kb < 4 * (jt + 1); kb++) {
+					if constexpr (QROW) acc[rt][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt][kb], zop[base + kb], acc[rt][jt], 0, 0, 0);
+					else acc[rt][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(zop[base + kb], av[rt][kb], acc[rt][jt], 0, 0, 0);
+				}
 			}
 		});
 #pragma unroll
 		for (int rt = 0; rt < 2; rt++) {
-			const size_t row = row0 + 16 * rt + li;
 #pragma unroll
 			for (int jt = 0; jt < NT; jt++)
 #pragma unroll
 				for (int reg = 0; reg < 4; reg++) {
-					const int col = 16 * jt + lq + 4 * reg;
-					if (row < m && col < n) q[(size_t)col * ldq + row] = acc[rt][jt][reg];
+					if constexpr (QROW) {
+						const size_t row = row0 + 16 * rt + lq + 4 * reg;
+						const int col = 16 * jt + li;
+						if (row < m && col < n) q[row * ldq + col] = acc[rt][jt][reg];
+					} else {
+						const size_t row = row0 + 16 * rt + li;
+						const int col = 16 * jt + lq + 4 * reg;
+						if (row < m && col < n) q[(size_t)col * ldq + row] = acc[rt][jt][reg];
+					}
 				}
 		}
 	}
@@ -216,20 +252,6 @@ __global__ __launch_bounds__(1024) void trimul_f64_kernel(double* d, size_t ldd,
 	for (int reg = 0; reg < 4; reg++) {
 		const int i = 16 * ti + lq + 4 * reg, j = 16 * tj + li;
 		if (i < ext && j < ext) d[(size_t)j * ldd + i] = (i <= j) ? c[reg] : 0.0;
-	}
-}
-
-// v[kb] = S[row][4 kb + lq] for kb < KB from a ROW-major S (ld: the row stride), the registers the column-major loops of gramq_f64_kernel
-// and lsq_f64_kernel fill; zero where the row is not live or the column is >= n (neither is read).
-// The direct address: one load instruction reads sixteen 32-byte pieces, one per row, and the four k-blocks 4 g .. 4 g + 3 together use
-// every byte of the 128-byte lines they touch.  Measured against wide loads with a 4 x 4 exchange between the four lane quarters
-// (v_permlane32_swap, v_permlane16_swap), which was slower: DESIGN.md section 9 has both figures.
-template <int KB>
-__device__ __forceinline__ void load_rows_rm(double (&v)[KB], const double* __restrict__ s, size_t ld, size_t row, bool live, int n, int lq) {
-#pragma unroll
-	for (int kb = 0; kb < KB; kb++) {
-		const int col = 4 * kb + lq;
-		v[kb] = (live && col < n) ? s[row * ld + col] : 0.0;
 	}
 }
 

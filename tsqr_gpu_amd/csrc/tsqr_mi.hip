@@ -2469,31 +2469,38 @@ int f64_factor(hipStream_t st, double* wq, double* wr, const double* src, size_t
 	return f64_chol(st, wq, m, n, r, ldr, first, slot, comm);
 }
 
-// Q = A Z on a persistent grid: as many workgroups as are resident at once, each wave striding over 32-row blocks
-template <int NT> int f64_apply(hipStream_t st, int dev, double* q, size_t ldq, const double* a, size_t lda, size_t m, size_t n, const double* z) {
+// Q = A Z on a persistent grid: as many workgroups as are resident at once, each wave striding over 32-row blocks.  AROW, QROW: a is
+// read, q is written row-major (the leading dimension is then the row stride); the resident count is that of the instantiation launched
+template <int NT, bool AROW, bool QROW>
+int f64_apply(hipStream_t st, int dev, double* q, size_t ldq, const double* a, size_t lda, size_t m, size_t n, const double* z) {
 	static DevOnce once;
 	static std::atomic<int> resident[MAX_DEV];
 	if (once.need(dev)) {
-		resident[dev].store(f64_apply_resident<NT>(dev));
+		resident[dev].store(f64_apply_resident<NT, AROW, QROW>(dev));
 		once.done(dev);
 	}
 	const size_t nblocks = cdiv(m, 32);
 	const size_t wgs = f64_apply_wgs(nblocks, (size_t)resident[dev].load());
-	hipLaunchKernelGGL(tsqrmi::apply_f64_kernel<NT>, dim3((unsigned)wgs), dim3(256), 0, st, q, ldq, a, lda, m, (int)n, z, nblocks);
+	hipLaunchKernelGGL((tsqrmi::apply_f64_kernel<NT, AROW, QROW>), dim3((unsigned)wgs), dim3(256), 0, st, q, ldq, a, lda, m, (int)n, z, nblocks);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
 
-// sweep k (0-based): sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R
+// sweep k (0-based): sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R.  a_layout, q_layout
+// (tsqr_mi_qr_f64_lay): sweep 0 reads A in a_layout -- the Gram pass and the apply pass, which writes Q in q_layout; later sweeps read
+// and write Q in q_layout.  R and every launch between the two passes do not depend on a layout.
 int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-              double* wq, double* wr, const Comm* comm) {
+              double* wq, double* wr, const Comm* comm, int a_layout = TSQR_MI_COL_MAJOR, int q_layout = TSQR_MI_COL_MAJOR) {
 	const bool first = k == 0;
 	const double* src = first ? a : q;
 	const size_t lds = first ? lda : ldq;
-	int rc = f64_factor(st, wq, wr, src, lds, m, n, first ? r : wq + F64_R2, first ? ldr : 64, first, k & 3, comm);
+	const int src_layout = first ? a_layout : q_layout;
+	int rc = f64_factor(st, wq, wr, src, lds, m, n, first ? r : wq + F64_R2, first ? ldr : 64, first, k & 3, comm, src_layout);
 	if (rc) return rc;
 	const double* z = wq + F64_Z;
-	rc = with_nt((int)(np_of(n) / 16), [&](auto nt) { return f64_apply<decltype(nt)::value>(st, dev, q, ldq, src, lds, m, n, z); });
+	rc = with_apply(n, src_layout, q_layout, [&](auto nt, auto ar, auto qr) {
+		return f64_apply<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(st, dev, q, ldq, src, lds, m, n, z);
+	});
 	if (rc || first) return rc;
 	f64_rmul_launch(st, r, ldr, wq + F64_R2, (int)n);
 	HIPCHK(hipGetLastError());
@@ -2549,12 +2556,14 @@ int f64_ladder(int reorth, hipStream_t st, Sweep sweep) {
 }
 
 // wide: the sweeps of tsqr_mi_qr_f64_wide for n > 64 (f64w_sweep); the verdict words and their meaning are the same.
+// a_layout, q_layout: the n <= 64 sweeps only (f64_sweep); the wide and the row-partitioned entries are column-major.
 int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
-                hipStream_t st, bool wide = false, const Comm* comm = nullptr) {
+                hipStream_t st, bool wide = false, const Comm* comm = nullptr, int a_layout = TSQR_MI_COL_MAJOR,
+                int q_layout = TSQR_MI_COL_MAJOR) {
 	const int dev = cur_device();
 	return f64_ladder(reorth, st, [&](int k) {
 		return wide ? f64w_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm)
-		            : f64_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm);
+		            : f64_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm, a_layout, q_layout);
 	});
 }
 
@@ -2681,15 +2690,23 @@ size_t tsqr_mi_working_r_size_f64(size_t m, size_t n) {
 }
 int tsqr_mi_last_sweeps_f64(void) { return t_sweeps64; }
 
-int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-                   void* wq, void* wr, void* stream) {
+int tsqr_mi_qr_f64_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                       size_t m, size_t n, void* wq, void* wr, void* stream) {
 	t_sweeps64 = 0;
-	if (n > m || m == 0 || n == 0 || ldq < m || lda < m || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (!f64_layout_ok(a_layout) || !f64_layout_ok(q_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > m || m == 0 || n == 0 || ldq < f64_min_ld(q_layout, m, n) || lda < f64_min_ld(a_layout, m, n) || ldr < n)
+		return TSQR_MI_ERROR_INVALID_SIZE;
 	if (n > PW) { t_last_error = "tsqr_mi_qr_f64 supports n <= 64 (tsqr_mi_qr_f64_wide: n <= 1024)"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
 	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	if (rc) return rc;
 	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
-	                   reinterpret_cast<hipStream_t>(stream));
+	                   reinterpret_cast<hipStream_t>(stream), false, nullptr, a_layout, q_layout);
+}
+
+int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
+                   void* wq, void* wr, void* stream) {
+	return tsqr_mi_qr_f64_lay(TSQR_MI_COL_MAJOR, TSQR_MI_COL_MAJOR, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream);
 }
 
 }  // extern "C"
