@@ -445,7 +445,8 @@ inline state_t lstsq_fp64(
 }
 // Not in the reference: double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide, include/tsqr_mi.h for the
 // contract): qr_fp64 itself for n <= 64, whole-matrix CholeskyQR sweeps with the same ladder beyond.  Returns success_factorization,
-// error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.
+// error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.  a_layout, q_layout (tsqr_mi_qr_f64_wide_lay): the
+// layouts of a and of q as for qr_fp64 -- they need not agree; in place, q_ptr == a_ptr, needs equal layouts and ldq == lda.
 template <bool Reorthogonalize>
 struct buffer_fp64_wide {
 	double* dwq;
@@ -485,8 +486,9 @@ inline state_t qr_fp64_wide(
 		double* const a_ptr, const std::size_t lda,
 		const std::size_t m, const std::size_t n,
 		buffer_fp64_wide<Reorthogonalize>& bf,
-		handle_t const stream = nullptr) {
-	const int st = tsqr_mi_qr_f64_wide(Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major, const layout_t q_layout = col_major) {
+	const int st = tsqr_mi_qr_f64_wide_lay(a_layout, q_layout, Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, a_ptr, lda, m, n, bf.dwq, bf.dwr, stream);
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qr_fp64_wide: ") + tsqr_mi_last_error());
 	return st;
 }

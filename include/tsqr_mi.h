@@ -423,8 +423,7 @@ int tsqr_mi_lstsq_f64_lay(int a_layout, int b_layout, int reorth, int refine, do
  * the same matrix, for all four layout pairs.  With both layouts TSQR_MI_COL_MAJOR the call IS tsqr_mi_qr_f64 (which calls this one).
  * The accuracy bands, the ladder and the non-finite rules of tsqr_mi_qr_f64 hold unchanged.  In place as there: q == a is allowed with
  * a_layout == q_layout and ldq == lda; Q and R must not overlap A otherwise, nor each other.
- * Column-major only: the wide entry (tsqr_mi_qr_f64_wide beyond n = 64) and the row-partitioned entries (tsqr_mi_qr_f64_dist*) below
- * take no layout.
+ * Beyond n = 64: tsqr_mi_qr_f64_wide_lay below.  Column-major only: the row-partitioned entries (tsqr_mi_qr_f64_dist*) take no layout.
  * Returns what tsqr_mi_qr_f64 returns; 1 also for a layout other than 0 or 1, for a row-major operand with a leading dimension below
  * n (not below m), and for q == a with different layouts or ldq != lda; 2 for n > 64 (tsqr_mi_last_error says so).  Arguments are
  * checked before any HIP call.
@@ -450,6 +449,31 @@ size_t tsqr_mi_working_q_size_f64_wide(size_t m, size_t n);
 size_t tsqr_mi_working_r_size_f64_wide(size_t m, size_t n);
 int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
                         size_t m, size_t n, void* wq, void* wr, void* stream);
+
+/*
+ * tsqr_mi_qr_f64_wide on operands in either layout (not in the reference): a_layout is how A is stored, q_layout how Q is written, each
+ * TSQR_MI_COL_MAJOR (element (i, j) at p[i + j * ld], ld >= m) or TSQR_MI_ROW_MAJOR (element (i, j) at p[i * ld + j], ld >= n -- a
+ * contiguous C or torch array of shape (m, n)); the two need not agree.  R is column-major.  1 <= n <= 1024, n <= m; the work space is
+ * that of tsqr_mi_working_{q,r}_size_f64_wide for every layout.  No copy of A or Q is made; nothing between n and the leading dimension
+ * of a row-major operand, or behind row m, is read or written.  n <= 64 IS tsqr_mi_qr_f64_lay.
+ * Method, 64 < n: the sweeps of tsqr_mi_qr_f64_wide.  Only two kernels touch A or Q -- the Gram pass and the apply pass
+ * (gram_wide_f64_kernel, apply_wide_f64_kernel, tsqr_f64_wide.hip) -- and each takes the layout as a template flag; everything between
+ * them works on 64 x 64 blocks of the work space.  Sweep 1 reads A in a_layout and writes Q in q_layout; later sweeps read and write Q
+ * in q_layout, in place.
+ * Bit-for-bit relation: the row-major kernels put the values of A into the registers the column-major kernels hold them in, on the same
+ * launch plans (a column beyond n in the last block is an exact zero and is never loaded), and a row-major Q is formed by the same
+ * products summed in the same order with the MFMA operands swapped, so Q -- read as a matrix --, R, the state and
+ * tsqr_mi_last_sweeps_f64 are BITWISE those of tsqr_mi_qr_f64_wide on a column-major copy of the same matrix, for all four layout
+ * pairs.  With both layouts TSQR_MI_COL_MAJOR the call IS tsqr_mi_qr_f64_wide (which calls this one).  Its accuracy bands, ladder and
+ * non-finite rules hold unchanged.
+ * In place: q == a is allowed with a_layout == q_layout and ldq == lda; Q and R must not overlap A otherwise, nor each other.
+ * The row-partitioned entries (tsqr_mi_qr_f64_dist*) below stay column-major.
+ * Returns what tsqr_mi_qr_f64_wide returns.  Checked in this order, before any HIP call: 1 for a layout other than 0 or 1; 1 for n > m,
+ * m == 0, n == 0, ldr < n or a leading dimension below m (column-major) or n (row-major); 2 for n > 1024 (tsqr_mi_last_error says so);
+ * 1 for q == a with different layouts or ldq != lda.
+ */
+int tsqr_mi_qr_f64_wide_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                            size_t m, size_t n, void* wq, void* wr, void* stream);
 
 /*
  * Row-partitioned double-precision QR (not in the reference): tsqr_mi_qr_f64_wide for a matrix whose rows are spread over the ranks, one

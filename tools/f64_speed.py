@@ -22,7 +22,15 @@ Redirect the JSON line (profiles/fp64_rowmajor_speed.json).
 --qr-row-major: instead, the full QR's layout entry (tsqr_mi_qr_f64_lay, reorth 0 and 1) at the shapes and under the protocol of
 --row-major: (i) the layout entry on row-major A and Q, (ii) tsqr_mi_qr_f64 on operands transposed beforehand, (iii) the transposing
 copy of A (t().contiguous().t()), tsqr_mi_qr_f64 and a transposing copy of Q back into row-major storage, waited for.  Asserts that Q
-and R of (i) are bitwise those of (ii) in every case.  Redirect the JSON line (profiles/fp64_qr_rowmajor_speed.json)."""
+and R of (i) are bitwise those of (ii) in every case.  Redirect the JSON line (profiles/fp64_qr_rowmajor_speed.json).
+--wide-row-major: instead, the wide entry's layout form (tsqr_mi_qr_f64_wide_lay, reorth 0 and 1) at 2^18 x 128, 2^18 x 256 and
+2^16 x 1024, Gaussian, three arms interleaved call by call in this process on the same operands: (a) the layout entry on row-major A and
+Q, (b) tsqr_mi_qr_f64_wide on operands transposed beforehand, (c) what a contiguous tensor cost before: the transposing copy of A,
+tsqr_mi_qr_f64_wide and a transposing copy of Q back, waited for.  Per arm the median of --calls (default here: 20) blocking calls; the
+ratios a / b and a / c; asserts that Q and R of (a) are bitwise those of (b).  With --parent-lib PATH (another build of libtsqr_mi.so,
+the parent commit's) arm (b) alone is also run in fresh processes, alternating PATH (through TSQR_MI_LIB) and the in-tree library, two
+runs each: the parent's two medians give the spread the in-tree median is read against, and the checksums of Q and R of the
+column-major call are compared.  Writes the JSON to --out (default profiles/fp64_wide_rowmajor_speed.json) and prints it."""
 import argparse
 import json
 import math
@@ -330,6 +338,143 @@ def qr_row_major(torch, bq, calls, warmup):
     print(json.dumps(out))
 
 
+WIDE_RM_SHAPES = ((18, 128), (18, 256), (16, 1024))
+
+
+def bits_checksum(torch, t):
+    """two 64-bit words over the bit patterns of t's elements in storage order: their wrap-around sum, and the same with element k
+    weighted by 2 k + 1 (so that a permutation shows)"""
+    v = t.contiguous().view(-1).view(torch.int64)
+    w = torch.arange(v.numel(), dtype=torch.int64, device=v.device) * 2 + 1
+    return [int(v.sum().item()), int((v * w).sum().item())]
+
+
+def wide_col_only(torch, bq, calls, warmup):
+    """arm (b) of --wide-row-major alone, through an entry every build has: the child processes of --parent-lib"""
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    out = {"lib": bq.LIB_PATH, "cases": []}
+    for lg, n in WIDE_RM_SHAPES:
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a_cm = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g).t().contiguous()     # (n, m): column-major m x n
+        q_cm = torch.empty_like(a_cm)
+        r = torch.empty(n, n, dtype=torch.float64, device="cuda")
+        wq = torch.empty(L.tsqr_mi_working_q_size_f64_wide(m, n), dtype=torch.float64, device="cuda")
+        wr = torch.empty(L.tsqr_mi_working_r_size_f64_wide(m, n), dtype=torch.float64, device="cuda")
+        st = vp(torch.cuda.current_stream().cuda_stream)
+        for reorth in (0, 1):
+            ts = []
+            for i in range(warmup + calls):
+                t0 = time.perf_counter()
+                rc = L.tsqr_mi_qr_f64_wide(reorth, vp(q_cm.data_ptr()), m, vp(r.data_ptr()), n, vp(a_cm.data_ptr()), m, m, n,
+                                           vp(wq.data_ptr()), vp(wr.data_ptr()), st)
+                dt = time.perf_counter() - t0
+                assert rc == 0, bq.last_error()
+                if i >= warmup:
+                    ts.append(dt)
+            out["cases"].append({"m": m, "n": n, "reorth": reorth, "median_ms": sorted(ts)[len(ts) // 2] * 1e3, "min_ms": min(ts) * 1e3,
+                                 "sweeps": bq.last_sweeps_f64(), "q_checksum": bits_checksum(torch, q_cm), "r_checksum": bits_checksum(torch, r)})
+        del a_cm, q_cm, r, wq, wr
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
+def wide_parent_ab(parent_lib, calls, warmup):
+    """arm (b) in four fresh processes, parent / in-tree / parent / in-tree, before this process touches the GPU"""
+    import subprocess
+    runs = []
+    for lib in (parent_lib, None, parent_lib, None):
+        env = dict(os.environ)
+        env.pop("TSQR_MI_LIB", None)
+        if lib:
+            env["TSQR_MI_LIB"] = os.path.abspath(lib)
+        res = subprocess.run([sys.executable, os.path.abspath(__file__), "--wide-col-only", "--calls", str(calls), "--warmup", str(warmup)],
+                             env=env, capture_output=True, text=True, check=True)
+        runs.append(json.loads(res.stdout.strip().splitlines()[-1]))
+    p1, n1, p2, n2 = runs
+    cases = []
+    for cp1, cn1, cp2, cn2 in zip(p1["cases"], n1["cases"], p2["cases"], n2["cases"]):
+        pm, nm = [cp1["median_ms"], cp2["median_ms"]], [cn1["median_ms"], cn2["median_ms"]]
+        spread = max(pm) / min(pm)
+        cases.append({"m": cp1["m"], "n": cp1["n"], "reorth": cp1["reorth"], "parent_medians_ms": pm, "in_tree_medians_ms": nm,
+                      "parent_spread_max_over_min": spread, "ratio_in_tree_over_parent": (sum(nm) / 2) / (sum(pm) / 2),
+                      "worst_in_tree_over_best_parent": max(nm) / min(pm),
+                      "in_tree_within_parent_spread": bool(max(nm) <= max(pm)),
+                      "sweeps_parent": cp1["sweeps"], "sweeps_in_tree": cn1["sweeps"],
+                      "q_checksum": cn1["q_checksum"], "r_checksum": cn1["r_checksum"],
+                      "checksums_equal_to_parent": bool(all(c["q_checksum"] == cp1["q_checksum"] and c["r_checksum"] == cp1["r_checksum"]
+                                                            and c["sweeps"] == cp1["sweeps"] for c in (cn1, cp2, cn2)))})
+    return {"protocol": "tsqr_mi_qr_f64_wide alone, one fresh process per run in the order parent, in-tree, parent, in-tree; the median "
+                        "of %d blocking calls after %d warm-up calls" % (calls, warmup), "cases": cases}
+
+
+def wide_row_major(torch, bq, calls, warmup, parent):
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    out = {"tool": "f64_speed --wide-row-major", "calls": calls, "warmup": warmup, "cases": []}
+    for lg, n in WIDE_RM_SHAPES:
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a_rm = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g)        # row-major m x n
+        a_cm = a_rm.t().contiguous()                                                       # (n, m): column-major m x n
+        q_rm, q_cm = torch.empty_like(a_rm), torch.empty_like(a_cm)
+        r = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(2)]
+        wq = torch.empty(L.tsqr_mi_working_q_size_f64_wide(m, n), dtype=torch.float64, device="cuda")
+        wr = torch.empty(L.tsqr_mi_working_r_size_f64_wide(m, n), dtype=torch.float64, device="cuda")
+        work = (vp(wq.data_ptr()), vp(wr.data_ptr()), vp(torch.cuda.current_stream().cuda_stream))
+
+        def row(reorth):
+            return L.tsqr_mi_qr_f64_wide_lay(1, 1, reorth, vp(q_rm.data_ptr()), n, vp(r[0].data_ptr()), n, vp(a_rm.data_ptr()), n, m, n, *work)
+
+        def col(reorth, a=None):
+            a = a_cm if a is None else a
+            return L.tsqr_mi_qr_f64_wide(reorth, vp(q_cm.data_ptr()), m, vp(r[1].data_ptr()), n, vp(a.data_ptr()), m, m, n, *work)
+
+        def copy_in_out(reorth):
+            a_c = a_rm.t().contiguous()                     # (the copy is enqueued on the stream of the call behind it)
+            rc = col(reorth, a_c)
+            q_out = q_cm.t().contiguous()                   # Q back in the caller's layout
+            torch.cuda.synchronize()
+            del q_out
+            return rc
+
+        for reorth in (0, 1):
+            arms = [("a_row_major", lambda: row(reorth)), ("b_col_major", lambda: col(reorth)),
+                    ("c_copy_in_col_major_copy_out", lambda: copy_in_out(reorth))]
+            ts = {name: [] for name, _ in arms}
+            for i in range(warmup + calls):
+                for name, fn in arms:
+                    t0 = time.perf_counter()
+                    rc = fn()                               # (blocking: returns when the stream has drained)
+                    dt = time.perf_counter() - t0
+                    assert rc == 0, bq.last_error()
+                    if i >= warmup:
+                        ts[name].append(dt)
+            med = {k: sorted(v)[len(v) // 2] * 1e3 for k, v in ts.items()}
+            arms[1][1]()
+            sweeps_b = bq.last_sweeps_f64()
+            arms[0][1]()
+            sweeps_a = bq.last_sweeps_f64()
+            q_equal, r_equal = bool(torch.equal(q_rm, q_cm.t())), bool(torch.equal(r[0], r[1]))
+            assert q_equal and r_equal and sweeps_a == sweeps_b, (m, n, reorth, q_equal, r_equal, sweeps_a, sweeps_b)
+            out["cases"].append({"m": m, "n": n, "call": "qr_f64_wide_reorth%d" % reorth, "sweeps": sweeps_a,
+                                 "a_row_major_median_ms": med["a_row_major"], "b_col_major_median_ms": med["b_col_major"],
+                                 "c_copy_in_col_major_copy_out_median_ms": med["c_copy_in_col_major_copy_out"],
+                                 "min_ms": {k: min(v) * 1e3 for k, v in ts.items()},
+                                 "ratio_a_over_b": med["a_row_major"] / med["b_col_major"],
+                                 "ratio_a_over_c": med["a_row_major"] / med["c_copy_in_col_major_copy_out"],
+                                 "a_faster_than_c": bool(med["a_row_major"] < med["c_copy_in_col_major_copy_out"]),
+                                 "q_bitwise_equal": q_equal, "r_bitwise_equal": r_equal})
+        del a_rm, a_cm, q_rm, q_cm, r, wq, wr
+        torch.cuda.empty_cache()
+    if parent is not None:
+        out["column_major_call_against_parent"] = parent
+    return out
+
+
 def dist1(torch, bq, calls, warmup):
     import ctypes
     rccl = ctypes.CDLL("librccl.so")
@@ -379,7 +524,7 @@ def dist1(torch, bq, calls, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--calls", type=int, default=None, help="blocking calls per case or arm (default 50; --wide-row-major: 20)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cases", default="", help="comma-separated case names (default: all)")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch.linalg.qr baseline")
@@ -388,9 +533,25 @@ def main():
     ap.add_argument("--row-major", action="store_true", help="time the layout entries on row-major operands next to the column-major entries")
     ap.add_argument("--qr-row-major", action="store_true", help="time tsqr_mi_qr_f64_lay on row-major A and Q next to tsqr_mi_qr_f64")
     ap.add_argument("--dist1", action="store_true", help="time the one-rank row-partitioned call over raw RCCL next to the plain entry")
+    ap.add_argument("--wide-row-major", action="store_true", help="time tsqr_mi_qr_f64_wide_lay on row-major A and Q next to tsqr_mi_qr_f64_wide")
+    ap.add_argument("--wide-col-only", action="store_true", help="arm (b) of --wide-row-major alone (the child processes of --parent-lib)")
+    ap.add_argument("--parent-lib", default="", help="--wide-row-major: another build of libtsqr_mi.so to run arm (b) against")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp64_wide_rowmajor_speed.json"), help="--wide-row-major: the JSON file")
     args = ap.parse_args()
+    wide_rm = args.wide_row_major or args.wide_col_only
+    if args.calls is None:
+        args.calls = 20 if wide_rm else 50
+    parent = wide_parent_ab(args.parent_lib, args.calls, args.warmup) if args.wide_row_major and args.parent_lib else None
     import torch
     from tsqr_gpu_amd import blockqr as bq
+    if args.wide_col_only:
+        return wide_col_only(torch, bq, args.calls, args.warmup)
+    if args.wide_row_major:
+        out = wide_row_major(torch, bq, args.calls, args.warmup, parent)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+        print(json.dumps(out))
+        return
     if args.dist1:
         return dist1(torch, bq, args.calls, args.warmup)
     if args.r_only:

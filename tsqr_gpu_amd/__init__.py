@@ -6,4 +6,4 @@ dist.py    row-partitioned multi-GPU TSQR (one process per GPU, R factors all-ga
 """
 from .blockqr import (buffer, buffer_f64_r, compute_mode, error_invalid_matrix_size, error_unsupported_mode,  # noqa: F401
                       get_batch_size, get_batch_size_log2, get_working_l_size, get_working_q_size,
-                      get_working_r_size, lstsq_f64, qr, qr_f64_tensor, r_f64, success_factorization, tsqr_colmun_size)
+                      get_working_r_size, lstsq_f64, qr, qr_f64_tensor, qr_f64_wide_tensor, r_f64, success_factorization, tsqr_colmun_size)

@@ -56,7 +56,7 @@ C_ABI_SYMBOLS = [
     "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
     "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
     "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
-    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay",
+    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay",
 ]
 
 COL_MAJOR, ROW_MAJOR = 0, 1              # TSQR_MI_COL_MAJOR, TSQR_MI_ROW_MAJOR: the layout arguments of the *_lay entries
@@ -220,6 +220,9 @@ def lib():
     if hasattr(L, "tsqr_mi_qr_f64_lay"):                 # (as above: an older build factors column-major operands only)
         L.tsqr_mi_qr_f64_lay.restype = ci
         L.tsqr_mi_qr_f64_lay.argtypes = [ci, ci] + L.tsqr_mi_qr_f64.argtypes
+    if hasattr(L, "tsqr_mi_qr_f64_wide_lay"):            # (as above: an older build's wide entry is column-major only)
+        L.tsqr_mi_qr_f64_wide_lay.restype = ci
+        L.tsqr_mi_qr_f64_wide_lay.argtypes = [ci, ci] + L.tsqr_mi_qr_f64_wide.argtypes
     _lib = L
     return L
 
@@ -521,7 +524,8 @@ def check_f64_operands(m, n, ldq, ldr, lda, q, r, a, row_major=False):
 
 
 def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize, row_major=False):
-    """The body of qr_f64 (entry _F64) and qr_f64_wide (_F64_WIDE).  row_major (qr_f64 only): tsqr_mi_qr_f64_lay with q and a row-major."""
+    """The body of qr_f64 (entry _F64) and qr_f64_wide (_F64_WIDE).  row_major: the entry's _lay form (tsqr_mi_qr_f64_lay,
+    tsqr_mi_qr_f64_wide_lay) with q and a row-major."""
     import torch
     name, nmax, qr_fn, wq_fn, wr_fn = entry
     if row_major:
@@ -575,11 +579,15 @@ class buffer_f64_wide(buffer_f64):
     _entry = _F64_WIDE
 
 
-def qr_f64_wide(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None):
+def qr_f64_wide(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False):
     """Double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide; qr_f64 itself for n <= 64): the arguments,
-    operand rules and states of qr_f64, error_unsupported_mode for n > 1024.  bf is a buffer_f64_wide.  Operands are checked before
-    anything is launched (TypeError / ValueError, check_f64_operands).  last_sweeps_f64() tells how many sweeps the call took."""
-    return _qr_f64(_F64_WIDE, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize)
+    operand rules and states of qr_f64, error_unsupported_mode for n > 1024.  row_major=True (tsqr_mi_qr_f64_wide_lay): q and a hold
+    ROW-major data, element (i, j) at i * ld + j with ld >= n, read and written where they lie; r stays column-major, and q, r, the
+    state and the sweep count have the bits of the column-major call on the same matrix; in place needs q == a and ldq == lda.
+    bf is a buffer_f64_wide (the same for both layouts).  Operands are checked before anything is launched (TypeError / ValueError,
+    check_f64_operands).  last_sweeps_f64() tells how many sweeps the call took.  qr_f64_wide_tensor is the same factorisation on a
+    two-dimensional tensor with any strides."""
+    return _qr_f64(_F64_WIDE, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize, row_major)
 
 
 class buffer_f64_r(buffer_f64):
@@ -715,11 +723,51 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
 
 
 class QrError(RuntimeError):
-    """qr_f64_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
+    """qr_f64_tensor or qr_f64_wide_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
 
     def __init__(self, state, text):
         RuntimeError.__init__(self, text)
         self.state = state
+
+
+def _qr_f64_tensor(entry, a, reorth, overwrite_a, stream):
+    """The body of qr_f64_tensor (entry _F64) and qr_f64_wide_tensor (_F64_WIDE) on the entry's _lay form."""
+    import torch
+    name, nmax, qr_fn, wq_fn, wr_fn = entry
+    name, qr_fn = name + "_tensor", qr_fn + "_lay"
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
+        raise TypeError("%s: a must be a float64 tensor, got %s" % (name, getattr(a, "dtype", type(a).__name__)))
+    if not a.is_cuda:
+        raise TypeError("%s: a is not a GPU tensor" % name)
+    if a.dim() != 2:
+        raise ValueError("%s: a must be m x n, got %s" % (name, tuple(a.shape)))
+    m, n = a.shape
+    L = lib()
+    call = getattr(L, qr_fn)
+    z = ctypes.c_void_p(0)
+    if m == 0 or n == 0 or n > m or n > nmax:
+        st = call(COL_MAJOR, COL_MAJOR, int(bool(reorth)), z, max(m, 1), z, max(n, 1), z, max(m, 1), m, n, z, z, z)
+        raise QrError(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
+    ac, lda, layout = _operand_f64(a)
+    if overwrite_a and ac.data_ptr() == a.data_ptr():
+        q, ldq = a, lda                                    # (in place: the same layout and leading dimension)
+    elif layout == ROW_MAJOR:
+        q, ldq = torch.empty((m, n), dtype=torch.float64, device=a.device), n
+    else:
+        q, ldq = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+    r = torch.empty((n, n), dtype=torch.float64, device=a.device)
+    wq = torch.empty(getattr(L, wq_fn)(m, n), dtype=torch.float64, device=a.device)
+    wr = torch.empty(getattr(L, wr_fn)(m, n), dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        st = call(layout, layout, int(bool(reorth)), q.data_ptr(), ldq, r.data_ptr(), n, ac.data_ptr(), lda, m, n,
+                  wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("%s failed: %s" % (qr_fn, last_error()))
+    if st:
+        raise QrError(st, "%s: state %d: %s" % (name, st, last_error()))
+    return q, r.t()
 
 
 def qr_f64_tensor(a, reorth=False, overwrite_a=False, stream=None):
@@ -734,39 +782,16 @@ def qr_f64_tensor(a, reorth=False, overwrite_a=False, stream=None):
     two-dimensional, QrError (.state) when the C entry returns a state other than 0: sizes it does not support (n > m, an empty a:
     error_invalid_matrix_size; n > 64: error_unsupported_mode) or error_not_finite from the ladder (Inf or NaN in a, or a
     rank-deficient a).  last_sweeps_f64() tells how many sweeps the call took."""
-    import torch
-    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
-        raise TypeError("qr_f64_tensor: a must be a float64 tensor, got %s" % getattr(a, "dtype", type(a).__name__))
-    if not a.is_cuda:
-        raise TypeError("qr_f64_tensor: a is not a GPU tensor")
-    if a.dim() != 2:
-        raise ValueError("qr_f64_tensor: a must be m x n, got %s" % (tuple(a.shape),))
-    m, n = a.shape
-    L = lib()
-    z = ctypes.c_void_p(0)
-    if m == 0 or n == 0 or n > m or n > 64:
-        st = L.tsqr_mi_qr_f64_lay(COL_MAJOR, COL_MAJOR, int(bool(reorth)), z, max(m, 1), z, max(n, 1), z, max(m, 1), m, n, z, z, z)
-        raise QrError(st, "qr_f64_tensor: state %d for a %d x %d%s" % (st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
-    ac, lda, layout = _operand_f64(a)
-    if overwrite_a and ac.data_ptr() == a.data_ptr():
-        q, ldq = a, lda                                    # (in place: the same layout and leading dimension)
-    elif layout == ROW_MAJOR:
-        q, ldq = torch.empty((m, n), dtype=torch.float64, device=a.device), n
-    else:
-        q, ldq = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
-    r = torch.empty((n, n), dtype=torch.float64, device=a.device)
-    wq = torch.empty(L.tsqr_mi_working_q_size_f64(m, n), dtype=torch.float64, device=a.device)
-    wr = torch.empty(L.tsqr_mi_working_r_size_f64(m, n), dtype=torch.float64, device=a.device)
-    with torch.cuda.device(a.device):
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        st = L.tsqr_mi_qr_f64_lay(layout, layout, int(bool(reorth)), q.data_ptr(), ldq, r.data_ptr(), n, ac.data_ptr(), lda, m, n,
-                                  wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
-    if st < 0:
-        raise RuntimeError("tsqr_mi_qr_f64_lay failed: %s" % last_error())
-    if st:
-        raise QrError(st, "qr_f64_tensor: state %d: %s" % (st, last_error()))
-    return q, r.t()
+    return _qr_f64_tensor(_F64, a, reorth, overwrite_a, stream)
+
+
+def qr_f64_wide_tensor(a, reorth=False, overwrite_a=False, stream=None):
+    """qr_f64_tensor for 1 <= n <= 1024 (tsqr_mi_qr_f64_wide_lay: include/tsqr_mi.h has the method and the accuracy bands): the same
+    contract -- a is used where it lies when its columns or its rows are contiguous (_operand_f64's rule) and copied once into
+    column-major storage otherwise, q has a's shape and layout, the same bits of q and r whichever way a is stored, overwrite_a, a work
+    space per call, TypeError / ValueError / QrError (.state; error_unsupported_mode for n > 1024).  For n <= 64 the result has the bits
+    of qr_f64_tensor.  last_sweeps_f64() tells how many sweeps the call took."""
+    return _qr_f64_tensor(_F64_WIDE, a, reorth, overwrite_a, stream)
 
 
 def get_working_q_size_f64_dist(m_local, n, nranks):

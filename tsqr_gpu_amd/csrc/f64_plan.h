@@ -187,4 +187,21 @@ int f64w_chain(hipStream_t st, tsqrmi::WideF64 wa) {
 	return 0;
 }
 
+// The two passes of the wide entry that touch A or Q, on stream st.  a_layout, q_layout as for the n <= 64 launchers above (the leading
+// dimension of a row-major operand is its row stride); the grids, the partition and the partials do not depend on them.
+inline void f64w_gram_launch(hipStream_t st, const F64WPlan& g, const tsqrmi::GramWideF64Args& ga, int a_layout = 0) {
+	with_layout(a_layout, [&](auto ar) {
+		hipLaunchKernelGGL((tsqrmi::gram_wide_f64_kernel<decltype(ar)::value>), dim3((unsigned)(g.ngroups * g.nslices)), dim3(256), 0, st, ga);
+	});
+}
+inline void f64w_apply_launch(hipStream_t st, double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, int nb, const double* zw,
+                              int a_layout = 0, int q_layout = 0) {
+	with_layout(a_layout, [&](auto ar) {
+		with_layout(q_layout, [&](auto qr) {
+			hipLaunchKernelGGL((tsqrmi::apply_wide_f64_kernel<decltype(ar)::value, decltype(qr)::value>), dim3((unsigned)cdiv(m, 128)), dim3(256),
+			                   0, st, q, ldq, a, lda, m, n, nb, zw);
+		});
+	});
+}
+
 }  // namespace

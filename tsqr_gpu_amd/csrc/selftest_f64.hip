@@ -211,17 +211,26 @@ int tsqr_selftest_f64_lsq_update(double* xw, double* x, size_t ldx, const double
 }
 
 // ---- 64 < n <= 1024 ---------------------------------------------------------------------------------------------------------------------
-// Gram pass + reduction: gs[bs + 1] in the block store's layout.  cps > 0 overrides the chunks per slice; part holds part_cap doubles.
-int tsqr_selftest_f64w_gram(double* gs, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, size_t cps) {
-	if (m == 0 || n <= (int)PW || n > (int)F64W_MAX_N || lda < m) return -100;
+// The Gram and apply entries come in two forms, like those of n <= 64 above: _lay takes a layout per operand (0 column-major; 1
+// row-major, the leading dimension is then the row stride, >= n) and goes through the launchers the product uses (f64_plan.h); the plain
+// entry is _lay at layout 0.
+// Gram pass + reduction: gs[bs + 1] in the block store's layout.  cps > 0 overrides the chunks per slice -- the same partition for
+// every layout; part holds part_cap doubles.
+int tsqr_selftest_f64w_gram_lay(int a_layout, double* gs, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap,
+                                size_t cps) {
+	if (a_layout != 0 && a_layout != 1) return -100;
+	if (m == 0 || n <= (int)PW || n > (int)F64W_MAX_N || lda < (a_layout ? (size_t)n : m)) return -100;
 	F64WPlan g = f64w_plan(m, (size_t)n);
 	if (cps > 0) { g.cps = cps; g.nslices = (int)cdiv(g.nch, g.cps); }
 	if (g.nslices <= 0 || g.npairs <= 0 || (size_t)g.nslices * g.bs > part_cap) return -100;
 	const tsqrmi::GramWideF64Args ga{a, lda, m, n, g.npairs, g.ngroups, g.cps, g.nch, part};
-	hipLaunchKernelGGL(tsqrmi::gram_wide_f64_kernel, dim3((unsigned)(g.ngroups * g.nslices)), dim3(256), 0, 0, ga);
+	f64w_gram_launch(0, g, ga, a_layout);
 	HIPCHK(hipGetLastError());
 	launch_reduce1(0, gs, part, g.nslices, (int)g.bs, (double)m);
 	return f64_sync();
+}
+int tsqr_selftest_f64w_gram(double* gs, const double* a, size_t lda, size_t m, int n, double* part, size_t part_cap, size_t cps) {
+	return tsqr_selftest_f64w_gram_lay(0, gs, a, lda, m, n, part, part_cap, cps);
 }
 
 // The blocked Cholesky step on the work space wq (f64w_plan(m, n).wq doubles, the summed blocks at o_gs), status slot 0, with the
@@ -252,11 +261,17 @@ int tsqr_selftest_f64w_chain(double* wq, size_t m, int n, int mode, unsigned* ho
 	return f64_sync();
 }
 
-// apply_wide_f64_kernel: q = a Z, Z in the block store zw
-int tsqr_selftest_f64w_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* zw) {
-	if (m == 0 || n <= (int)PW || n > (int)F64W_MAX_N || lda < m || ldq < m) return -100;
-	hipLaunchKernelGGL(tsqrmi::apply_wide_f64_kernel, dim3((unsigned)cdiv(m, 128)), dim3(256), 0, 0, q, ldq, a, lda, m, n, (int)cdiv((size_t)n, PW), zw);
+// apply_wide_f64_kernel<AROW, QROW>: q = a Z, Z in the block store zw.  q == a (in place) needs equal layouts and leading dimensions.
+int tsqr_selftest_f64w_apply_lay(int a_layout, int q_layout, double* q, size_t ldq, const double* a, size_t lda, size_t m, int n,
+                                 const double* zw) {
+	if ((a_layout != 0 && a_layout != 1) || (q_layout != 0 && q_layout != 1)) return -100;
+	if (m == 0 || n <= (int)PW || n > (int)F64W_MAX_N || lda < (a_layout ? (size_t)n : m) || ldq < (q_layout ? (size_t)n : m)) return -100;
+	if (q == a && (a_layout != q_layout || ldq != lda)) return -100;
+	f64w_apply_launch(0, q, ldq, a, lda, m, n, (int)cdiv((size_t)n, PW), zw, a_layout, q_layout);
 	return f64_sync();
+}
+int tsqr_selftest_f64w_apply(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, const double* zw) {
+	return tsqr_selftest_f64w_apply_lay(0, 0, q, ldq, a, lda, m, n, zw);
 }
 
 // rcopy_wide_f64_kernel: r (n x n, ldr) = R of the block store rw

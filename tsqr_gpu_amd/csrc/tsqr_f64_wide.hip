@@ -15,6 +15,10 @@
 //   apply_wide_f64_kernel  : Q = A Z, in place allowed
 //   rcopy / rsave / rmul_wide_f64_kernel : R out (first sweep), R <- R_k R through a work-space copy (later sweeps)
 // The block products run on sixteen waves, one 16 x 16 output tile each, both operands staged in LDS (tile_product_f64).
+// Only the two kernels that touch A or Q know a layout (tsqr_mi_qr_f64_wide_lay): gram_wide_f64_kernel<AROW> and
+// apply_wide_f64_kernel<AROW, QROW>, one body each with the layout as a template flag like the n <= 64 kernels of tsqr_f64.hip.  Element
+// (i, j) of a row-major operand lies at s[i * ld + j], ld >= n.  A row-major instance puts the same value into the same register and a
+// row-major Q swaps the MFMA operands, so every bit of G, R and Q is that of the column-major instance on the transposed copy.
 #include <hip/hip_runtime.h>
 
 namespace tsqrmi {
@@ -103,6 +107,11 @@ __device__ __forceinline__ double wide_wg_sum(double v, double* red) {
 // waves of a workgroup take four consecutive pairs (they share block J: one read from memory, the others from the caches) of the same
 // slice, and consecutive workgroups take the same slice: the rows of a slice are read from memory about once.  Partials:
 // part[(slice * npairs + p) * 4096 + 64 c + r], the block store's layout, summed by gram_reduce1_kernel over the slices.
+// AROW: A is row-major (g.lda: the row stride, >= n).  The same 32 registers receive the same values -- lane (c, q) holds rows
+// 16 ch + 4 q .. + 3 of column 64 blk + 16 t + c -- so every partial has the bits of the column-major instance on the transposed copy.
+// The loads are 8 bytes per lane, one row per instruction: the sixteen lanes of a quarter cover 128 contiguous bytes of that row.  A
+// column >= n of the zero-padded last block is an exact zero and is NEVER loaded: in row-major storage that address is the next row's
+// data (lda == n), padding (lda > n) or, on the last row, beyond the allocation.  Rows >= m likewise.
 struct GramWideF64Args {
 	const double* a; size_t lda; size_t m; int n;
 	int npairs, ngroups;                 // pairs, workgroups per slice (four pairs each)
@@ -110,6 +119,7 @@ struct GramWideF64Args {
 	double* part;
 };
 
+template <bool AROW>
 __global__ __launch_bounds__(256) void gram_wide_f64_kernel(const GramWideF64Args g) {
 	const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
 	const int grp = blockIdx.x % g.ngroups, slice = blockIdx.x / g.ngroups;
@@ -128,6 +138,12 @@ __global__ __launch_bounds__(256) void gram_wide_f64_kernel(const GramWideF64Arg
 #pragma unroll
 		for (int t = 0; t < 8; t++) {
 			const int col = 64 * (t < 4 ? I : J) + 16 * (t & 3) + c;
+			if constexpr (AROW) {
+				const double* src = g.a + row0 * g.lda + col;
+#pragma unroll
+				for (int i = 0; i < 4; i++) x[t][i] = (col < g.n && (full || row0 + i < g.m)) ? src[(size_t)i * g.lda] : 0.0;
+				continue;
+			}
 			const double* src = g.a + (size_t)col * g.lda + row0;
 			if (col < g.n && full) {
 				const f64x2u v0 = *reinterpret_cast<const f64x2u*>(src);
@@ -351,6 +367,19 @@ __global__ __launch_bounds__(64) void cholw_verdict_kernel(const WideF64 a) {
 // lanes hold sixteen consecutive rows of one column of Q.  In place (q == a, ldq == lda) is safe: no two waves share a row, and output
 // block J is the LAST consumer of input block J -- its stores depend on every load of its products, and the blocks J' < J that follow
 // read columns < 64 (J' + 1) <= 64 J only.  (q and a are not __restrict__: the compiler keeps the next block's loads behind the stores.)
+// Both register sets are the same for every layout: zop[jt], lane (li, lq) holds Z[64 K + 4 kb + lq][64 J + 16 jt + li]; av[rt], lane
+// (li, lq) holds A[row0 + 16 rt + li][64 K + 4 kb + lq] (load_rows_rm's rule, tsqr_f64.hip).  AROW: A is row-major (lda: the row stride,
+// >= n) -- another address for the same register.  QROW: Q is row-major (ldq: the row stride, >= n): the MFMA operands are swapped
+// (apply_f64_kernel), D[r][j] = sum_k A[r][k] Z[k][j], register reg of lane (li, lq) holds Q[row0 + 16 rt + lq + 4 reg][64 J + 16 jt + li]
+// and one store instruction writes four 128-byte row segments.  Either order adds to the accumulator of an entry of Q the same four
+// products of the same k-block in the same order -- the swap transposes the tile and exchanges the two factors of each product, and
+// IEEE multiplication is commutative -- so Q has the same bits for all four layout pairs
+// (tests/test_gpu_f64_wide_rowmajor_passes.py compares them on the device).
+// In place with any one layout (q == a, the same layout, ldq == lda) stays safe by the argument above, which speaks of rows and column
+// blocks, not of addresses: a wave owns its 32 rows, output block J is stored after every load of the blocks K <= J, the blocks that
+// follow read columns < 64 J only, and the rows of a row-major operand with ld >= n do not overlap.  Nothing at a row >= m or at a
+// column in [n, ld) is read or written.
+template <bool AROW, bool QROW>
 __global__ __launch_bounds__(256) void apply_wide_f64_kernel(double* q, size_t ldq, const double* a, size_t lda, size_t m, int n, int nb,
                                                              const double* __restrict__ zw) {
 	const int lane = threadIdx.x & 63, li = lane & 15, lq = lane >> 4;
@@ -372,25 +401,34 @@ __global__ __launch_bounds__(256) void apply_wide_f64_kernel(double* q, size_t l
 #pragma unroll
 				for (int rt = 0; rt < 2; rt++) {
 					const size_t row = row0 + 16 * rt + li;
-					av[rt] = (col < n && (full || row < m)) ? a[(size_t)col * lda + row] : 0.0;
+					av[rt] = (col < n && (full || row < m)) ? (AROW ? a[row * lda + col] : a[(size_t)col * lda + row]) : 0.0;
 				}
 #pragma unroll
 				for (int jt = 0; jt < 4; jt++) zop[jt] = zb[(16 * jt + li) * 64 + 4 * kb + lq];
 #pragma unroll
 				for (int jt = 0; jt < 4; jt++)
 #pragma unroll
-					for (int rt = 0; rt < 2; rt++) acc[rt][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(zop[jt], av[rt], acc[rt][jt], 0, 0, 0);
+					for (int rt = 0; rt < 2; rt++) {
+						if constexpr (QROW) acc[rt][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt], zop[jt], acc[rt][jt], 0, 0, 0);
+						else acc[rt][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(zop[jt], av[rt], acc[rt][jt], 0, 0, 0);
+					}
 			}
 		}
 #pragma unroll
 		for (int rt = 0; rt < 2; rt++) {
-			const size_t row = row0 + 16 * rt + li;
 #pragma unroll
 			for (int jt = 0; jt < 4; jt++)
 #pragma unroll
 				for (int reg = 0; reg < 4; reg++) {
-					const int col = 64 * J + 16 * jt + lq + 4 * reg;
-					if (row < m && col < n) q[(size_t)col * ldq + row] = acc[rt][jt][reg];
+					if constexpr (QROW) {
+						const size_t row = row0 + 16 * rt + lq + 4 * reg;
+						const int col = 64 * J + 16 * jt + li;
+						if (row < m && col < n) q[row * ldq + col] = acc[rt][jt][reg];
+					} else {
+						const size_t row = row0 + 16 * rt + li;
+						const int col = 64 * J + 16 * jt + lq + 4 * reg;
+						if (row < m && col < n) q[(size_t)col * ldq + row] = acc[rt][jt][reg];
+					}
 				}
 		}
 	}

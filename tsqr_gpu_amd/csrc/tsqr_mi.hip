@@ -2508,7 +2508,7 @@ int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, 
 }
 
 int f64w_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-               double* wq, double* wr, const Comm* comm);
+               double* wq, double* wr, const Comm* comm, int a_layout = TSQR_MI_COL_MAJOR, int q_layout = TSQR_MI_COL_MAJOR);
 
 // The ladder (include/tsqr_mi.h): verdict 0 of sweep 0 with "one sweep suffices" ends a reorth = 0 call, any other accepted first
 // sweep is followed by one more (CholeskyQR2), a shifted sweep by two more (shifted CholeskyQR3), a rejected one ends the call (state 3).
@@ -2556,13 +2556,13 @@ int f64_ladder(int reorth, hipStream_t st, Sweep sweep) {
 }
 
 // wide: the sweeps of tsqr_mi_qr_f64_wide for n > 64 (f64w_sweep); the verdict words and their meaning are the same.
-// a_layout, q_layout: the n <= 64 sweeps only (f64_sweep); the wide and the row-partitioned entries are column-major.
+// a_layout, q_layout: the layouts of A and Q (tsqr_mi_qr_f64_lay, tsqr_mi_qr_f64_wide_lay); the row-partitioned entries are column-major.
 int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
                 hipStream_t st, bool wide = false, const Comm* comm = nullptr, int a_layout = TSQR_MI_COL_MAJOR,
                 int q_layout = TSQR_MI_COL_MAJOR) {
 	const int dev = cur_device();
 	return f64_ladder(reorth, st, [&](int k) {
-		return wide ? f64w_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm)
+		return wide ? f64w_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm, a_layout, q_layout)
 		            : f64_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm, a_layout, q_layout);
 	});
 }
@@ -2721,16 +2721,19 @@ namespace {
 
 // (F64W_MAX_N, F64W_WR_CAP, F64W_TARGET_WGS, F64WPlan, f64w_plan and the blocked Cholesky step f64w_chain: f64_plan.h)
 
-// sweep k (0-based) of the wide entry: sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R
+// sweep k (0-based) of the wide entry: sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R.  a_layout,
+// q_layout (tsqr_mi_qr_f64_wide_lay) as in f64_sweep: sweep 0 reads A in a_layout -- the Gram pass and the apply pass, which writes Q in
+// q_layout; later sweeps read and write Q in q_layout.  Everything between the two passes works on the block store and knows no layout.
 int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-               double* wq, double* wr, const Comm* comm) {
+               double* wq, double* wr, const Comm* comm, int a_layout, int q_layout) {
 	const bool first = k == 0;
 	const double* src = first ? a : q;
 	const size_t lds = first ? lda : ldq;
+	const int src_layout = first ? a_layout : q_layout;
 	const F64WPlan g = f64w_plan(m, n);
 	if (g.nslices <= 0 || g.npairs <= 0) { t_last_error = "fp64 wide Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
 	const tsqrmi::GramWideF64Args ga{src, lds, m, (int)n, g.npairs, g.ngroups, g.cps, g.nch, wr};
-	hipLaunchKernelGGL(tsqrmi::gram_wide_f64_kernel, dim3((unsigned)(g.ngroups * g.nslices)), dim3(256), 0, st, ga);
+	f64w_gram_launch(st, g, ga, src_layout);
 	HIPCHK(hipGetLastError());
 	const int nelem = (int)g.bs;
 	launch_reduce1(st, wq + g.o_gs, wr, g.nslices, nelem, (double)m);
@@ -2753,8 +2756,7 @@ int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double
 	wa.run_if = wa.status; wa.shift_coef = rule.shift_coef;
 	rc = f64w_chain(st, wa);
 	if (rc) return rc;
-	hipLaunchKernelGGL(tsqrmi::apply_wide_f64_kernel, dim3((unsigned)cdiv(m, 128)), dim3(256), 0, st, q, ldq, src, lds, m, (int)n, g.nb,
-	                   (const double*)(wq + g.o_zw));
+	f64w_apply_launch(st, q, ldq, src, lds, m, (int)n, g.nb, (const double*)(wq + g.o_zw), src_layout, q_layout);
 	HIPCHK(hipGetLastError());
 	if (first) {
 		hipLaunchKernelGGL(tsqrmi::rcopy_wide_f64_kernel, dim3((unsigned)cdiv(n * n, 256)), dim3(256), 0, st, r, ldr, (const double*)(wq + g.o_rw), (int)n);
@@ -2785,16 +2787,24 @@ size_t tsqr_mi_working_r_size_f64_wide(size_t m, size_t n) {
 	return (size_t)g.nslices * g.bs;
 }
 
-int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-                        void* wq, void* wr, void* stream) {
+int tsqr_mi_qr_f64_wide_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                            size_t m, size_t n, void* wq, void* wr, void* stream) {
 	t_sweeps64 = 0;
-	if (n > m || m == 0 || n == 0 || ldq < m || lda < m || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (!f64_layout_ok(a_layout) || !f64_layout_ok(q_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > m || m == 0 || n == 0 || ldq < f64_min_ld(q_layout, m, n) || lda < f64_min_ld(a_layout, m, n) || ldr < n)
+		return TSQR_MI_ERROR_INVALID_SIZE;
 	if (n > F64W_MAX_N) { t_last_error = "tsqr_mi_qr_f64_wide supports n <= 1024"; return TSQR_MI_ERROR_UNSUPPORTED; }
-	if (n <= PW) return tsqr_mi_qr_f64(reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream);
+	if (q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
+	if (n <= PW) return tsqr_mi_qr_f64_lay(a_layout, q_layout, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream);
 	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	if (rc) return rc;
 	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
-	                   reinterpret_cast<hipStream_t>(stream), true);
+	                   reinterpret_cast<hipStream_t>(stream), true, nullptr, a_layout, q_layout);
+}
+
+int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
+                        void* wq, void* wr, void* stream) {
+	return tsqr_mi_qr_f64_wide_lay(TSQR_MI_COL_MAJOR, TSQR_MI_COL_MAJOR, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream);
 }
 
 // ---- row-partitioned fp64: one call per rank, the ladder of tsqr_mi_qr_f64_wide with the exchange of f64_exchange in every sweep ----
