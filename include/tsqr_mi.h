@@ -363,7 +363,11 @@ int tsqr_mi_r_f64(int reorth, double* r, size_t ldr, const double* a, size_t lda
  * entry's), Z = inverse(R) as the product of the sweeps' inverses, then refine + 1 passes that each read A and B once:
  *   X_0 = Z (Q~^T B),   X <- X + Z (Q~^T (B - A X)),   Q~ = A Z formed 16 rows at a time in registers, never stored
  * (lsq_f64_kernel).  The ladder waits on the host as tsqr_mi_r_f64 does; the passes behind it are enqueued back to
- * back with one wait at the end.
+ * back with one wait at the end.  Stagnation rule, from the second correction on and one right-hand side at a time: a correction
+ * whose max_k |D[k][j]|, D = Q~^T (B - A X), is above half of that of the pass before is not applied, and right-hand side j keeps its X
+ * for the rest of the call -- past convergence a correction is the rounding noise of its own pass and only redraws the error of X
+ * (measured without the rule: refine = 3 ended 2.15 times above refine = 2 on a 300 x 17 matrix of cond 1e6).  refine = 0 and 1
+ * return the bits they always returned; refine >= 2 never returns an X that an earlier pass refused to change.
  * Accuracy: each correction pass contracts the error of X by a factor of order cond(A)^2 u, so the method is NOT a substitute for
  * Householder QR beyond cond(A) of about 1e7.  Claimed for cond(A) <= 1e6 and refine >= 1: ||X - X*||_F / ||X*||_F within a small
  * factor of LAPACK's fp64 least-squares solve on the same data (DESIGN.md section 9 and profiles/fp64_lstsq_accuracy.md have the
@@ -374,8 +378,25 @@ int tsqr_mi_r_f64(int reorth, double* r, size_t ldr, const double* a, size_t lda
  * cond(A)^2 u when the residual is small.
  * Non-finite B: B enters the residual through a matrix product with an identity operand, so ONE Inf or NaN in row i of B makes row i of
  * the residual non-finite for all right-hand sides, hence every column of X; the call returns 0.  Non-finite A is the ladder's state 3.
+ * Magnitudes.  A: the column norms of tsqr_mi_qr_f64, [2^-511, 2^512) (||A||_F < 2^512 on the shifted path).  B: a column b of B is in
+ * contract when it is zero or
+ *     2^-960 max(1, ||A||_F)  <=  ||b||_2  <=  2^1000 min(1, sigma_min(A)).
+ * Above, the largest intermediates are |D| <= ||q|| ||b|| and |X| <= ||b|| / sigma_min(A); below, the correction pass of a consistent
+ * system carries a residual of u ||b|| and an update of u ||b|| / ||A||, which must keep a few digits above the subnormal spacing.  The
+ * columns of B do not interact (finite B): column c of X depends on column c of B alone, bit for bit.  Inside these ranges the call is
+ * covariant under powers of two, bit for bit: A diag(2^k_c) and B diag(2^j_c) return diag(2^-k_c) X diag(2^j_c) and R diag(2^k_c) with
+ * the same state and sweeps -- uniform k on every rung of the ladder, per-column k while the ladder does not shift
+ * (tests/test_gpu_f64_lstsq_scale.py; measured there too: a Gaussian column scaled by 2^-1000 or 2^1012, beyond either end, still came
+ * back with the unscaled column's bits).
+ * State 0 and state 3.  State 3 is the ladder's verdict and no rank test: it is returned for Inf or NaN in A, for column norms outside
+ * the range above, and for an exactly zero column (the ladder ends at its cap).  A matrix with dependent but non-zero columns -- a
+ * copied column, a column that is the rounded sum of two others, a tail of copies -- is ACCEPTED on the shifted path: state 0, R
+ * bitwise tsqr_mi_r_f64's, and an X that is finite, deterministic and NOT a least-squares solution.  Measured (4097 x 64 and
+ * 1029 x 51, profiles/fp64_lstsq_scale_tests.md): entries of X of 1e14 .. 7e18; for B in the range of A, ||B - A X||_F of 15 .. 46
+ * (||B||_F 360 .. 1470; the minimum is 1e-13) with one dependent column and 2e5 -- a hundred times ||B||_F -- with a tail of copies.  A
+ * caller that cannot rule out dependent columns must test R (its smallest diagonal entry against its largest) before it uses X.
  * Returns 0; 1 (m, n or nrhs == 0, n > m, lda < m, ldb < m, ldr < n or ldx < n); 2 (n > 64, nrhs > 16, refine outside 0 .. 4;
- * tsqr_mi_last_error says which); 3 = TSQR_MI_ERROR_NOT_FINITE from the ladder (rank-deficient or non-finite A; x is undefined); or
+ * tsqr_mi_last_error says which); 3 = TSQR_MI_ERROR_NOT_FINITE from the ladder (see above; x is undefined); or
  * -(hipError_t).  Sizes are checked before any HIP call.  tsqr_mi_last_sweeps_f64 reports this entry's ladder too.
  */
 size_t tsqr_mi_working_q_size_f64_lstsq(size_t m, size_t n, size_t nrhs);

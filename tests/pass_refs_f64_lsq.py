@@ -7,6 +7,7 @@ import numpy as np
 
 from tests import pass_refs_f64 as p64
 from tests import pass_refs_f64_r as p64r
+from tests import pass_refs_f64_scale as ps
 
 U = p64.U
 LD = p64.LD
@@ -115,17 +116,31 @@ def explicit_inverse(r):
     return z
 
 
+def stagnation_step(x, dx, d, state, p):
+    """lsq_update_f64_kernel's stagnation rule for pass p (0-based) on fp64 arrays: right-hand side j takes its update dx[:, j] unless
+    p >= 2 and max_k |D[k][j]| is above half of the pass before (or the column has stopped already); a column that is refused stops for
+    good.  state: max |D| per column of the pass before, -1 once stopped (None before the first pass).  Returns (X, state)."""
+    with np.errstate(invalid="ignore"):
+        dm = np.fmax.reduce(np.abs(d), axis=0, initial=0.0)                  # (fmax: a NaN is skipped, as on the device)
+        apply = np.ones(d.shape[1], bool) if p < 2 else (state >= 0.0) & ~(dm > 0.5 * state)
+    x = dx if x is None else np.where(apply[None, :], x + dx, x)
+    return x, np.where(apply, dm, -1.0)
+
+
 def model_lstsq(a, b, refine=1, defect=None):
     """fp64 model of the algorithm of tsqr_mi_lstsq_f64, tile-free: R from Householder QR, an explicit Z = inverse(R), Q~ = A Z,
-    X_0 = Z (Q~^T B), then `refine` times X <- X + Z (Q~^T (B - A X)).  Returns (X, R).  defect 'x_sign': the correction is formed from
-    B + A X (the model's own yardstick test)."""
+    X_0 = Z (Q~^T B), then `refine` times X <- X + Z (Q~^T (B - A X)), from the second correction on under the stagnation rule
+    (stagnation_step).  Returns (X, R).  defect 'x_sign': the correction is formed from B + A X (the model's own yardstick test);
+    'no_stagnation_rule': every correction is applied."""
     r = householder_r(a)
     z = explicit_inverse(r)
     q = a @ z
-    x = z @ (q.T @ b)
-    for _ in range(refine):
+    d = q.T @ b
+    x, state = stagnation_step(None, z @ d, d, None, 0)
+    for p in range(1, refine + 1):
         res = b + a @ x if defect == "x_sign" else b - a @ x
-        x = x + z @ (q.T @ res)
+        d = q.T @ res
+        x, state = stagnation_step(x, z @ d, d, state, 0 if defect == "no_stagnation_rule" else p)
     return x, r
 
 
@@ -170,6 +185,8 @@ def normal_residual(a, b, x):
 # ---- the inputs of the entry's accuracy test (tests/test_gpu_f64_lstsq.py; the CPU test runs model_lstsq on the same) --------------------
 SHAPES = ((1, 1, 1), (65, 64, 16), (1000, 7, 3), (9211, 51, 5), (4096, 64, 16))        # (m, n, nrhs), Gaussian A
 CONDS = (1.0, 1e4, 1e6)                                                                    # at 4096 x 64, nrhs 16
+RUNG_SHAPES = ((777, 33, 16), (300, 17, 3), (1029, 51, 5))     # NP != n, NT = 3, 2, 4: both conditioned rungs of the ladder behind f64r_zmul
+RUNG_CONDS = (1e4, 1e6)
 RHS_KINDS = ("consistent", "gaussian")
 FLOOR_COEF = 4.0                                           # the absolute floor of the assertion: 4 n u ("a few n u")
 
@@ -183,7 +200,13 @@ def accuracy_cases():
     for cond in CONDS:
         for kind in RHS_KINDS:
             out.append(("cond%.0e_4096x64_%s" % (cond, kind), 4096, 64, 16, cond, kind))
-    return out
+    return out + rung_cases()
+
+
+def rung_cases():
+    """the cases at RUNG_SHAPES: cond 1e4 and 1e6 with a column tail (n = 16 k + 1, 51) and a ragged last row tile"""
+    return [("cond%.0e_%dx%d_%s" % (cond, m, n, kind), m, n, nrhs, cond, kind)
+            for m, n, nrhs in RUNG_SHAPES for cond in RUNG_CONDS for kind in RHS_KINDS]
 
 
 def accuracy_input(m, n, nrhs, cond, kind):
@@ -198,3 +221,178 @@ def accuracy_input(m, n, nrhs, cond, kind):
 
 def floor_of(n):
     return FLOOR_COEF * n * U
+
+
+# ---- the scaling, range and dependent-column tests of the entry (tests/test_gpu_f64_lstsq_scale.py) ---------------------------------------
+# Generators and exact scalers: tests/pass_refs_f64_scale.py.  What scales how (the code is products, FMAs and MFMA accumulates behind a
+# ladder that is itself covariant): A -> A diag(2^k_c), B -> B diag(2^j_c) gives Z' = diag(2^-k_c) Z, (A Z)' = A Z, residual' and
+# D' = D diag(2^j_c), X' = diag(2^-k_c) X diag(2^j_c), R' = R diag(2^k_c) -- exactly, while nothing leaves the normal range.
+SCALE_SHAPES = ((4097, 64, 16), (1029, 51, 5), (777, 33, 16), (300, 17, 3), (100, 7, 1), (65, 1, 1))     # NT 4, 4, 3, 2, 1, 1
+SCALE_K = ps.UNIFORM_K                                     # A -> 2^k A
+SCALE_J = (-400, 0, 401)                                   # B -> 2^j B
+SCALE_REFINES = (0, 1, 2)
+B_SPAN = 400                                               # B -> B diag(2^j_c), j_c in [-B_SPAN, B_SPAN]
+RANGE_LOG2 = 1000.0                                        # every intermediate of a covariance case inside [2^-1000, 2^1000]
+# The documented range of B (include/tsqr_mi.h): a non-zero column b of B is in contract when
+#     2^B_LOW_LOG2 max(1, ||A||_F)  <=  ||b||_2  <=  2^B_HIGH_LOG2 min(1, sigma_min(A)).
+# Above: the largest intermediates are |D| <= ||q|| ||b|| and |X| <= ||b|| / sigma_min (a row of A X is again of B's size).  Below: on
+# a consistent system the correction passes carry a residual of u ||b|| / sqrt(m) per entry, D of u ||b|| and an update of
+# u ||b|| / ||A||; with (m + n) cond(A) <= 2^43 roundings at the subnormal spacing 2^-1074 they stay below u of the result while
+# ||b|| >= 2^(-1074 + 53 + 43 + margin) max(1, ||A||).
+B_LOW_LOG2, B_HIGH_LOG2 = -960, 1000
+RANGE_SHAPES = ((4097, 64, 5), (1029, 51, 5))              # Gaussian A; one column (RANGE_COLUMN) of B scaled by 2^j
+RANGE_COLUMN = 2
+RANGE_J_INSIDE = (-950, 985)                               # just inside each end (shown from the data on the CPU)
+RANGE_J_BEYOND = (-1000, 1012)                             # beyond each end; the entries of B themselves stay normal and finite
+DEPENDENT_SHAPES = ((4097, 64, 16), (1029, 51, 5))
+
+
+def _frozen(a):
+    a.setflags(write=False)
+    return a
+
+
+def scale_rhs(a, nrhs, seed):
+    """m x nrhs right-hand sides for A: even columns consistent (A x*, x* Gaussian: a residual of rounding size, so that the correction
+    passes carry u ||b||), odd columns Gaussian (a residual as large as b)"""
+    rng = np.random.default_rng(seed)
+    b = rng.standard_normal((a.shape[0], nrhs))
+    xs = rng.standard_normal((a.shape[1], nrhs))
+    b[:, 0::2] = (a @ xs)[:, 0::2]
+    return b
+
+
+_scale_cache = {}
+
+
+def scale_case(m, n, nrhs, name):
+    """(A, B) of a covariance case, shared and read-only: A = pass_refs_f64_scale.uniform_input(name) ('gauss', 'cond1e6', 'cond1e12') or
+    the ladder matrix of that name (graded_inputs); B = scale_rhs on it"""
+    key = (m, n, nrhs, name)
+    if key not in _scale_cache:
+        graded = dict(ps.graded_inputs(m, n))
+        a = graded[name] if name in graded else ps.uniform_input(name, m, n)
+        salt = 11 + sorted(set(ps.UNIFORM_INPUTS) | set(ps.GRADED_LADDER_ROWS) | {"gauss"}).index(name)
+        _scale_cache[key] = (a, _frozen(scale_rhs(a, nrhs, ps.shape_seed(m, n, salt))))
+    return _scale_cache[key]
+
+
+def rhs_groups(nrhs):
+    """the column sets the accuracy rule is applied to: the consistent and the Gaussian columns of scale_rhs, each on its own"""
+    return [("consistent", np.arange(0, nrhs, 2))] + ([("gaussian", np.arange(1, nrhs, 2))] if nrhs > 1 else [])
+
+
+def b_exponents(m, n, nrhs):
+    """j_c of the per-column scaling of B: integers in [-B_SPAN, B_SPAN], both extremes present from two columns on"""
+    return ps.graded_exponents(np.random.default_rng(ps.shape_seed(m, n, 5)), nrhs, B_SPAN)
+
+
+def uniform_pairs():
+    return [(k, j) for k in SCALE_K for j in SCALE_J]
+
+
+def scale_x(x, k, j):
+    """diag(2^-k_c) X diag(2^j_c), exact (asserted by scaling back); k, j: an integer or one integer per row / column"""
+    x = np.asarray(x, np.float64)
+    e = (-np.broadcast_to(np.asarray(k), (x.shape[0],))[:, None] + np.broadcast_to(np.asarray(j), (x.shape[1],))[None, :]).astype(np.int32)
+    with np.errstate(over="ignore", under="ignore"):
+        out = np.ldexp(x, e)
+        back = np.ldexp(out, -e)
+    assert np.array_equal(back.view(np.int64), np.ascontiguousarray(x).view(np.int64)), "the scaling rounded: an entry left the normal range"
+    return out
+
+
+def same_bits(x, y):
+    x, y = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
+    return x.shape == y.shape and np.array_equal(x.view(np.int64), y.view(np.int64))
+
+
+def model_trace(a, b, refine, round_d=None):
+    """model_lstsq with its intermediates: (X, R, Z, [residual of every pass], [D of every pass], [X after every pass]).  round_d: the
+    seeded defect of the covariance check -- D is rounded to that type (np.float32: a narrowed accumulate) before it is used."""
+    r = householder_r(a)
+    z = explicit_inverse(r)
+    q = a @ z
+    res_all, d_all, x_all = [], [], []
+    x = None
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        state = None
+        for p in range(refine + 1):
+            res = b if x is None else b - a @ x
+            d = q.T @ res
+            if round_d is not None:
+                d = d.astype(round_d).astype(np.float64)
+            x, state = stagnation_step(x, z @ d, d, state, p)
+            res_all.append(res); d_all.append(d); x_all.append(x)
+    return x, r, z, res_all, d_all, x_all
+
+
+def log2_span(x, row_exp=0, col_exp=0):
+    """(lowest, highest) log2 of the non-zero magnitudes of diag(2^row_exp) x diag(2^col_exp), taken in longdouble (exponent range
+    2^+-16383: nothing under test can leave it, so an fp64 underflow cannot hide here)"""
+    p64.require_longdouble()
+    x = np.asarray(x, LD)
+    e = (np.broadcast_to(np.asarray(row_exp), (x.shape[0],))[:, None] + np.broadcast_to(np.asarray(col_exp), (x.shape[1],))[None, :])
+    v = np.abs(np.ldexp(x, e.astype(np.int32)))
+    v = v[v != 0]
+    if v.size == 0:
+        return 0.0, 0.0
+    return float(np.log2(v.min())), float(np.log2(v.max()))
+
+
+def scaled_spans(trace, k, j):
+    """{name: (lowest, highest) log2} of Z, the residuals, D and X of every pass of the call on A diag(2^k) and B diag(2^j), from the
+    trace of the unscaled model"""
+    _, _, z, res_all, d_all, x_all = trace
+    out = {"Z": log2_span(z, row_exp=-np.asarray(k))}
+    for p, (res, d, x) in enumerate(zip(res_all, d_all, x_all)):
+        out["residual%d" % p] = log2_span(res, col_exp=j)
+        out["D%d" % p] = log2_span(d, col_exp=j)
+        out["X%d" % p] = log2_span(x, row_exp=-np.asarray(k), col_exp=j)
+    return out
+
+
+def column_err(x, ref, cols):
+    """rel_err on a set of columns"""
+    return rel_err(np.asarray(x)[:, cols], ref[:, cols])
+
+
+def b_range_log2(a):
+    """(lowest, highest) log2 of the 2-norm of a non-zero column of B that include/tsqr_mi.h puts in contract for this A"""
+    sv = np.linalg.svd(a, compute_uv=False)
+    fro = float(np.sqrt(np.sum(sv * sv)))
+    return B_LOW_LOG2 + np.log2(max(1.0, fro)), B_HIGH_LOG2 + np.log2(min(1.0, float(sv[-1])))
+
+
+def range_case(m, n, nrhs, kind):
+    """(A, B) of the range test: Gaussian A, B consistent or Gaussian (accuracy_input's kinds)"""
+    key = ("range", m, n, nrhs, kind)
+    if key not in _scale_cache:
+        a = ps.gaussian(m, n)
+        rng = np.random.default_rng(ps.shape_seed(m, n, 17))
+        b = a @ rng.standard_normal((n, nrhs)) if kind == "consistent" else rng.standard_normal((m, nrhs))
+        _scale_cache[key] = (a, _frozen(b))
+    return _scale_cache[key]
+
+
+def scale_one_column(b, col, j):
+    k = np.zeros(b.shape[1], dtype=np.int64)
+    k[col] = j
+    return ps.scale_columns(b, k)
+
+
+def independent_columns(name, n, j0):
+    """the columns that remain when the dependent ones of pass_refs_f64_scale.dependent_cases are pivoted out"""
+    return np.arange(j0) if name.startswith("d_") else np.array([c for c in range(n) if c != j0])
+
+
+def min_residual_ld(a, b, keep):
+    """min_X ||B - A X||_F in longdouble over the independent columns `keep` of A (the dependent ones add nothing to the range)"""
+    al, bl = a[:, keep].astype(LD), b.astype(LD)
+    e = bl - al @ lstsq_ld(a[:, keep], b)
+    return float(np.sqrt(np.sum(e * e)))
+
+
+def residual_ld(a, b, x):
+    e = b.astype(LD) - a.astype(LD) @ np.asarray(x, LD)
+    return float(np.sqrt(np.sum(e * e)))

@@ -680,10 +680,13 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
     (stride(1) == 1, stride(0) >= its column count: every contiguous torch tensor), or when it has a single column; any other operand
     (a[:, ::2], an expanded or overlapping view) is copied once into column-major storage.  The result has the same bits whichever way
     the operand is stored.  reorth: the R-only ladder's argument (r_f64); refine: correction
-    passes, 0 .. 4.  Blocking.  Returns (x, r): x n x nrhs (n when b is one-dimensional), r the n x n upper-triangular factor, bitwise
+    passes, 0 .. 4 (from the second on, a right-hand side whose correction did not halve keeps its x and stops).  Blocking.  Returns (x, r): x n x nrhs (n when b is one-dimensional), r the n x n upper-triangular factor, bitwise
     r_f64's on the same a.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for shapes that do not fit together, LstsqError
     (.state) when the C entry returns a state other than 0: sizes it does not support, or error_not_finite from the ladder (Inf or NaN
-    in a, or a rank-deficient a).  last_sweeps_f64() tells how many sweeps the ladder took."""
+    in a, a column norm outside [2^-511, 2^512), or an exactly zero column).  That state is no rank test: dependent but non-zero columns
+    (a copied column, a sum of two others) are accepted on the shifted path, and the x that comes back is finite and NOT a
+    least-squares solution (entries of 1e14 and more; include/tsqr_mi.h has the measured residuals and the range of b's magnitudes) --
+    test r before using x when the columns may be dependent.  last_sweeps_f64() tells how many sweeps the ladder took."""
     import torch
     for opname, t in (("a", a), ("b", b)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:

@@ -118,7 +118,8 @@ inline void f64r_gramq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::Gr
 constexpr size_t F64L_MAX_NRHS = 16;
 constexpr int F64L_MAX_REFINE = 4;
 // wq (doubles): [the F64R_WQ layout][X, NP x 16 (ld NP): 1024][summed D: 4 tiles of 256 + the row-count word of the reduction]
-constexpr size_t F64L_X = F64R_WQ, F64L_D = F64L_X + 1024, F64L_WQ = F64L_D + 1024 + 8;
+// [max |D| of the pass before, one per right-hand side: the stagnation rule of lsq_update_f64_kernel: 16]
+constexpr size_t F64L_X = F64R_WQ, F64L_D = F64L_X + 1024, F64L_DPREV = F64L_D + 1024 + 8, F64L_WQ = F64L_DPREV + 16;
 
 // one pass of the least-squares entry on stream st: lsq_f64_kernel<NT, AROW, BROW> on the R-only plan's grid
 inline void f64r_lsq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::LsqArgs64& la, int a_layout = 0, int b_layout = 0) {

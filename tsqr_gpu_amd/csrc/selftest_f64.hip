@@ -206,7 +206,8 @@ int tsqr_selftest_f64_lsq(double* dsum, const double* a, size_t lda, const doubl
 // lsq_update_f64_kernel: xw (NP x 16, ld NP) <- xw + z d (first: xw taken as zero), and x (n x nrhs, ldx) too when last
 int tsqr_selftest_f64_lsq_update(double* xw, double* x, size_t ldx, const double* z, const double* d, int n, int nrhs, int first, int last) {
 	if (n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || ldx < (size_t)n) return -100;
-	hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel, dim3(1), dim3(1024), 0, 0, xw, x, ldx, z, d, n, (int)np_of((size_t)n), nrhs, first, last);
+	hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel, dim3(1), dim3(1024), 0, 0, xw, x, ldx, z, d, n, (int)np_of((size_t)n), nrhs, first, last,
+	                   (double*)nullptr, 0);                  // (no stagnation rule: every update is applied)
 	return f64_sync();
 }
 

@@ -439,16 +439,35 @@ __global__ __launch_bounds__(256) void lsq_f64_kernel(const LsqArgs64 a) {
 // partials of lsq_f64_kernel, D[k][j] at ((k >> 4) * 4 + ((k & 15) >> 2)) * 64 + (k & 3) * 16 + j.  Z upper triangular: row i sums
 // k = i .. n - 1, in that order, one fused multiply-add each, so the bits do not depend on how the compiler contracts.  last: the result
 // also goes to the caller's x (n x nrhs, ldx).  Thread (i, j) reads and writes no entry of X but its own.
+// dprev (16 doubles, or null: every update is applied): the stagnation rule of the refinement, one right-hand side at a time.  dprev[j]
+// holds max_k |D[k][j]| of the pass before, or -1 once right-hand side j has stopped.  With guard set (the entry sets it from the
+// second correction on) an update whose max_k |D[k][j]| is above half of the one before is NOT applied and right-hand side j stops for
+// the rest of the call: past convergence a correction is the rounding noise of its own pass, and applying it only redraws the error of
+// X.  D = Q~^T (B - A X) is the correction measured in Q-space: it keeps its bits under a column scaling of A and scales exactly with
+// column j of B, so the verdict is the same for A diag(2^k_c), B diag(2^j_c).  A NaN in D is skipped by the maximum, +Inf compares as
+// not above +Inf: non-finite data are applied as before.
 __global__ __launch_bounds__(1024) void lsq_update_f64_kernel(double* xw, double* x, size_t ldx, const double* __restrict__ z,
-                                                              const double* __restrict__ d, int n, int NP, int nrhs, int first, int last) {
+                                                              const double* __restrict__ d, int n, int NP, int nrhs, int first, int last,
+                                                              double* dprev, int guard) {
 	const int i = threadIdx.x & 63, j = threadIdx.x >> 6;
+	bool apply = true;
+	if (dprev) {                                          // (uniform over the workgroup: every thread reaches the barrier)
+		double dm = 0.0;
+		if (j < nrhs)
+			for (int k = 0; k < n; k++) dm = fmax(dm, fabs(d[((k >> 4) * 4 + ((k & 15) >> 2)) * 64 + (k & 3) * 16 + j]));
+		const double pv = dprev[j];
+		if (guard) apply = pv >= 0.0 && !(dm > 0.5 * pv);
+		__syncthreads();                                  // every thread of right-hand side j has read dprev[j]
+		if (i == 0) dprev[j] = apply ? dm : -1.0;
+	}
 	if (i >= NP) return;
 	double v = 0.0;
 	if (i < n && j < nrhs) {
 		double s = 0.0;
-		for (int k = i; k < n; k++)
-			s = __builtin_fma(z[(size_t)k * NP + i], d[((k >> 4) * 4 + ((k & 15) >> 2)) * 64 + (k & 3) * 16 + j], s);
-		v = (first ? 0.0 : xw[(size_t)j * NP + i]) + s;
+		if (apply)
+			for (int k = i; k < n; k++)
+				s = __builtin_fma(z[(size_t)k * NP + i], d[((k >> 4) * 4 + ((k & 15) >> 2)) * 64 + (k & 3) * 16 + j], s);
+		v = apply ? (first ? 0.0 : xw[(size_t)j * NP + i]) + s : xw[(size_t)j * NP + i];
 		if (last) x[(size_t)j * ldx + i] = v;
 	}
 	xw[(size_t)j * NP + i] = v;

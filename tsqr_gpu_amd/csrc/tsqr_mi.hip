@@ -2606,7 +2606,8 @@ int r_f64_core(int a_layout, int reorth, double* r, size_t ldr, const double* a,
 // The least-squares entry behind the R-only ladder (corrected semi-normal equations carried out in Q-space; include/tsqr_mi.h).  The
 // ladder's last sweep s left Z_1 ... Z_(s-1) in wq[F64R_ZACC] (nothing for s = 1) and Z_s in wq[F64_Z]: one copy or one product
 // (f64r_zacc) completes Z = inverse(R).  Then refine + 1 passes, each lsq_f64_kernel (D = (A Z)^T (B - A X), X null the first time), the reduction
-// and X <- X + Z D, enqueued back to back; one wait at the end.
+// and X <- X + Z D, enqueued back to back; one wait at the end.  From the second correction on a right-hand side whose D did not halve is
+// left as it is and stops (lsq_update_f64_kernel's stagnation rule; its state lies in wq[F64L_DPREV]): refine <= 1 is untouched by it.
 int lstsq_f64_core(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
                    const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, double* wq, double* wr, hipStream_t st) {
 	if (const int rc = r_f64_core(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, st)) return rc;
@@ -2622,7 +2623,7 @@ int lstsq_f64_core(int a_layout, int b_layout, int reorth, int refine, double* x
 		launch_reduce1(st, dsum, wr, g.nblocks, g.NT * 256, (double)m);
 		HIPCHK(hipGetLastError());
 		hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel, dim3(1), dim3(1024), 0, st, xw, x, ldx, (const double*)zacc, (const double*)dsum,
-		                   (int)n, (int)NP, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0);
+		                   (int)n, (int)NP, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0, wq + F64L_DPREV, p >= 2 ? 1 : 0);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipStreamSynchronize(st));
