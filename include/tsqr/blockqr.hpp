@@ -102,6 +102,39 @@ template <> struct entry<half_t> {
 		return tsqr_mi_qr_f16(mode, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, reorth_w, d_wl, h_wl, stream);
 	}
 };
+// Work space of a double-precision entry: two device arrays of doubles.  The buffers of the fp64 entries derive from it and add
+// only their allocate(...), which names the entry's two size functions; they stay distinct types on purpose.
+struct buffer_fp64_base {
+	double* dwq;
+	double* dwr;
+	std::size_t total_memory_size;
+
+	buffer_fp64_base() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
+	~buffer_fp64_base() { destroy(); }
+	buffer_fp64_base(const buffer_fp64_base&) = delete;
+	buffer_fp64_base& operator=(const buffer_fp64_base&) = delete;
+
+	void destroy() {
+		if (dwq) (void)hipFree(dwq);
+		dwq = nullptr;
+		if (dwr) (void)hipFree(dwr);
+		dwr = nullptr;
+	}
+
+	std::size_t get_device_memory_size() const { return total_memory_size; }
+
+protected:
+	void allocate_doubles(const std::size_t wq_doubles, const std::size_t wr_doubles) {
+		if (dwq != nullptr || dwr != nullptr) {
+			throw std::runtime_error("The buffer has been already allocated");
+		}
+		const auto wq_size = sizeof(double) * wq_doubles;
+		const auto wr_size = sizeof(double) * wr_doubles;
+		check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
+		check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
+		total_memory_size = wq_size + wr_size;
+	}
+};
 }  // namespace detail
 
 template <mtk::qr::compute_mode mode, bool Reorthogonalize>
@@ -292,35 +325,8 @@ inline state_t qr_batch(
 const state_t error_not_finite = TSQR_MI_ERROR_NOT_FINITE;
 
 template <bool Reorthogonalize>
-struct buffer_fp64 {
-	double* dwq;
-	double* dwr;
-	std::size_t total_memory_size;
-
-	buffer_fp64() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
-	~buffer_fp64() { destroy(); }
-	buffer_fp64(const buffer_fp64&) = delete;
-	buffer_fp64& operator=(const buffer_fp64&) = delete;
-
-	void allocate(const std::size_t m, const std::size_t n) {
-		if (dwq != nullptr || dwr != nullptr) {
-			throw std::runtime_error("The buffer has been already allocated");
-		}
-		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64(m, n);
-		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64(m, n);
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
-		total_memory_size = wq_size + wr_size;
-	}
-
-	void destroy() {
-		if (dwq) (void)hipFree(dwq);
-		dwq = nullptr;
-		if (dwr) (void)hipFree(dwr);
-		dwr = nullptr;
-	}
-
-	std::size_t get_device_memory_size() const { return total_memory_size; }
+struct buffer_fp64 : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n) { allocate_doubles(tsqr_mi_working_q_size_f64(m, n), tsqr_mi_working_r_size_f64(m, n)); }
 };
 
 // layout_t: how a (for qr_fp64 also q, for lstsq_fp64 also b) is stored.  row_major: element (i, j) at ptr[i * ld + j], ld >= the column
@@ -348,35 +354,8 @@ inline state_t qr_fp64(
 // Not in the reference: the R factor of qr_fp64 alone, Q never formed (tsqr_mi_r_f64, include/tsqr_mi.h for the contract): a is read
 // only, no m x n work space.  Returns the states of qr_fp64.
 template <bool Reorthogonalize>
-struct buffer_fp64_r {
-	double* dwq;
-	double* dwr;
-	std::size_t total_memory_size;
-
-	buffer_fp64_r() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
-	~buffer_fp64_r() { destroy(); }
-	buffer_fp64_r(const buffer_fp64_r&) = delete;
-	buffer_fp64_r& operator=(const buffer_fp64_r&) = delete;
-
-	void allocate(const std::size_t m, const std::size_t n) {
-		if (dwq != nullptr || dwr != nullptr) {
-			throw std::runtime_error("The buffer has been already allocated");
-		}
-		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_r(m, n);
-		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_r(m, n);
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
-		total_memory_size = wq_size + wr_size;
-	}
-
-	void destroy() {
-		if (dwq) (void)hipFree(dwq);
-		dwq = nullptr;
-		if (dwr) (void)hipFree(dwr);
-		dwr = nullptr;
-	}
-
-	std::size_t get_device_memory_size() const { return total_memory_size; }
+struct buffer_fp64_r : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n) { allocate_doubles(tsqr_mi_working_q_size_f64_r(m, n), tsqr_mi_working_r_size_f64_r(m, n)); }
 };
 
 template <bool Reorthogonalize>
@@ -396,35 +375,8 @@ inline state_t r_fp64(
 // for the contract and the accuracy statement): a and b are read only, no work space of size m.  Returns the states of r_fp64;
 // error_unsupported_mode also for nrhs > 16 or refine outside 0 .. 4.
 template <bool Reorthogonalize>
-struct buffer_fp64_lstsq {
-	double* dwq;
-	double* dwr;
-	std::size_t total_memory_size;
-
-	buffer_fp64_lstsq() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
-	~buffer_fp64_lstsq() { destroy(); }
-	buffer_fp64_lstsq(const buffer_fp64_lstsq&) = delete;
-	buffer_fp64_lstsq& operator=(const buffer_fp64_lstsq&) = delete;
-
-	void allocate(const std::size_t m, const std::size_t n, const std::size_t nrhs) {
-		if (dwq != nullptr || dwr != nullptr) {
-			throw std::runtime_error("The buffer has been already allocated");
-		}
-		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs);
-		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_lstsq(m, n, nrhs);
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
-		total_memory_size = wq_size + wr_size;
-	}
-
-	void destroy() {
-		if (dwq) (void)hipFree(dwq);
-		dwq = nullptr;
-		if (dwr) (void)hipFree(dwr);
-		dwr = nullptr;
-	}
-
-	std::size_t get_device_memory_size() const { return total_memory_size; }
+struct buffer_fp64_lstsq : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n, const std::size_t nrhs) { allocate_doubles(tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs), tsqr_mi_working_r_size_f64_lstsq(m, n, nrhs)); }
 };
 
 template <bool Reorthogonalize>
@@ -448,35 +400,8 @@ inline state_t lstsq_fp64(
 // error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.  a_layout, q_layout (tsqr_mi_qr_f64_wide_lay): the
 // layouts of a and of q as for qr_fp64 -- they need not agree; in place, q_ptr == a_ptr, needs equal layouts and ldq == lda.
 template <bool Reorthogonalize>
-struct buffer_fp64_wide {
-	double* dwq;
-	double* dwr;
-	std::size_t total_memory_size;
-
-	buffer_fp64_wide() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
-	~buffer_fp64_wide() { destroy(); }
-	buffer_fp64_wide(const buffer_fp64_wide&) = delete;
-	buffer_fp64_wide& operator=(const buffer_fp64_wide&) = delete;
-
-	void allocate(const std::size_t m, const std::size_t n) {
-		if (dwq != nullptr || dwr != nullptr) {
-			throw std::runtime_error("The buffer has been already allocated");
-		}
-		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_wide(m, n);
-		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_wide(m, n);
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
-		total_memory_size = wq_size + wr_size;
-	}
-
-	void destroy() {
-		if (dwq) (void)hipFree(dwq);
-		dwq = nullptr;
-		if (dwr) (void)hipFree(dwr);
-		dwr = nullptr;
-	}
-
-	std::size_t get_device_memory_size() const { return total_memory_size; }
+struct buffer_fp64_wide : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n) { allocate_doubles(tsqr_mi_working_q_size_f64_wide(m, n), tsqr_mi_working_r_size_f64_wide(m, n)); }
 };
 
 template <bool Reorthogonalize>
@@ -497,35 +422,8 @@ inline state_t qr_fp64_wide(
 // caller's ncclComm_t -- the caller links RCCL, ncclAllReduce is taken from the global symbol scope.  R is the same on every rank.
 // Returns success_factorization, error_invalid_matrix_size, error_unsupported_mode (n > 1024, or no ncclAllReduce) or error_not_finite.
 template <bool Reorthogonalize>
-struct buffer_fp64_dist {
-	double* dwq;
-	double* dwr;
-	std::size_t total_memory_size;
-
-	buffer_fp64_dist() : dwq(nullptr), dwr(nullptr), total_memory_size(0lu) {}
-	~buffer_fp64_dist() { destroy(); }
-	buffer_fp64_dist(const buffer_fp64_dist&) = delete;
-	buffer_fp64_dist& operator=(const buffer_fp64_dist&) = delete;
-
-	void allocate(const std::size_t m_local, const std::size_t n, const int nranks) {
-		if (dwq != nullptr || dwr != nullptr) {
-			throw std::runtime_error("The buffer has been already allocated");
-		}
-		const auto wq_size = sizeof(double) * tsqr_mi_working_q_size_f64_dist(m_local, n, nranks);
-		const auto wr_size = sizeof(double) * tsqr_mi_working_r_size_f64_dist(m_local, n, nranks);
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwq), wq_size), "hipMalloc(dwq)");
-		detail::check(hipMalloc(reinterpret_cast<void**>(&dwr), wr_size), "hipMalloc(dwr)");
-		total_memory_size = wq_size + wr_size;
-	}
-
-	void destroy() {
-		if (dwq) (void)hipFree(dwq);
-		dwq = nullptr;
-		if (dwr) (void)hipFree(dwr);
-		dwr = nullptr;
-	}
-
-	std::size_t get_device_memory_size() const { return total_memory_size; }
+struct buffer_fp64_dist : detail::buffer_fp64_base {
+	void allocate(const std::size_t m_local, const std::size_t n, const int nranks) { allocate_doubles(tsqr_mi_working_q_size_f64_dist(m_local, n, nranks), tsqr_mi_working_r_size_f64_dist(m_local, n, nranks)); }
 };
 
 template <bool Reorthogonalize>

@@ -2,10 +2,10 @@
 call, the Python operand checks of qr_f64, and a C++ caller of mtk::qr::qr_fp64 that compiles and links."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import pytest
+
+from abi_util import compile_and_link
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -140,13 +140,5 @@ int main() {
 
 
 def test_cpp_qr_fp64_compiles_and_links(bq):
-    lib_dir = os.path.dirname(bq.LIB_PATH)
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sample_fp64.cpp")
-        with open(src, "w") as f:
-            f.write(CPP_SAMPLE)
-        exe = os.path.join(td, "sample_fp64")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-o", exe, src,
-                               "-L" + lib_dir, "-ltsqr_mi", "-Wl,-rpath," + lib_dir])
+    with compile_and_link(CPP_SAMPLE, "sample_fp64") as exe:
         assert os.path.exists(exe)

@@ -3,11 +3,10 @@ work-space sizes, the argument checks that come before any HIP call and before a
 dist.RowPartitionedQRF64's binding, and a C++ caller of mtk::qr::qr_fp64_dist that compiles and links."""
 import ctypes
 import os
-import re
-import subprocess
-import tempfile
 
 import pytest
+
+from abi_util import compile_and_link, header_flat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,14 +22,9 @@ CALLED = []
 CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)(lambda *a: CALLED.append(a) or 0)
 
 
-def _squash(text):
-    """one line, the ' * ' in front of a comment's continuation lines taken out"""
-    return re.sub(r"\s+", " ", re.sub(r"\n \* ", "\n", text))
-
-
 def test_f64_dist_symbols_and_prototypes(bq):
     L = ctypes.CDLL(bq.LIB_PATH)
-    hdr = _squash(open(os.path.join(ROOT, "include", "tsqr_mi.h")).read())
+    hdr = header_flat()
     for sym, proto in PROTOTYPES.items():
         assert hasattr(L, sym), sym
         assert proto in hdr, proto
@@ -157,13 +151,5 @@ int main() {
 
 
 def test_cpp_qr_fp64_dist_compiles_and_links(bq):
-    lib_dir = os.path.dirname(bq.LIB_PATH)
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sample_fp64_dist.cpp")
-        with open(src, "w") as f:
-            f.write(CPP_SAMPLE)
-        exe = os.path.join(td, "sample_fp64_dist")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-o", exe, src,
-                               "-L" + lib_dir, "-ltsqr_mi", "-Wl,-rpath," + lib_dir])
+    with compile_and_link(CPP_SAMPLE, "sample_fp64_dist") as exe:
         assert os.path.exists(exe)

@@ -3,11 +3,10 @@ checks that come before any HIP call, the Python operand checks of lstsq_f64, an
 links (with hipcc, the way tests/test_f64_r_abi.py builds its sample)."""
 import ctypes
 import os
-import re
-import subprocess
-import tempfile
 
 import pytest
+
+from abi_util import compile_and_link, header_flat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -16,8 +15,7 @@ SYMBOLS = ("tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_wor
 
 def test_lstsq_symbols_exported_with_the_stated_signatures(bq):
     L = ctypes.CDLL(bq.LIB_PATH)
-    hdr = open(os.path.join(ROOT, "include", "tsqr_mi.h")).read()
-    flat = re.sub(r"\s+", " ", hdr)
+    flat = header_flat()
     for sym in SYMBOLS:
         assert hasattr(L, sym), sym
         assert sym in bq.C_ABI_SYMBOLS, sym
@@ -148,13 +146,5 @@ int main() {
 
 
 def test_cpp_lstsq_fp64_compiles_and_links(bq):
-    lib_dir = os.path.dirname(bq.LIB_PATH)
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sample_fp64_lstsq.cpp")
-        with open(src, "w") as f:
-            f.write(CPP_SAMPLE)
-        exe = os.path.join(td, "sample_fp64_lstsq")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-o", exe, src,
-                               "-L" + lib_dir, "-ltsqr_mi", "-Wl,-rpath," + lib_dir])
+    with compile_and_link(CPP_SAMPLE, "sample_fp64_lstsq") as exe:
         assert os.path.exists(exe)

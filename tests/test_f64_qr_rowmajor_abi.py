@@ -4,11 +4,11 @@ argument errors of qr_f64_tensor, and a C++ caller of the layout arguments of mt
 import ctypes
 import inspect
 import os
-import re
 import subprocess
-import tempfile
 
 import pytest
+
+from abi_util import compile_and_link, header_flat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COL, ROW = 0, 1
@@ -16,7 +16,7 @@ COL, ROW = 0, 1
 
 def test_symbol_prototype_and_hook(bq):
     L = ctypes.CDLL(bq.LIB_PATH)
-    flat = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "tsqr_mi.h")).read())
+    flat = header_flat()
     assert hasattr(L, "tsqr_mi_qr_f64_lay")
     assert "tsqr_mi_qr_f64_lay" in bq.C_ABI_SYMBOLS
     assert ("int tsqr_mi_qr_f64_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, "
@@ -152,13 +152,8 @@ def test_python_surfaces_are_checked_on_the_cpu(bq):
 
 
 def test_cpp_layout_sample_compiles_links_and_runs(bq):
-    lib_dir = os.path.dirname(bq.LIB_PATH)
     src = os.path.join(ROOT, "tests", "cpp", "sample_fp64_qr_rowmajor.cpp")
-    with tempfile.TemporaryDirectory() as td:
-        exe = os.path.join(td, "sample_fp64_qr_rowmajor")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-o", exe, src,
-                               "-L" + lib_dir, "-ltsqr_mi", "-Wl,-rpath," + lib_dir])
+    with compile_and_link(src, "sample_fp64_qr_rowmajor") as exe:
         out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
         assert out.returncode == 0, out.stdout + out.stderr
         assert "argument checks ok" in out.stdout

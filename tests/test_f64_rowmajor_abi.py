@@ -3,11 +3,11 @@ before any HIP call, the layout lstsq_f64 chooses for an operand (strides only: 
 check_f64_r_operands, and a C++ caller of the layout arguments of mtk::qr::r_fp64 / lstsq_fp64 (tests/cpp/sample_fp64_rowmajor.cpp)."""
 import ctypes
 import os
-import re
 import subprocess
-import tempfile
 
 import pytest
+
+from abi_util import compile_and_link, header_flat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COL, ROW = 0, 1
@@ -15,7 +15,7 @@ COL, ROW = 0, 1
 
 def test_layout_symbols_and_constants(bq):
     L = ctypes.CDLL(bq.LIB_PATH)
-    flat = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "tsqr_mi.h")).read())
+    flat = header_flat()
     for sym in ("tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay"):
         assert hasattr(L, sym), sym
         assert sym in bq.C_ABI_SYMBOLS, sym
@@ -137,13 +137,8 @@ def test_r_f64_row_major_keyword_is_checked_on_the_cpu(bq):
 
 
 def test_cpp_layout_sample_compiles_links_and_runs(bq):
-    lib_dir = os.path.dirname(bq.LIB_PATH)
     src = os.path.join(ROOT, "tests", "cpp", "sample_fp64_rowmajor.cpp")
-    with tempfile.TemporaryDirectory() as td:
-        exe = os.path.join(td, "sample_fp64_rowmajor")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-o", exe, src,
-                               "-L" + lib_dir, "-ltsqr_mi", "-Wl,-rpath," + lib_dir])
+    with compile_and_link(src, "sample_fp64_rowmajor") as exe:
         out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
         assert out.returncode == 0, out.stdout + out.stderr
         assert "argument checks ok" in out.stdout

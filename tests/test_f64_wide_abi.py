@@ -3,10 +3,10 @@ the Gram partials included), argument checks that come before any HIP call, the 
 of mtk::qr::qr_fp64_wide that compiles and links."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import pytest
+
+from abi_util import compile_and_link
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -127,13 +127,5 @@ int main() {
 
 
 def test_cpp_qr_fp64_wide_compiles_and_links(bq):
-    lib_dir = os.path.dirname(bq.LIB_PATH)
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sample_fp64_wide.cpp")
-        with open(src, "w") as f:
-            f.write(CPP_SAMPLE)
-        exe = os.path.join(td, "sample_fp64_wide")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-o", exe, src,
-                               "-L" + lib_dir, "-ltsqr_mi", "-Wl,-rpath," + lib_dir])
+    with compile_and_link(CPP_SAMPLE, "sample_fp64_wide") as exe:
         assert os.path.exists(exe)

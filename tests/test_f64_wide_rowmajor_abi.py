@@ -5,11 +5,11 @@ layout arguments of mtk::qr::qr_fp64_wide (tests/cpp/sample_fp64_wide_rowmajor.c
 import ctypes
 import inspect
 import os
-import re
 import subprocess
-import tempfile
 
 import pytest
+
+from abi_util import compile_and_link, header_flat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COL, ROW = 0, 1
@@ -17,7 +17,7 @@ COL, ROW = 0, 1
 
 def test_symbol_prototype_and_hooks(bq):
     L = ctypes.CDLL(bq.LIB_PATH)
-    flat = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "tsqr_mi.h")).read())
+    flat = header_flat()
     assert hasattr(L, "tsqr_mi_qr_f64_wide_lay")
     assert "tsqr_mi_qr_f64_wide_lay" in bq.C_ABI_SYMBOLS
     assert ("int tsqr_mi_qr_f64_wide_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, "
@@ -193,13 +193,8 @@ def test_qr_f64_wide_tensor_argument_errors(bq):
 
 
 def test_cpp_layout_sample_compiles_links_and_runs(bq):
-    lib_dir = os.path.dirname(bq.LIB_PATH)
     src = os.path.join(ROOT, "tests", "cpp", "sample_fp64_wide_rowmajor.cpp")
-    with tempfile.TemporaryDirectory() as td:
-        exe = os.path.join(td, "sample_fp64_wide_rowmajor")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-o", exe, src,
-                               "-L" + lib_dir, "-ltsqr_mi", "-Wl,-rpath," + lib_dir])
+    with compile_and_link(src, "sample_fp64_wide_rowmajor") as exe:
         out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
         assert out.returncode == 0, out.stdout + out.stderr
         assert "argument checks ok" in out.stdout

@@ -38,27 +38,6 @@ error_invalid_matrix_size = 1         # reference src/blockqr.hpp:29
 error_unsupported_mode = 2            # new: modes without a gfx950 implementation
 error_not_finite = 3                  # new, qr_f64 only: A holds an Inf or NaN
 
-C_ABI_SYMBOLS = [
-    "tsqr_mi_version", "tsqr_mi_last_error",
-    "tsqr_mi_working_q_size", "tsqr_mi_working_r_size", "tsqr_mi_working_l_size",
-    "tsqr_mi_working_reorth_size", "tsqr_mi_batch_size_log2", "tsqr_mi_batch_size",
-    "tsqr_mi_qr_f32", "tsqr_mi_local_r_f32", "tsqr_mi_apply_rinv_f32", "tsqr_mi_rmul_f32",
-    "tsqr_mi_qr_f32_dist", "tsqr_mi_set_tuning", "tsqr_mi_profile_enable", "tsqr_mi_profile_read",
-    "tsqr_mi_set_policy", "tsqr_mi_last_engine", "tsqr_mi_set_tuning2",
-    "tsqr_mi_gram_elems", "tsqr_mi_gram_f32", "tsqr_mi_chol_f32", "tsqr_mi_chol_status", "tsqr_mi_stream_wait", "tsqr_mi_apply_z_f32", "tsqr_mi_validate_f32",
-    "tsqr_mi_working_q_size_dist", "tsqr_mi_working_r_size_dist", "tsqr_mi_qr_f32_dist_cb",
-    "tsqr_mi_qr_f32_loop", "tsqr_mi_qr_f32_dist_fn", "tsqr_mi_qr_f32_dist_fn_loop", "tsqr_mi_qr_f32_dist_cb_loop",
-    "tsqr_mi_qr_f16", "tsqr_mi_qr_f16_loop", "tsqr_mi_working_q_size_f16", "tsqr_mi_working_r_size_f16",
-    "tsqr_mi_qr_f32_submit", "tsqr_mi_qr_f32_finish", "tsqr_mi_set_loop_depth", "tsqr_mi_qr_f32_batch", "tsqr_mi_qr_f16_batch",
-    "tsqr_mi_qr_f32_dist_fn_batch", "tsqr_mi_qr_f32_dist_cb_batch",
-    "tsqr_mi_qr_f64", "tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64", "tsqr_mi_last_sweeps_f64",
-    "tsqr_mi_qr_f64_wide", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide",
-    "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
-    "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
-    "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
-    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay",
-]
-
 COL_MAJOR, ROW_MAJOR = 0, 1              # TSQR_MI_COL_MAJOR, TSQR_MI_ROW_MAJOR: the layout arguments of the *_lay entries
 
 
@@ -89,6 +68,65 @@ class Ticket(ctypes.Structure):
 
 FP16_MODES = (compute_mode.fp16_notc, compute_mode.fp16_tc_nocor)     # io type half in the reference (src/tsqr.hpp:38-39)
 
+def _c_signatures():
+    """{symbol: (restype, argtypes)} of the C ABI (include/tsqr_mi.h), in the header's order of introduction."""
+    sz, vp, ci = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int
+    pu, pd, pt = ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(Ticket)
+    qr32 = [ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp]
+    # (mode, reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, gather, <transport: 3 x void*>, nranks, stream)
+    dist32 = [ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, ci, vp]
+    batch32 = [ci, ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    dist_batch32 = [ci] + dist32 + [vp]                # (count, ..., states)
+    qr64 = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp]
+    r64 = [ci, vp, sz, vp, sz, sz, sz, vp, vp, vp]
+    lstsq64 = [ci, ci, vp, sz, vp, sz, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]
+    dist64 = qr64[:-1]                                 # (reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, <transport>, nranks, stream)
+    return {
+        "tsqr_mi_version": (ci, []), "tsqr_mi_last_error": (ctypes.c_char_p, []),
+        "tsqr_mi_working_q_size": (sz, [sz, sz]), "tsqr_mi_working_r_size": (sz, [sz, sz]), "tsqr_mi_working_l_size": (sz, [sz]),
+        "tsqr_mi_working_reorth_size": (sz, [sz]), "tsqr_mi_batch_size_log2": (sz, [sz]), "tsqr_mi_batch_size": (sz, [sz]),
+        "tsqr_mi_qr_f32": (ci, qr32), "tsqr_mi_local_r_f32": (ci, [vp, sz, vp, sz, sz, sz, vp, vp, vp]),
+        "tsqr_mi_apply_rinv_f32": (ci, [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp]), "tsqr_mi_rmul_f32": (ci, [vp, sz, vp, sz, sz, vp, vp]),
+        "tsqr_mi_qr_f32_dist": (ci, [ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, ci, vp]),
+        "tsqr_mi_set_tuning": (None, [ci, ci]), "tsqr_mi_profile_enable": (None, [ci]),
+        "tsqr_mi_profile_read": (ci, [pd, ctypes.POINTER(ctypes.c_long), ci]),
+        "tsqr_mi_set_policy": (None, [ci]), "tsqr_mi_last_engine": (ci, []), "tsqr_mi_set_tuning2": (None, [ci, ci]),
+        "tsqr_mi_gram_elems": (sz, [sz]), "tsqr_mi_gram_f32": (ci, [ci, vp, vp, sz, sz, sz, vp, vp, vp]),
+        "tsqr_mi_chol_f32": (ci, [ci, vp, sz, vp, sz, sz, vp, pu, vp]), "tsqr_mi_chol_status": (ci, [vp, sz, sz, pu, vp]),
+        "tsqr_mi_stream_wait": (ci, [vp]), "tsqr_mi_apply_z_f32": (ci, [ci, vp, sz, vp, sz, sz, sz, vp, vp]),
+        "tsqr_mi_validate_f32": (ci, [vp, sz, vp, sz, vp, sz, sz, sz, vp, pd, pd, vp]),
+        "tsqr_mi_working_q_size_dist": (sz, [sz, sz, ci]), "tsqr_mi_working_r_size_dist": (sz, [sz, sz, ci]),
+        "tsqr_mi_qr_f32_dist_cb": (ci, dist32),
+        "tsqr_mi_qr_f32_loop": (ci, [ci] + qr32), "tsqr_mi_qr_f32_dist_fn": (ci, dist32),
+        "tsqr_mi_qr_f32_dist_fn_loop": (ci, [ci] + dist32), "tsqr_mi_qr_f32_dist_cb_loop": (ci, [ci] + dist32),
+        "tsqr_mi_qr_f16": (ci, qr32), "tsqr_mi_qr_f16_loop": (ci, [ci] + qr32),
+        "tsqr_mi_working_q_size_f16": (sz, [sz, sz]), "tsqr_mi_working_r_size_f16": (sz, [sz, sz]),
+        "tsqr_mi_qr_f32_submit": (ci, qr32 + [pt]), "tsqr_mi_qr_f32_finish": (ci, [pt]), "tsqr_mi_set_loop_depth": (None, [ci]),
+        "tsqr_mi_qr_f32_batch": (ci, batch32), "tsqr_mi_qr_f16_batch": (ci, batch32),
+        "tsqr_mi_qr_f32_dist_fn_batch": (ci, dist_batch32), "tsqr_mi_qr_f32_dist_cb_batch": (ci, dist_batch32),
+        "tsqr_mi_qr_f64": (ci, qr64), "tsqr_mi_working_q_size_f64": (sz, [sz, sz]), "tsqr_mi_working_r_size_f64": (sz, [sz, sz]),
+        "tsqr_mi_last_sweeps_f64": (ci, []),
+        "tsqr_mi_qr_f64_wide": (ci, qr64), "tsqr_mi_working_q_size_f64_wide": (sz, [sz, sz]), "tsqr_mi_working_r_size_f64_wide": (sz, [sz, sz]),
+        "tsqr_mi_working_q_size_f64_dist": (sz, [sz, sz, ci]), "tsqr_mi_working_r_size_f64_dist": (sz, [sz, sz, ci]),
+        "tsqr_mi_qr_f64_dist": (ci, dist64 + [vp, ci, vp]), "tsqr_mi_qr_f64_dist_fn": (ci, dist64 + [vp, vp, ci, vp]),
+        "tsqr_mi_qr_f64_dist_cb": (ci, dist64 + [vp, vp, ci, vp]),
+        "tsqr_mi_r_f64": (ci, r64), "tsqr_mi_working_q_size_f64_r": (sz, [sz, sz]), "tsqr_mi_working_r_size_f64_r": (sz, [sz, sz]),
+        "tsqr_mi_lstsq_f64": (ci, lstsq64),
+        "tsqr_mi_working_q_size_f64_lstsq": (sz, [sz, sz, sz]), "tsqr_mi_working_r_size_f64_lstsq": (sz, [sz, sz, sz]),
+        "tsqr_mi_r_f64_lay": (ci, [ci] + r64), "tsqr_mi_lstsq_f64_lay": (ci, [ci, ci] + lstsq64),
+        "tsqr_mi_qr_f64_lay": (ci, [ci, ci] + qr64), "tsqr_mi_qr_f64_wide_lay": (ci, [ci, ci] + qr64),
+    }
+
+
+C_SIGNATURES = _c_signatures()
+C_ABI_SYMBOLS = list(C_SIGNATURES)
+# TSQR_MI_LIB may name an older build for an A/B of the entries both have: these, the newest, may be missing from it
+OPTIONAL_SYMBOLS = {
+    "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
+    "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
+    "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
+    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay"}
+
 _lib = None
 
 
@@ -105,124 +143,11 @@ def lib():
     # pulls the system libamdhip64 and the process ends up with two runtimes -- "no ROCm-capable device")
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    sz, vp, ci = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int
-    L.tsqr_mi_version.restype = ci
-    L.tsqr_mi_last_error.restype = ctypes.c_char_p
-    for name, args in [("tsqr_mi_working_q_size", [sz, sz]), ("tsqr_mi_working_r_size", [sz, sz]),
-                       ("tsqr_mi_working_l_size", [sz]), ("tsqr_mi_working_reorth_size", [sz]),
-                       ("tsqr_mi_batch_size_log2", [sz]), ("tsqr_mi_batch_size", [sz])]:
-        getattr(L, name).restype = sz
-        getattr(L, name).argtypes = args
-    L.tsqr_mi_qr_f32.restype = ci
-    L.tsqr_mi_qr_f32.argtypes = [ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp]
-    L.tsqr_mi_local_r_f32.restype = ci
-    L.tsqr_mi_local_r_f32.argtypes = [vp, sz, vp, sz, sz, sz, vp, vp, vp]
-    L.tsqr_mi_apply_rinv_f32.restype = ci
-    L.tsqr_mi_apply_rinv_f32.argtypes = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp]
-    L.tsqr_mi_gram_elems.restype = sz
-    L.tsqr_mi_gram_elems.argtypes = [sz]
-    L.tsqr_mi_gram_f32.restype = ci
-    L.tsqr_mi_gram_f32.argtypes = [ci, vp, vp, sz, sz, sz, vp, vp, vp]
-    L.tsqr_mi_chol_f32.restype = ci
-    L.tsqr_mi_chol_f32.argtypes = [ci, vp, sz, vp, sz, sz, vp, ctypes.POINTER(ctypes.c_uint), vp]
-    L.tsqr_mi_chol_status.restype = ci
-    L.tsqr_mi_chol_status.argtypes = [vp, sz, sz, ctypes.POINTER(ctypes.c_uint), vp]
-    L.tsqr_mi_stream_wait.restype = ci
-    L.tsqr_mi_stream_wait.argtypes = [vp]
-    L.tsqr_mi_apply_z_f32.restype = ci
-    L.tsqr_mi_apply_z_f32.argtypes = [ci, vp, sz, vp, sz, sz, sz, vp, vp]
-    L.tsqr_mi_validate_f32.restype = ci
-    L.tsqr_mi_validate_f32.argtypes = [vp, sz, vp, sz, vp, sz, sz, sz, vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp]
-    L.tsqr_mi_rmul_f32.restype = ci
-    L.tsqr_mi_rmul_f32.argtypes = [vp, sz, vp, sz, sz, vp, vp]
-    L.tsqr_mi_qr_f32_dist.restype = ci
-    L.tsqr_mi_qr_f32_dist.argtypes = [ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, ci, vp]
-    L.tsqr_mi_qr_f32_dist_cb.restype = ci
-    L.tsqr_mi_qr_f32_dist_cb.argtypes = [ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, ci, vp]
-    L.tsqr_mi_qr_f32_loop.restype = ci
-    L.tsqr_mi_qr_f32_loop.argtypes = [ci] + L.tsqr_mi_qr_f32.argtypes
-    L.tsqr_mi_qr_f32_submit.restype = ci
-    L.tsqr_mi_qr_f32_submit.argtypes = L.tsqr_mi_qr_f32.argtypes + [ctypes.POINTER(Ticket)]
-    L.tsqr_mi_qr_f32_finish.restype = ci
-    L.tsqr_mi_qr_f32_finish.argtypes = [ctypes.POINTER(Ticket)]
-    L.tsqr_mi_qr_f32_batch.restype = ci
-    L.tsqr_mi_qr_f32_batch.argtypes = [ci, ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
-    L.tsqr_mi_qr_f16_batch.restype = ci
-    L.tsqr_mi_qr_f16_batch.argtypes = L.tsqr_mi_qr_f32_batch.argtypes
-    L.tsqr_mi_set_loop_depth.restype = None
-    L.tsqr_mi_set_loop_depth.argtypes = [ci]
-    L.tsqr_mi_qr_f16.restype = ci
-    L.tsqr_mi_qr_f16.argtypes = L.tsqr_mi_qr_f32.argtypes
-    L.tsqr_mi_qr_f16_loop.restype = ci
-    L.tsqr_mi_qr_f16_loop.argtypes = [ci] + L.tsqr_mi_qr_f32.argtypes
-    for name in ("tsqr_mi_working_q_size_f16", "tsqr_mi_working_r_size_f16"):
-        getattr(L, name).restype = sz
-        getattr(L, name).argtypes = [sz, sz]
-    L.tsqr_mi_qr_f32_dist_fn.restype = ci
-    L.tsqr_mi_qr_f32_dist_fn.argtypes = [ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, ci, vp]
-    L.tsqr_mi_qr_f32_dist_fn_loop.restype = ci
-    L.tsqr_mi_qr_f32_dist_fn_loop.argtypes = [ci] + L.tsqr_mi_qr_f32_dist_fn.argtypes
-    L.tsqr_mi_qr_f32_dist_cb_loop.restype = ci
-    L.tsqr_mi_qr_f32_dist_cb_loop.argtypes = [ci] + L.tsqr_mi_qr_f32_dist_cb.argtypes
-    # (count, mode, reorth, q[], ldq, r[], ldr, a[], lda, m_local, n, wq, wr, gather, <transport: 3 x void*>, nranks, stream, states)
-    L.tsqr_mi_qr_f32_dist_fn_batch.restype = ci
-    L.tsqr_mi_qr_f32_dist_fn_batch.argtypes = [ci, ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, ci, vp, vp]
-    L.tsqr_mi_qr_f32_dist_cb_batch.restype = ci
-    L.tsqr_mi_qr_f32_dist_cb_batch.argtypes = [ci, ci, ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, ci, vp, vp]
-    for name in ("tsqr_mi_working_q_size_dist", "tsqr_mi_working_r_size_dist"):
-        getattr(L, name).restype = sz
-        getattr(L, name).argtypes = [sz, sz, ci]
-    L.tsqr_mi_profile_enable.restype = None
-    L.tsqr_mi_profile_enable.argtypes = [ci]
-    L.tsqr_mi_profile_read.restype = ci
-    L.tsqr_mi_profile_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long), ci]
-    L.tsqr_mi_set_policy.restype = None
-    L.tsqr_mi_set_policy.argtypes = [ci]
-    L.tsqr_mi_last_engine.restype = ci
-    L.tsqr_mi_set_tuning2.restype = None
-    L.tsqr_mi_set_tuning2.argtypes = [ci, ci]
-    L.tsqr_mi_set_tuning.restype = None
-    L.tsqr_mi_set_tuning.argtypes = [ci, ci]
-    for name in ("tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide"):
-        getattr(L, name).restype = sz
-        getattr(L, name).argtypes = [sz, sz]
-    for name in ("tsqr_mi_qr_f64", "tsqr_mi_qr_f64_wide"):
-        getattr(L, name).restype = ci
-        getattr(L, name).argtypes = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp, vp]
-    L.tsqr_mi_last_sweeps_f64.restype = ci
-    L.tsqr_mi_last_sweeps_f64.argtypes = []
-    if hasattr(L, "tsqr_mi_qr_f64_dist_cb"):             # (TSQR_MI_LIB may name an older build for an A/B of the entries both have)
-        for name in ("tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [sz, sz, ci]
-        # (reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, <transport>, nranks, stream)
-        f64_dist_head = [ci, vp, sz, vp, sz, vp, sz, sz, sz, vp, vp]
-        for name, transport in (("tsqr_mi_qr_f64_dist", [vp]), ("tsqr_mi_qr_f64_dist_fn", [vp, vp]), ("tsqr_mi_qr_f64_dist_cb", [vp, vp])):
-            getattr(L, name).restype = ci
-            getattr(L, name).argtypes = f64_dist_head + transport + [ci, vp]
-    if hasattr(L, "tsqr_mi_r_f64"):                      # (as above: an older build has no R-only entry)
-        for name in ("tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [sz, sz]
-        L.tsqr_mi_r_f64.restype = ci
-        L.tsqr_mi_r_f64.argtypes = [ci, vp, sz, vp, sz, sz, sz, vp, vp, vp]
-    if hasattr(L, "tsqr_mi_lstsq_f64"):                  # (as above: an older build has no least-squares entry)
-        for name in ("tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [sz, sz, sz]
-        L.tsqr_mi_lstsq_f64.restype = ci
-        L.tsqr_mi_lstsq_f64.argtypes = [ci, ci, vp, sz, vp, sz, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]
-    if hasattr(L, "tsqr_mi_r_f64_lay"):                  # (as above: an older build reads column-major operands only)
-        L.tsqr_mi_r_f64_lay.restype = ci
-        L.tsqr_mi_r_f64_lay.argtypes = [ci] + L.tsqr_mi_r_f64.argtypes
-        L.tsqr_mi_lstsq_f64_lay.restype = ci
-        L.tsqr_mi_lstsq_f64_lay.argtypes = [ci, ci] + L.tsqr_mi_lstsq_f64.argtypes
-    if hasattr(L, "tsqr_mi_qr_f64_lay"):                 # (as above: an older build factors column-major operands only)
-        L.tsqr_mi_qr_f64_lay.restype = ci
-        L.tsqr_mi_qr_f64_lay.argtypes = [ci, ci] + L.tsqr_mi_qr_f64.argtypes
-    if hasattr(L, "tsqr_mi_qr_f64_wide_lay"):            # (as above: an older build's wide entry is column-major only)
-        L.tsqr_mi_qr_f64_wide_lay.restype = ci
-        L.tsqr_mi_qr_f64_wide_lay.argtypes = [ci, ci] + L.tsqr_mi_qr_f64_wide.argtypes
+    for name, (restype, argtypes) in C_SIGNATURES.items():
+        if name in OPTIONAL_SYMBOLS and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)                          # (AttributeError: a symbol every build must have is missing)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -460,9 +385,69 @@ def qr_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream=None, mode=None, reort
     return bind_batch(qs, ldq, rs, ldr, as_, lda, m, n, bf, stream, mode, reorthogonalize)()
 
 
-# the two fp64 entries: (Python name, widest n, C entry, its work-space size functions)
-_F64 = ("qr_f64", 64, "tsqr_mi_qr_f64", "tsqr_mi_working_q_size_f64", "tsqr_mi_working_r_size_f64")
-_F64_WIDE = ("qr_f64_wide", 1024, "tsqr_mi_qr_f64_wide", "tsqr_mi_working_q_size_f64_wide", "tsqr_mi_working_r_size_f64_wide")
+class _F64Entry:
+    """One fp64 entry: its Python name, the widest n, the C symbol (the layout form is symbol + "_lay") and the two functions, named
+    by their suffix, that size its work space."""
+
+    def __init__(self, name, nmax, symbol, size_suffix):
+        self.name, self.nmax, self.symbol = name, nmax, symbol
+        self.wq_fn, self.wr_fn = "tsqr_mi_working_q_size" + size_suffix, "tsqr_mi_working_r_size" + size_suffix
+
+    def sizes(self, *dims):
+        """doubles of (wq, wr) for a call of these dimensions"""
+        L = _lib or lib()
+        return getattr(L, self.wq_fn)(*dims), getattr(L, self.wr_fn)(*dims)
+
+    def check_buffer(self, bf, *dims):
+        """bf allocated, and for at least these dimensions"""
+        if bf.dwq is None:
+            raise RuntimeError("%s: the buffer is not allocated" % self.name)
+        L = _lib or lib()                              # (sizes() spelled out: this runs in every blocking call)
+        if bf.dwq.numel() < getattr(L, self.wq_fn)(*dims) or bf.dwr.numel() < getattr(L, self.wr_fn)(*dims):
+            raise ValueError("%s: the buffer was allocated for a smaller matrix" % self.name)
+
+    def work_space(self, device, *dims):
+        """(wq, wr) allocated for one call"""
+        import torch
+        return tuple(torch.empty(size, dtype=torch.float64, device=device) for size in self.sizes(*dims))
+
+
+_F64 = _F64Entry("qr_f64", 64, "tsqr_mi_qr_f64", "_f64")
+_F64_WIDE = _F64Entry("qr_f64_wide", 1024, "tsqr_mi_qr_f64_wide", "_f64_wide")
+_F64_R = _F64Entry("r_f64", 64, "tsqr_mi_r_f64", "_f64_r")
+_F64_LSTSQ = _F64Entry("lstsq_f64", 64, "tsqr_mi_lstsq_f64", "_f64_lstsq")
+
+
+def _null_state(fn, *scalars):
+    """The state (and last_error text) of a shape the C entry fn does not run, fetched with every pointer null: scalars are its other
+    arguments in order; its checks come before any HIP call."""
+    rest = iter(scalars)
+    args = [None if t is ctypes.c_void_p else next(rest) for t in fn.argtypes]
+    assert next(rest, None) is None, "more scalars than %s takes" % fn.__name__
+    return fn(*args)
+
+
+def _check_f64_tensors(who, operands):
+    """Every (name, operand) a float64 tensor, then every operand on the GPU (all dtype checks come first).  Raises TypeError."""
+    import torch
+    tensor, f64 = torch.Tensor, torch.float64
+    for opname, t in operands:
+        if not isinstance(t, tensor) or t.dtype != f64:
+            raise TypeError("%s: %s must be a float64 tensor, got %s" % (who, opname, getattr(t, "dtype", type(t).__name__)))
+    for opname, t in operands:
+        if not t.is_cuda:
+            raise TypeError("%s: %s is not a GPU tensor" % (who, opname))
+
+
+def _f64_call(label, fn, stream, *args):
+    """fn(*args, stream) on the current stream unless one is given; a negative state (a HIP failure) raises RuntimeError"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream()
+    st = fn(*args, stream.cuda_stream)
+    if st < 0:
+        raise RuntimeError("%s failed: %s" % (label, last_error()))
+    return st
 
 
 class buffer_f64:
@@ -479,8 +464,7 @@ class buffer_f64:
         import torch
         if self.dwq is not None or self.dwr is not None:
             raise RuntimeError("The buffer has been already allocated")
-        self.dwq, self.dwr = (torch.empty(max(getattr(lib(), size_fn)(m, n), 1), dtype=torch.float64, device=self.device)
-                              for size_fn in self._entry[3:])
+        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device) for size in self._entry.sizes(m, n))
 
     def free(self):
         self.dwq = self.dwr = None
@@ -489,76 +473,56 @@ class buffer_f64:
         return 0 if self.dwq is None else 8 * (self.dwq.numel() + self.dwr.numel())
 
 
-def _f64_spans(who, n, ops):
-    """ld >= rows and room for (n - 1) ld + rows doubles for every (name, (address, elements), ld, rows) of ops; returns the byte span
-    of each operand.  Raises ValueError."""
-    span = {}
-    for name, (addr, numel), ld, rows in ops:
+def _f64_spans(who, ops):
+    """ld >= rows and room for (cols - 1) ld + rows doubles for every (name, (address, elements), ld, rows, cols, row_major) of ops; a
+    row-major operand is checked as its transposed view, cols "columns" of rows contiguous elements.  Returns the byte span
+    (first, past the last) of each operand, in the order of ops.  Raises ValueError."""
+    span = []
+    for name, (addr, numel), ld, rows, cols, row_major in ops:
+        if row_major:
+            rows, cols = cols, rows
         if ld < rows:
             raise ValueError("%s: ld%s = %d is smaller than the %d rows of %s" % (who, name, ld, rows, name))
-        need = (n - 1) * ld + rows
+        need = (cols - 1) * ld + rows
         if numel < need:
-            raise ValueError("%s: %s holds %d elements, an operand of %d x %d with ld %d needs %d" % (who, name, numel, rows, n, ld, need))
-        span[name] = (addr, addr + 8 * need)
+            raise ValueError("%s: %s holds %d elements, an operand of %d x %d with ld %d needs %d" % (who, name, numel, rows, cols, ld, need))
+        span.append((addr, addr + 8 * need))
     return span
-
-
-def _apart(span, x, y):
-    return span[x][1] <= span[y][0] or span[y][1] <= span[x][0]
 
 
 def check_f64_operands(m, n, ldq, ldr, lda, q, r, a, row_major=False):
     """The size and overlap rules of qr_f64 on (address, elements) pairs: ld >= rows, room for (n - 1) ld + rows doubles, q either
     the very operand a (same address and ld: in place) or apart from it, r apart from both.  row_major: q and a are row-major --
     ld >= n and room for (m - 1) ld + n doubles each (check_f64_r_operands' rule); r stays column-major.  Raises ValueError."""
-    if row_major:
-        span = _f64_spans("qr_f64", n, (("r", r, ldr, n),))
-        span.update(_f64_spans("qr_f64", m, (("q", q, ldq, n), ("a", a, lda, n))))   # (the transposed view: m "columns" of n contiguous elements)
+    ops = (("q", q, ldq, m, n, row_major), ("a", a, lda, m, n, row_major))
+    if row_major:                                       # (r is checked first row-major, between q and a column-major)
+        sr, sq, sa = _f64_spans("qr_f64", (("r", r, ldr, n, n, False),) + ops)
     else:
-        span = _f64_spans("qr_f64", n, (("q", q, ldq, m), ("r", r, ldr, n), ("a", a, lda, m)))
-    if not (q[0] == a[0] and ldq == lda) and not _apart(span, "q", "a"):
+        sq, sr, sa = _f64_spans("qr_f64", (ops[0], ("r", r, ldr, n, n, False), ops[1]))
+    if not (q[0] == a[0] and ldq == lda) and sq[0] < sa[1] and sa[0] < sq[1]:
         raise ValueError("qr_f64: q overlaps a without being a (in place needs q == a and ldq == lda)")
-    for other in ("q", "a"):
-        if not _apart(span, "r", other):
+    for other, so in (("q", sq), ("a", sa)):
+        if sr[0] < so[1] and so[0] < sr[1]:
             raise ValueError("qr_f64: r overlaps %s" % other)
 
 
 def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize, row_major=False):
     """The body of qr_f64 (entry _F64) and qr_f64_wide (_F64_WIDE).  row_major: the entry's _lay form (tsqr_mi_qr_f64_lay,
     tsqr_mi_qr_f64_wide_lay) with q and a row-major."""
-    import torch
-    name, nmax, qr_fn, wq_fn, wr_fn = entry
-    if row_major:
-        lay_fn = getattr(lib(), qr_fn + "_lay")
-        qr_fn = qr_fn + "_lay"
-        call = lambda *args: lay_fn(ROW_MAJOR, ROW_MAJOR, *args)
-    else:
-        call = getattr(lib(), qr_fn)
+    symbol = entry.symbol + "_lay" if row_major else entry.symbol
+    fn = getattr(lib(), symbol)
+    head = (ROW_MAJOR, ROW_MAJOR) if row_major else ()       # (the layout form's two leading arguments)
     reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    for opname, t in (("q", q), ("r", r), ("a", a)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise TypeError("%s: %s must be a float64 tensor, got %s" % (name, opname, getattr(t, "dtype", type(t).__name__)))
-    for opname, t in (("q", q), ("r", r), ("a", a)):
-        if not t.is_cuda:
-            raise TypeError("%s: %s is not a GPU tensor" % (name, opname))
+    _check_f64_tensors(entry.name, (("q", q), ("r", r), ("a", a)))
     if n > m or m == 0 or n == 0:
         return error_invalid_matrix_size
-    if n > nmax:
-        return call(int(reorth), None, ldq, None, ldr, None, lda, m, n, None, None, None)
+    if n > entry.nmax:
+        return _null_state(fn, *head, int(reorth), ldq, ldr, lda, m, n)
     check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()),
                        row_major=bool(row_major))
-    if bf.dwq is None:
-        raise RuntimeError("%s: the buffer is not allocated" % name)
-    L = lib()
-    if bf.dwq.numel() < getattr(L, wq_fn)(m, n) or bf.dwr.numel() < getattr(L, wr_fn)(m, n):
-        raise ValueError("%s: the buffer was allocated for a smaller matrix" % name)
-    if stream is None:
-        stream = torch.cuda.current_stream()
-    st = call(int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
-              bf.dwq.data_ptr(), bf.dwr.data_ptr(), stream.cuda_stream)
-    if st < 0:
-        raise RuntimeError("%s failed: %s" % (qr_fn, last_error()))
-    return st
+    entry.check_buffer(bf, m, n)
+    return _f64_call(symbol, fn, stream, *head, int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
+                     bf.dwq.data_ptr(), bf.dwr.data_ptr())
 
 
 def qr_f64(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False):
@@ -592,18 +556,14 @@ def qr_f64_wide(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=N
 
 class buffer_f64_r(buffer_f64):
     """Work space of r_f64 (tsqr_mi_working_{q,r}_size_f64_r doubles on the GPU: no m x n part); reorthogonalize as in buffer_f64."""
-    _entry = ("r_f64", 64, "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r")
+    _entry = _F64_R
 
 
 def check_f64_r_operands(m, n, ldr, lda, r, a, row_major=False):
     """check_f64_operands' rules for the two operands of r_f64: ld >= rows, room for (n - 1) ld + rows doubles, r apart from a.
     row_major: a is row-major -- lda >= n and room for (m - 1) lda + n doubles, the span r has to stay clear of."""
-    if row_major:
-        span = _f64_spans("r_f64", n, (("r", r, ldr, n),))
-        span.update(_f64_spans("r_f64", m, (("a", a, lda, n),)))     # (the transposed view: m "columns" of n contiguous elements)
-    else:
-        span = _f64_spans("r_f64", n, (("r", r, ldr, n), ("a", a, lda, m)))
-    if not _apart(span, "r", "a"):
+    sr, sa = _f64_spans("r_f64", (("r", r, ldr, n, n, False), ("a", a, lda, m, n, row_major)))
+    if sr[0] < sa[1] and sa[0] < sr[1]:
         raise ValueError("r_f64: r overlaps a")
 
 
@@ -615,32 +575,19 @@ def r_f64(r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major
     error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite.  Operands are checked before anything is launched:
     TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a leading dimension below the rows, or r overlapping a.
     last_sweeps_f64() tells how many sweeps the call took."""
-    import torch
+    entry = _F64_R
     reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    for opname, t in (("r", r), ("a", a)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise TypeError("r_f64: %s must be a float64 tensor, got %s" % (opname, getattr(t, "dtype", type(t).__name__)))
-    for opname, t in (("r", r), ("a", a)):
-        if not t.is_cuda:
-            raise TypeError("r_f64: %s is not a GPU tensor" % opname)
+    _check_f64_tensors(entry.name, (("r", r), ("a", a)))
     if n > m or m == 0 or n == 0:
         return error_invalid_matrix_size
-    L = lib()
+    fn = lib().tsqr_mi_r_f64_lay
     layout = ROW_MAJOR if row_major else COL_MAJOR
-    if n > 64:
-        return L.tsqr_mi_r_f64_lay(layout, int(reorth), None, ldr, None, lda, m, n, None, None, None)
+    if n > entry.nmax:
+        return _null_state(fn, layout, int(reorth), ldr, lda, m, n)
     check_f64_r_operands(m, n, ldr, lda, (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()), row_major=bool(row_major))
-    if bf.dwq is None:
-        raise RuntimeError("r_f64: the buffer is not allocated")
-    if bf.dwq.numel() < L.tsqr_mi_working_q_size_f64_r(m, n) or bf.dwr.numel() < L.tsqr_mi_working_r_size_f64_r(m, n):
-        raise ValueError("r_f64: the buffer was allocated for a smaller matrix")
-    if stream is None:
-        stream = torch.cuda.current_stream()
-    st = L.tsqr_mi_r_f64_lay(layout, int(reorth), r.data_ptr(), ldr, a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr(),
-                             stream.cuda_stream)
-    if st < 0:
-        raise RuntimeError("tsqr_mi_r_f64 failed: %s" % last_error())
-    return st
+    entry.check_buffer(bf, m, n)
+    return _f64_call(entry.symbol, fn, stream, layout, int(reorth), r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
+                     bf.dwq.data_ptr(), bf.dwr.data_ptr())
 
 
 class LstsqError(RuntimeError):
@@ -651,11 +598,16 @@ class LstsqError(RuntimeError):
         self.state = state
 
 
+def _columns_contiguous(t):
+    rows, cols = t.shape
+    return t.stride(0) == 1 and (cols == 1 or t.stride(1) >= max(rows, 1))
+
+
 def _colmajor_f64(t):
     """(tensor whose storage holds t column-major, its leading dimension): t itself when its columns are already contiguous (stride 1
     down a column, at least the row count between columns), a column-major copy otherwise -- the operand of the call is never written"""
     rows, cols = t.shape
-    if t.stride(0) == 1 and (cols == 1 or t.stride(1) >= max(rows, 1)):
+    if _columns_contiguous(t):
         return t, (t.stride(1) if cols > 1 else max(rows, 1))
     return t.t().contiguous().t(), max(rows, 1)
 
@@ -664,10 +616,8 @@ def _operand_f64(t):
     """(tensor, leading dimension, layout) under which lstsq_f64 hands the two-dimensional t to tsqr_mi_lstsq_f64_lay.  Used where it
     lies: columns contiguous (_colmajor_f64's rule: COL_MAJOR), rows contiguous (stride(1) == 1 and stride(0) >= cols: ROW_MAJOR), or a
     single column (any stride(0) >= 1: ROW_MAJOR with that stride).  Any other operand: _colmajor_f64's copy."""
-    rows, cols = t.shape
-    if t.stride(0) == 1 and (cols == 1 or t.stride(1) >= max(rows, 1)):
-        return _colmajor_f64(t) + (COL_MAJOR,)
-    if (t.stride(1) == 1 or cols == 1) and t.stride(0) >= max(cols, 1):
+    cols = t.shape[1]
+    if not _columns_contiguous(t) and (t.stride(1) == 1 or cols == 1) and t.stride(0) >= max(cols, 1):
         return t, t.stride(0), ROW_MAJOR
     return _colmajor_f64(t) + (COL_MAJOR,)
 
@@ -688,37 +638,26 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
     least-squares solution (entries of 1e14 and more; include/tsqr_mi.h has the measured residuals and the range of b's magnitudes) --
     test r before using x when the columns may be dependent.  last_sweeps_f64() tells how many sweeps the ladder took."""
     import torch
-    for opname, t in (("a", a), ("b", b)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise TypeError("lstsq_f64: %s must be a float64 tensor, got %s" % (opname, getattr(t, "dtype", type(t).__name__)))
-    for opname, t in (("a", a), ("b", b)):
-        if not t.is_cuda:
-            raise TypeError("lstsq_f64: %s is not a GPU tensor" % opname)
+    entry = _F64_LSTSQ
+    _check_f64_tensors(entry.name, (("a", a), ("b", b)))
     if a.dim() != 2 or b.dim() not in (1, 2) or b.shape[0] != a.shape[0]:
         raise ValueError("lstsq_f64: a must be m x n and b m x nrhs (or m), got %s and %s" % (tuple(a.shape), tuple(b.shape)))
     vector = b.dim() == 1
     b2 = b.unsqueeze(1) if vector else b
     m, n = a.shape
     nrhs = b2.shape[1]
-    L = lib()
-    z = ctypes.c_void_p(0)
-    if m == 0 or n == 0 or nrhs == 0 or n > m or n > 64 or nrhs > 16 or not 0 <= int(refine) <= 4:
-        st = L.tsqr_mi_lstsq_f64(int(bool(reorth)), int(refine), z, max(n, 1), z, max(n, 1), z, max(m, 1), z, max(m, 1), m, n, nrhs, z, z, z)
+    if m == 0 or n == 0 or nrhs == 0 or n > m or n > entry.nmax or nrhs > 16 or not 0 <= int(refine) <= 4:
+        st = _null_state(lib().tsqr_mi_lstsq_f64, int(bool(reorth)), int(refine), max(n, 1), max(n, 1), max(m, 1), max(m, 1), m, n, nrhs)
         raise LstsqError(st, "lstsq_f64: state %d for a %d x %d, nrhs %d, refine %d%s"
                          % (st, m, n, nrhs, int(refine), (": " + last_error()) if st == error_unsupported_mode else ""))
     ac, lda, a_layout = _operand_f64(a)
     bc, ldb, b_layout = _operand_f64(b2)
     x = torch.empty((nrhs, n), dtype=torch.float64, device=a.device)
     r = torch.empty((n, n), dtype=torch.float64, device=a.device)
-    wq = torch.empty(L.tsqr_mi_working_q_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device=a.device)
-    wr = torch.empty(L.tsqr_mi_working_r_size_f64_lstsq(m, n, nrhs), dtype=torch.float64, device=a.device)
+    wq, wr = entry.work_space(a.device, m, n, nrhs)
     with torch.cuda.device(a.device):
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        st = L.tsqr_mi_lstsq_f64_lay(a_layout, b_layout, int(bool(reorth)), int(refine), x.data_ptr(), n, r.data_ptr(), n, ac.data_ptr(), lda,
-                                     bc.data_ptr(), ldb, m, n, nrhs, wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
-    if st < 0:
-        raise RuntimeError("tsqr_mi_lstsq_f64 failed: %s" % last_error())
+        st = _f64_call(entry.symbol, lib().tsqr_mi_lstsq_f64_lay, stream, a_layout, b_layout, int(bool(reorth)), int(refine), x.data_ptr(), n,
+                       r.data_ptr(), n, ac.data_ptr(), lda, bc.data_ptr(), ldb, m, n, nrhs, wq.data_ptr(), wr.data_ptr())
     if st:
         raise LstsqError(st, "lstsq_f64: state %d: %s" % (st, last_error()))
     x = x.t()
@@ -736,20 +675,14 @@ class QrError(RuntimeError):
 def _qr_f64_tensor(entry, a, reorth, overwrite_a, stream):
     """The body of qr_f64_tensor (entry _F64) and qr_f64_wide_tensor (_F64_WIDE) on the entry's _lay form."""
     import torch
-    name, nmax, qr_fn, wq_fn, wr_fn = entry
-    name, qr_fn = name + "_tensor", qr_fn + "_lay"
-    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
-        raise TypeError("%s: a must be a float64 tensor, got %s" % (name, getattr(a, "dtype", type(a).__name__)))
-    if not a.is_cuda:
-        raise TypeError("%s: a is not a GPU tensor" % name)
+    name, symbol = entry.name + "_tensor", entry.symbol + "_lay"
+    _check_f64_tensors(name, (("a", a),))
     if a.dim() != 2:
         raise ValueError("%s: a must be m x n, got %s" % (name, tuple(a.shape)))
     m, n = a.shape
-    L = lib()
-    call = getattr(L, qr_fn)
-    z = ctypes.c_void_p(0)
-    if m == 0 or n == 0 or n > m or n > nmax:
-        st = call(COL_MAJOR, COL_MAJOR, int(bool(reorth)), z, max(m, 1), z, max(n, 1), z, max(m, 1), m, n, z, z, z)
+    fn = getattr(lib(), symbol)
+    if m == 0 or n == 0 or n > m or n > entry.nmax:
+        st = _null_state(fn, COL_MAJOR, COL_MAJOR, int(bool(reorth)), max(m, 1), max(n, 1), max(m, 1), m, n)
         raise QrError(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
     ac, lda, layout = _operand_f64(a)
     if overwrite_a and ac.data_ptr() == a.data_ptr():
@@ -759,15 +692,10 @@ def _qr_f64_tensor(entry, a, reorth, overwrite_a, stream):
     else:
         q, ldq = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
     r = torch.empty((n, n), dtype=torch.float64, device=a.device)
-    wq = torch.empty(getattr(L, wq_fn)(m, n), dtype=torch.float64, device=a.device)
-    wr = torch.empty(getattr(L, wr_fn)(m, n), dtype=torch.float64, device=a.device)
+    wq, wr = entry.work_space(a.device, m, n)
     with torch.cuda.device(a.device):
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        st = call(layout, layout, int(bool(reorth)), q.data_ptr(), ldq, r.data_ptr(), n, ac.data_ptr(), lda, m, n,
-                  wq.data_ptr(), wr.data_ptr(), stream.cuda_stream)
-    if st < 0:
-        raise RuntimeError("%s failed: %s" % (qr_fn, last_error()))
+        st = _f64_call(symbol, fn, stream, layout, layout, int(bool(reorth)), q.data_ptr(), ldq, r.data_ptr(), n, ac.data_ptr(), lda, m, n,
+                       wq.data_ptr(), wr.data_ptr())
     if st:
         raise QrError(st, "%s: state %d: %s" % (name, st, last_error()))
     return q, r.t()

@@ -2486,29 +2486,34 @@ int f64_apply(hipStream_t st, int dev, double* q, size_t ldq, const double* a, s
 	return 0;
 }
 
+// One call of the QR entries with Q (qr_f64_core builds it; the sweeps read it).  comm: null but for the row-partitioned entries.
+struct F64Call {
+	hipStream_t st; int dev;
+	double* q; size_t ldq; double* r; size_t ldr; double* a; size_t lda; size_t m, n;
+	double *wq, *wr; const Comm* comm; int a_layout, q_layout;
+};
+
+// what sweep k (0-based) reads: A in a_layout for sweep 0, the Q of the sweep before in q_layout after that
+struct F64Src { const double* p; size_t ld; int layout; };
+F64Src f64_src(const F64Call& c, int k) { return k == 0 ? F64Src{c.a, c.lda, c.a_layout} : F64Src{c.q, c.ldq, c.q_layout}; }
+
 // sweep k (0-based): sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R.  a_layout, q_layout
 // (tsqr_mi_qr_f64_lay): sweep 0 reads A in a_layout -- the Gram pass and the apply pass, which writes Q in q_layout; later sweeps read
 // and write Q in q_layout.  R and every launch between the two passes do not depend on a layout.
-int f64_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-              double* wq, double* wr, const Comm* comm, int a_layout = TSQR_MI_COL_MAJOR, int q_layout = TSQR_MI_COL_MAJOR) {
+int f64_sweep(const F64Call& c, int k) {
 	const bool first = k == 0;
-	const double* src = first ? a : q;
-	const size_t lds = first ? lda : ldq;
-	const int src_layout = first ? a_layout : q_layout;
-	int rc = f64_factor(st, wq, wr, src, lds, m, n, first ? r : wq + F64_R2, first ? ldr : 64, first, k & 3, comm, src_layout);
+	const F64Src src = f64_src(c, k);
+	int rc = f64_factor(c.st, c.wq, c.wr, src.p, src.ld, c.m, c.n, first ? c.r : c.wq + F64_R2, first ? c.ldr : 64, first, k & 3, c.comm, src.layout);
 	if (rc) return rc;
-	const double* z = wq + F64_Z;
-	rc = with_apply(n, src_layout, q_layout, [&](auto nt, auto ar, auto qr) {
-		return f64_apply<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(st, dev, q, ldq, src, lds, m, n, z);
+	const double* z = c.wq + F64_Z;
+	rc = with_apply(c.n, src.layout, c.q_layout, [&](auto nt, auto ar, auto qr) {
+		return f64_apply<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(c.st, c.dev, c.q, c.ldq, src.p, src.ld, c.m, c.n, z);
 	});
 	if (rc || first) return rc;
-	f64_rmul_launch(st, r, ldr, wq + F64_R2, (int)n);
+	f64_rmul_launch(c.st, c.r, c.ldr, c.wq + F64_R2, (int)c.n);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
-
-int f64w_sweep(hipStream_t st, int dev, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-               double* wq, double* wr, const Comm* comm, int a_layout = TSQR_MI_COL_MAJOR, int q_layout = TSQR_MI_COL_MAJOR);
 
 // The ladder (include/tsqr_mi.h): verdict 0 of sweep 0 with "one sweep suffices" ends a reorth = 0 call, any other accepted first
 // sweep is followed by one more (CholeskyQR2), a shifted sweep by two more (shifted CholeskyQR3), a rejected one ends the call (state 3).
@@ -2555,16 +2560,68 @@ int f64_ladder(int reorth, hipStream_t st, Sweep sweep) {
 	return TSQR_MI_SUCCESS;
 }
 
-// wide: the sweeps of tsqr_mi_qr_f64_wide for n > 64 (f64w_sweep); the verdict words and their meaning are the same.
-// a_layout, q_layout: the layouts of A and Q (tsqr_mi_qr_f64_lay, tsqr_mi_qr_f64_wide_lay); the row-partitioned entries are column-major.
-int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, double* wq, double* wr,
-                hipStream_t st, bool wide = false, const Comm* comm = nullptr, int a_layout = TSQR_MI_COL_MAJOR,
-                int q_layout = TSQR_MI_COL_MAJOR) {
-	const int dev = cur_device();
-	return f64_ladder(reorth, st, [&](int k) {
-		return wide ? f64w_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm, a_layout, q_layout)
-		            : f64_sweep(st, dev, k, q, ldq, r, ldr, a, lda, m, n, wq, wr, comm, a_layout, q_layout);
-	});
+// (F64W_MAX_N, F64W_WR_CAP, F64W_TARGET_WGS, F64WPlan, f64w_plan and the blocked Cholesky step f64w_chain: f64_plan.h)
+
+// sweep k (0-based) of the wide entry: sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R.  a_layout,
+// q_layout (tsqr_mi_qr_f64_wide_lay) as in f64_sweep: sweep 0 reads A in a_layout -- the Gram pass and the apply pass, which writes Q in
+// q_layout; later sweeps read and write Q in q_layout.  Everything between the two passes works on the block store and knows no layout.
+// A sweep: the Gram pass and its reduction; the blocked Cholesky step -- plain, then the shifted chain enqueued behind it, each of its
+// launches skipping itself when the plain verdict was 0 -- so that a one-sweep call still waits on the stream once; the apply pass; R out
+// or R <- R_k R.
+int f64w_sweep(const F64Call& c, int k) {
+	const bool first = k == 0;
+	const F64Src src = f64_src(c, k);
+	const hipStream_t st = c.st;
+	const size_t m = c.m, n = c.n, ldr = c.ldr;
+	double *const r = c.r, *const wq = c.wq, *const wr = c.wr;
+	const F64WPlan g = f64w_plan(m, n);
+	if (g.nslices <= 0 || g.npairs <= 0) { t_last_error = "fp64 wide Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	const tsqrmi::GramWideF64Args ga{src.p, src.ld, m, (int)n, g.npairs, g.ngroups, g.cps, g.nch, wr};
+	f64w_gram_launch(st, g, ga, src.layout);
+	HIPCHK(hipGetLastError());
+	const int nelem = (int)g.bs;
+	launch_reduce1(st, wq + g.o_gs, wr, g.nslices, nelem, (double)m);
+	HIPCHK(hipGetLastError());
+	if (const int rc = f64_exchange(c.comm, wq + g.o_gs, g.bs, st)) return rc;
+	tsqrmi::WideF64 wa{};
+	wa.gs = wq + g.o_gs; wa.w = wq + g.o_w; wa.rw = wq + g.o_rw; wa.zw = wq + g.o_zw; wa.ta = wq + g.o_ta; wa.zd = wq + g.o_zd;
+	wa.sb = wq + g.o_sb;
+	wa.bst = reinterpret_cast<unsigned*>(wq + g.o_bst);
+	const int slot = k & 3;
+	wa.status = reinterpret_cast<unsigned*>(wq + g.o_status) + 4 * slot;
+	wa.host_status = t_own64.dev + 4 * slot;
+	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64, tsqr_f64.hip, states the rule)
+	wa.max_scond = rule.max_scond; wa.alone_max = rule.alone_max;
+	wa.n = (int)n; wa.nb = g.nb;
+	if (c.comm && c.comm->active()) { wa.rows_dev = wq + g.o_gs + g.bs; wa.first = first ? 1 : 0; }   // (the rule of the GLOBAL row count, on the device)
+	wa.run_if = nullptr; wa.shift_coef = 0.0;
+	int rc = f64w_chain(st, wa);
+	if (rc) return rc;
+	wa.run_if = wa.status; wa.shift_coef = rule.shift_coef;
+	rc = f64w_chain(st, wa);
+	if (rc) return rc;
+	f64w_apply_launch(st, c.q, c.ldq, src.p, src.ld, m, (int)n, g.nb, (const double*)(wq + g.o_zw), src.layout, c.q_layout);
+	HIPCHK(hipGetLastError());
+	if (first) {
+		hipLaunchKernelGGL(tsqrmi::rcopy_wide_f64_kernel, dim3((unsigned)cdiv(n * n, 256)), dim3(256), 0, st, r, ldr, (const double*)(wq + g.o_rw), (int)n);
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
+	hipLaunchKernelGGL(tsqrmi::rsave_wide_f64_kernel, dim3((unsigned)cdiv(g.bs, 256)), dim3(256), 0, st, wq + g.o_rc, (const double*)r, ldr, (int)n, g.npairs);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(tsqrmi::rmul_wide_f64_kernel, dim3((unsigned)g.npairs), dim3(1024), 0, st, r, ldr, (const double*)(wq + g.o_rw),
+	                   (const double*)(wq + g.o_rc), (int)n);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// The ladder on the sweeps of one call: f64_sweep for n <= 64, the whole-matrix sweeps of tsqr_mi_qr_f64_wide (f64w_sweep) beyond; the
+// verdict words and their meaning are the same.  a_layout, q_layout: the layouts of A and Q (tsqr_mi_qr_f64_lay, tsqr_mi_qr_f64_wide_lay).
+int qr_f64_core(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n, void* wq, void* wr,
+                void* stream, const Comm* comm, int a_layout, int q_layout) {
+	const F64Call c{reinterpret_cast<hipStream_t>(stream), cur_device(), q, ldq, r, ldr, a, lda, m, n,
+	                reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr), comm, a_layout, q_layout};
+	return f64_ladder(reorth, c.st, [&](int k) { return n > PW ? f64w_sweep(c, k) : f64_sweep(c, k); });
 }
 
 // Z_acc = Z_1 ... Z_k, the inverse of R after k sweeps, from Z_k in wq[F64_Z]: a copy for k = 1, else Z_acc <- Z_acc Z_k (trimul_f64_kernel)
@@ -2639,22 +2696,31 @@ size_t tsqr_mi_working_r_size_f64_lstsq(size_t m, size_t n, size_t nrhs) {
 	return (m == 0 || n == 0 || nrhs == 0) ? 0 : f64r_wr_doubles(m, std::min(n, PW));
 }
 
-// rows of storage between the leading-dimension steps of an operand with `rows` rows and `cols` columns in the given layout
-static bool f64_layout_ok(int layout) { return layout == TSQR_MI_COL_MAJOR || layout == TSQR_MI_ROW_MAJOR; }
-static size_t f64_min_ld(int layout, size_t rows, size_t cols) { return layout == TSQR_MI_ROW_MAJOR ? cols : rows; }
+// One operand of a single-GPU fp64 entry, as the entry's prologue checks it.  Results (r, x) are column-major.
+struct F64Operand { int layout; size_t rows, cols, ld; };
+
+// What every single-GPU _lay entry decides first, in the order that is its contract: the sweep count cleared; a layout other than the two
+// (state 1); an empty operand, n > m or a leading dimension below the operand's extent along it -- the rows column-major, the columns
+// row-major (state 1; neither sets a text); n above the entry's cap (state 2 with cap_text).  0: go on.  No HIP call.
+static int f64_prologue(std::initializer_list<F64Operand> ops, size_t m, size_t n, size_t cap, const char* cap_text) {
+	t_sweeps64 = 0;
+	for (const F64Operand& o : ops)
+		if (o.layout != TSQR_MI_COL_MAJOR && o.layout != TSQR_MI_ROW_MAJOR) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > m) return TSQR_MI_ERROR_INVALID_SIZE;
+	for (const F64Operand& o : ops)
+		if (o.rows == 0 || o.cols == 0 || o.ld < (o.layout == TSQR_MI_ROW_MAJOR ? o.cols : o.rows)) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n > cap) { t_last_error = cap_text; return TSQR_MI_ERROR_UNSUPPORTED; }
+	return 0;
+}
 
 int tsqr_mi_lstsq_f64_lay(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr,
                           const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
                           void* wq, void* wr, void* stream) {
-	t_sweeps64 = 0;
-	if (!f64_layout_ok(a_layout) || !f64_layout_ok(b_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > m || m == 0 || n == 0 || nrhs == 0 || lda < f64_min_ld(a_layout, m, n) || ldb < f64_min_ld(b_layout, m, nrhs) || ldr < n || ldx < n)
-		return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > PW) { t_last_error = "tsqr_mi_lstsq_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	const F64Operand A{a_layout, m, n, lda}, B{b_layout, m, nrhs, ldb}, R{TSQR_MI_COL_MAJOR, n, n, ldr}, X{TSQR_MI_COL_MAJOR, n, nrhs, ldx};
+	if (const int rc = f64_prologue({A, B, R, X}, m, n, PW, "tsqr_mi_lstsq_f64 supports n <= 64")) return rc;
 	if (nrhs > F64L_MAX_NRHS) { t_last_error = "tsqr_mi_lstsq_f64 supports nrhs <= 16"; return TSQR_MI_ERROR_UNSUPPORTED; }
 	if (refine < 0 || refine > F64L_MAX_REFINE) { t_last_error = "tsqr_mi_lstsq_f64 supports 0 <= refine <= 4"; return TSQR_MI_ERROR_UNSUPPORTED; }
-	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
-	if (rc) return rc;
+	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	return lstsq_f64_core(a_layout, b_layout, reorth, refine, x, ldx, r, ldr, a, lda, b, ldb, m, n, nrhs, reinterpret_cast<double*>(wq),
 	                      reinterpret_cast<double*>(wr), reinterpret_cast<hipStream_t>(stream));
 }
@@ -2669,12 +2735,9 @@ size_t tsqr_mi_working_r_size_f64_r(size_t m, size_t n) { return (m == 0 || n ==
 
 int tsqr_mi_r_f64_lay(int a_layout, int reorth, double* r, size_t ldr, const double* a, size_t lda, size_t m, size_t n,
                       void* wq, void* wr, void* stream) {
-	t_sweeps64 = 0;
-	if (!f64_layout_ok(a_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > m || m == 0 || n == 0 || lda < f64_min_ld(a_layout, m, n) || ldr < n) return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > PW) { t_last_error = "tsqr_mi_r_f64 supports n <= 64"; return TSQR_MI_ERROR_UNSUPPORTED; }
-	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
-	if (rc) return rc;
+	const F64Operand A{a_layout, m, n, lda}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
+	if (const int rc = f64_prologue({A, R}, m, n, PW, "tsqr_mi_r_f64 supports n <= 64")) return rc;
+	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	return r_f64_core(a_layout, reorth, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
 	                  reinterpret_cast<hipStream_t>(stream));
 }
@@ -2693,16 +2756,11 @@ int tsqr_mi_last_sweeps_f64(void) { return t_sweeps64; }
 
 int tsqr_mi_qr_f64_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
                        size_t m, size_t n, void* wq, void* wr, void* stream) {
-	t_sweeps64 = 0;
-	if (!f64_layout_ok(a_layout) || !f64_layout_ok(q_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > m || m == 0 || n == 0 || ldq < f64_min_ld(q_layout, m, n) || lda < f64_min_ld(a_layout, m, n) || ldr < n)
-		return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > PW) { t_last_error = "tsqr_mi_qr_f64 supports n <= 64 (tsqr_mi_qr_f64_wide: n <= 1024)"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	const F64Operand A{a_layout, m, n, lda}, Q{q_layout, m, n, ldq}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
+	if (const int rc = f64_prologue({A, Q, R}, m, n, PW, "tsqr_mi_qr_f64 supports n <= 64 (tsqr_mi_qr_f64_wide: n <= 1024)")) return rc;
 	if (q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
-	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
-	if (rc) return rc;
-	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
-	                   reinterpret_cast<hipStream_t>(stream), false, nullptr, a_layout, q_layout);
+	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream, nullptr, a_layout, q_layout);
 }
 
 int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
@@ -2714,66 +2772,9 @@ int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, dou
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The wide fp64 entry (tsqr_mi_qr_f64_wide): n <= 64 is tsqr_mi_qr_f64 itself; 64 < n <= 1024 runs the same ladder (qr_f64_core) with
-// whole-matrix sweeps on nb = ceil(n / 64) column blocks (kernels and block storage: tsqr_f64_wide.hip).  A sweep: the Gram pass and
-// its reduction; the blocked Cholesky step -- plain, then the shifted chain enqueued behind it, each of its launches skipping itself
-// when the plain verdict was 0 -- so that a one-sweep call still waits on the stream once; the apply pass; R out or R <- R_k R.
+// whole-matrix sweeps on nb = ceil(n / 64) column blocks (f64w_sweep, beside f64_sweep above; kernels and block storage:
+// tsqr_f64_wide.hip).
 // ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// (F64W_MAX_N, F64W_WR_CAP, F64W_TARGET_WGS, F64WPlan, f64w_plan and the blocked Cholesky step f64w_chain: f64_plan.h)
-
-// sweep k (0-based) of the wide entry: sweep 0 factors A into r and writes Q; sweep k >= 1 factors Q in place, R <- R_k R.  a_layout,
-// q_layout (tsqr_mi_qr_f64_wide_lay) as in f64_sweep: sweep 0 reads A in a_layout -- the Gram pass and the apply pass, which writes Q in
-// q_layout; later sweeps read and write Q in q_layout.  Everything between the two passes works on the block store and knows no layout.
-int f64w_sweep(hipStream_t st, int /*dev*/, int k, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
-               double* wq, double* wr, const Comm* comm, int a_layout, int q_layout) {
-	const bool first = k == 0;
-	const double* src = first ? a : q;
-	const size_t lds = first ? lda : ldq;
-	const int src_layout = first ? a_layout : q_layout;
-	const F64WPlan g = f64w_plan(m, n);
-	if (g.nslices <= 0 || g.npairs <= 0) { t_last_error = "fp64 wide Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
-	const tsqrmi::GramWideF64Args ga{src, lds, m, (int)n, g.npairs, g.ngroups, g.cps, g.nch, wr};
-	f64w_gram_launch(st, g, ga, src_layout);
-	HIPCHK(hipGetLastError());
-	const int nelem = (int)g.bs;
-	launch_reduce1(st, wq + g.o_gs, wr, g.nslices, nelem, (double)m);
-	HIPCHK(hipGetLastError());
-	if (const int rc = f64_exchange(comm, wq + g.o_gs, g.bs, st)) return rc;
-	tsqrmi::WideF64 wa{};
-	wa.gs = wq + g.o_gs; wa.w = wq + g.o_w; wa.rw = wq + g.o_rw; wa.zw = wq + g.o_zw; wa.ta = wq + g.o_ta; wa.zd = wq + g.o_zd;
-	wa.sb = wq + g.o_sb;
-	wa.bst = reinterpret_cast<unsigned*>(wq + g.o_bst);
-	const int slot = k & 3;
-	wa.status = reinterpret_cast<unsigned*>(wq + g.o_status) + 4 * slot;
-	wa.host_status = t_own64.dev + 4 * slot;
-	const F64Rule rule = f64_rule(m, n, first);          // (f64_plan.h; CholArgs64, tsqr_f64.hip, states the rule)
-	wa.max_scond = rule.max_scond; wa.alone_max = rule.alone_max;
-	wa.n = (int)n; wa.nb = g.nb;
-	if (comm && comm->active()) { wa.rows_dev = wq + g.o_gs + g.bs; wa.first = first ? 1 : 0; }   // (the rule of the GLOBAL row count, on the device)
-	wa.run_if = nullptr; wa.shift_coef = 0.0;
-	int rc = f64w_chain(st, wa);
-	if (rc) return rc;
-	wa.run_if = wa.status; wa.shift_coef = rule.shift_coef;
-	rc = f64w_chain(st, wa);
-	if (rc) return rc;
-	f64w_apply_launch(st, q, ldq, src, lds, m, (int)n, g.nb, (const double*)(wq + g.o_zw), src_layout, q_layout);
-	HIPCHK(hipGetLastError());
-	if (first) {
-		hipLaunchKernelGGL(tsqrmi::rcopy_wide_f64_kernel, dim3((unsigned)cdiv(n * n, 256)), dim3(256), 0, st, r, ldr, (const double*)(wq + g.o_rw), (int)n);
-		HIPCHK(hipGetLastError());
-		return 0;
-	}
-	hipLaunchKernelGGL(tsqrmi::rsave_wide_f64_kernel, dim3((unsigned)cdiv(g.bs, 256)), dim3(256), 0, st, wq + g.o_rc, (const double*)r, ldr, (int)n, g.npairs);
-	HIPCHK(hipGetLastError());
-	hipLaunchKernelGGL(tsqrmi::rmul_wide_f64_kernel, dim3((unsigned)g.npairs), dim3(1024), 0, st, r, ldr, (const double*)(wq + g.o_rw),
-	                   (const double*)(wq + g.o_rc), (int)n);
-	HIPCHK(hipGetLastError());
-	return 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 size_t tsqr_mi_working_q_size_f64_wide(size_t m, size_t n) {
@@ -2790,17 +2791,12 @@ size_t tsqr_mi_working_r_size_f64_wide(size_t m, size_t n) {
 
 int tsqr_mi_qr_f64_wide_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
                             size_t m, size_t n, void* wq, void* wr, void* stream) {
-	t_sweeps64 = 0;
-	if (!f64_layout_ok(a_layout) || !f64_layout_ok(q_layout)) return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > m || m == 0 || n == 0 || ldq < f64_min_ld(q_layout, m, n) || lda < f64_min_ld(a_layout, m, n) || ldr < n)
-		return TSQR_MI_ERROR_INVALID_SIZE;
-	if (n > F64W_MAX_N) { t_last_error = "tsqr_mi_qr_f64_wide supports n <= 1024"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	const F64Operand A{a_layout, m, n, lda}, Q{q_layout, m, n, ldq}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
+	if (const int rc = f64_prologue({A, Q, R}, m, n, F64W_MAX_N, "tsqr_mi_qr_f64_wide supports n <= 1024")) return rc;
 	if (q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
 	if (n <= PW) return tsqr_mi_qr_f64_lay(a_layout, q_layout, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream);
-	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
-	if (rc) return rc;
-	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
-	                   reinterpret_cast<hipStream_t>(stream), true, nullptr, a_layout, q_layout);
+	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream, nullptr, a_layout, q_layout);
 }
 
 int tsqr_mi_qr_f64_wide(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m, size_t n,
@@ -2825,10 +2821,8 @@ static int qr_f64_dist(const Comm& comm, int reorth, double* q, size_t ldq, doub
 		t_last_error = "tsqr_mi_qr_f64_dist needs an all-reduce: a callback, or an ncclComm_t with the ncclAllReduce entry point of the library that created it";
 		return TSQR_MI_ERROR_UNSUPPORTED;
 	}
-	const int rc = latch_all();                          // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
-	if (rc) return rc;
-	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m_local, n, reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr),
-	                   reinterpret_cast<hipStream_t>(stream), n > PW, &comm);
+	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m_local, n, wq, wr, stream, &comm, TSQR_MI_COL_MAJOR, TSQR_MI_COL_MAJOR);
 }
 
 int tsqr_mi_qr_f64_dist_cb(int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda, size_t m_local, size_t n,
