@@ -351,6 +351,35 @@ inline state_t qr_fp64(
 	return st;
 }
 
+// Not in the reference: a = u diag(s) v^T in double precision, 1 <= n <= m, n <= 64 (tsqr_mi_svd_f64, include/tsqr_mi.h for the
+// contract): the ladder of qr_fp64 into u, one-sided Jacobi on R, u <- u W.  s takes n values, descending; v (n x n, column-major, ldv;
+// may be null) takes V.  ComputeU = false: u_ptr is ignored, a is read only and the work space is that of r_fp64.  a_layout, u_layout
+// as for qr_fp64 (in place, u_ptr == a_ptr, needs equal layouts and ldu == lda).  Returns the states of qr_fp64 or error_no_convergence.
+const state_t error_no_convergence = TSQR_MI_ERROR_NO_CONVERGENCE;
+
+template <bool Reorthogonalize, bool ComputeU = true>
+struct buffer_fp64_svd : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n) {
+		allocate_doubles(tsqr_mi_working_q_size_f64_svd(m, n, ComputeU ? 1 : 0), tsqr_mi_working_r_size_f64_svd(m, n, ComputeU ? 1 : 0));
+	}
+};
+
+template <bool Reorthogonalize, bool ComputeU = true>
+inline state_t svd_fp64(
+		double* const u_ptr, const std::size_t ldu,
+		double* const s_ptr,
+		double* const v_ptr, const std::size_t ldv,
+		double* const a_ptr, const std::size_t lda,
+		const std::size_t m, const std::size_t n,
+		buffer_fp64_svd<Reorthogonalize, ComputeU>& bf,
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major, const layout_t u_layout = col_major) {
+	const int st = tsqr_mi_svd_f64(a_layout, u_layout, ComputeU ? 1 : 0, Reorthogonalize ? 1 : 0, u_ptr, ldu, s_ptr, v_ptr, ldv, a_ptr, lda, m, n,
+	                               bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::svd_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
+
 // Not in the reference: the R factor of qr_fp64 alone, Q never formed (tsqr_mi_r_f64, include/tsqr_mi.h for the contract): a is read
 // only, no m x n work space.  Returns the states of qr_fp64.
 template <bool Reorthogonalize>

@@ -51,6 +51,7 @@ enum tsqr_mi_compute_mode {
                                            * column norms (the range is judged on the column norms of the sweep's input, the diagonal of its Gram matrix):
                                            * [2^-511, 2^512), and ||A||_F < 2^512 for input that takes the shifted path (its trace).  Inside
                                            * it, scaling the columns by powers of two changes no bit of Q (tests/test_gpu_f64_scale.py) */
+#define TSQR_MI_ERROR_NO_CONVERGENCE  4   /* new, tsqr_mi_svd_f64 only: the Jacobi iteration reached its cap of 30 sweeps; s, v and u are undefined */
 /* negative return values: -(hipError_t) of the failing runtime call */
 
 int tsqr_mi_version(void);
@@ -451,6 +452,43 @@ int tsqr_mi_lstsq_f64_lay(int a_layout, int b_layout, int reorth, int refine, do
  */
 int tsqr_mi_qr_f64_lay(int a_layout, int q_layout, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
                        size_t m, size_t n, void* wq, void* wr, void* stream);
+
+/*
+ * Singular value decomposition of a tall-skinny matrix in double precision (not in the reference): A = U diag(s) V^T, 1 <= n <= 64,
+ * n <= m.  a (m x n, lda, a_layout) and u (m x n, ldu, u_layout) as the operands of tsqr_mi_qr_f64_lay; s: n doubles, descending and
+ * non-negative; v: n x n column-major with leading dimension ldv, holding V (not V^T), or NULL when V is not wanted.  Blocking.
+ * Bitwise deterministic from call to call.  The signs of the columns of U and V are those the fixed rotation order produces:
+ * unspecified but reproducible.
+ * Method: QR, one-sided Jacobi on R, then a product.  R = W diag(s) V^T on one workgroup (svd_r_f64_kernel, tsqr_f64.hip: Hestenes
+ * rotations in round-robin order on R scaled by a power of two to max |r_ij| in [1, 2), dgesvj's criterion
+ * |a_pq| <= sqrt(n) 2^-53 sqrt(a_pp a_qq), at most 30 sweeps).  The rotations act on the columns of R^T, which converges in fewer
+ * sweeps than R: s_j are the column norms, V the normalised columns and W the product of the rotations.  A column whose norm is
+ * exactly zero gives a zero column of V (W stays orthonormal) -- possible by underflow only, because the ladder's R has a positive
+ * diagonal.
+ *   jobu = 1  the ladder of tsqr_mi_qr_f64_lay, called as it stands (reorth as there), writes Q into u and R into the work space;
+ *             then U = Q W in place over Q on the fp64 matrix cores (applyd_f64_kernel).  u == a is allowed as there: one layout and
+ *             ldu == lda; A is untouched otherwise.  Work space: that entry's plus a block that does not depend on m --
+ *             wq of tsqr_mi_working_q_size_f64(m, n) + 8200 doubles, wr of tsqr_mi_working_r_size_f64(m, n) doubles.
+ *             ||U^T U - I||_F stays within that entry's band (1e-11; 1e-12 with reorth = 1) up to the orthogonality of W.
+ *   jobu = 0  u, ldu and u_layout are ignored and A is read only: the ladder of tsqr_mi_r_f64_lay -- no m x n buffer, that entry's
+ *             work-space sizes -- and s and V from its R.  That work space has no block that outlives a sweep, so R is kept in 32 KiB of
+ *             device memory the library owns per host thread and device (allocated at the first such call).
+ * Returns the states of those entries in their order -- 1 for a layout other than 0 or 1 (a_layout; u_layout with jobu = 1), for n > m,
+ * m == 0, n == 0, a leading dimension below its operand's extent (ldv < n when v is given), a jobu other than 0 or 1, or u == a with
+ * different layouts or leading dimensions; 2 for n > 64 -- all before any HIP call; 3 = TSQR_MI_ERROR_NOT_FINITE from the ladder, before
+ * the SVD kernel runs; 4 = TSQR_MI_ERROR_NO_CONVERGENCE when the sweep cap is reached (s, v and u are then undefined); or -(hipError_t).
+ * State 3 is the ladder's verdict and no rank test; the numerical rank is read off s.
+ * tsqr_mi_last_sweeps_f64 reports the ladder of this entry too; tsqr_mi_last_jacobi_sweeps_f64 the Jacobi sweeps of the calling
+ * thread's last tsqr_mi_svd_f64, the final sweep without a rotation included (0 when the kernel did not run).
+ * Not provided: n > 64, the row-partitioned and batched forms, and the m x m U.
+ */
+size_t tsqr_mi_working_q_size_f64_svd(size_t m, size_t n, int jobu);
+size_t tsqr_mi_working_r_size_f64_svd(size_t m, size_t n, int jobu);
+int tsqr_mi_svd_f64(int a_layout, int u_layout, int jobu, int reorth,
+                    double* u, size_t ldu, double* s, double* v, size_t ldv,
+                    double* a, size_t lda, size_t m, size_t n,
+                    void* wq, void* wr, void* stream);
+int tsqr_mi_last_jacobi_sweeps_f64(void);
 
 /*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,

@@ -30,7 +30,14 @@ tsqr_mi_qr_f64_wide and a transposing copy of Q back, waited for.  Per arm the m
 ratios a / b and a / c; asserts that Q and R of (a) are bitwise those of (b).  With --parent-lib PATH (another build of libtsqr_mi.so,
 the parent commit's) arm (b) alone is also run in fresh processes, alternating PATH (through TSQR_MI_LIB) and the in-tree library, two
 runs each: the parent's two medians give the spread the in-tree median is read against, and the checksums of Q and R of the
-column-major call are compared.  Writes the JSON to --out (default profiles/fp64_wide_rowmajor_speed.json) and prints it."""
+column-major call are compared.  Writes the JSON to --out (default profiles/fp64_wide_rowmajor_speed.json) and prints it.
+--svd: instead, the SVD entry (tsqr_mi_svd_f64, reorth = 0, column-major Gaussian operands) at 2^16, 2^20 and 2^23 rows x 64 and
+2^20 x 16 (--cases 2p20x64,... picks some): jobu = 1 interleaved call by call with tsqr_mi_qr_f64_lay, jobu = 0 with tsqr_mi_r_f64_lay,
+on the same operands in this process; per arm the median of --calls blocking calls, the ladder and Jacobi sweep counts, the difference
+svd - qr (what the Jacobi kernel and the dense apply add), and torch.linalg.svd(float64, full_matrices=False) and
+torch.linalg.svdvals on the same matrix (median of three; --no-torch skips them).  Writes the JSON to --svd-out (default
+profiles/fp64_svd_speed.json) and prints it.  --svd-arms svd_jobu1 runs that arm alone and writes no file: the run to put under a
+kernel trace for the per-kernel split (profiles/fp64_svd_kernel_stats_2p20x64.csv)."""
 import argparse
 import json
 import math
@@ -522,6 +529,90 @@ def dist1(torch, bq, calls, warmup):
     print(json.dumps(out))
 
 
+SVD_SHAPES = ((16, 64), (20, 64), (23, 64), (20, 16))
+
+
+def svd(torch, bq, calls, warmup, only, no_torch, only_arms=()):
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    out = {"tool": "f64_speed --svd", "calls": calls, "warmup": warmup, "reorth": 0, "layout": "column-major", "cases": []}
+    for lg, n in SVD_SHAPES:
+        if only and "2p%dx%d" % (lg, n) not in only:
+            continue
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a_rm = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g)
+        a = a_rm.t().contiguous()                           # (n, m): column-major m x n
+        u, q = torch.empty_like(a), torch.empty_like(a)
+        s = [torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(2)]
+        v = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(2)]
+        r = torch.empty(n, n, dtype=torch.float64, device="cuda")
+        stream = vp(torch.cuda.current_stream().cuda_stream)
+        work = {}
+        for key, fq, fr, extra in (("svd1", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (1,)),
+                                   ("svd0", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (0,)),
+                                   ("qr", L.tsqr_mi_working_q_size_f64, L.tsqr_mi_working_r_size_f64, ()),
+                                   ("r", L.tsqr_mi_working_q_size_f64_r, L.tsqr_mi_working_r_size_f64_r, ())):
+            wq = torch.empty(fq(m, n, *extra), dtype=torch.float64, device="cuda")
+            wr = torch.empty(fr(m, n, *extra), dtype=torch.float64, device="cuda")
+            work[key] = (wq, wr, (vp(wq.data_ptr()), vp(wr.data_ptr()), stream))
+        arms = [("svd_jobu1", lambda: L.tsqr_mi_svd_f64(0, 0, 1, 0, vp(u.data_ptr()), m, vp(s[1].data_ptr()), vp(v[1].data_ptr()), n,
+                                                        vp(a.data_ptr()), m, m, n, *work["svd1"][2])),
+                ("qr_f64_lay", lambda: L.tsqr_mi_qr_f64_lay(0, 0, 0, vp(q.data_ptr()), m, vp(r.data_ptr()), n, vp(a.data_ptr()), m, m, n,
+                                                            *work["qr"][2])),
+                ("svd_jobu0", lambda: L.tsqr_mi_svd_f64(0, 0, 0, 0, None, m, vp(s[0].data_ptr()), vp(v[0].data_ptr()), n,
+                                                        vp(a.data_ptr()), m, m, n, *work["svd0"][2])),
+                ("r_f64_lay", lambda: L.tsqr_mi_r_f64_lay(0, 0, vp(r.data_ptr()), n, vp(a.data_ptr()), m, m, n, *work["r"][2]))]
+        if only_arms:
+            arms = [arm for arm in arms if arm[0] in only_arms]
+        ts = {name: [] for name, _ in arms}
+        for i in range(warmup + calls):
+            for name, fn in arms:
+                t0 = time.perf_counter()
+                rc = fn()                                   # (blocking: returns when the stream has drained)
+                dt = time.perf_counter() - t0
+                assert rc == 0, (name, rc, bq.last_error())
+                if i >= warmup:
+                    ts[name].append(dt)
+        med = {k: sorted(x)[len(x) // 2] * 1e3 for k, x in ts.items()}
+        if only_arms:                                       # (a run under a kernel trace: the medians of the chosen arms, nothing else)
+            out["cases"].append({"m": m, "n": n, "median_ms": med})
+            continue
+        sweeps = {}
+        for name, fn in arms:
+            fn()
+            sweeps[name] = (L.tsqr_mi_last_sweeps_f64(), L.tsqr_mi_last_jacobi_sweeps_f64())
+        um = u.t()
+        orth = torch.linalg.norm(um.T @ um - torch.eye(n, dtype=torch.float64, device="cuda")).item()
+        res = (torch.linalg.norm(a_rm - (um * s[1]) @ v[1]) / torch.linalg.norm(a_rm)).item()    # (v[1] read as a tensor is V^T)
+        case = {"m": m, "n": n, "svd_jobu1_median_ms": med["svd_jobu1"], "qr_f64_lay_median_ms": med["qr_f64_lay"],
+                "svd_jobu0_median_ms": med["svd_jobu0"], "r_f64_lay_median_ms": med["r_f64_lay"],
+                "jobu1_minus_qr_ms": med["svd_jobu1"] - med["qr_f64_lay"], "jobu0_minus_r_ms": med["svd_jobu0"] - med["r_f64_lay"],
+                "ladder_sweeps": sweeps["svd_jobu1"][0], "jacobi_sweeps": sweeps["svd_jobu1"][1],
+                "ladder_sweeps_jobu0": sweeps["svd_jobu0"][0], "jacobi_sweeps_jobu0": sweeps["svd_jobu0"][1],
+                "s_bitwise_equal_jobu0_jobu1": bool(torch.equal(s[0], s[1])), "orth_fro": orth, "residual": res}
+        if not no_torch:
+            def torch_median(fn, reps=3):
+                fn()
+                torch.cuda.synchronize()
+                tt = []
+                for _ in range(reps):
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    tt.append(time.perf_counter() - t0)
+                return sorted(tt)[len(tt) // 2] * 1e3
+            case["torch_linalg_svd_ms"] = torch_median(lambda: torch.linalg.svd(a_rm, full_matrices=False))
+            case["torch_linalg_svdvals_ms"] = torch_median(lambda: torch.linalg.svdvals(a_rm))
+            case["speedup_jobu1_vs_torch_svd"] = case["torch_linalg_svd_ms"] / med["svd_jobu1"]
+            case["speedup_jobu0_vs_torch_svdvals"] = case["torch_linalg_svdvals_ms"] / med["svd_jobu0"]
+        out["cases"].append(case)
+        del a_rm, a, u, q, s, v, r, work
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=None, help="blocking calls per case or arm (default 50; --wide-row-major: 20)")
@@ -536,6 +627,9 @@ def main():
     ap.add_argument("--wide-row-major", action="store_true", help="time tsqr_mi_qr_f64_wide_lay on row-major A and Q next to tsqr_mi_qr_f64_wide")
     ap.add_argument("--wide-col-only", action="store_true", help="arm (b) of --wide-row-major alone (the child processes of --parent-lib)")
     ap.add_argument("--parent-lib", default="", help="--wide-row-major: another build of libtsqr_mi.so to run arm (b) against")
+    ap.add_argument("--svd", action="store_true", help="time tsqr_mi_svd_f64 (jobu 1 and 0) next to tsqr_mi_qr_f64_lay, tsqr_mi_r_f64_lay and torch.linalg.svd")
+    ap.add_argument("--svd-arms", default="", help="--svd: run only these arms (svd_jobu1, qr_f64_lay, svd_jobu0, r_f64_lay) and write no file: for a kernel trace")
+    ap.add_argument("--svd-out", default=os.path.join(ROOT, "profiles", "fp64_svd_speed.json"), help="--svd: the JSON file ('' writes none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp64_wide_rowmajor_speed.json"), help="--wide-row-major: the JSON file")
     args = ap.parse_args()
     wide_rm = args.wide_row_major or args.wide_col_only
@@ -550,6 +644,14 @@ def main():
         out = wide_row_major(torch, bq, args.calls, args.warmup, parent)
         with open(args.out, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
+        print(json.dumps(out))
+        return
+    if args.svd:
+        only_arms = [c for c in args.svd_arms.split(",") if c]
+        out = svd(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], args.no_torch, only_arms)
+        if args.svd_out and not only_arms:
+            with open(args.svd_out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
         print(json.dumps(out))
         return
     if args.dist1:

@@ -37,6 +37,7 @@ success_factorization = 0             # reference src/blockqr.hpp:28
 error_invalid_matrix_size = 1         # reference src/blockqr.hpp:29
 error_unsupported_mode = 2            # new: modes without a gfx950 implementation
 error_not_finite = 3                  # new, qr_f64 only: A holds an Inf or NaN
+error_no_convergence = 4              # new, svd_f64 only: the Jacobi iteration reached its cap of 30 sweeps
 
 COL_MAJOR, ROW_MAJOR = 0, 1              # TSQR_MI_COL_MAJOR, TSQR_MI_ROW_MAJOR: the layout arguments of the *_lay entries
 
@@ -115,6 +116,10 @@ def _c_signatures():
         "tsqr_mi_working_q_size_f64_lstsq": (sz, [sz, sz, sz]), "tsqr_mi_working_r_size_f64_lstsq": (sz, [sz, sz, sz]),
         "tsqr_mi_r_f64_lay": (ci, [ci] + r64), "tsqr_mi_lstsq_f64_lay": (ci, [ci, ci] + lstsq64),
         "tsqr_mi_qr_f64_lay": (ci, [ci, ci] + qr64), "tsqr_mi_qr_f64_wide_lay": (ci, [ci, ci] + qr64),
+        "tsqr_mi_working_q_size_f64_svd": (sz, [sz, sz, ci]), "tsqr_mi_working_r_size_f64_svd": (sz, [sz, sz, ci]),
+        # (a_layout, u_layout, jobu, reorth, u, ldu, s, v, ldv, a, lda, m, n, wq, wr, stream)
+        "tsqr_mi_svd_f64": (ci, [ci, ci, ci, ci, vp, sz, vp, vp, sz, vp, sz, sz, sz, vp, vp, vp]),
+        "tsqr_mi_last_jacobi_sweeps_f64": (ci, []),
     }
 
 
@@ -125,7 +130,8 @@ OPTIONAL_SYMBOLS = {
     "tsqr_mi_working_q_size_f64_dist", "tsqr_mi_working_r_size_f64_dist", "tsqr_mi_qr_f64_dist", "tsqr_mi_qr_f64_dist_fn", "tsqr_mi_qr_f64_dist_cb",
     "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
     "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
-    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay"}
+    "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay",
+    "tsqr_mi_working_q_size_f64_svd", "tsqr_mi_working_r_size_f64_svd", "tsqr_mi_svd_f64", "tsqr_mi_last_jacobi_sweeps_f64"}
 
 _lib = None
 
@@ -416,6 +422,7 @@ _F64 = _F64Entry("qr_f64", 64, "tsqr_mi_qr_f64", "_f64")
 _F64_WIDE = _F64Entry("qr_f64_wide", 1024, "tsqr_mi_qr_f64_wide", "_f64_wide")
 _F64_R = _F64Entry("r_f64", 64, "tsqr_mi_r_f64", "_f64_r")
 _F64_LSTSQ = _F64Entry("lstsq_f64", 64, "tsqr_mi_lstsq_f64", "_f64_lstsq")
+_F64_SVD = _F64Entry("svd_f64", 64, "tsqr_mi_svd_f64", "_f64_svd")       # (its size functions take jobu behind m and n)
 
 
 def _null_state(fn, *scalars):
@@ -725,6 +732,129 @@ def qr_f64_wide_tensor(a, reorth=False, overwrite_a=False, stream=None):
     return _qr_f64_tensor(_F64_WIDE, a, reorth, overwrite_a, stream)
 
 
+class SvdError(RuntimeError):
+    """svd_f64_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode, error_not_finite or
+    error_no_convergence)"""
+
+    def __init__(self, state, text):
+        RuntimeError.__init__(self, text)
+        self.state = state
+
+
+class buffer_f64_svd(buffer_f64):
+    """Work space of svd_f64 (tsqr_mi_working_{q,r}_size_f64_svd doubles on the GPU).  compute_u: the jobu the space is sized for --
+    True: the QR entry's space and the SVD block; False: the R-only entry's (no m x n part; it does not serve a call with compute_u).
+    reorthogonalize as in buffer_f64."""
+    _entry = _F64_SVD
+
+    def __init__(self, reorthogonalize=False, device="cuda", compute_u=True):
+        buffer_f64.__init__(self, reorthogonalize, device)
+        self.compute_u = bool(compute_u)
+
+    def allocate(self, m, n):
+        import torch
+        if self.dwq is not None or self.dwr is not None:
+            raise RuntimeError("The buffer has been already allocated")
+        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device)
+                              for size in self._entry.sizes(m, n, int(self.compute_u)))
+
+
+def check_f64_svd_operands(m, n, ldu, ldv, lda, u, s, v, a, row_major=False):
+    """The size and overlap rules of svd_f64 on (address, elements) pairs (u and v may be None: not used): check_f64_operands' rules for
+    u and a (row_major: both row-major), v n x n column-major with ldv >= n, s of n elements; u either the very operand a (same address
+    and ld: in place) or apart from it; s and v apart from u, from a and from each other.  Raises ValueError."""
+    ops = [("a", a, lda, m, n, row_major), ("s", s, n, n, 1, False)]
+    if u is not None:
+        ops.append(("u", u, ldu, m, n, row_major))
+    if v is not None:
+        ops.append(("v", v, ldv, n, n, False))
+    span = dict(zip((o[0] for o in ops), _f64_spans("svd_f64", ops)))
+    names = list(span)
+    for i, x in enumerate(names):
+        for y in names[i + 1:]:
+            if {x, y} == {"a", "u"} and u[0] == a[0] and ldu == lda:
+                continue                                   # (in place)
+            if span[x][0] < span[y][1] and span[y][0] < span[x][1]:
+                raise ValueError("svd_f64: %s overlaps %s%s" % (x, y, " without being a (in place needs u == a and ldu == lda)"
+                                                                 if {x, y} == {"a", "u"} else ""))
+
+
+def svd_f64(u, ldu, s, v, ldv, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False, compute_u=True):
+    """Double-precision tall-skinny SVD (tsqr_mi_svd_f64), a = u diag(s) v^T, 1 <= n <= 64, n <= m: u, s, v, a are float64 GPU tensors
+    (only data_ptr and numel are used); a and u hold column-major data, or ROW-major data with row_major=True (element (i, j) at
+    i * ld + j, ld >= n) as in qr_f64; s takes n values, descending; v (n x n, column-major, ldv; None: not wanted) takes V, not its
+    transpose.  compute_u=False (jobu = 0): u is not used (None is fine), a is read only, and bf must have been made with
+    compute_u=False or True -- the larger space serves both.  u may be a itself (in place, ldu == lda).  bf is a buffer_f64_svd.
+    Blocking; returns the state: 0, error_invalid_matrix_size, error_unsupported_mode (n > 64), error_not_finite (the ladder's verdict)
+    or error_no_convergence.  Operands are checked before anything is launched: TypeError for a wrong dtype or a CPU tensor,
+    ValueError for a short tensor, a short leading dimension or overlapping operands.  last_sweeps_f64() tells how many sweeps the
+    ladder took, last_jacobi_sweeps_f64() how many the Jacobi iteration took.  The signs of the columns of u and v are reproducible
+    but not specified."""
+    entry = _F64_SVD
+    fn = lib().tsqr_mi_svd_f64
+    jobu = 1 if compute_u else 0
+    layout = ROW_MAJOR if row_major else COL_MAJOR
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    operands = [("s", s), ("a", a)] + ([("u", u)] if jobu else []) + ([("v", v)] if v is not None else [])
+    _check_f64_tensors(entry.name, operands)
+    if n > m or m == 0 or n == 0:
+        return error_invalid_matrix_size
+    if n > entry.nmax:
+        return _null_state(fn, layout, layout, jobu, int(reorth), ldu, ldv, lda, m, n)
+    pair = lambda t: (t.data_ptr(), t.numel())
+    check_f64_svd_operands(m, n, ldu, ldv, lda, pair(u) if jobu else None, pair(s), None if v is None else pair(v), pair(a),
+                           row_major=bool(row_major))
+    if bf.dwq is None:
+        raise RuntimeError("svd_f64: the buffer is not allocated")
+    need = entry.sizes(m, n, jobu)
+    if bf.dwq.numel() < need[0] or bf.dwr.numel() < need[1]:
+        raise ValueError("svd_f64: the buffer was allocated for a smaller matrix (or without compute_u)")
+    return _f64_call(entry.symbol, fn, stream, layout, layout, jobu, int(reorth), u.data_ptr() if jobu else None, ldu, s.data_ptr(),
+                     None if v is None else v.data_ptr(), ldv, a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr())
+
+
+def svd_f64_tensor(a, reorth=False, compute_uv=True, overwrite_a=False, stream=None):
+    """(U, S, Vh) of the double-precision tall-skinny SVD (tsqr_mi_svd_f64: include/tsqr_mi.h has the method) of a two-dimensional
+    float64 GPU tensor a, m x n with 1 <= n <= 64, n <= m, any strides: the shapes of torch.linalg.svd(a, full_matrices=False) -- U m x n,
+    S of n values, descending, Vh n x n = V transposed.  compute_uv=False returns S alone (jobu = 0: Q is never formed and a is only
+    read).  a is read where it lies when its columns or its rows are contiguous (_operand_f64's rule, as for qr_f64_tensor) and copied
+    once into column-major storage otherwise; U has a's layout, and U, S and Vh have the same bits whichever way a is stored.
+    overwrite_a=True: when a is used where it lies, U IS a.  reorth: the ladder's argument (qr_f64).  The work space is allocated per
+    call.  Blocking.  The signs of the columns of U and rows of Vh are reproducible but not specified.  Raises TypeError for a wrong
+    dtype or a CPU tensor, ValueError for a tensor that is not two-dimensional, SvdError (.state) when the C entry returns a state other
+    than 0: sizes it does not support, error_not_finite from the ladder (Inf or NaN in a, a zero column), or error_no_convergence."""
+    import torch
+    entry = _F64_SVD
+    name = entry.name + "_tensor"
+    _check_f64_tensors(name, (("a", a),))
+    if a.dim() != 2:
+        raise ValueError("%s: a must be m x n, got %s" % (name, tuple(a.shape)))
+    m, n = a.shape
+    fn = lib().tsqr_mi_svd_f64
+    jobu = 1 if compute_uv else 0
+    if m == 0 or n == 0 or n > m or n > entry.nmax:
+        st = _null_state(fn, COL_MAJOR, COL_MAJOR, jobu, int(bool(reorth)), max(m, 1), max(n, 1), max(m, 1), m, n)
+        raise SvdError(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
+    ac, lda, layout = _operand_f64(a)
+    u, ldu = None, lda
+    if jobu:
+        if overwrite_a and ac.data_ptr() == a.data_ptr():
+            u = a                                              # (in place: the same layout and leading dimension)
+        elif layout == ROW_MAJOR:
+            u, ldu = torch.empty((m, n), dtype=torch.float64, device=a.device), n
+        else:
+            u, ldu = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+    s = torch.empty(n, dtype=torch.float64, device=a.device)
+    v = torch.empty((n, n), dtype=torch.float64, device=a.device) if jobu else None      # (column-major V: read as a tensor, it is Vh)
+    wq, wr = entry.work_space(a.device, m, n, jobu)
+    with torch.cuda.device(a.device):
+        st = _f64_call(entry.symbol, fn, stream, layout, layout, jobu, int(bool(reorth)), u.data_ptr() if jobu else None, ldu,
+                       s.data_ptr(), v.data_ptr() if jobu else None, n, ac.data_ptr(), lda, m, n, wq.data_ptr(), wr.data_ptr())
+    if st:
+        raise SvdError(st, "%s: state %d: %s" % (name, st, last_error()))
+    return (u, s, v) if jobu else s
+
+
 def get_working_q_size_f64_dist(m_local, n, nranks):
     """Doubles of wq for tsqr_mi_qr_f64_dist* (dist.RowPartitionedQRF64 allocates them itself)."""
     return lib().tsqr_mi_working_q_size_f64_dist(m_local, n, nranks)
@@ -738,6 +868,11 @@ def get_working_r_size_f64_dist(m_local, n, nranks):
 def last_sweeps_f64():
     """Sweeps of this thread's last qr_f64 / qr_f64_wide / r_f64 / lstsq_f64 / row-partitioned fp64 call, plus 100 when it took the shifted path."""
     return lib().tsqr_mi_last_sweeps_f64()
+
+
+def last_jacobi_sweeps_f64():
+    """Jacobi sweeps of this thread's last svd_f64 / svd_f64_tensor call, the final sweep without a rotation included."""
+    return lib().tsqr_mi_last_jacobi_sweeps_f64()
 
 
 def set_tuning(level0_waves=0, tree_chunks_per_wave=0):

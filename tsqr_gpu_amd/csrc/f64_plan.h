@@ -133,6 +133,33 @@ inline void f64r_lsq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::LsqA
 	});
 }
 
+// ---- tsqr_mi_svd_f64 (n <= 64) ------------------------------------------------------------------------------------------------------------
+// jobu = 1 runs the ladder of tsqr_mi_qr_f64_lay on the F64_WQ layout with R in the block behind it, then svd_r_f64_kernel and
+// applyd_f64_kernel.  wq (doubles): [the F64_WQ layout][R, n x n with ld 64: 4096][W, NP x NP with ld NP: 4096][status words: 8]
+constexpr size_t F64S_R = F64_WQ, F64S_W = F64S_R + 4096, F64S_STATUS = F64S_W + 4096, F64S_WQ = F64S_STATUS + 8;
+constexpr size_t F64S_BLOCK = F64S_WQ - F64_WQ;         // what jobu = 1 adds to the QR entry's wq; wr is the QR entry's
+// jobu = 0 runs the ladder of tsqr_mi_r_f64_lay on that entry's work space, unchanged in size (F64R_WQ, f64r_wr_doubles).
+
+// svd_r_f64_kernel on stream st: one workgroup
+inline void f64_svd_r_launch(hipStream_t st, const tsqrmi::SvdArgs64& sa) {
+	hipLaunchKernelGGL(tsqrmi::svd_r_f64_kernel, dim3(1), dim3(1024), 0, st, sa);
+}
+
+// the workgroups of applyd_f64_kernel<NT, AROW, QROW> resident at once on device dev (f64_apply_resident for this kernel) ...
+template <int NT, bool AROW = false, bool QROW = false> int f64_applyd_resident(int dev) {
+	int nb = 0, cus = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tsqrmi::applyd_f64_kernel<NT, AROW, QROW>), 256, 0) != hipSuccess || nb < 1) {
+		(void)hipGetLastError(); nb = 1;
+	}
+	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
+	return nb * cus;
+}
+// ... and the kernel on a grid of wgs workgroups (f64_apply_wgs of the 32-row blocks and the resident count): u = q w, in place allowed
+template <int NT, bool AROW, bool QROW>
+inline void f64_applyd_launch(hipStream_t st, size_t wgs, double* u, size_t ldu, const double* q, size_t ldq, size_t m, int n, const double* w) {
+	hipLaunchKernelGGL((tsqrmi::applyd_f64_kernel<NT, AROW, QROW>), dim3((unsigned)wgs), dim3(256), 0, st, u, ldu, q, ldq, m, n, w, cdiv(m, 32));
+}
+
 // ---- tsqr_mi_qr_f64_wide (64 < n <= 1024) ----------------------------------------------------------------------------------------------
 constexpr size_t F64W_MAX_N = 1024;
 constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m

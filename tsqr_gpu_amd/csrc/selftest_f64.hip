@@ -211,6 +211,40 @@ int tsqr_selftest_f64_lsq_update(double* xw, double* x, size_t ldx, const double
 	return f64_sync();
 }
 
+// ---- n <= 64, SVD (tsqr_mi_svd_f64) ---------------------------------------------------------------------------------------------------------
+// svd_r_f64_kernel through the product's launcher: r (n x n upper triangular, ldr) in; s[n], w (NP x NP, ld NP), v (n x n, ldv; may be
+// null) and status[2] (sweeps, 0 converged / 1 cap reached) out.  transpose: 1 the product's choice (the columns of R^T rotate), 0 those of R.
+int tsqr_selftest_f64_svd_r(const double* r, size_t ldr, double* s, double* w, double* v, size_t ldv, unsigned* status, int n, int transpose) {
+	if (n <= 0 || n > (int)PW || ldr < (size_t)n || (v && ldv < (size_t)n) || (transpose != 0 && transpose != 1)) return -100;
+	tsqrmi::SvdArgs64 sa{};
+	sa.r = r; sa.ldr = ldr; sa.s = s; sa.w = w; sa.v = v; sa.ldv = ldv; sa.status = status; sa.host_status = nullptr; sa.n = n;
+	sa.transpose = transpose;
+	f64_svd_r_launch(0, sa);
+	return f64_sync();
+}
+
+// applyd_f64_kernel<NT, QROW, UROW>: u = q w (w: NP x NP, ld NP, zero padded) with the layout of the operand read and of the operand
+// written, as tsqr_selftest_f64_apply_lay; wgs > 0 overrides the grid, 0: the resident workgroups of that instantiation, as f64_applyd
+// takes them.  u == q (in place) needs equal layouts and leading dimensions.
+int tsqr_selftest_f64_applyd_lay(int q_layout, int u_layout, double* u, size_t ldu, const double* q, size_t ldq, size_t m, int n,
+                                 const double* w, int wgs) {
+	if ((q_layout != 0 && q_layout != 1) || (u_layout != 0 && u_layout != 1)) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || ldq < (q_layout ? (size_t)n : m) || ldu < (u_layout ? (size_t)n : m) || wgs > 65535) return -100;
+	if (u == q && (q_layout != u_layout || ldu != ldq)) return -100;
+	return with_apply((size_t)n, q_layout, u_layout, [&](auto nt, auto ar, auto qr) {
+		constexpr int NT = decltype(nt)::value;
+		constexpr bool AR = decltype(ar)::value, QR = decltype(qr)::value;
+		size_t g = (size_t)wgs;
+		if (wgs <= 0) {
+			int dev = 0;
+			(void)hipGetDevice(&dev);
+			g = f64_apply_wgs(cdiv(m, 32), (size_t)f64_applyd_resident<NT, AR, QR>(dev));
+		}
+		f64_applyd_launch<NT, AR, QR>(0, g, u, ldu, q, ldq, m, n, w);
+		return f64_sync();
+	});
+}
+
 // ---- 64 < n <= 1024 ---------------------------------------------------------------------------------------------------------------------
 // The Gram and apply entries come in two forms, like those of n <= 64 above: _lay takes a layout per operand (0 column-major; 1
 // row-major, the leading dimension is then the row stride, >= n) and goes through the launchers the product uses (f64_plan.h); the plain

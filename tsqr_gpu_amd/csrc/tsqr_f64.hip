@@ -12,6 +12,9 @@
 // and of the least-squares entry (tsqr_mi_lstsq_f64), whose passes behind that ladder stream A and B and store nothing of size m:
 //   lsq_f64_kernel        : per-workgroup partials of (A Z)^T (B - A X), each 16-row block of A Z and of the residual held in registers
 //   lsq_update_f64_kernel : X <- X + Z D on one workgroup
+// and of the SVD entry (tsqr_mi_svd_f64), behind the ladder of either entry above:
+//   svd_r_f64_kernel  : R = W diag(s) V^T by one-sided Jacobi on one workgroup, R held in LDS
+//   applyd_f64_kernel : U = Q W on v_mfma_f64_16x16x4_f64 for a dense W staged in LDS, in place allowed
 // The four passes that read A (and B) take the layout of each operand as a template flag (AROW, BROW: tsqr_mi_r_f64_lay,
 // tsqr_mi_lstsq_f64_lay, tsqr_mi_qr_f64_lay).  Element (i, j) of a row-major operand lies at s[i * ld + j], ld >= the column count.  A
 // row-major kernel is the column-major one with another address for the same register: at every MFMA lane (li, lq) of k-block kb holds
@@ -471,6 +474,204 @@ __global__ __launch_bounds__(1024) void lsq_update_f64_kernel(double* xw, double
 		if (last) x[(size_t)j * ldx + i] = v;
 	}
 	xw[(size_t)j * NP + i] = v;
+}
+
+// ---- the SVD entry (tsqr_mi_svd_f64): R = W diag(s) V^T on one workgroup, then U = Q W ----------------------------------------------------
+struct SvdArgs64 {
+	const double* r; size_t ldr;         // n x n upper triangular (only i <= j is read)
+	double* s;                           // n singular values out: descending, non-negative
+	double* w;                           // NP x NP (ld NP) out, zero padded, chol_f64_kernel's layout of Z; null: not wanted
+	double* v; size_t ldv;               // n x n out; null: not wanted
+	unsigned* status;                    // device words [0] sweeps, [1] 0 converged / 1 the cap was reached; null: not wanted
+	unsigned* host_status;               // device-visible alias of pinned host words receiving the same two values; null: not wanted
+	int n;
+	int transpose;                       // 0: the columns of R rotate (W: normalised columns, V: the rotations); 1: those of R^T (roles swapped)
+};
+constexpr int SVD_MAX_SWEEPS = 30;      // dgesvj's cap
+
+// The sum of x over the 64 lanes, the same bits in every lane.  The butterfly alone does not give that: when x is a product the compiler
+// may fuse it into the first addition, each lane then adds its own UNROUNDED product to its partner's rounded one, and the lanes end
+// one ulp apart -- enough to give the rows of a column pair different rotations (clustered singular values turn one ulp of a_pp into
+// a visible change of the angle; measured: 30 sweeps without convergence on the R of a Gaussian 4096 x 64 matrix).  So lane 0's sum is
+// the sum, for every lane.
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+	return __shfl(x, 0, 64);
+}
+
+// One-sided (Hestenes) Jacobi on the n x n factor R, n <= 64, held in LDS: M = R (or R^T) and J = I, 64 x 64 column-major each; lane i of a
+// wave holds row i of the two columns of a pair.  M is first scaled by the power of two that brings max |r_ij| into [1, 2) -- exact, and
+// s is scaled back at the end -- so that the inner products stay in range for every column norm the ladder accepts, and a factor
+// 2^k R gives the bits of R in W and V.  An odd n is padded with a column that never rotates.  Round-robin order (the circle method on
+// NE = n rounded up to even players): NE - 1 steps of NE / 2 disjoint pairs, pair k of a step on wave k mod 16, one barrier per step.
+// Pair (p, q), p < q: a_pp, a_qq, a_pq by wave reductions; skipped when |a_pq| <= sqrt(n) 2^-53 sqrt(a_pp) sqrt(a_qq) (dgesvj's
+// criterion), else zeta = (a_qq - a_pp) / (2 a_pq), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), c = 1 / sqrt(1 + t^2), s = c t and
+// (m_p, m_q) <- (c m_p - s m_q, s m_p + c m_q), the same for J.  A sweep without a rotation ends the iteration; SVD_MAX_SWEEPS is the cap.
+// The computed c^2 + s^2 is 1 only to rounding and a column takes part in several hundred rotations, all of which scale m_j and j_j
+// alike: the norms d_j = ||j_j||_2 drift from 1 by some 1e-14 at n = 64, and that drift -- not the angles -- is nearly all of
+// ||J^T J - I||_F (kernel_model in tests/pass_refs_f64_svd.py, cond 1e6, n = 64: 1.34e-13, of which 1.9e-14 off the diagonal).  So the end divides it out:
+// sigma_j = ||m_j||_2 / d_j, J <- J diag(d)^-1, X = the columns of M normalised by their own norms (a column of norm exactly zero --
+// possible by underflow only: R of the ladder has a positive diagonal -- stays zero).  sigma is sorted descending (ties: the lower
+// column first) with its columns, and (W, V) = (X, J), or (J, X) when transposed.
+// Everything is a fixed function of the input: two runs give the same bits.  No scratch; 67 KB of LDS.
+__global__ __launch_bounds__(1024) void svd_r_f64_kernel(const SvdArgs64 a) {
+	__shared__ double M[64 * 64], J[64 * 64];
+	__shared__ double sig[64], mnorm[64], jnorm[64], wmax[16];
+	__shared__ int rank_of[64];
+	__shared__ unsigned rotated;
+	const int t = threadIdx.x, lane = t & 63, wv = t >> 6, n = a.n;
+	const int NE = (n + 1) & ~1, NP = 16 * ((n + 15) / 16);
+	double x[4], mx = 0.0;
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		x[u] = (i <= j && j < n) ? a.r[(size_t)j * a.ldr + i] : 0.0;
+		mx = fmax(mx, fabs(x[u]));
+	}
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+	if (lane == 0) wmax[wv] = mx;
+	__syncthreads();
+#pragma unroll
+	for (int k = 0; k < 16; k++) mx = fmax(mx, wmax[k]);
+	const int ex = (mx > 0.0 && mx < INFINITY) ? ilogb(mx) : 0;     // 2^ex <= max |r_ij| < 2^(ex + 1)
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		M[a.transpose ? i * 64 + j : j * 64 + i] = scalbn(x[u], -ex);
+		J[e] = (i == j && j < n) ? 1.0 : 0.0;
+	}
+	if (t == 0) rotated = 0u;
+	__syncthreads();
+	const double tol = sqrt((double)n) * 0x1p-53;
+	const int npairs = NE / 2, nsteps = NE - 1;
+	unsigned sweeps = 0, failed = 1;
+	while (sweeps < (unsigned)SVD_MAX_SWEEPS) {
+		for (int st = 0; st < nsteps; st++) {
+			for (int k = wv; k < npairs; k += 16) {
+				const int c0 = k == 0 ? st : (st + k) % nsteps, c1 = k == 0 ? NE - 1 : (st - k + nsteps) % nsteps;
+				const int p = c0 < c1 ? c0 : c1, q = c0 < c1 ? c1 : c0;
+				if (q >= n) continue;                        // (the padding column of an odd n)
+				const double mp = M[p * 64 + lane], mq = M[q * 64 + lane];
+				const double app = wave_sum_f64(mp * mp), aqq = wave_sum_f64(mq * mq), apq = wave_sum_f64(mp * mq);
+				if (!(fabs(apq) > tol * (sqrt(app) * sqrt(aqq)))) continue;   // (uniform over the wave: every lane holds the same sums)
+				const double zeta = (aqq - app) / (2.0 * apq);
+				const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+				if (tt == 0.0) continue;                     // (zeta beyond the range: the rotation is the identity)
+				const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
+				const double jp = J[p * 64 + lane], jq = J[q * 64 + lane];
+				M[p * 64 + lane] = c * mp - s * mq;
+				M[q * 64 + lane] = s * mp + c * mq;
+				J[p * 64 + lane] = c * jp - s * jq;
+				J[q * 64 + lane] = s * jp + c * jq;
+				if (lane == 0) rotated = 1u;
+			}
+			__syncthreads();
+		}
+		sweeps++;
+		const unsigned any = rotated;
+		__syncthreads();                                     // every thread has read the flag of this sweep
+		if (t == 0) rotated = 0u;
+		__syncthreads();
+		if (!any) { failed = 0; break; }
+	}
+	for (int j = wv; j < 64; j += 16) {
+		const double mj = M[j * 64 + lane], jj = J[j * 64 + lane];
+		const double ss = wave_sum_f64(mj * mj), dd = wave_sum_f64(jj * jj);
+		if (lane == 0) { mnorm[j] = sqrt(ss); jnorm[j] = j < n ? sqrt(dd) : 1.0; sig[j] = sqrt(ss) / (j < n ? sqrt(dd) : 1.0); }
+	}
+	__syncthreads();
+	if (t < n) {
+		int before = 0;
+		for (int k = 0; k < n; k++) before += (sig[k] > sig[t] || (sig[k] == sig[t] && k < t)) ? 1 : 0;
+		rank_of[t] = before;
+		a.s[before] = scalbn(sig[t], ex);
+	}
+	__syncthreads();
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		if (a.w && i < NP && j < NP && (i >= n || j >= n)) a.w[(size_t)j * NP + i] = 0.0;
+		if (i < n && j < n) {
+			const int d = rank_of[j];
+			const double xn = mnorm[j] > 0.0 ? M[e] / mnorm[j] : 0.0, jv = J[e] / jnorm[j];
+			if (a.w) a.w[(size_t)d * NP + i] = a.transpose ? jv : xn;
+			if (a.v) a.v[(size_t)d * a.ldv + i] = a.transpose ? xn : jv;
+		}
+	}
+	if (t == 0) {
+		if (a.status) { a.status[0] = sweeps; a.status[1] = failed; }
+		if (a.host_status) { volatile unsigned* hs = a.host_status; hs[1] = failed; hs[0] = sweeps; }
+	}
+}
+
+// U = Q W for a dense W (NP x NP, ld NP, zero padded: svd_r_f64_kernel's): apply_f64_kernel's structure -- 32-row blocks per wave on a
+// persistent grid; av, lane (li, lq) holds Q[row0 + li][4 kb + lq] for every layout (AROW: q is row-major, load_rows_rm; QROW: u is); the operand
+// swap for a row-major result -- with all 4 NT k-blocks in every output tile.  The 4 NT^2 operands of W (lane (li, lq) of operand
+// (jt, kb) holds W[4 kb + lq][16 jt + li]) would take 128 VGPRs at NT = 4, so they are staged in LDS once per workgroup, in operand
+// order: operand (jt, kb) is 64 consecutive doubles, lane l reads element l -- one conflict-free 8-byte read feeds the MFMAs of both
+// 16-row tiles.  Output tile jt is stored as soon as its KB products are summed: the registers are av (2 KB doubles) and two accumulators.
+// Every entry of U is the accumulator plus the four products of k-blocks 0 .. KB - 1 in that order, the factors exchanged by the swap
+// (IEEE multiplication is commutative): the same bits for all four layout pairs.
+// In place (u == q, the same layout and leading dimension) is safe for apply_f64_kernel's reason: a wave loads all n columns of its 32
+// rows before it stores any of them, and no two waves share a row.  Nothing at a row >= m or at a column between n and the leading
+// dimension is read or written.
+template <int NT, bool AROW, bool QROW>
+__global__ __launch_bounds__(256) void applyd_f64_kernel(double* u, size_t ldu, const double* q, size_t ldq, size_t m, int n,
+                                                         const double* __restrict__ w, size_t nblocks) {
+	constexpr int NP = 16 * NT, KB = 4 * NT;
+	__shared__ double wl[NT * KB * 64];
+	for (int e = threadIdx.x; e < NT * KB * 64; e += 256) {
+		const int l = e & 63, b = e >> 6, jt = b / KB, kb = b % KB;
+		wl[e] = w[(size_t)(16 * jt + (l & 15)) * NP + 4 * kb + (l >> 4)];
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & 63, li = lane & 15, lq = lane >> 4;
+	const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (size_t)gridDim.x * 4;
+	for (size_t blk = gw; blk < nblocks; blk += nw) {
+		const size_t row0 = blk * 32;
+		double av[2][KB];
+#pragma unroll
+		for (int rt = 0; rt < 2; rt++) {
+			const size_t row = row0 + 16 * rt + li;
+			if constexpr (AROW) load_rows_rm<KB>(av[rt], q, ldq, row, row < m, n, lq);
+			else {
+#pragma unroll
+				for (int kb = 0; kb < KB; kb++) {
+					const int col = 4 * kb + lq;
+					av[rt][kb] = (row < m && col < n) ? q[(size_t)col * ldq + row] : 0.0;
+				}
+			}
+		}
+#pragma unroll
+		for (int jt = 0; jt < NT; jt++) {
+			f64x4 acc[2] = {f64x4{0.0, 0.0, 0.0, 0.0}, f64x4{0.0, 0.0, 0.0, 0.0}};
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) {
+				const double wop = wl[(jt * KB + kb) * 64 + lane];
+#pragma unroll
+				for (int rt = 0; rt < 2; rt++) {
+					if constexpr (QROW) acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt][kb], wop, acc[rt], 0, 0, 0);
+					else acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(wop, av[rt][kb], acc[rt], 0, 0, 0);
+				}
+			}
+#pragma unroll
+			for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+				for (int reg = 0; reg < 4; reg++) {
+					if constexpr (QROW) {
+						const size_t row = row0 + 16 * rt + lq + 4 * reg;
+						const int col = 16 * jt + li;
+						if (row < m && col < n) u[row * ldu + col] = acc[rt][reg];
+					} else {
+						const size_t row = row0 + 16 * rt + li;
+						const int col = 16 * jt + lq + 4 * reg;
+						if (row < m && col < n) u[(size_t)col * ldu + row] = acc[rt][reg];
+					}
+				}
+		}
+	}
 }
 
 }  // namespace tsqrmi

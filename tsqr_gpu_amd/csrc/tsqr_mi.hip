@@ -2771,6 +2771,105 @@ int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, dou
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The SVD entry (tsqr_mi_svd_f64, n <= 64): the ladder of tsqr_mi_qr_f64_lay (jobu = 1: Q into u, R into wq[F64S_R]) or of
+// tsqr_mi_r_f64_lay (jobu = 0), called as they stand; then svd_r_f64_kernel on R (s, V, and W into wq[F64S_W]) and, for jobu = 1,
+// U = Q W in place (applyd_f64_kernel), enqueued back to back with one wait at the end.  The sweep count and the convergence word of the
+// Jacobi kernel arrive in the thread's pinned verdict words, which the ladder has finished with when it returns.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+thread_local int t_jacobi64 = 0;
+// The columns of R^T rotate (svd_r_f64_kernel's transpose = 1): W is the product of the rotations and V the normalised columns.  Drmac's
+// observation: the lower triangle converges in far fewer sweeps (measured, n = 64: cond 1e6 9 sweeps against 18, cond 1e12 9 against 25:
+// profiles/fp64_svd_accuracy.md).
+constexpr int F64S_TRANSPOSE = 1;
+
+// R of a jobu = 0 call.  The work space of the R-only entry, whose sizes that call keeps, has no block that outlives a sweep of its
+// ladder, so R lives in 32 KiB of device memory the library owns per host thread and device, allocated at the first such call.
+struct OwnSvdR {
+	double* p[MAX_DEV] = {};
+	~OwnSvdR() { for (double* d : p) if (d) (void)hipFree(d); }
+	double* get(int dev) {
+		if (!p[dev] && hipMalloc(reinterpret_cast<void**>(&p[dev]), 4096 * sizeof(double)) != hipSuccess) { p[dev] = nullptr; (void)hipGetLastError(); }
+		return p[dev];
+	}
+};
+thread_local OwnSvdR t_svd_r;
+
+// U = Q W in place on a persistent grid, as f64_apply launches Q = A Z: the resident count is that of the instantiation launched
+template <int NT, bool AROW, bool QROW>
+int f64_applyd(hipStream_t st, int dev, double* u, size_t ldu, const double* q, size_t ldq, size_t m, size_t n, const double* w) {
+	static DevOnce once;
+	static std::atomic<int> resident[MAX_DEV];
+	if (once.need(dev)) {
+		resident[dev].store(f64_applyd_resident<NT, AROW, QROW>(dev));
+		once.done(dev);
+	}
+	f64_applyd_launch<NT, AROW, QROW>(st, f64_apply_wgs(cdiv(m, 32), (size_t)resident[dev].load()), u, ldu, q, ldq, m, (int)n, w);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+int svd_f64_core(int a_layout, int u_layout, int jobu, int reorth, double* u, size_t ldu, double* s, double* v, size_t ldv,
+                 double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, void* stream) {
+	const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+	const int dev = cur_device();
+	double* r = jobu ? wq + F64S_R : t_svd_r.get(dev);
+	if (!r) { t_last_error = "tsqr_mi_svd_f64: could not allocate the device block that holds R"; return -(int)hipErrorOutOfMemory; }
+	const int rc = jobu ? tsqr_mi_qr_f64_lay(a_layout, u_layout, reorth, u, ldu, r, 64, a, lda, m, n, wq, wr, stream)
+	                    : tsqr_mi_r_f64_lay(a_layout, reorth, r, 64, a, lda, m, n, wq, wr, stream);
+	if (rc) return rc;                                   // (state 3 included: the SVD kernel does not run)
+	volatile unsigned* words = t_own64.host;             // (the ladder allocated them and has read its verdicts: the stream is idle)
+	words[0] = 0u; words[1] = 1u;                        // (a kernel that never reported reads as not converged)
+	tsqrmi::SvdArgs64 sa{};
+	sa.r = r; sa.ldr = 64; sa.s = s; sa.v = v; sa.ldv = ldv; sa.n = (int)n; sa.transpose = F64S_TRANSPOSE;
+	sa.w = jobu ? wq + F64S_W : nullptr;
+	sa.status = jobu ? reinterpret_cast<unsigned*>(wq + F64S_STATUS) : nullptr;
+	sa.host_status = t_own64.dev;
+	f64_svd_r_launch(st, sa);
+	HIPCHK(hipGetLastError());
+	if (jobu) {
+		const int ra = with_apply(n, u_layout, u_layout, [&](auto nt, auto ar, auto qr) {
+			return f64_applyd<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(st, dev, u, ldu, u, ldu, m, n, wq + F64S_W);
+		});
+		if (ra) return ra;
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	t_jacobi64 = (int)words[0];
+	if (words[1] != 0u) {
+		t_last_error = "tsqr_mi_svd_f64: the Jacobi iteration reached its cap of 30 sweeps";
+		return TSQR_MI_ERROR_NO_CONVERGENCE;
+	}
+	return TSQR_MI_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tsqr_mi_working_q_size_f64_svd(size_t m, size_t n, int jobu) {
+	return jobu ? ((m == 0 || n == 0) ? 0 : F64S_WQ) : tsqr_mi_working_q_size_f64_r(m, n);
+}
+size_t tsqr_mi_working_r_size_f64_svd(size_t m, size_t n, int jobu) {
+	return jobu ? tsqr_mi_working_r_size_f64(m, n) : tsqr_mi_working_r_size_f64_r(m, n);
+}
+int tsqr_mi_last_jacobi_sweeps_f64(void) { return t_jacobi64; }
+
+int tsqr_mi_svd_f64(int a_layout, int u_layout, int jobu, int reorth, double* u, size_t ldu, double* s, double* v, size_t ldv,
+                    double* a, size_t lda, size_t m, size_t n, void* wq, void* wr, void* stream) {
+	t_jacobi64 = 0;
+	t_sweeps64 = 0;
+	if (jobu != 0 && jobu != 1) return TSQR_MI_ERROR_INVALID_SIZE;
+	const F64Operand A{a_layout, m, n, lda}, U{jobu ? u_layout : TSQR_MI_COL_MAJOR, m, n, jobu ? ldu : m}, V{TSQR_MI_COL_MAJOR, n, n, v ? ldv : n};
+	if (const int rc = f64_prologue({A, U, V}, m, n, PW, "tsqr_mi_svd_f64 supports n <= 64")) return rc;
+	if (jobu && u == a && (a_layout != u_layout || ldu != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
+	return svd_f64_core(a_layout, u_layout, jobu, reorth, u, ldu, s, v, ldv, a, lda, m, n, reinterpret_cast<double*>(wq),
+	                    reinterpret_cast<double*>(wr), stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // The wide fp64 entry (tsqr_mi_qr_f64_wide): n <= 64 is tsqr_mi_qr_f64 itself; 64 < n <= 1024 runs the same ladder (qr_f64_core) with
 // whole-matrix sweeps on nb = ceil(n / 64) column blocks (f64w_sweep, beside f64_sweep above; kernels and block storage:
 // tsqr_f64_wide.hip).
