@@ -380,6 +380,34 @@ inline state_t svd_fp64(
 	return st;
 }
 
+// Not in the reference: a P = q r with column pivoting in double precision, 1 <= n <= m, n <= 64 (tsqr_mi_qrcp_f64, include/tsqr_mi.h for
+// the contract): the ladder of qr_fp64 into q, a Householder QR with column pivoting of R on one workgroup, q <- q H.  r (n x n,
+// column-major, ldr) takes R, diag(R) >= 0 and non-increasing; jpvt takes n 0-based pivots (device memory): column j of a P is column
+// jpvt[j] of a.  ComputeQ = false: q_ptr is ignored, a is read only and the work space is that of r_fp64.  a_layout, q_layout as for
+// qr_fp64 (in place, q_ptr == a_ptr, needs equal layouts and ldq == lda).  Returns the states of qr_fp64.
+template <bool Reorthogonalize, bool ComputeQ = true>
+struct buffer_fp64_qrcp : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n) {
+		allocate_doubles(tsqr_mi_working_q_size_f64_qrcp(m, n, ComputeQ ? 1 : 0), tsqr_mi_working_r_size_f64_qrcp(m, n, ComputeQ ? 1 : 0));
+	}
+};
+
+template <bool Reorthogonalize, bool ComputeQ = true>
+inline state_t qrcp_fp64(
+		double* const q_ptr, const std::size_t ldq,
+		double* const r_ptr, const std::size_t ldr,
+		int* const jpvt_ptr,
+		double* const a_ptr, const std::size_t lda,
+		const std::size_t m, const std::size_t n,
+		buffer_fp64_qrcp<Reorthogonalize, ComputeQ>& bf,
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major, const layout_t q_layout = col_major) {
+	const int st = tsqr_mi_qrcp_f64(a_layout, q_layout, ComputeQ ? 1 : 0, Reorthogonalize ? 1 : 0, q_ptr, ldq, r_ptr, ldr, jpvt_ptr, a_ptr, lda, m, n,
+	                                bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::qrcp_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
+
 // Not in the reference: the R factor of qr_fp64 alone, Q never formed (tsqr_mi_r_f64, include/tsqr_mi.h for the contract): a is read
 // only, no m x n work space.  Returns the states of qr_fp64.
 template <bool Reorthogonalize>

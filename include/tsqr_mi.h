@@ -491,6 +491,44 @@ int tsqr_mi_svd_f64(int a_layout, int u_layout, int jobu, int reorth,
 int tsqr_mi_last_jacobi_sweeps_f64(void);
 
 /*
+ * QR with column pivoting of a tall-skinny matrix in double precision (not in the reference): A P = Q R, 1 <= n <= 64, n <= m --
+ * what LAPACK's dgeqp3 and scipy.linalg.qr(pivoting=True, mode="economic") return.  a (m x n, lda, a_layout) and q (m x n, ldq,
+ * q_layout) as the operands of tsqr_mi_qr_f64_lay; r: n x n column-major with leading dimension ldr, upper triangular with exact
+ * zeros below the diagonal, diag(R) >= 0 and non-increasing, and R_kk^2 >= sum_{i=k..j} R_ij^2 for every j > k up to rounding (the
+ * Businger-Golub property); jpvt: n int values on the device, 0-based: column j of A P is column jpvt[j] of A.  Blocking.  Bitwise
+ * deterministic from call to call.
+ * Method: QR, a small pivoted QR of R, then a product.  A = Q0 R0 by the ladder, R0 into r; R0 P = H R on one workgroup in place on r
+ * (qrcp_r_f64_kernel, tsqr_f64.hip: Householder reflectors built as dlarfg builds them on R0 scaled by a power of two to
+ * max |r_ij| in [1, 2); at every step the squared norms of the remaining part of every remaining column are summed afresh, never
+ * downdated; the pivot is the largest, the lowest index on a tie; a column that is exactly zero gives H_k = I and R_kk = 0 without a
+ * division; a negative R_kk is made positive by negating row k of R and column k of H, which is exact).  n steps, no iteration, no
+ * state of its own.
+ *   jobq = 1  the ladder of tsqr_mi_qr_f64_lay, called as it stands (reorth as there), writes Q0 into q; then Q = Q0 H in place on
+ *             the fp64 matrix cores (applyd_f64_kernel).  q == a is allowed as there: one layout and ldq == lda; A is untouched
+ *             otherwise.  Work space: that entry's plus a block that does not depend on m -- wq of
+ *             tsqr_mi_working_q_size_f64(m, n) + 4104 doubles (H and status words), wr of tsqr_mi_working_r_size_f64(m, n) doubles.
+ *   jobq = 0  q, ldq and q_layout are ignored and A is read only: the ladder of tsqr_mi_r_f64_lay -- no m x n buffer, exactly that
+ *             entry's work-space sizes, nothing allocated -- and R and jpvt from its R0; H is not formed.
+ * Band: the claims hold where those of tsqr_mi_qr_f64_lay do, cond(A) <= 1e12: ||Q^T Q - I||_F <= 1e-11 (1e-12 with reorth = 1) up to
+ * the orthogonality of H (a few n 2^-53), ||A P - Q R||_F / ||A||_F <= 1e-13.  Outside it the call returns what the ladder returns,
+ * and diag(R) is then evidence of the same standing as s of tsqr_mi_svd_f64: state 3 is the ladder's verdict and no rank test, and a
+ * matrix with an exactly copied column is accepted by the ladder on its shifted path (as documented for tsqr_mi_lstsq_f64) -- R0 is
+ * then the factor of a perturbed matrix and the trailing diagonal of R is small but carries no bound.
+ * Returns the states of those entries in their order -- 1 for a layout other than 0 or 1 (a_layout; q_layout with jobq = 1), for n > m,
+ * m == 0, n == 0, a leading dimension below its operand's extent, a jobq other than 0 or 1, or q == a with different layouts or
+ * leading dimensions; 2 for n > 64 -- all before any HIP call; 3 = TSQR_MI_ERROR_NOT_FINITE from the ladder, before the pivoting kernel
+ * runs (r, jpvt and q are then undefined; jpvt is not written); or -(hipError_t).  tsqr_mi_last_sweeps_f64 reports the ladder of this
+ * entry too.  The pointers r, jpvt, a (and q with jobq = 1) and the work space are not checked: they must be valid device memory.
+ * Not provided: n > 64, the row-partitioned and batched forms, the m x m Q, and a rank-aware least-squares solve on top of it.
+ */
+size_t tsqr_mi_working_q_size_f64_qrcp(size_t m, size_t n, int jobq);
+size_t tsqr_mi_working_r_size_f64_qrcp(size_t m, size_t n, int jobq);
+int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth,
+                     double* q, size_t ldq, double* r, size_t ldr, int* jpvt,
+                     double* a, size_t lda, size_t m, size_t n,
+                     void* wq, void* wr, void* stream);
+
+/*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
  * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
  * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column

@@ -1,0 +1,80 @@
+"""SHA-256 (first 16 hex digits) of the results of the fp64 entries that take a tensor -- qr_f64_tensor, qr_f64_wide_tensor, lstsq_f64
+(3 right-hand sides), svd_f64_tensor with and without U -- at 9211 x 51, 2^20 x 64, 100 x 7 and 65536 x 128, torch.randn with seed
+m + n generated on the device, handed over row-major ("row") and with column-major strides ("col"), reorth 0 and 1.  The entries are
+bitwise deterministic, so two builds of libtsqr_mi.so that are meant to compute the same thing must print the same table:
+
+  python tools/f64_checksums.py --parent-lib PATH    PATH: another build of libtsqr_mi.so (the parent commit's)
+
+runs the table once with PATH (through TSQR_MI_LIB) and once with the in-tree library, in two fresh processes, prints every line with
+== or != and exits 2 when a line differs.  Without --parent-lib it prints the in-tree table alone.  profiles/fp64_qrcp_parent_checksums.md
+was printed by this tool."""
+import argparse
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SHAPES = ((9211, 51), (1 << 20, 64), (100, 7), (65536, 128))
+
+
+def table():
+    import torch
+    from tsqr_gpu_amd import blockqr as bq
+    sha = lambda t: hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
+    out = {}
+    for m, n in SHAPES:
+        g = torch.Generator(device="cuda").manual_seed(m + n)
+        a = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g)
+        b = torch.randn(m, 3, dtype=torch.float64, device="cuda", generator=g)
+        for reorth in (False, True):
+            for name, x in (("row", a), ("col", a.t().contiguous().t())):
+                key = "%dx%d r%d %s " % (m, n, reorth, name)
+                q, r = bq.qr_f64_wide_tensor(x, reorth=reorth)
+                out[key + "qr_wide"] = (sha(q), sha(r), bq.last_sweeps_f64())
+                if n <= 64:
+                    q, r = bq.qr_f64_tensor(x, reorth=reorth)
+                    out[key + "qr"] = (sha(q), sha(r), bq.last_sweeps_f64())
+                    xs, r = bq.lstsq_f64(x, b, reorth=reorth)
+                    out[key + "lstsq"] = (sha(xs), sha(r), bq.last_sweeps_f64())
+                    u, s, vh = bq.svd_f64_tensor(x, reorth=reorth)
+                    out[key + "svd1"] = (sha(u), sha(s), sha(vh), bq.last_jacobi_sweeps_f64())
+                    out[key + "svd0"] = (sha(bq.svd_f64_tensor(x, reorth=reorth, compute_uv=False)),)
+    return out
+
+
+def table_in_child(lib):
+    """the table of a fresh process that loads lib ('' the in-tree library), as lists"""
+    env = dict(os.environ)
+    env.pop("TSQR_MI_LIB", None)
+    if lib:
+        env["TSQR_MI_LIB"] = os.path.abspath(lib)
+    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError("the run with %s failed (%d): %s" % (lib or "the in-tree library", res.returncode, res.stderr[-2000:]))
+    return json.loads([line for line in res.stdout.splitlines() if line.startswith("CHECKSUMS ")][0][10:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", default="", help="another build of libtsqr_mi.so to compare the in-tree one against")
+    ap.add_argument("--child", action="store_true", help="print the table of this process's library as one JSON line (used by the tool itself)")
+    args = ap.parse_args()
+    if args.child:
+        print("CHECKSUMS " + json.dumps(table(), sort_keys=True))
+        return 0
+    tree = table_in_child("")
+    parent = table_in_child(args.parent_lib) if args.parent_lib else None
+    for key in sorted(tree):
+        mark = "" if parent is None else (" ==" if parent.get(key) == tree[key] else " != %s" % (parent.get(key),))
+        print(key, tree[key], mark.strip())
+    if parent is None:
+        return 0
+    print("entries:", len(tree), "all equal:", parent == tree)
+    return 0 if parent == tree else 2
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -37,7 +37,13 @@ on the same operands in this process; per arm the median of --calls blocking cal
 svd - qr (what the Jacobi kernel and the dense apply add), and torch.linalg.svd(float64, full_matrices=False) and
 torch.linalg.svdvals on the same matrix (median of three; --no-torch skips them).  Writes the JSON to --svd-out (default
 profiles/fp64_svd_speed.json) and prints it.  --svd-arms svd_jobu1 runs that arm alone and writes no file: the run to put under a
-kernel trace for the per-kernel split (profiles/fp64_svd_kernel_stats_2p20x64.csv)."""
+kernel trace for the per-kernel split (profiles/fp64_svd_kernel_stats_2p20x64.csv).
+--qrcp: instead, the pivoted QR entry (tsqr_mi_qrcp_f64, reorth = 0, column-major Gaussian operands) at the shapes of --svd (--cases
+picks some): six arms interleaved call by call on the same operands in this process -- jobq = 1, tsqr_mi_qr_f64_lay, jobq = 0,
+tsqr_mi_r_f64_lay, tsqr_mi_svd_f64 with jobu = 0 and with jobu = 1; per arm the median of --calls blocking calls, the ladder sweeps, what
+the pivoting kernel and the dense apply add to the entry under them, and the ratio jobq = 0 / svd jobu = 0: the two answers to "what is
+the numerical rank".  Writes the JSON to --qrcp-out (default profiles/fp64_qrcp_speed.json) and prints it.  --qrcp-arms qrcp_jobq1
+runs that arm alone and writes no file: the run to put under a kernel trace (profiles/fp64_qrcp_kernel_stats_2p20x64.csv)."""
 import argparse
 import json
 import math
@@ -613,6 +619,83 @@ def svd(torch, bq, calls, warmup, only, no_torch, only_arms=()):
     return out
 
 
+def qrcp(torch, bq, calls, warmup, only, only_arms=()):
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    out = {"tool": "f64_speed --qrcp", "calls": calls, "warmup": warmup, "reorth": 0, "layout": "column-major", "cases": []}
+    for lg, n in SVD_SHAPES:
+        if only and "2p%dx%d" % (lg, n) not in only:
+            continue
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a_rm = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g)
+        a = a_rm.t().contiguous()                           # (n, m): column-major m x n
+        q = [torch.empty_like(a) for _ in range(3)]         # Q of jobq = 1, of the QR entry, U of the SVD
+        r = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(4)]
+        jp = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2)]
+        s = torch.empty(n, dtype=torch.float64, device="cuda")
+        v = torch.empty(n, n, dtype=torch.float64, device="cuda")
+        stream = vp(torch.cuda.current_stream().cuda_stream)
+        work = {}
+        for key, fq, fr, extra in (("qrcp1", L.tsqr_mi_working_q_size_f64_qrcp, L.tsqr_mi_working_r_size_f64_qrcp, (1,)),
+                                   ("qrcp0", L.tsqr_mi_working_q_size_f64_qrcp, L.tsqr_mi_working_r_size_f64_qrcp, (0,)),
+                                   ("svd1", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (1,)),
+                                   ("svd0", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (0,)),
+                                   ("qr", L.tsqr_mi_working_q_size_f64, L.tsqr_mi_working_r_size_f64, ()),
+                                   ("r", L.tsqr_mi_working_q_size_f64_r, L.tsqr_mi_working_r_size_f64_r, ())):
+            wq = torch.empty(fq(m, n, *extra), dtype=torch.float64, device="cuda")
+            wr = torch.empty(fr(m, n, *extra), dtype=torch.float64, device="cuda")
+            work[key] = (wq, wr, (vp(wq.data_ptr()), vp(wr.data_ptr()), stream))
+        ap_ = vp(a.data_ptr())
+        arms = [("qrcp_jobq1", lambda: L.tsqr_mi_qrcp_f64(0, 0, 1, 0, vp(q[0].data_ptr()), m, vp(r[0].data_ptr()), n, vp(jp[0].data_ptr()),
+                                                          ap_, m, m, n, *work["qrcp1"][2])),
+                ("qr_f64_lay", lambda: L.tsqr_mi_qr_f64_lay(0, 0, 0, vp(q[1].data_ptr()), m, vp(r[1].data_ptr()), n, ap_, m, m, n, *work["qr"][2])),
+                ("qrcp_jobq0", lambda: L.tsqr_mi_qrcp_f64(0, 0, 0, 0, None, m, vp(r[2].data_ptr()), n, vp(jp[1].data_ptr()),
+                                                          ap_, m, m, n, *work["qrcp0"][2])),
+                ("r_f64_lay", lambda: L.tsqr_mi_r_f64_lay(0, 0, vp(r[3].data_ptr()), n, ap_, m, m, n, *work["r"][2])),
+                ("svd_jobu0", lambda: L.tsqr_mi_svd_f64(0, 0, 0, 0, None, m, vp(s.data_ptr()), vp(v.data_ptr()), n, ap_, m, m, n, *work["svd0"][2])),
+                ("svd_jobu1", lambda: L.tsqr_mi_svd_f64(0, 0, 1, 0, vp(q[2].data_ptr()), m, vp(s.data_ptr()), vp(v.data_ptr()), n,
+                                                        ap_, m, m, n, *work["svd1"][2]))]
+        if only_arms:
+            arms = [arm for arm in arms if arm[0] in only_arms]
+        ts = {name: [] for name, _ in arms}
+        for i in range(warmup + calls):
+            for name, fn in arms:
+                t0 = time.perf_counter()
+                rc = fn()                                   # (blocking: returns when the stream has drained)
+                dt = time.perf_counter() - t0
+                assert rc == 0, (name, rc, bq.last_error())
+                if i >= warmup:
+                    ts[name].append(dt)
+        med = {k: sorted(x)[len(x) // 2] * 1e3 for k, x in ts.items()}
+        if only_arms:                                       # (a run under a kernel trace: the medians of the chosen arms, nothing else)
+            out["cases"].append({"m": m, "n": n, "median_ms": med})
+            continue
+        sweeps = {}
+        for name, fn in arms:
+            fn()
+            sweeps[name] = L.tsqr_mi_last_sweeps_f64()
+        qm, p = q[0].t(), jp[0].long()
+        orth = torch.linalg.norm(qm.T @ qm - torch.eye(n, dtype=torch.float64, device="cuda")).item()
+        res = (torch.linalg.norm(a_rm[:, p] - qm @ r[0].t()) / torch.linalg.norm(a_rm)).item()
+        d = torch.diagonal(r[0])
+        case = {"m": m, "n": n}
+        case.update({name + "_median_ms": med[name] for name, _ in arms})
+        case.update({"jobq1_minus_qr_ms": med["qrcp_jobq1"] - med["qr_f64_lay"], "jobq0_minus_r_ms": med["qrcp_jobq0"] - med["r_f64_lay"],
+                     "jobq0_over_svd_jobu0": med["qrcp_jobq0"] / med["svd_jobu0"], "jobq1_over_svd_jobu1": med["qrcp_jobq1"] / med["svd_jobu1"],
+                     "ladder_sweeps": sweeps["qrcp_jobq1"], "ladder_sweeps_jobq0": sweeps["qrcp_jobq0"],
+                     "r_and_jpvt_bitwise_equal_jobq0_jobq1": bool(torch.equal(r[0], r[2]) and torch.equal(jp[0], jp[1])),
+                     "diag_nonincreasing": bool((d[1:] <= d[:-1]).all().item() and (d >= 0).all().item()),
+                     "orth_fro": orth, "residual": res,
+                     "checksum_q_qr_f64_lay": float(q[1].sum().item()), "checksum_r_qr_f64_lay": float(r[1].sum().item()),
+                     "checksum_r_r_f64_lay": float(r[3].sum().item()), "checksum_s_svd": float(s.sum().item())})
+        out["cases"].append(case)
+        del a_rm, a, q, r, jp, s, v, work
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=None, help="blocking calls per case or arm (default 50; --wide-row-major: 20)")
@@ -630,6 +713,9 @@ def main():
     ap.add_argument("--svd", action="store_true", help="time tsqr_mi_svd_f64 (jobu 1 and 0) next to tsqr_mi_qr_f64_lay, tsqr_mi_r_f64_lay and torch.linalg.svd")
     ap.add_argument("--svd-arms", default="", help="--svd: run only these arms (svd_jobu1, qr_f64_lay, svd_jobu0, r_f64_lay) and write no file: for a kernel trace")
     ap.add_argument("--svd-out", default=os.path.join(ROOT, "profiles", "fp64_svd_speed.json"), help="--svd: the JSON file ('' writes none)")
+    ap.add_argument("--qrcp", action="store_true", help="time tsqr_mi_qrcp_f64 (jobq 1 and 0) next to tsqr_mi_qr_f64_lay, tsqr_mi_r_f64_lay and tsqr_mi_svd_f64")
+    ap.add_argument("--qrcp-arms", default="", help="--qrcp: run only these arms (qrcp_jobq1, qr_f64_lay, qrcp_jobq0, r_f64_lay, svd_jobu0, svd_jobu1) and write no file")
+    ap.add_argument("--qrcp-out", default=os.path.join(ROOT, "profiles", "fp64_qrcp_speed.json"), help="--qrcp: the JSON file ('' writes none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp64_wide_rowmajor_speed.json"), help="--wide-row-major: the JSON file")
     args = ap.parse_args()
     wide_rm = args.wide_row_major or args.wide_col_only
@@ -651,6 +737,14 @@ def main():
         out = svd(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], args.no_torch, only_arms)
         if args.svd_out and not only_arms:
             with open(args.svd_out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        print(json.dumps(out))
+        return
+    if args.qrcp:
+        only_arms = [c for c in args.qrcp_arms.split(",") if c]
+        out = qrcp(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], only_arms)
+        if args.qrcp_out and not only_arms:
+            with open(args.qrcp_out, "w") as f:
                 f.write(json.dumps(out, indent=1) + "\n")
         print(json.dumps(out))
         return

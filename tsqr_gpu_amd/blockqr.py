@@ -120,6 +120,9 @@ def _c_signatures():
         # (a_layout, u_layout, jobu, reorth, u, ldu, s, v, ldv, a, lda, m, n, wq, wr, stream)
         "tsqr_mi_svd_f64": (ci, [ci, ci, ci, ci, vp, sz, vp, vp, sz, vp, sz, sz, sz, vp, vp, vp]),
         "tsqr_mi_last_jacobi_sweeps_f64": (ci, []),
+        "tsqr_mi_working_q_size_f64_qrcp": (sz, [sz, sz, ci]), "tsqr_mi_working_r_size_f64_qrcp": (sz, [sz, sz, ci]),
+        # (a_layout, q_layout, jobq, reorth, q, ldq, r, ldr, jpvt, a, lda, m, n, wq, wr, stream)
+        "tsqr_mi_qrcp_f64": (ci, [ci, ci, ci, ci, vp, sz, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp]),
     }
 
 
@@ -131,7 +134,8 @@ OPTIONAL_SYMBOLS = {
     "tsqr_mi_r_f64", "tsqr_mi_working_q_size_f64_r", "tsqr_mi_working_r_size_f64_r",
     "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
     "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay",
-    "tsqr_mi_working_q_size_f64_svd", "tsqr_mi_working_r_size_f64_svd", "tsqr_mi_svd_f64", "tsqr_mi_last_jacobi_sweeps_f64"}
+    "tsqr_mi_working_q_size_f64_svd", "tsqr_mi_working_r_size_f64_svd", "tsqr_mi_svd_f64", "tsqr_mi_last_jacobi_sweeps_f64",
+    "tsqr_mi_working_q_size_f64_qrcp", "tsqr_mi_working_r_size_f64_qrcp", "tsqr_mi_qrcp_f64"}
 
 _lib = None
 
@@ -423,6 +427,7 @@ _F64_WIDE = _F64Entry("qr_f64_wide", 1024, "tsqr_mi_qr_f64_wide", "_f64_wide")
 _F64_R = _F64Entry("r_f64", 64, "tsqr_mi_r_f64", "_f64_r")
 _F64_LSTSQ = _F64Entry("lstsq_f64", 64, "tsqr_mi_lstsq_f64", "_f64_lstsq")
 _F64_SVD = _F64Entry("svd_f64", 64, "tsqr_mi_svd_f64", "_f64_svd")       # (its size functions take jobu behind m and n)
+_F64_QRCP = _F64Entry("qrcp_f64", 64, "tsqr_mi_qrcp_f64", "_f64_qrcp")   # (jobq behind m and n)
 
 
 def _null_state(fn, *scalars):
@@ -853,6 +858,137 @@ def svd_f64_tensor(a, reorth=False, compute_uv=True, overwrite_a=False, stream=N
     if st:
         raise SvdError(st, "%s: state %d: %s" % (name, st, last_error()))
     return (u, s, v) if jobu else s
+
+
+class QrcpError(RuntimeError):
+    """qrcp_f64_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
+
+    def __init__(self, state, text):
+        RuntimeError.__init__(self, text)
+        self.state = state
+
+
+class buffer_f64_qrcp(buffer_f64):
+    """Work space of qrcp_f64 (tsqr_mi_working_{q,r}_size_f64_qrcp doubles on the GPU).  compute_q: the jobq the space is sized for --
+    True: the QR entry's space and the block for H; False: the R-only entry's (no m x n part; it does not serve a call with compute_q).
+    reorthogonalize as in buffer_f64."""
+    _entry = _F64_QRCP
+
+    def __init__(self, reorthogonalize=False, device="cuda", compute_q=True):
+        buffer_f64.__init__(self, reorthogonalize, device)
+        self.compute_q = bool(compute_q)
+
+    def allocate(self, m, n):
+        import torch
+        if self.dwq is not None or self.dwr is not None:
+            raise RuntimeError("The buffer has been already allocated")
+        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device)
+                              for size in self._entry.sizes(m, n, int(self.compute_q)))
+
+
+def check_f64_qrcp_operands(m, n, ldq, ldr, lda, q, r, jpvt, a, row_major=False):
+    """The size and overlap rules of qrcp_f64 on (address, elements) pairs (q may be None: not used): check_f64_operands' rules for q
+    and a (row_major: both row-major), r n x n column-major with ldr >= n, jpvt of n 4-byte elements; q either the very operand a
+    (same address and ld: in place) or apart from it; r and jpvt apart from q, from a and from each other.  Raises ValueError."""
+    ops = [("a", a, lda, m, n, row_major), ("r", r, ldr, n, n, False)]
+    if q is not None:
+        ops.append(("q", q, ldq, m, n, row_major))
+    span = dict(zip((o[0] for o in ops), _f64_spans("qrcp_f64", ops)))
+    if jpvt[1] < n:
+        raise ValueError("qrcp_f64: jpvt holds %d elements, %d pivots need %d" % (jpvt[1], n, n))
+    span["jpvt"] = (jpvt[0], jpvt[0] + 4 * n)
+    names = list(span)
+    for i, x in enumerate(names):
+        for y in names[i + 1:]:
+            if {x, y} == {"a", "q"} and q[0] == a[0] and ldq == lda:
+                continue                                   # (in place)
+            if span[x][0] < span[y][1] and span[y][0] < span[x][1]:
+                raise ValueError("qrcp_f64: %s overlaps %s%s" % (x, y, " without being a (in place needs q == a and ldq == lda)"
+                                                                  if {x, y} == {"a", "q"} else ""))
+
+
+def _check_jpvt(who, jpvt):
+    import torch
+    if not isinstance(jpvt, torch.Tensor) or jpvt.dtype != torch.int32:
+        raise TypeError("%s: jpvt must be an int32 tensor, got %s" % (who, getattr(jpvt, "dtype", type(jpvt).__name__)))
+    if not jpvt.is_cuda:
+        raise TypeError("%s: jpvt is not a GPU tensor" % who)
+
+
+def qrcp_f64(q, ldq, r, ldr, jpvt, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False, compute_q=True):
+    """Double-precision tall-skinny QR with column pivoting (tsqr_mi_qrcp_f64), a P = q r, 1 <= n <= 64, n <= m: q, r, a are float64 GPU
+    tensors and jpvt an int32 GPU tensor (only data_ptr and numel are used); a and q hold column-major data, or ROW-major data with
+    row_major=True (element (i, j) at i * ld + j, ld >= n) as in qr_f64; r (n x n, column-major, ldr) takes R -- upper triangular,
+    diag(R) >= 0 and non-increasing; jpvt takes n 0-based pivots: column j of a P is column jpvt[j] of a.  compute_q=False (jobq = 0):
+    q is not used (None is fine), a is read only, and bf must have been made with compute_q=False or True -- the larger space serves
+    both.  q may be a itself (in place, ldq == lda).  bf is a buffer_f64_qrcp.  Blocking; returns the state: 0,
+    error_invalid_matrix_size, error_unsupported_mode (n > 64) or error_not_finite (the ladder's verdict; no rank test -- the rank is
+    read off diag(R)).  Operands are checked before anything is launched: TypeError for a wrong dtype or a CPU tensor, ValueError for a
+    short tensor, a short leading dimension or overlapping operands.  last_sweeps_f64() tells how many sweeps the ladder took."""
+    entry = _F64_QRCP
+    fn = lib().tsqr_mi_qrcp_f64
+    jobq = 1 if compute_q else 0
+    layout = ROW_MAJOR if row_major else COL_MAJOR
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    _check_f64_tensors(entry.name, [("r", r), ("a", a)] + ([("q", q)] if jobq else []))
+    _check_jpvt(entry.name, jpvt)
+    if n > m or m == 0 or n == 0:
+        return error_invalid_matrix_size
+    if n > entry.nmax:
+        return _null_state(fn, layout, layout, jobq, int(reorth), ldq, ldr, lda, m, n)
+    pair = lambda t: (t.data_ptr(), t.numel())
+    check_f64_qrcp_operands(m, n, ldq, ldr, lda, pair(q) if jobq else None, pair(r), pair(jpvt), pair(a), row_major=bool(row_major))
+    if bf.dwq is None:
+        raise RuntimeError("qrcp_f64: the buffer is not allocated")
+    need = entry.sizes(m, n, jobq)
+    if bf.dwq.numel() < need[0] or bf.dwr.numel() < need[1]:
+        raise ValueError("qrcp_f64: the buffer was allocated for a smaller matrix (or without compute_q)")
+    return _f64_call(entry.symbol, fn, stream, layout, layout, jobq, int(reorth), q.data_ptr() if jobq else None, ldq, r.data_ptr(), ldr,
+                     jpvt.data_ptr(), a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr())
+
+
+def qrcp_f64_tensor(a, reorth=False, compute_q=True, overwrite_a=False, stream=None):
+    """(q, r, p) of the double-precision tall-skinny QR with column pivoting (tsqr_mi_qrcp_f64: include/tsqr_mi.h has the method and the
+    band) of a two-dimensional float64 GPU tensor a, m x n with 1 <= n <= 64, n <= m, any strides: the shapes of
+    scipy.linalg.qr(a, mode="economic", pivoting=True) -- q m x n, r n x n upper triangular with diag(r) >= 0 and non-increasing, p an
+    int64 tensor of n pivots with a[:, p] = q @ r.  compute_q=False returns (r, p) (jobq = 0: Q is never formed and a is only read).
+    a is read where it lies when its columns or its rows are contiguous (_operand_f64's rule, as for qr_f64_tensor) and copied once
+    into column-major storage otherwise; q has a's layout, and q, r and p have the same bits whichever way a is stored.
+    overwrite_a=True: when a is used where it lies, q IS a.  reorth: the ladder's argument (qr_f64).  The work space is allocated per
+    call.  Blocking.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for a tensor that is not two-dimensional, QrcpError
+    (.state) when the C entry returns a state other than 0: sizes it does not support, or error_not_finite from the ladder (Inf or NaN
+    in a, a zero column).  That state is no rank test: the numerical rank is read off diag(r)."""
+    import torch
+    entry = _F64_QRCP
+    name = entry.name + "_tensor"
+    _check_f64_tensors(name, (("a", a),))
+    if a.dim() != 2:
+        raise ValueError("%s: a must be m x n, got %s" % (name, tuple(a.shape)))
+    m, n = a.shape
+    fn = lib().tsqr_mi_qrcp_f64
+    jobq = 1 if compute_q else 0
+    if m == 0 or n == 0 or n > m or n > entry.nmax:
+        st = _null_state(fn, COL_MAJOR, COL_MAJOR, jobq, int(bool(reorth)), max(m, 1), max(n, 1), max(m, 1), m, n)
+        raise QrcpError(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
+    ac, lda, layout = _operand_f64(a)
+    q, ldq = None, lda
+    if jobq:
+        if overwrite_a and ac.data_ptr() == a.data_ptr():
+            q = a                                              # (in place: the same layout and leading dimension)
+        elif layout == ROW_MAJOR:
+            q, ldq = torch.empty((m, n), dtype=torch.float64, device=a.device), n
+        else:
+            q, ldq = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+    r = torch.empty((n, n), dtype=torch.float64, device=a.device)
+    jpvt = torch.empty(n, dtype=torch.int32, device=a.device)
+    wq, wr = entry.work_space(a.device, m, n, jobq)
+    with torch.cuda.device(a.device):
+        st = _f64_call(entry.symbol, fn, stream, layout, layout, jobq, int(bool(reorth)), q.data_ptr() if jobq else None, ldq,
+                       r.data_ptr(), n, jpvt.data_ptr(), ac.data_ptr(), lda, m, n, wq.data_ptr(), wr.data_ptr())
+    if st:
+        raise QrcpError(st, "%s: state %d: %s" % (name, st, last_error()))
+    p = jpvt.to(torch.int64)
+    return (q, r.t(), p) if jobq else (r.t(), p)
 
 
 def get_working_q_size_f64_dist(m_local, n, nranks):

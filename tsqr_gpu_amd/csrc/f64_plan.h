@@ -160,6 +160,18 @@ inline void f64_applyd_launch(hipStream_t st, size_t wgs, double* u, size_t ldu,
 	hipLaunchKernelGGL((tsqrmi::applyd_f64_kernel<NT, AROW, QROW>), dim3((unsigned)wgs), dim3(256), 0, st, u, ldu, q, ldq, m, n, w, cdiv(m, 32));
 }
 
+// ---- tsqr_mi_qrcp_f64 (n <= 64) -----------------------------------------------------------------------------------------------------------
+// jobq = 1 runs the ladder of tsqr_mi_qr_f64_lay on the F64_WQ layout with R0 in the caller's r, then qrcp_r_f64_kernel in place on r
+// and applyd_f64_kernel.  wq (doubles): [the F64_WQ layout][H, NP x NP with ld NP: 4096][status words: 8]
+constexpr size_t F64P_H = F64_WQ, F64P_STATUS = F64P_H + 4096, F64P_WQ = F64P_STATUS + 8;
+constexpr size_t F64P_BLOCK = F64P_WQ - F64_WQ;         // what jobq = 1 adds to the QR entry's wq; wr is the QR entry's
+// jobq = 0 runs the ladder of tsqr_mi_r_f64_lay on that entry's work space, unchanged in size (F64R_WQ, f64r_wr_doubles); H is not formed.
+
+// qrcp_r_f64_kernel on stream st: one workgroup
+inline void f64_qrcp_r_launch(hipStream_t st, const tsqrmi::QrcpArgs64& pa) {
+	hipLaunchKernelGGL(tsqrmi::qrcp_r_f64_kernel, dim3(1), dim3(1024), 0, st, pa);
+}
+
 // ---- tsqr_mi_qr_f64_wide (64 < n <= 1024) ----------------------------------------------------------------------------------------------
 constexpr size_t F64W_MAX_N = 1024;
 constexpr size_t F64W_WR_CAP = size_t(8) << 20;         // doubles of Gram partials at most, for every m

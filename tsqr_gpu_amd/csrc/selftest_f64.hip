@@ -245,6 +245,17 @@ int tsqr_selftest_f64_applyd_lay(int q_layout, int u_layout, double* u, size_t l
 	});
 }
 
+// ---- n <= 64, pivoted QR (tsqr_mi_qrcp_f64) -------------------------------------------------------------------------------------------------
+// qrcp_r_f64_kernel through the product's launcher: r0 (n x n upper triangular, ldr0) in; r (n x n, ldr; may be r0 with ldr == ldr0),
+// jpvt[n], h (NP x NP, ld NP; may be null: not formed) and status[2] (steps, exactly zero pivot columns; may be null) out.
+int tsqr_selftest_f64_qrcp_r(const double* r0, size_t ldr0, double* r, size_t ldr, int* jpvt, double* h, unsigned* status, int n) {
+	if (n <= 0 || n > (int)PW || ldr0 < (size_t)n || ldr < (size_t)n || !r0 || !r || !jpvt || (r == r0 && ldr != ldr0)) return -100;
+	tsqrmi::QrcpArgs64 pa{};
+	pa.r0 = r0; pa.ldr0 = ldr0; pa.r = r; pa.ldr = ldr; pa.jpvt = jpvt; pa.h = h; pa.status = status; pa.n = n;
+	f64_qrcp_r_launch(0, pa);
+	return f64_sync();
+}
+
 // ---- 64 < n <= 1024 ---------------------------------------------------------------------------------------------------------------------
 // The Gram and apply entries come in two forms, like those of n <= 64 above: _lay takes a layout per operand (0 column-major; 1
 // row-major, the leading dimension is then the row stride, >= n) and goes through the launchers the product uses (f64_plan.h); the plain

@@ -15,6 +15,8 @@
 // and of the SVD entry (tsqr_mi_svd_f64), behind the ladder of either entry above:
 //   svd_r_f64_kernel  : R = W diag(s) V^T by one-sided Jacobi on one workgroup, R held in LDS
 //   applyd_f64_kernel : U = Q W on v_mfma_f64_16x16x4_f64 for a dense W staged in LDS, in place allowed
+// and of the pivoted QR entry (tsqr_mi_qrcp_f64), behind the same ladders and in front of applyd_f64_kernel:
+//   qrcp_r_f64_kernel : R0 P = H R by Householder QR with column pivoting on one workgroup, R0 and H^T held in LDS
 // The four passes that read A (and B) take the layout of each operand as a template flag (AROW, BROW: tsqr_mi_r_f64_lay,
 // tsqr_mi_lstsq_f64_lay, tsqr_mi_qr_f64_lay).  Element (i, j) of a row-major operand lies at s[i * ld + j], ld >= the column count.  A
 // row-major kernel is the column-major one with another address for the same register: at every MFMA lane (li, lq) of k-block kb holds
@@ -672,6 +674,141 @@ __global__ __launch_bounds__(256) void applyd_f64_kernel(double* u, size_t ldu, 
 				}
 		}
 	}
+}
+
+// ---- the pivoted QR entry (tsqr_mi_qrcp_f64): R0 P = H R on one workgroup, then Q = Q0 H (applyd_f64_kernel) ------------------------------
+struct QrcpArgs64 {
+	const double* r0; size_t ldr0;       // n x n upper triangular in (only i <= j is read)
+	double* r; size_t ldr;               // n x n out: R, exact zeros below the diagonal; may be r0 itself (ldr == ldr0)
+	int* jpvt;                           // n pivots out, 0-based: column j of R0 P is column jpvt[j] of R0
+	double* h;                           // NP x NP (ld NP) out, zero padded, chol_f64_kernel's layout of Z; null: not wanted, not formed
+	unsigned* status;                    // device words [0] steps taken (n), [1] steps whose pivot column was exactly zero; null: not wanted
+	int n;
+};
+
+// Householder QR with column pivoting (Businger-Golub) of the n x n factor R0, n <= 64, held in LDS: M = R0 and G = I, 64 x 64
+// column-major each; lane i of a wave holds row i of a column.  M is first scaled by the power of two that brings max |r_ij| into
+// [1, 2) -- exact, R is scaled back at the end -- so that no square leaves the range for any R0 the ladder accepts, and 2^k R0 gives the
+// bits of H and jpvt.  Step k = 0 .. n - 1, two barriers each:
+//   pivot      nrm[j] = sum_{i >= k} m_ij^2 of every column j >= k, summed AFRESH from the entries as they stand (by the wave that last
+//              wrote the column; never downdated, so dlaqp2's cancellation safeguard has nothing to guard); p = the largest, the lowest
+//              index on a tie, found by every wave for itself from the same 64 numbers;
+//   swap       whole columns k and p, the finished rows above k included, and the two entries of jpvt.  No copy: every wave reads
+//              x = column p and y = column k before the barrier, and behind it column k is written from x and position p from y;
+//   reflector  of x over rows k .. n - 1 as dlarfg builds it: alpha = x_k, s = sum_{i > k} x_i^2; s == 0: H_k = I (a zero column gives
+//              R_kk = 0, nothing is divided); else beta = -sign(alpha) sqrt(alpha^2 + s), tau = (beta - alpha) / beta,
+//              v = (1, x_{k+1..} / (alpha - beta)) -- every wave computes the same bits, every sum goes through wave_sum_f64;
+//   apply      c <- c - tau v (v^T c) to the trailing columns of M and to all n columns of G, which so accumulates H^T by the same
+//              column operation; the columns are dealt round-robin to the 16 waves, those of M first;
+//   sign       beta < 0: row k of M and of G is negated (exact), so diag(R) >= 0.
+// At the end R = M, H = G^T (transposed through M in a rotated image: no bank conflict).  No data-dependent iteration; everything is a fixed function of the input: two runs give the same bits.
+// h == null (the R-only form): G is neither updated nor written.  Nothing is written to global memory before the end; r may be r0.
+// No scratch; 66.4 KB of LDS.
+__global__ __launch_bounds__(1024) void qrcp_r_f64_kernel(const QrcpArgs64 a) {
+	__shared__ double M[64 * 64], G[64 * 64];
+	__shared__ double nrm[64], wmax[16];
+	__shared__ int piv[64];
+	const int t = threadIdx.x, lane = t & 63, wv = t >> 6, n = a.n;
+	const int NP = 16 * ((n + 15) / 16);
+	double x0[4], mx = 0.0;
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		x0[u] = (i <= j && j < n) ? a.r0[(size_t)j * a.ldr0 + i] : 0.0;
+		mx = fmax(mx, fabs(x0[u]));
+	}
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+	if (lane == 0) wmax[wv] = mx;
+	__syncthreads();
+#pragma unroll
+	for (int k = 0; k < 16; k++) mx = fmax(mx, wmax[k]);
+	const int ex = (mx > 0.0 && mx < INFINITY) ? ilogb(mx) : 0;     // 2^ex <= max |r_ij| < 2^(ex + 1)
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		M[e] = scalbn(x0[u], -ex);
+		G[e] = (i == j && j < n) ? 1.0 : 0.0;
+	}
+	if (t < 64) piv[t] = t;
+	__syncthreads();
+	for (int j = wv; j < n; j += 16) {
+		const double c = M[j * 64 + lane];
+		const double s = wave_sum_f64(c * c);
+		if (lane == 0) nrm[j] = s;
+	}
+	__syncthreads();
+	unsigned zero_cols = 0;
+	for (int k = 0; k < n; k++) {
+		double bv = (lane >= k && lane < n) ? nrm[lane] : -1.0;
+		int bi = lane;
+#pragma unroll
+		for (int o = 32; o >= 1; o >>= 1) {
+			const double ov = __shfl_xor(bv, o, 64);
+			const int oi = __shfl_xor(bi, o, 64);
+			if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+		}
+		int p = __shfl(bi, 0, 64);
+		if (p < k || p >= n) p = k;                          // (only a NaN among the norms gets here: stay inside the matrix)
+		const double x = M[p * 64 + lane], y = M[k * 64 + lane];
+		const int jp = piv[p], jk = piv[k];
+		__syncthreads();                                     // every wave holds the pivot, x and y: M, nrm and piv may be written
+		if (t == 0) { piv[k] = jp; piv[p] = jk; }
+		const double xr = (lane > k && lane < n) ? x : 0.0;
+		const double alpha = __shfl(x, k, 64);
+		const double s2 = wave_sum_f64(xr * xr);
+		double tau = 0.0, beta = alpha, v = 0.0;
+		if (s2 > 0.0) {
+			beta = -copysign(sqrt(alpha * alpha + s2), alpha);
+			tau = (beta - alpha) / beta;
+			v = xr / (alpha - beta);
+		} else if (alpha == 0.0) zero_cols++;
+		if (lane == k) v = 1.0;
+		const bool flip = beta < 0.0;
+		const int ntrail = n - k - 1, ntask = ntrail + (a.h ? n : 0);
+		for (int q = wv; q < ntask; q += 16) {
+			const bool ism = q < ntrail;                     // (uniform over the wave)
+			const int j = ism ? k + 1 + q : q - ntrail;
+			double* col = (ism ? M : G) + j * 64;
+			double c = (ism && j == p) ? y : col[lane];
+			if (tau != 0.0) {
+				const double d = wave_sum_f64(v * c);        // (v is zero above row k and from row n on)
+				if (lane >= k) c -= (tau * d) * v;
+			}
+			if (flip && lane == k) c = -c;
+			col[lane] = c;
+			if (ism) {
+				const double cr = lane > k ? c : 0.0;
+				const double s = wave_sum_f64(cr * cr);
+				if (lane == 0) nrm[j] = s;
+			}
+		}
+		if (wv == (ntask & 15)) M[k * 64 + lane] = lane < k ? x : (lane == k ? fabs(beta) : 0.0);
+		__syncthreads();
+	}
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		if (i < n && j < n) a.r[(size_t)j * a.ldr + i] = i <= j ? scalbn(M[e], ex) : 0.0;
+	}
+	if (a.h) {                                               // (uniform over the workgroup)
+		// H = G^T through M, which is free now: G(i, j) goes to row i of a row-major image whose rows are rotated by their index, so that
+		// both the write (lane = i) and the read of a column of H (lane = i, row j of the image) touch 64 different addresses mod 64
+		__syncthreads();
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			M[i * 64 + ((j + i) & 63)] = G[e];
+		}
+		__syncthreads();
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			if (i < NP && j < NP) a.h[(size_t)j * NP + i] = (i < n && j < n) ? M[j * 64 + ((i + j) & 63)] : 0.0;
+		}
+	}
+	if (t < n) a.jpvt[t] = piv[t];
+	if (t == 0 && a.status) { a.status[0] = (unsigned)n; a.status[1] = zero_cols; }
 }
 
 }  // namespace tsqrmi

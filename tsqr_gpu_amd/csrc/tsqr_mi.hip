@@ -2870,6 +2870,62 @@ int tsqr_mi_svd_f64(int a_layout, int u_layout, int jobu, int reorth, double* u,
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The pivoted QR entry (tsqr_mi_qrcp_f64, n <= 64): the ladder of tsqr_mi_qr_f64_lay (jobq = 1: Q0 into q) or of tsqr_mi_r_f64_lay
+// (jobq = 0), called as they stand with R0 into the caller's r; then qrcp_r_f64_kernel factors R0 P = H R in place on r (jpvt; H into
+// wq[F64P_H] for jobq = 1, not formed otherwise) and, for jobq = 1, Q = Q0 H in place (f64_applyd).  The ladder call blocks -- it reads
+// its verdict words -- so the stream is idle when the two kernels are enqueued, back to back, with one more wait behind them: two waits
+// per call at least.  Nothing is allocated; the kernel has no verdict of its own.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int qrcp_f64_core(int a_layout, int q_layout, int jobq, int reorth, double* q, size_t ldq, double* r, size_t ldr, int* jpvt,
+                  double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, void* stream) {
+	const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+	const int rc = jobq ? tsqr_mi_qr_f64_lay(a_layout, q_layout, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream)
+	                    : tsqr_mi_r_f64_lay(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, stream);
+	if (rc) return rc;                                   // (state 3 included: the pivoting kernel does not run)
+	tsqrmi::QrcpArgs64 pa{};
+	pa.r0 = r; pa.ldr0 = ldr; pa.r = r; pa.ldr = ldr; pa.jpvt = jpvt; pa.n = (int)n;
+	pa.h = jobq ? wq + F64P_H : nullptr;
+	pa.status = jobq ? reinterpret_cast<unsigned*>(wq + F64P_STATUS) : nullptr;
+	f64_qrcp_r_launch(st, pa);
+	HIPCHK(hipGetLastError());
+	if (jobq) {
+		const int dev = cur_device();
+		const int ra = with_apply(n, q_layout, q_layout, [&](auto nt, auto ar, auto qr) {
+			return f64_applyd<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(st, dev, q, ldq, q, ldq, m, n, wq + F64P_H);
+		});
+		if (ra) return ra;
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	return TSQR_MI_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tsqr_mi_working_q_size_f64_qrcp(size_t m, size_t n, int jobq) {
+	return jobq ? ((m == 0 || n == 0) ? 0 : F64P_WQ) : tsqr_mi_working_q_size_f64_r(m, n);
+}
+size_t tsqr_mi_working_r_size_f64_qrcp(size_t m, size_t n, int jobq) {
+	return jobq ? tsqr_mi_working_r_size_f64(m, n) : tsqr_mi_working_r_size_f64_r(m, n);
+}
+
+int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth, double* q, size_t ldq, double* r, size_t ldr, int* jpvt,
+                     double* a, size_t lda, size_t m, size_t n, void* wq, void* wr, void* stream) {
+	t_sweeps64 = 0;
+	if (jobq != 0 && jobq != 1) return TSQR_MI_ERROR_INVALID_SIZE;
+	const F64Operand A{a_layout, m, n, lda}, Q{jobq ? q_layout : TSQR_MI_COL_MAJOR, m, n, jobq ? ldq : m}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
+	if (const int rc = f64_prologue({A, Q, R}, m, n, PW, "tsqr_mi_qrcp_f64 supports n <= 64")) return rc;
+	if (jobq && q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
+	return qrcp_f64_core(a_layout, q_layout, jobq, reorth, q, ldq, r, ldr, jpvt, a, lda, m, n, reinterpret_cast<double*>(wq),
+	                     reinterpret_cast<double*>(wr), stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // The wide fp64 entry (tsqr_mi_qr_f64_wide): n <= 64 is tsqr_mi_qr_f64 itself; 64 < n <= 1024 runs the same ladder (qr_f64_core) with
 // whole-matrix sweeps on nb = ceil(n / 64) column blocks (f64w_sweep, beside f64_sweep above; kernels and block storage:
 // tsqr_f64_wide.hip).
