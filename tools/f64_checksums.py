@@ -1,6 +1,7 @@
 """SHA-256 (first 16 hex digits) of the results of the fp64 entries that take a tensor -- qr_f64_tensor, qr_f64_wide_tensor, lstsq_f64
-(3 right-hand sides), svd_f64_tensor with and without U -- at 9211 x 51, 2^20 x 64, 100 x 7 and 65536 x 128, torch.randn with seed
-m + n generated on the device, handed over row-major ("row") and with column-major strides ("col"), reorth 0 and 1.  The entries are
+(3 right-hand sides), svd_f64_tensor with and without U, qrcp_f64_tensor with and without Q -- at 9211 x 51, 2^20 x 64, 100 x 7 and
+65536 x 128, torch.randn with seed m + n generated on the device, handed over row-major ("row") and with column-major strides
+("col"), reorth 0 and 1; at 9211 x 51 also the three entries that can run in place, with overwrite_a=True on a clone.  The entries are
 bitwise deterministic, so two builds of libtsqr_mi.so that are meant to compute the same thing must print the same table:
 
   python tools/f64_checksums.py --parent-lib PATH    PATH: another build of libtsqr_mi.so (the parent commit's)
@@ -42,6 +43,20 @@ def table():
                     u, s, vh = bq.svd_f64_tensor(x, reorth=reorth)
                     out[key + "svd1"] = (sha(u), sha(s), sha(vh), bq.last_jacobi_sweeps_f64())
                     out[key + "svd0"] = (sha(bq.svd_f64_tensor(x, reorth=reorth, compute_uv=False)),)
+                    q, r, p = bq.qrcp_f64_tensor(x, reorth=reorth)
+                    out[key + "qrcp1"] = (sha(q), sha(r), sha(p), bq.last_sweeps_f64())
+                    r, p = bq.qrcp_f64_tensor(x, reorth=reorth, compute_q=False)
+                    out[key + "qrcp0"] = (sha(r), sha(p))
+                    if (m, n) == SHAPES[0]:                 # in place, on a clone (it keeps x's strides); the flag: q IS the clone
+                        c = x.clone()
+                        q, r = bq.qr_f64_tensor(c, reorth=reorth, overwrite_a=True)
+                        out[key + "qr overwrite_a"] = (sha(q), sha(r), q is c, bq.last_sweeps_f64())
+                        c = x.clone()
+                        u, s, vh = bq.svd_f64_tensor(c, reorth=reorth, overwrite_a=True)
+                        out[key + "svd1 overwrite_a"] = (sha(u), sha(s), sha(vh), u is c, bq.last_jacobi_sweeps_f64())
+                        c = x.clone()
+                        q, r, p = bq.qrcp_f64_tensor(c, reorth=reorth, overwrite_a=True)
+                        out[key + "qrcp1 overwrite_a"] = (sha(q), sha(r), sha(p), q is c, bq.last_sweeps_f64())
     return out
 
 

@@ -536,6 +536,47 @@ def dist1(torch, bq, calls, warmup):
 
 
 SVD_SHAPES = ((16, 64), (20, 64), (23, 64), (20, 16))
+# work spaces of the arms of --svd and --qrcp: key -> (suffix of the entry's two size functions, their arguments behind m and n)
+JOB_WORK = {"svd1": ("_svd", (1,)), "svd0": ("_svd", (0,)), "qrcp1": ("_qrcp", (1,)), "qrcp0": ("_qrcp", (0,)), "qr": ("", ()), "r": ("_r", ())}
+
+
+def job_work_spaces(torch, L, keys, m, n):
+    """{key: (wq, wr, (wq, wr, the current stream) as the three last arguments of a call)} for the keys of JOB_WORK"""
+    import ctypes
+    vp = ctypes.c_void_p
+    stream = vp(torch.cuda.current_stream().cuda_stream)
+    work = {}
+    for key in keys:
+        suffix, extra = JOB_WORK[key]
+        wq = torch.empty(getattr(L, "tsqr_mi_working_q_size_f64" + suffix)(m, n, *extra), dtype=torch.float64, device="cuda")
+        wr = torch.empty(getattr(L, "tsqr_mi_working_r_size_f64" + suffix)(m, n, *extra), dtype=torch.float64, device="cuda")
+        work[key] = (wq, wr, (vp(wq.data_ptr()), vp(wr.data_ptr()), stream))
+    return work
+
+
+def time_arms(bq, arms, calls, warmup, only_arms, read_sweeps):
+    """The (name, blocking call) arms interleaved, warmup + calls rounds; only_arms: these alone.  Returns (the arms run, {name: median
+    ms}, {name: read_sweeps() after one more call}) -- the last None under only_arms: a run under a kernel trace, which wants the
+    medians of the chosen arms and nothing else."""
+    if only_arms:
+        arms = [arm for arm in arms if arm[0] in only_arms]
+    ts = {name: [] for name, _ in arms}
+    for i in range(warmup + calls):
+        for name, fn in arms:
+            t0 = time.perf_counter()
+            rc = fn()                                       # (blocking: returns when the stream has drained)
+            dt = time.perf_counter() - t0
+            assert rc == 0, (name, rc, bq.last_error())
+            if i >= warmup:
+                ts[name].append(dt)
+    med = {k: sorted(x)[len(x) // 2] * 1e3 for k, x in ts.items()}
+    if only_arms:
+        return arms, med, None
+    sweeps = {}
+    for name, fn in arms:
+        fn()
+        sweeps[name] = read_sweeps()
+    return arms, med, sweeps
 
 
 def svd(torch, bq, calls, warmup, only, no_torch, only_arms=()):
@@ -554,15 +595,7 @@ def svd(torch, bq, calls, warmup, only, no_torch, only_arms=()):
         s = [torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(2)]
         v = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(2)]
         r = torch.empty(n, n, dtype=torch.float64, device="cuda")
-        stream = vp(torch.cuda.current_stream().cuda_stream)
-        work = {}
-        for key, fq, fr, extra in (("svd1", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (1,)),
-                                   ("svd0", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (0,)),
-                                   ("qr", L.tsqr_mi_working_q_size_f64, L.tsqr_mi_working_r_size_f64, ()),
-                                   ("r", L.tsqr_mi_working_q_size_f64_r, L.tsqr_mi_working_r_size_f64_r, ())):
-            wq = torch.empty(fq(m, n, *extra), dtype=torch.float64, device="cuda")
-            wr = torch.empty(fr(m, n, *extra), dtype=torch.float64, device="cuda")
-            work[key] = (wq, wr, (vp(wq.data_ptr()), vp(wr.data_ptr()), stream))
+        work = job_work_spaces(torch, L, ("svd1", "svd0", "qr", "r"), m, n)
         arms = [("svd_jobu1", lambda: L.tsqr_mi_svd_f64(0, 0, 1, 0, vp(u.data_ptr()), m, vp(s[1].data_ptr()), vp(v[1].data_ptr()), n,
                                                         vp(a.data_ptr()), m, m, n, *work["svd1"][2])),
                 ("qr_f64_lay", lambda: L.tsqr_mi_qr_f64_lay(0, 0, 0, vp(q.data_ptr()), m, vp(r.data_ptr()), n, vp(a.data_ptr()), m, m, n,
@@ -570,25 +603,11 @@ def svd(torch, bq, calls, warmup, only, no_torch, only_arms=()):
                 ("svd_jobu0", lambda: L.tsqr_mi_svd_f64(0, 0, 0, 0, None, m, vp(s[0].data_ptr()), vp(v[0].data_ptr()), n,
                                                         vp(a.data_ptr()), m, m, n, *work["svd0"][2])),
                 ("r_f64_lay", lambda: L.tsqr_mi_r_f64_lay(0, 0, vp(r.data_ptr()), n, vp(a.data_ptr()), m, m, n, *work["r"][2]))]
+        arms, med, sweeps = time_arms(bq, arms, calls, warmup, only_arms,
+                                      lambda: (L.tsqr_mi_last_sweeps_f64(), L.tsqr_mi_last_jacobi_sweeps_f64()))
         if only_arms:
-            arms = [arm for arm in arms if arm[0] in only_arms]
-        ts = {name: [] for name, _ in arms}
-        for i in range(warmup + calls):
-            for name, fn in arms:
-                t0 = time.perf_counter()
-                rc = fn()                                   # (blocking: returns when the stream has drained)
-                dt = time.perf_counter() - t0
-                assert rc == 0, (name, rc, bq.last_error())
-                if i >= warmup:
-                    ts[name].append(dt)
-        med = {k: sorted(x)[len(x) // 2] * 1e3 for k, x in ts.items()}
-        if only_arms:                                       # (a run under a kernel trace: the medians of the chosen arms, nothing else)
             out["cases"].append({"m": m, "n": n, "median_ms": med})
             continue
-        sweeps = {}
-        for name, fn in arms:
-            fn()
-            sweeps[name] = (L.tsqr_mi_last_sweeps_f64(), L.tsqr_mi_last_jacobi_sweeps_f64())
         um = u.t()
         orth = torch.linalg.norm(um.T @ um - torch.eye(n, dtype=torch.float64, device="cuda")).item()
         res = (torch.linalg.norm(a_rm - (um * s[1]) @ v[1]) / torch.linalg.norm(a_rm)).item()    # (v[1] read as a tensor is V^T)
@@ -636,17 +655,7 @@ def qrcp(torch, bq, calls, warmup, only, only_arms=()):
         jp = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2)]
         s = torch.empty(n, dtype=torch.float64, device="cuda")
         v = torch.empty(n, n, dtype=torch.float64, device="cuda")
-        stream = vp(torch.cuda.current_stream().cuda_stream)
-        work = {}
-        for key, fq, fr, extra in (("qrcp1", L.tsqr_mi_working_q_size_f64_qrcp, L.tsqr_mi_working_r_size_f64_qrcp, (1,)),
-                                   ("qrcp0", L.tsqr_mi_working_q_size_f64_qrcp, L.tsqr_mi_working_r_size_f64_qrcp, (0,)),
-                                   ("svd1", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (1,)),
-                                   ("svd0", L.tsqr_mi_working_q_size_f64_svd, L.tsqr_mi_working_r_size_f64_svd, (0,)),
-                                   ("qr", L.tsqr_mi_working_q_size_f64, L.tsqr_mi_working_r_size_f64, ()),
-                                   ("r", L.tsqr_mi_working_q_size_f64_r, L.tsqr_mi_working_r_size_f64_r, ())):
-            wq = torch.empty(fq(m, n, *extra), dtype=torch.float64, device="cuda")
-            wr = torch.empty(fr(m, n, *extra), dtype=torch.float64, device="cuda")
-            work[key] = (wq, wr, (vp(wq.data_ptr()), vp(wr.data_ptr()), stream))
+        work = job_work_spaces(torch, L, ("qrcp1", "qrcp0", "svd1", "svd0", "qr", "r"), m, n)
         ap_ = vp(a.data_ptr())
         arms = [("qrcp_jobq1", lambda: L.tsqr_mi_qrcp_f64(0, 0, 1, 0, vp(q[0].data_ptr()), m, vp(r[0].data_ptr()), n, vp(jp[0].data_ptr()),
                                                           ap_, m, m, n, *work["qrcp1"][2])),
@@ -657,25 +666,10 @@ def qrcp(torch, bq, calls, warmup, only, only_arms=()):
                 ("svd_jobu0", lambda: L.tsqr_mi_svd_f64(0, 0, 0, 0, None, m, vp(s.data_ptr()), vp(v.data_ptr()), n, ap_, m, m, n, *work["svd0"][2])),
                 ("svd_jobu1", lambda: L.tsqr_mi_svd_f64(0, 0, 1, 0, vp(q[2].data_ptr()), m, vp(s.data_ptr()), vp(v.data_ptr()), n,
                                                         ap_, m, m, n, *work["svd1"][2]))]
+        arms, med, sweeps = time_arms(bq, arms, calls, warmup, only_arms, L.tsqr_mi_last_sweeps_f64)
         if only_arms:
-            arms = [arm for arm in arms if arm[0] in only_arms]
-        ts = {name: [] for name, _ in arms}
-        for i in range(warmup + calls):
-            for name, fn in arms:
-                t0 = time.perf_counter()
-                rc = fn()                                   # (blocking: returns when the stream has drained)
-                dt = time.perf_counter() - t0
-                assert rc == 0, (name, rc, bq.last_error())
-                if i >= warmup:
-                    ts[name].append(dt)
-        med = {k: sorted(x)[len(x) // 2] * 1e3 for k, x in ts.items()}
-        if only_arms:                                       # (a run under a kernel trace: the medians of the chosen arms, nothing else)
             out["cases"].append({"m": m, "n": n, "median_ms": med})
             continue
-        sweeps = {}
-        for name, fn in arms:
-            fn()
-            sweeps[name] = L.tsqr_mi_last_sweeps_f64()
         qm, p = q[0].t(), jp[0].long()
         orth = torch.linalg.norm(qm.T @ qm - torch.eye(n, dtype=torch.float64, device="cuda")).item()
         res = (torch.linalg.norm(a_rm[:, p] - qm @ r[0].t()) / torch.linalg.norm(a_rm)).item()

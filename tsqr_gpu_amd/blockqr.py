@@ -408,13 +408,13 @@ class _F64Entry:
         L = _lib or lib()
         return getattr(L, self.wq_fn)(*dims), getattr(L, self.wr_fn)(*dims)
 
-    def check_buffer(self, bf, *dims):
-        """bf allocated, and for at least these dimensions"""
+    def check_buffer(self, bf, *dims, hint=""):
+        """bf allocated, and for at least these dimensions; hint: what else may have made it too small, appended to that message"""
         if bf.dwq is None:
             raise RuntimeError("%s: the buffer is not allocated" % self.name)
         L = _lib or lib()                              # (sizes() spelled out: this runs in every blocking call)
         if bf.dwq.numel() < getattr(L, self.wq_fn)(*dims) or bf.dwr.numel() < getattr(L, self.wr_fn)(*dims):
-            raise ValueError("%s: the buffer was allocated for a smaller matrix" % self.name)
+            raise ValueError("%s: the buffer was allocated for a smaller matrix%s" % (self.name, hint))
 
     def work_space(self, device, *dims):
         """(wq, wr) allocated for one call"""
@@ -472,11 +472,16 @@ class buffer_f64:
         self.device = device
         self.dwq = self.dwr = None
 
+    def _job(self):
+        """what the entry's size functions take behind m and n: the job flag of a buffer that is sized by one"""
+        return ()
+
     def allocate(self, m, n):
         import torch
         if self.dwq is not None or self.dwr is not None:
             raise RuntimeError("The buffer has been already allocated")
-        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device) for size in self._entry.sizes(m, n))
+        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device)
+                              for size in self._entry.sizes(m, n, *self._job()))
 
     def free(self):
         self.dwq = self.dwr = None
@@ -518,23 +523,35 @@ def check_f64_operands(m, n, ldq, ldr, lda, q, r, a, row_major=False):
             raise ValueError("qr_f64: r overlaps %s" % other)
 
 
+def _f64_run(entry, label, fn, head, tensors, lds, m, n, bf, stream, reorthogonalize, check, pointers, jpvt=None, job=(), hint=""):
+    """What a blocking entry on a buffer does, in the order that is its contract (qr_f64, qr_f64_wide, svd_f64, qrcp_f64): the reorth
+    default; every (name, tensor) of tensors a float64 GPU tensor (then jpvt an int32 one); the size state; the cap state, asked of fn
+    with every pointer null; check(), the entry's size and overlap rules; the buffer; the call.  head: fn's arguments in front of
+    reorth; lds: its leading dimensions in order; pointers(): its arguments between reorth and m, read only once the operands are
+    known to be tensors; job and hint: _F64Entry.check_buffer's."""
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    _check_f64_tensors(entry.name, tensors)
+    if jpvt is not None:
+        _check_jpvt(entry.name, jpvt)
+    if n > m or m == 0 or n == 0:
+        return error_invalid_matrix_size
+    if n > entry.nmax:
+        return _null_state(fn, *head, int(reorth), *lds, m, n)
+    check()
+    entry.check_buffer(bf, m, n, *job, hint=hint)
+    return _f64_call(label, fn, stream, *head, int(reorth), *pointers(), m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr())
+
+
 def _qr_f64(entry, q, ldq, r, ldr, a, lda, m, n, bf, stream, reorthogonalize, row_major=False):
     """The body of qr_f64 (entry _F64) and qr_f64_wide (_F64_WIDE).  row_major: the entry's _lay form (tsqr_mi_qr_f64_lay,
     tsqr_mi_qr_f64_wide_lay) with q and a row-major."""
     symbol = entry.symbol + "_lay" if row_major else entry.symbol
-    fn = getattr(lib(), symbol)
     head = (ROW_MAJOR, ROW_MAJOR) if row_major else ()       # (the layout form's two leading arguments)
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    _check_f64_tensors(entry.name, (("q", q), ("r", r), ("a", a)))
-    if n > m or m == 0 or n == 0:
-        return error_invalid_matrix_size
-    if n > entry.nmax:
-        return _null_state(fn, *head, int(reorth), ldq, ldr, lda, m, n)
-    check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()), (a.data_ptr(), a.numel()),
-                       row_major=bool(row_major))
-    entry.check_buffer(bf, m, n)
-    return _f64_call(symbol, fn, stream, *head, int(reorth), q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda, m, n,
-                     bf.dwq.data_ptr(), bf.dwr.data_ptr())
+    return _f64_run(entry, symbol, getattr(lib(), symbol), head, (("q", q), ("r", r), ("a", a)), (ldq, ldr, lda), m, n, bf, stream,
+                    reorthogonalize,
+                    lambda: check_f64_operands(m, n, ldq, ldr, lda, (q.data_ptr(), q.numel()), (r.data_ptr(), r.numel()),
+                                               (a.data_ptr(), a.numel()), row_major=bool(row_major)),
+                    lambda: (q.data_ptr(), ldq, r.data_ptr(), ldr, a.data_ptr(), lda))
 
 
 def qr_f64(q, ldq, r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False):
@@ -602,12 +619,16 @@ def r_f64(r, ldr, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major
                      bf.dwq.data_ptr(), bf.dwr.data_ptr())
 
 
-class LstsqError(RuntimeError):
-    """lstsq_f64 ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
+class _F64StateError(RuntimeError):
+    """A tensor-level fp64 entry ended with a non-zero state (.state); each entry raises its own subclass."""
 
     def __init__(self, state, text):
         RuntimeError.__init__(self, text)
         self.state = state
+
+
+class LstsqError(_F64StateError):
+    """lstsq_f64 ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
 
 
 def _columns_contiguous(t):
@@ -676,40 +697,58 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
     return (x[:, 0] if vector else x), r.t()
 
 
-class QrError(RuntimeError):
+class QrError(_F64StateError):
     """qr_f64_tensor or qr_f64_wide_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
 
-    def __init__(self, state, text):
-        RuntimeError.__init__(self, text)
-        self.state = state
 
-
-def _qr_f64_tensor(entry, a, reorth, overwrite_a, stream):
-    """The body of qr_f64_tensor (entry _F64) and qr_f64_wide_tensor (_F64_WIDE) on the entry's _lay form."""
-    import torch
-    name, symbol = entry.name + "_tensor", entry.symbol + "_lay"
+def _f64_tensor_operand(entry, symbol, error, a, reorth, job=()):
+    """How a tensor form (entry.name + "_tensor") starts: a a float64 GPU tensor (TypeError) with two dimensions (ValueError); a shape
+    the C entry `symbol` does not run raises error with the state that entry gives it, asked with every pointer null (job: its job
+    flag, behind the two layouts).  Returns (fn, m, n) and _operand_f64(a): the operand of the call, its leading dimension, its layout."""
+    name = entry.name + "_tensor"
     _check_f64_tensors(name, (("a", a),))
     if a.dim() != 2:
         raise ValueError("%s: a must be m x n, got %s" % (name, tuple(a.shape)))
     m, n = a.shape
     fn = getattr(lib(), symbol)
     if m == 0 or n == 0 or n > m or n > entry.nmax:
-        st = _null_state(fn, COL_MAJOR, COL_MAJOR, int(bool(reorth)), max(m, 1), max(n, 1), max(m, 1), m, n)
-        raise QrError(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
-    ac, lda, layout = _operand_f64(a)
+        st = _null_state(fn, COL_MAJOR, COL_MAJOR, *job, int(bool(reorth)), max(m, 1), max(n, 1), max(m, 1), m, n)
+        raise error(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
+    return (fn, m, n) + _operand_f64(a)
+
+
+def _f64_q_for(a, ac, lda, layout, overwrite_a):
+    """(q, ldq) for the m x n factor a tensor form returns beside a, of which it hands ac (ld lda, layout) to the call: a itself when
+    overwrite_a holds and a is used where it lies (in place: the same layout and leading dimension), a fresh tensor otherwise,
+    row-major for a row-major operand and with column-major strides for a column-major one."""
+    import torch
+    m, n = a.shape
     if overwrite_a and ac.data_ptr() == a.data_ptr():
-        q, ldq = a, lda                                    # (in place: the same layout and leading dimension)
-    elif layout == ROW_MAJOR:
-        q, ldq = torch.empty((m, n), dtype=torch.float64, device=a.device), n
-    else:
-        q, ldq = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+        return a, lda
+    if layout == ROW_MAJOR:
+        return torch.empty((m, n), dtype=torch.float64, device=a.device), n
+    return torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+
+
+def _f64_tensor_call(entry, label, error, a, fn, stream, *args):
+    """_f64_call on a's device; a state other than 0 raises error"""
+    import torch
+    with torch.cuda.device(a.device):
+        st = _f64_call(label, fn, stream, *args)
+    if st:
+        raise error(st, "%s_tensor: state %d: %s" % (entry.name, st, last_error()))
+
+
+def _qr_f64_tensor(entry, a, reorth, overwrite_a, stream):
+    """The body of qr_f64_tensor (entry _F64) and qr_f64_wide_tensor (_F64_WIDE) on the entry's _lay form."""
+    import torch
+    symbol = entry.symbol + "_lay"
+    fn, m, n, ac, lda, layout = _f64_tensor_operand(entry, symbol, QrError, a, reorth)
+    q, ldq = _f64_q_for(a, ac, lda, layout, overwrite_a)
     r = torch.empty((n, n), dtype=torch.float64, device=a.device)
     wq, wr = entry.work_space(a.device, m, n)
-    with torch.cuda.device(a.device):
-        st = _f64_call(symbol, fn, stream, layout, layout, int(bool(reorth)), q.data_ptr(), ldq, r.data_ptr(), n, ac.data_ptr(), lda, m, n,
-                       wq.data_ptr(), wr.data_ptr())
-    if st:
-        raise QrError(st, "%s: state %d: %s" % (name, st, last_error()))
+    _f64_tensor_call(entry, symbol, QrError, a, fn, stream, layout, layout, int(bool(reorth)), q.data_ptr(), ldq, r.data_ptr(), n,
+                     ac.data_ptr(), lda, m, n, wq.data_ptr(), wr.data_ptr())
     return q, r.t()
 
 
@@ -737,13 +776,22 @@ def qr_f64_wide_tensor(a, reorth=False, overwrite_a=False, stream=None):
     return _qr_f64_tensor(_F64_WIDE, a, reorth, overwrite_a, stream)
 
 
-class SvdError(RuntimeError):
+def _f64_apart(who, span, pair, in_place, rule):
+    """span: {name: (first byte, past the last)} in the order the operands are examined.  Every two of them apart, except the two of
+    `pair` when in_place holds (they are one operand); where those two overlap otherwise, the message ends with rule.  Raises
+    ValueError."""
+    names = list(span)
+    for i, x in enumerate(names):
+        for y in names[i + 1:]:
+            if {x, y} == pair and in_place:
+                continue
+            if span[x][0] < span[y][1] and span[y][0] < span[x][1]:
+                raise ValueError("%s: %s overlaps %s%s" % (who, x, y, rule if {x, y} == pair else ""))
+
+
+class SvdError(_F64StateError):
     """svd_f64_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode, error_not_finite or
     error_no_convergence)"""
-
-    def __init__(self, state, text):
-        RuntimeError.__init__(self, text)
-        self.state = state
 
 
 class buffer_f64_svd(buffer_f64):
@@ -756,12 +804,8 @@ class buffer_f64_svd(buffer_f64):
         buffer_f64.__init__(self, reorthogonalize, device)
         self.compute_u = bool(compute_u)
 
-    def allocate(self, m, n):
-        import torch
-        if self.dwq is not None or self.dwr is not None:
-            raise RuntimeError("The buffer has been already allocated")
-        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device)
-                              for size in self._entry.sizes(m, n, int(self.compute_u)))
+    def _job(self):
+        return (int(self.compute_u),)
 
 
 def check_f64_svd_operands(m, n, ldu, ldv, lda, u, s, v, a, row_major=False):
@@ -774,14 +818,8 @@ def check_f64_svd_operands(m, n, ldu, ldv, lda, u, s, v, a, row_major=False):
     if v is not None:
         ops.append(("v", v, ldv, n, n, False))
     span = dict(zip((o[0] for o in ops), _f64_spans("svd_f64", ops)))
-    names = list(span)
-    for i, x in enumerate(names):
-        for y in names[i + 1:]:
-            if {x, y} == {"a", "u"} and u[0] == a[0] and ldu == lda:
-                continue                                   # (in place)
-            if span[x][0] < span[y][1] and span[y][0] < span[x][1]:
-                raise ValueError("svd_f64: %s overlaps %s%s" % (x, y, " without being a (in place needs u == a and ldu == lda)"
-                                                                 if {x, y} == {"a", "u"} else ""))
+    _f64_apart("svd_f64", span, {"a", "u"}, u is not None and u[0] == a[0] and ldu == lda,
+               " without being a (in place needs u == a and ldu == lda)")
 
 
 def svd_f64(u, ldu, s, v, ldv, a, lda, m, n, bf, stream=None, reorthogonalize=None, row_major=False, compute_u=True):
@@ -796,26 +834,17 @@ def svd_f64(u, ldu, s, v, ldv, a, lda, m, n, bf, stream=None, reorthogonalize=No
     ladder took, last_jacobi_sweeps_f64() how many the Jacobi iteration took.  The signs of the columns of u and v are reproducible
     but not specified."""
     entry = _F64_SVD
-    fn = lib().tsqr_mi_svd_f64
     jobu = 1 if compute_u else 0
     layout = ROW_MAJOR if row_major else COL_MAJOR
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    operands = [("s", s), ("a", a)] + ([("u", u)] if jobu else []) + ([("v", v)] if v is not None else [])
-    _check_f64_tensors(entry.name, operands)
-    if n > m or m == 0 or n == 0:
-        return error_invalid_matrix_size
-    if n > entry.nmax:
-        return _null_state(fn, layout, layout, jobu, int(reorth), ldu, ldv, lda, m, n)
     pair = lambda t: (t.data_ptr(), t.numel())
-    check_f64_svd_operands(m, n, ldu, ldv, lda, pair(u) if jobu else None, pair(s), None if v is None else pair(v), pair(a),
-                           row_major=bool(row_major))
-    if bf.dwq is None:
-        raise RuntimeError("svd_f64: the buffer is not allocated")
-    need = entry.sizes(m, n, jobu)
-    if bf.dwq.numel() < need[0] or bf.dwr.numel() < need[1]:
-        raise ValueError("svd_f64: the buffer was allocated for a smaller matrix (or without compute_u)")
-    return _f64_call(entry.symbol, fn, stream, layout, layout, jobu, int(reorth), u.data_ptr() if jobu else None, ldu, s.data_ptr(),
-                     None if v is None else v.data_ptr(), ldv, a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr())
+    return _f64_run(entry, entry.symbol, lib().tsqr_mi_svd_f64, (layout, layout, jobu),
+                    [("s", s), ("a", a)] + ([("u", u)] if jobu else []) + ([("v", v)] if v is not None else []), (ldu, ldv, lda),
+                    m, n, bf, stream, reorthogonalize,
+                    lambda: check_f64_svd_operands(m, n, ldu, ldv, lda, pair(u) if jobu else None, pair(s),
+                                                   None if v is None else pair(v), pair(a), row_major=bool(row_major)),
+                    lambda: (u.data_ptr() if jobu else None, ldu, s.data_ptr(), None if v is None else v.data_ptr(), ldv,
+                             a.data_ptr(), lda),
+                    job=(jobu,), hint=" (or without compute_u)")
 
 
 def svd_f64_tensor(a, reorth=False, compute_uv=True, overwrite_a=False, stream=None):
@@ -830,42 +859,20 @@ def svd_f64_tensor(a, reorth=False, compute_uv=True, overwrite_a=False, stream=N
     than 0: sizes it does not support, error_not_finite from the ladder (Inf or NaN in a, a zero column), or error_no_convergence."""
     import torch
     entry = _F64_SVD
-    name = entry.name + "_tensor"
-    _check_f64_tensors(name, (("a", a),))
-    if a.dim() != 2:
-        raise ValueError("%s: a must be m x n, got %s" % (name, tuple(a.shape)))
-    m, n = a.shape
-    fn = lib().tsqr_mi_svd_f64
     jobu = 1 if compute_uv else 0
-    if m == 0 or n == 0 or n > m or n > entry.nmax:
-        st = _null_state(fn, COL_MAJOR, COL_MAJOR, jobu, int(bool(reorth)), max(m, 1), max(n, 1), max(m, 1), m, n)
-        raise SvdError(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
-    ac, lda, layout = _operand_f64(a)
-    u, ldu = None, lda
-    if jobu:
-        if overwrite_a and ac.data_ptr() == a.data_ptr():
-            u = a                                              # (in place: the same layout and leading dimension)
-        elif layout == ROW_MAJOR:
-            u, ldu = torch.empty((m, n), dtype=torch.float64, device=a.device), n
-        else:
-            u, ldu = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+    fn, m, n, ac, lda, layout = _f64_tensor_operand(entry, entry.symbol, SvdError, a, reorth, (jobu,))
+    u, ldu = _f64_q_for(a, ac, lda, layout, overwrite_a) if jobu else (None, lda)
     s = torch.empty(n, dtype=torch.float64, device=a.device)
     v = torch.empty((n, n), dtype=torch.float64, device=a.device) if jobu else None      # (column-major V: read as a tensor, it is Vh)
     wq, wr = entry.work_space(a.device, m, n, jobu)
-    with torch.cuda.device(a.device):
-        st = _f64_call(entry.symbol, fn, stream, layout, layout, jobu, int(bool(reorth)), u.data_ptr() if jobu else None, ldu,
-                       s.data_ptr(), v.data_ptr() if jobu else None, n, ac.data_ptr(), lda, m, n, wq.data_ptr(), wr.data_ptr())
-    if st:
-        raise SvdError(st, "%s: state %d: %s" % (name, st, last_error()))
+    _f64_tensor_call(entry, entry.symbol, SvdError, a, fn, stream, layout, layout, jobu, int(bool(reorth)),
+                     u.data_ptr() if jobu else None, ldu, s.data_ptr(), v.data_ptr() if jobu else None, n, ac.data_ptr(), lda, m, n,
+                     wq.data_ptr(), wr.data_ptr())
     return (u, s, v) if jobu else s
 
 
-class QrcpError(RuntimeError):
+class QrcpError(_F64StateError):
     """qrcp_f64_tensor ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
-
-    def __init__(self, state, text):
-        RuntimeError.__init__(self, text)
-        self.state = state
 
 
 class buffer_f64_qrcp(buffer_f64):
@@ -878,12 +885,8 @@ class buffer_f64_qrcp(buffer_f64):
         buffer_f64.__init__(self, reorthogonalize, device)
         self.compute_q = bool(compute_q)
 
-    def allocate(self, m, n):
-        import torch
-        if self.dwq is not None or self.dwr is not None:
-            raise RuntimeError("The buffer has been already allocated")
-        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device)
-                              for size in self._entry.sizes(m, n, int(self.compute_q)))
+    def _job(self):
+        return (int(self.compute_q),)
 
 
 def check_f64_qrcp_operands(m, n, ldq, ldr, lda, q, r, jpvt, a, row_major=False):
@@ -897,14 +900,8 @@ def check_f64_qrcp_operands(m, n, ldq, ldr, lda, q, r, jpvt, a, row_major=False)
     if jpvt[1] < n:
         raise ValueError("qrcp_f64: jpvt holds %d elements, %d pivots need %d" % (jpvt[1], n, n))
     span["jpvt"] = (jpvt[0], jpvt[0] + 4 * n)
-    names = list(span)
-    for i, x in enumerate(names):
-        for y in names[i + 1:]:
-            if {x, y} == {"a", "q"} and q[0] == a[0] and ldq == lda:
-                continue                                   # (in place)
-            if span[x][0] < span[y][1] and span[y][0] < span[x][1]:
-                raise ValueError("qrcp_f64: %s overlaps %s%s" % (x, y, " without being a (in place needs q == a and ldq == lda)"
-                                                                  if {x, y} == {"a", "q"} else ""))
+    _f64_apart("qrcp_f64", span, {"a", "q"}, q is not None and q[0] == a[0] and ldq == lda,
+               " without being a (in place needs q == a and ldq == lda)")
 
 
 def _check_jpvt(who, jpvt):
@@ -926,25 +923,15 @@ def qrcp_f64(q, ldq, r, ldr, jpvt, a, lda, m, n, bf, stream=None, reorthogonaliz
     read off diag(R)).  Operands are checked before anything is launched: TypeError for a wrong dtype or a CPU tensor, ValueError for a
     short tensor, a short leading dimension or overlapping operands.  last_sweeps_f64() tells how many sweeps the ladder took."""
     entry = _F64_QRCP
-    fn = lib().tsqr_mi_qrcp_f64
     jobq = 1 if compute_q else 0
     layout = ROW_MAJOR if row_major else COL_MAJOR
-    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
-    _check_f64_tensors(entry.name, [("r", r), ("a", a)] + ([("q", q)] if jobq else []))
-    _check_jpvt(entry.name, jpvt)
-    if n > m or m == 0 or n == 0:
-        return error_invalid_matrix_size
-    if n > entry.nmax:
-        return _null_state(fn, layout, layout, jobq, int(reorth), ldq, ldr, lda, m, n)
     pair = lambda t: (t.data_ptr(), t.numel())
-    check_f64_qrcp_operands(m, n, ldq, ldr, lda, pair(q) if jobq else None, pair(r), pair(jpvt), pair(a), row_major=bool(row_major))
-    if bf.dwq is None:
-        raise RuntimeError("qrcp_f64: the buffer is not allocated")
-    need = entry.sizes(m, n, jobq)
-    if bf.dwq.numel() < need[0] or bf.dwr.numel() < need[1]:
-        raise ValueError("qrcp_f64: the buffer was allocated for a smaller matrix (or without compute_q)")
-    return _f64_call(entry.symbol, fn, stream, layout, layout, jobq, int(reorth), q.data_ptr() if jobq else None, ldq, r.data_ptr(), ldr,
-                     jpvt.data_ptr(), a.data_ptr(), lda, m, n, bf.dwq.data_ptr(), bf.dwr.data_ptr())
+    return _f64_run(entry, entry.symbol, lib().tsqr_mi_qrcp_f64, (layout, layout, jobq),
+                    [("r", r), ("a", a)] + ([("q", q)] if jobq else []), (ldq, ldr, lda), m, n, bf, stream, reorthogonalize,
+                    lambda: check_f64_qrcp_operands(m, n, ldq, ldr, lda, pair(q) if jobq else None, pair(r), pair(jpvt), pair(a),
+                                                    row_major=bool(row_major)),
+                    lambda: (q.data_ptr() if jobq else None, ldq, r.data_ptr(), ldr, jpvt.data_ptr(), a.data_ptr(), lda),
+                    jpvt=jpvt, job=(jobq,), hint=" (or without compute_q)")
 
 
 def qrcp_f64_tensor(a, reorth=False, compute_q=True, overwrite_a=False, stream=None):
@@ -960,33 +947,15 @@ def qrcp_f64_tensor(a, reorth=False, compute_q=True, overwrite_a=False, stream=N
     in a, a zero column).  That state is no rank test: the numerical rank is read off diag(r)."""
     import torch
     entry = _F64_QRCP
-    name = entry.name + "_tensor"
-    _check_f64_tensors(name, (("a", a),))
-    if a.dim() != 2:
-        raise ValueError("%s: a must be m x n, got %s" % (name, tuple(a.shape)))
-    m, n = a.shape
-    fn = lib().tsqr_mi_qrcp_f64
     jobq = 1 if compute_q else 0
-    if m == 0 or n == 0 or n > m or n > entry.nmax:
-        st = _null_state(fn, COL_MAJOR, COL_MAJOR, jobq, int(bool(reorth)), max(m, 1), max(n, 1), max(m, 1), m, n)
-        raise QrcpError(st, "%s: state %d for a %d x %d%s" % (name, st, m, n, (": " + last_error()) if st == error_unsupported_mode else ""))
-    ac, lda, layout = _operand_f64(a)
-    q, ldq = None, lda
-    if jobq:
-        if overwrite_a and ac.data_ptr() == a.data_ptr():
-            q = a                                              # (in place: the same layout and leading dimension)
-        elif layout == ROW_MAJOR:
-            q, ldq = torch.empty((m, n), dtype=torch.float64, device=a.device), n
-        else:
-            q, ldq = torch.empty((n, m), dtype=torch.float64, device=a.device).t(), m
+    fn, m, n, ac, lda, layout = _f64_tensor_operand(entry, entry.symbol, QrcpError, a, reorth, (jobq,))
+    q, ldq = _f64_q_for(a, ac, lda, layout, overwrite_a) if jobq else (None, lda)
     r = torch.empty((n, n), dtype=torch.float64, device=a.device)
     jpvt = torch.empty(n, dtype=torch.int32, device=a.device)
     wq, wr = entry.work_space(a.device, m, n, jobq)
-    with torch.cuda.device(a.device):
-        st = _f64_call(entry.symbol, fn, stream, layout, layout, jobq, int(bool(reorth)), q.data_ptr() if jobq else None, ldq,
-                       r.data_ptr(), n, jpvt.data_ptr(), ac.data_ptr(), lda, m, n, wq.data_ptr(), wr.data_ptr())
-    if st:
-        raise QrcpError(st, "%s: state %d: %s" % (name, st, last_error()))
+    _f64_tensor_call(entry, entry.symbol, QrcpError, a, fn, stream, layout, layout, jobq, int(bool(reorth)),
+                     q.data_ptr() if jobq else None, ldq, r.data_ptr(), n, jpvt.data_ptr(), ac.data_ptr(), lda, m, n,
+                     wq.data_ptr(), wr.data_ptr())
     p = jpvt.to(torch.int64)
     return (q, r.t(), p) if jobq else (r.t(), p)
 

@@ -2713,6 +2713,12 @@ static int f64_prologue(std::initializer_list<F64Operand> ops, size_t m, size_t 
 	return 0;
 }
 
+// The in-place rule of the entries that write a Q (state 1, behind f64_prologue): q that is a itself is one operand, so it has one
+// layout and one stride.
+static bool f64_in_place_broken(const void* q, int q_layout, size_t ldq, const void* a, int a_layout, size_t lda) {
+	return q == a && (a_layout != q_layout || ldq != lda);
+}
+
 int tsqr_mi_lstsq_f64_lay(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr,
                           const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
                           void* wq, void* wr, void* stream) {
@@ -2758,7 +2764,7 @@ int tsqr_mi_qr_f64_lay(int a_layout, int q_layout, int reorth, double* q, size_t
                        size_t m, size_t n, void* wq, void* wr, void* stream) {
 	const F64Operand A{a_layout, m, n, lda}, Q{q_layout, m, n, ldq}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
 	if (const int rc = f64_prologue({A, Q, R}, m, n, PW, "tsqr_mi_qr_f64 supports n <= 64 (tsqr_mi_qr_f64_wide: n <= 1024)")) return rc;
-	if (q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
+	if (f64_in_place_broken(q, q_layout, ldq, a, a_layout, lda)) return TSQR_MI_ERROR_INVALID_SIZE;
 	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream, nullptr, a_layout, q_layout);
 }
@@ -2771,13 +2777,69 @@ int tsqr_mi_qr_f64(int reorth, double* q, size_t ldq, double* r, size_t ldr, dou
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The SVD entry (tsqr_mi_svd_f64, n <= 64): the ladder of tsqr_mi_qr_f64_lay (jobu = 1: Q into u, R into wq[F64S_R]) or of
-// tsqr_mi_r_f64_lay (jobu = 0), called as they stand; then svd_r_f64_kernel on R (s, V, and W into wq[F64S_W]) and, for jobu = 1,
-// U = Q W in place (applyd_f64_kernel), enqueued back to back with one wait at the end.  The sweep count and the convergence word of the
-// Jacobi kernel arrive in the thread's pinned verdict words, which the ladder has finished with when it returns.
+// The entries with a job flag (tsqr_mi_svd_f64, tsqr_mi_qrcp_f64; n <= 64): the ladder, then one single-workgroup kernel on R, then --
+// job = 1 -- Q times the n x n matrix that kernel left in the work space, in place.  The sizes, the prologue and the path from the
+// ladder to the last wait (f64_job_core) stand here once; an entry adds its kernel launch, as a callable, and what that kernel reports.
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
+// job = 1: the QR entry's space with `block` doubles of wq (the entry's n x n matrices behind F64_WQ); job = 0: the R-only entry's
+size_t f64_job_wq(size_t m, size_t n, int job, size_t block) { return !job ? tsqr_mi_working_q_size_f64_r(m, n) : (m == 0 || n == 0) ? 0 : block; }
+size_t f64_job_wr(size_t m, size_t n, int job) { return job ? tsqr_mi_working_r_size_f64(m, n) : tsqr_mi_working_r_size_f64_r(m, n); }
+
+// What a job entry decides first: the sweep count cleared; a flag other than 0 or 1 (state 1, before everything else); f64_prologue
+// on a, on q -- job = 0: not used, it stands in the checks column-major with ld = m -- and on the entry's n x n result; for job = 1
+// the in-place rule.  0: go on.  No HIP call.
+int f64_job_prologue(int job, int a_layout, int q_layout, const void* q, size_t ldq, const void* a, size_t lda, size_t ld_small,
+                     size_t m, size_t n, const char* cap_text) {
+	t_sweeps64 = 0;
+	if (job != 0 && job != 1) return TSQR_MI_ERROR_INVALID_SIZE;
+	const F64Operand A{a_layout, m, n, lda}, Q{job ? q_layout : TSQR_MI_COL_MAJOR, m, n, job ? ldq : m}, S{TSQR_MI_COL_MAJOR, n, n, ld_small};
+	if (const int rc = f64_prologue({A, Q, S}, m, n, PW, cap_text)) return rc;
+	if (job && f64_in_place_broken(q, q_layout, ldq, a, a_layout, lda)) return TSQR_MI_ERROR_INVALID_SIZE;
+	return 0;
+}
+
+// U = Q W in place on a persistent grid, as f64_apply launches Q = A Z: the resident count is that of the instantiation launched
+template <int NT, bool AROW, bool QROW>
+int f64_applyd(hipStream_t st, int dev, double* u, size_t ldu, const double* q, size_t ldq, size_t m, size_t n, const double* w) {
+	static DevOnce once;
+	static std::atomic<int> resident[MAX_DEV];
+	if (once.need(dev)) {
+		resident[dev].store(f64_applyd_resident<NT, AROW, QROW>(dev));
+		once.done(dev);
+	}
+	f64_applyd_launch<NT, AROW, QROW>(st, f64_apply_wgs(cdiv(m, 32), (size_t)resident[dev].load()), u, ldu, q, ldq, m, (int)n, w);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// The common path: the ladder of tsqr_mi_qr_f64_lay (job = 1: Q into q) or of tsqr_mi_r_f64_lay (job = 0), called as they stand with R
+// into r; a state other than 0 (3 included) ends the call there.  The ladder call blocks -- it reads its verdict words -- so the stream is
+// idle when launch_r(st), the entry's kernel on R, and for job = 1 q = q w in place (w: n x n, from that kernel) are enqueued back to
+// back, with one more wait behind them: two waits per call at least.
+template <class LaunchR>
+int f64_job_core(int a_layout, int q_layout, int job, int reorth, double* q, size_t ldq, double* r, size_t ldr, double* a, size_t lda,
+                 size_t m, size_t n, double* wq, double* wr, void* stream, const double* w, LaunchR launch_r) {
+	const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+	const int rc = job ? tsqr_mi_qr_f64_lay(a_layout, q_layout, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream)
+	                   : tsqr_mi_r_f64_lay(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, stream);
+	if (rc) return rc;
+	launch_r(st);
+	HIPCHK(hipGetLastError());
+	if (job) {
+		const int dev = cur_device();
+		const int ra = with_apply(n, q_layout, q_layout, [&](auto nt, auto ar, auto qr) {
+			return f64_applyd<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(st, dev, q, ldq, q, ldq, m, n, w);
+		});
+		if (ra) return ra;
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	return TSQR_MI_SUCCESS;
+}
+
+// ---- tsqr_mi_svd_f64: R into wq[F64S_R]; svd_r_f64_kernel on R writes s, V, and W into wq[F64S_W]; U = Q W.  The sweep count and the
+// convergence word of the Jacobi kernel arrive in the thread's pinned verdict words, which the ladder has finished with when it returns. ----
 thread_local int t_jacobi64 = 0;
 // The columns of R^T rotate (svd_r_f64_kernel's transpose = 1): W is the product of the rotations and V the normalised columns.  Drmac's
 // observation: the lower triangle converges in far fewer sweeps (measured, n = 64: cond 1e6 9 sweeps against 18, cond 1e12 9 against 25:
@@ -2796,45 +2858,22 @@ struct OwnSvdR {
 };
 thread_local OwnSvdR t_svd_r;
 
-// U = Q W in place on a persistent grid, as f64_apply launches Q = A Z: the resident count is that of the instantiation launched
-template <int NT, bool AROW, bool QROW>
-int f64_applyd(hipStream_t st, int dev, double* u, size_t ldu, const double* q, size_t ldq, size_t m, size_t n, const double* w) {
-	static DevOnce once;
-	static std::atomic<int> resident[MAX_DEV];
-	if (once.need(dev)) {
-		resident[dev].store(f64_applyd_resident<NT, AROW, QROW>(dev));
-		once.done(dev);
-	}
-	f64_applyd_launch<NT, AROW, QROW>(st, f64_apply_wgs(cdiv(m, 32), (size_t)resident[dev].load()), u, ldu, q, ldq, m, (int)n, w);
-	HIPCHK(hipGetLastError());
-	return 0;
-}
-
 int svd_f64_core(int a_layout, int u_layout, int jobu, int reorth, double* u, size_t ldu, double* s, double* v, size_t ldv,
                  double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, void* stream) {
-	const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-	const int dev = cur_device();
-	double* r = jobu ? wq + F64S_R : t_svd_r.get(dev);
+	double* r = jobu ? wq + F64S_R : t_svd_r.get(cur_device());
 	if (!r) { t_last_error = "tsqr_mi_svd_f64: could not allocate the device block that holds R"; return -(int)hipErrorOutOfMemory; }
-	const int rc = jobu ? tsqr_mi_qr_f64_lay(a_layout, u_layout, reorth, u, ldu, r, 64, a, lda, m, n, wq, wr, stream)
-	                    : tsqr_mi_r_f64_lay(a_layout, reorth, r, 64, a, lda, m, n, wq, wr, stream);
-	if (rc) return rc;                                   // (state 3 included: the SVD kernel does not run)
-	volatile unsigned* words = t_own64.host;             // (the ladder allocated them and has read its verdicts: the stream is idle)
-	words[0] = 0u; words[1] = 1u;                        // (a kernel that never reported reads as not converged)
-	tsqrmi::SvdArgs64 sa{};
-	sa.r = r; sa.ldr = 64; sa.s = s; sa.v = v; sa.ldv = ldv; sa.n = (int)n; sa.transpose = F64S_TRANSPOSE;
-	sa.w = jobu ? wq + F64S_W : nullptr;
-	sa.status = jobu ? reinterpret_cast<unsigned*>(wq + F64S_STATUS) : nullptr;
-	sa.host_status = t_own64.dev;
-	f64_svd_r_launch(st, sa);
-	HIPCHK(hipGetLastError());
-	if (jobu) {
-		const int ra = with_apply(n, u_layout, u_layout, [&](auto nt, auto ar, auto qr) {
-			return f64_applyd<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(st, dev, u, ldu, u, ldu, m, n, wq + F64S_W);
-		});
-		if (ra) return ra;
-	}
-	HIPCHK(hipStreamSynchronize(st));
+	double* w = jobu ? wq + F64S_W : nullptr;
+	const int rc = f64_job_core(a_layout, u_layout, jobu, reorth, u, ldu, r, 64, a, lda, m, n, wq, wr, stream, w, [&](hipStream_t st) {
+		volatile unsigned* words = t_own64.host;         // (the ladder allocated them and has read its verdicts: the stream is idle)
+		words[0] = 0u; words[1] = 1u;                    // (a kernel that never reported reads as not converged)
+		tsqrmi::SvdArgs64 sa{};
+		sa.r = r; sa.ldr = 64; sa.s = s; sa.v = v; sa.ldv = ldv; sa.n = (int)n; sa.transpose = F64S_TRANSPOSE; sa.w = w;
+		sa.status = jobu ? reinterpret_cast<unsigned*>(wq + F64S_STATUS) : nullptr;
+		sa.host_status = t_own64.dev;
+		f64_svd_r_launch(st, sa);
+	});
+	if (rc) return rc;                                   // (state 3 included: the SVD kernel did not run)
+	volatile unsigned* words = t_own64.host;
 	t_jacobi64 = (int)words[0];
 	if (words[1] != 0u) {
 		t_last_error = "tsqr_mi_svd_f64: the Jacobi iteration reached its cap of 30 sweeps";
@@ -2843,82 +2882,41 @@ int svd_f64_core(int a_layout, int u_layout, int jobu, int reorth, double* u, si
 	return TSQR_MI_SUCCESS;
 }
 
+// ---- tsqr_mi_qrcp_f64: R0 into the caller's r; qrcp_r_f64_kernel factors R0 P = H R in place on r (jpvt; H into wq[F64P_H] for
+// jobq = 1, not formed otherwise); Q = Q0 H.  Nothing is allocated; the kernel has no verdict of its own. ----
+int qrcp_f64_core(int a_layout, int q_layout, int jobq, int reorth, double* q, size_t ldq, double* r, size_t ldr, int* jpvt,
+                  double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, void* stream) {
+	double* h = jobq ? wq + F64P_H : nullptr;
+	return f64_job_core(a_layout, q_layout, jobq, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream, h, [&](hipStream_t st) {
+		tsqrmi::QrcpArgs64 pa{};
+		pa.r0 = r; pa.ldr0 = ldr; pa.r = r; pa.ldr = ldr; pa.jpvt = jpvt; pa.n = (int)n; pa.h = h;
+		pa.status = jobq ? reinterpret_cast<unsigned*>(wq + F64P_STATUS) : nullptr;
+		f64_qrcp_r_launch(st, pa);
+	});
+}
+
 }  // namespace
 
 extern "C" {
 
-size_t tsqr_mi_working_q_size_f64_svd(size_t m, size_t n, int jobu) {
-	return jobu ? ((m == 0 || n == 0) ? 0 : F64S_WQ) : tsqr_mi_working_q_size_f64_r(m, n);
-}
-size_t tsqr_mi_working_r_size_f64_svd(size_t m, size_t n, int jobu) {
-	return jobu ? tsqr_mi_working_r_size_f64(m, n) : tsqr_mi_working_r_size_f64_r(m, n);
-}
+size_t tsqr_mi_working_q_size_f64_svd(size_t m, size_t n, int jobu) { return f64_job_wq(m, n, jobu, F64S_WQ); }
+size_t tsqr_mi_working_r_size_f64_svd(size_t m, size_t n, int jobu) { return f64_job_wr(m, n, jobu); }
 int tsqr_mi_last_jacobi_sweeps_f64(void) { return t_jacobi64; }
 
 int tsqr_mi_svd_f64(int a_layout, int u_layout, int jobu, int reorth, double* u, size_t ldu, double* s, double* v, size_t ldv,
                     double* a, size_t lda, size_t m, size_t n, void* wq, void* wr, void* stream) {
 	t_jacobi64 = 0;
-	t_sweeps64 = 0;
-	if (jobu != 0 && jobu != 1) return TSQR_MI_ERROR_INVALID_SIZE;
-	const F64Operand A{a_layout, m, n, lda}, U{jobu ? u_layout : TSQR_MI_COL_MAJOR, m, n, jobu ? ldu : m}, V{TSQR_MI_COL_MAJOR, n, n, v ? ldv : n};
-	if (const int rc = f64_prologue({A, U, V}, m, n, PW, "tsqr_mi_svd_f64 supports n <= 64")) return rc;
-	if (jobu && u == a && (a_layout != u_layout || ldu != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
+	if (const int rc = f64_job_prologue(jobu, a_layout, u_layout, u, ldu, a, lda, v ? ldv : n, m, n, "tsqr_mi_svd_f64 supports n <= 64")) return rc;
 	return svd_f64_core(a_layout, u_layout, jobu, reorth, u, ldu, s, v, ldv, a, lda, m, n, reinterpret_cast<double*>(wq),
 	                    reinterpret_cast<double*>(wr), stream);
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The pivoted QR entry (tsqr_mi_qrcp_f64, n <= 64): the ladder of tsqr_mi_qr_f64_lay (jobq = 1: Q0 into q) or of tsqr_mi_r_f64_lay
-// (jobq = 0), called as they stand with R0 into the caller's r; then qrcp_r_f64_kernel factors R0 P = H R in place on r (jpvt; H into
-// wq[F64P_H] for jobq = 1, not formed otherwise) and, for jobq = 1, Q = Q0 H in place (f64_applyd).  The ladder call blocks -- it reads
-// its verdict words -- so the stream is idle when the two kernels are enqueued, back to back, with one more wait behind them: two waits
-// per call at least.  Nothing is allocated; the kernel has no verdict of its own.
-// ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-int qrcp_f64_core(int a_layout, int q_layout, int jobq, int reorth, double* q, size_t ldq, double* r, size_t ldr, int* jpvt,
-                  double* a, size_t lda, size_t m, size_t n, double* wq, double* wr, void* stream) {
-	const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-	const int rc = jobq ? tsqr_mi_qr_f64_lay(a_layout, q_layout, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream)
-	                    : tsqr_mi_r_f64_lay(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, stream);
-	if (rc) return rc;                                   // (state 3 included: the pivoting kernel does not run)
-	tsqrmi::QrcpArgs64 pa{};
-	pa.r0 = r; pa.ldr0 = ldr; pa.r = r; pa.ldr = ldr; pa.jpvt = jpvt; pa.n = (int)n;
-	pa.h = jobq ? wq + F64P_H : nullptr;
-	pa.status = jobq ? reinterpret_cast<unsigned*>(wq + F64P_STATUS) : nullptr;
-	f64_qrcp_r_launch(st, pa);
-	HIPCHK(hipGetLastError());
-	if (jobq) {
-		const int dev = cur_device();
-		const int ra = with_apply(n, q_layout, q_layout, [&](auto nt, auto ar, auto qr) {
-			return f64_applyd<decltype(nt)::value, decltype(ar)::value, decltype(qr)::value>(st, dev, q, ldq, q, ldq, m, n, wq + F64P_H);
-		});
-		if (ra) return ra;
-	}
-	HIPCHK(hipStreamSynchronize(st));
-	return TSQR_MI_SUCCESS;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t tsqr_mi_working_q_size_f64_qrcp(size_t m, size_t n, int jobq) {
-	return jobq ? ((m == 0 || n == 0) ? 0 : F64P_WQ) : tsqr_mi_working_q_size_f64_r(m, n);
-}
-size_t tsqr_mi_working_r_size_f64_qrcp(size_t m, size_t n, int jobq) {
-	return jobq ? tsqr_mi_working_r_size_f64(m, n) : tsqr_mi_working_r_size_f64_r(m, n);
-}
+size_t tsqr_mi_working_q_size_f64_qrcp(size_t m, size_t n, int jobq) { return f64_job_wq(m, n, jobq, F64P_WQ); }
+size_t tsqr_mi_working_r_size_f64_qrcp(size_t m, size_t n, int jobq) { return f64_job_wr(m, n, jobq); }
 
 int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth, double* q, size_t ldq, double* r, size_t ldr, int* jpvt,
                      double* a, size_t lda, size_t m, size_t n, void* wq, void* wr, void* stream) {
-	t_sweeps64 = 0;
-	if (jobq != 0 && jobq != 1) return TSQR_MI_ERROR_INVALID_SIZE;
-	const F64Operand A{a_layout, m, n, lda}, Q{jobq ? q_layout : TSQR_MI_COL_MAJOR, m, n, jobq ? ldq : m}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
-	if (const int rc = f64_prologue({A, Q, R}, m, n, PW, "tsqr_mi_qrcp_f64 supports n <= 64")) return rc;
-	if (jobq && q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
+	if (const int rc = f64_job_prologue(jobq, a_layout, q_layout, q, ldq, a, lda, ldr, m, n, "tsqr_mi_qrcp_f64 supports n <= 64")) return rc;
 	return qrcp_f64_core(a_layout, q_layout, jobq, reorth, q, ldq, r, ldr, jpvt, a, lda, m, n, reinterpret_cast<double*>(wq),
 	                     reinterpret_cast<double*>(wr), stream);
 }
@@ -2948,7 +2946,7 @@ int tsqr_mi_qr_f64_wide_lay(int a_layout, int q_layout, int reorth, double* q, s
                             size_t m, size_t n, void* wq, void* wr, void* stream) {
 	const F64Operand A{a_layout, m, n, lda}, Q{q_layout, m, n, ldq}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
 	if (const int rc = f64_prologue({A, Q, R}, m, n, F64W_MAX_N, "tsqr_mi_qr_f64_wide supports n <= 1024")) return rc;
-	if (q == a && (a_layout != q_layout || ldq != lda)) return TSQR_MI_ERROR_INVALID_SIZE;   // (in place: one operand, one layout, one stride)
+	if (f64_in_place_broken(q, q_layout, ldq, a, a_layout, lda)) return TSQR_MI_ERROR_INVALID_SIZE;
 	if (n <= PW) return tsqr_mi_qr_f64_lay(a_layout, q_layout, reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream);
 	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
 	return qr_f64_core(reorth, q, ldq, r, ldr, a, lda, m, n, wq, wr, stream, nullptr, a_layout, q_layout);
