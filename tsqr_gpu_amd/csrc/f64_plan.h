@@ -133,6 +133,15 @@ inline void f64r_lsq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::LsqA
 	});
 }
 
+// X <- X + Z D on stream st, one workgroup.  ZDENSE clear: Z upper triangular, the least-squares entry -- the only form the library
+// instantiates; set: a dense Z (lsq_rank_f64.hip, the test library)
+template <bool ZDENSE = false>
+inline void f64_lsq_update_launch(hipStream_t st, double* xw, double* x, size_t ldx, const double* z, const double* d, int n, int nrhs,
+                                  int first, int last, double* dprev, int guard) {
+	hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel<ZDENSE>, dim3(1), dim3(1024), 0, st, xw, x, ldx, z, d, n, (int)np_of((size_t)n), nrhs,
+	                   first, last, dprev, guard);
+}
+
 // ---- tsqr_mi_svd_f64 (n <= 64) ------------------------------------------------------------------------------------------------------------
 // jobu = 1 runs the ladder of tsqr_mi_qr_f64_lay on the F64_WQ layout with R in the block behind it, then svd_r_f64_kernel and
 // applyd_f64_kernel.  wq (doubles): [the F64_WQ layout][R, n x n with ld 64: 4096][W, NP x NP with ld NP: 4096][status words: 8]

@@ -1,0 +1,180 @@
+// lsq_rank_f64.hip -- the device passes of a rank-aware fp64 least-squares solve (n <= 64, nrhs <= 16) and their launchers: preparatory
+// code that NO entry of libtsqr_mi.so calls yet (DESIGN.md section 9 says what an entry still needs).  Included by selftest.hip alone,
+// behind tsqr_f64.hip and f64_plan.h, so the kernels are built into the test library only and the product library does not carry them:
+//   lsq_rank_f64_kernel  : the rank from the diagonal of a pivoted R and Zeff = P1 inverse(R11), the inverse factor of the retained
+//                          columns, on one workgroup
+//   lsq_dense_f64_kernel : lsq_f64_kernel for a dense Z staged in LDS
+// The third pass, X <- X + Z D for a dense Z, is lsq_update_f64_kernel<true> (tsqr_f64.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace tsqrmi {
+
+// The dense-Z form of lsq_f64_kernel (the rank-aware solve): Z is a dense NP x NP matrix (ld NP, zero padded: lsq_rank_f64_kernel's
+// row-permuted triangle), so every output tile of stage 1 sums all 4 NT k-blocks, in the order 0 .. 4 NT - 1.  The 4 NT^2 operands
+// would take 128 VGPRs at NT = 4 next to av, nx, xop and the accumulators, so they are staged in LDS once per workgroup in operand
+// order, applyd_f64_kernel's scheme: operand (jt, kb) is 64 consecutive doubles, lane l reads element l, one conflict-free 8-byte read
+// per MFMA.  Everything else -- the tile loop, the loads and the prefetch, stages 2 and 3, the partials -- is lsq_f64_kernel's, line
+// for line.  It is a kernel of its own and not a flag of lsq_f64_kernel because that kernel's device code must not move: with the
+// dense form behind a template flag, eight of its sixteen instantiations came out of the compiler with another closing workgroup sum
+// (DESIGN.md section 9).  The copy of the tile loop has to be kept in step with lsq_f64_kernel by hand.  On an upper triangular Z the k-blocks the triangular form skips add products with exact zeros, so both
+// kernels give the same D whenever no product of A with a skipped zero is non-finite.
+template <int NT, bool AROW, bool BROW>
+__global__ __launch_bounds__(256) void lsq_dense_f64_kernel(const LsqArgs64 a) {
+	constexpr int NP = 16 * NT, KB = 4 * NT;
+	__shared__ double red[2 * NT * 256];
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
+	const int gw = blockIdx.x * 4 + wv;
+	__shared__ double zl[NT * KB * 64];
+	for (int e = threadIdx.x; e < NT * KB * 64; e += 256) {
+		const int l = e & 63, b = e >> 6, jt = b / KB, kb = b % KB;
+		zl[e] = a.z[(size_t)(16 * jt + (l & 15)) * NP + 4 * kb + (l >> 4)];
+	}
+	__syncthreads();                                       // (every wave of the workgroup, idle ones included)
+	f64x4 acc[NT];
+#pragma unroll
+	for (int t = 0; t < NT; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+	if (gw < a.nwaves) {
+		double xop[KB], idop[4];
+#pragma unroll
+		for (int kb = 0; kb < KB; kb++) {
+			const int row = 4 * kb + lq;
+			xop[kb] = -((a.x && row < a.n && li < a.nrhs) ? a.x[(size_t)li * NP + row] : 0.0);
+		}
+#pragma unroll
+		for (int kb = 0; kb < 4; kb++) idop[kb] = (4 * kb + lq == li) ? 1.0 : 0.0;
+		// a tile beyond the last reads nothing and leaves zeros (gramq_f64_kernel's load_tile, and the same for the tile of B)
+		auto load_tile = [&](double (&av)[KB], double (&bv)[4], int tile) {
+			const size_t row = (size_t)tile * 16 + li;
+			const bool live = tile < a.ntiles && row < a.m;
+			if constexpr (AROW) load_rows_rm<KB>(av, a.a, a.lda, row, live, a.n, lq);
+			else {
+#pragma unroll
+				for (int kb = 0; kb < KB; kb++) {
+					const int col = 4 * kb + lq;
+					av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+				}
+			}
+			if constexpr (BROW) load_rows_rm<4>(bv, a.b, a.ldb, row, live, a.nrhs, lq);
+			else {
+#pragma unroll
+				for (int kb = 0; kb < 4; kb++) {
+					const int col = 4 * kb + lq;
+					bv[kb] = (live && col < a.nrhs) ? a.b[(size_t)col * a.ldb + row] : 0.0;
+				}
+			}
+		};
+		double av[KB], nx[KB], bv[4], nb[4];
+		load_tile(av, bv, gw);
+		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
+			load_tile(nx, nb, tile + a.nwaves);
+			f64x4 qt[NT];
+#pragma unroll
+			for (int jt = 0; jt < NT; jt++) {
+				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+				for (int kb = 0; kb < KB; kb++)
+					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zl[(jt * KB + kb) * 64 + lane], qt[jt], 0, 0, 0);
+			}
+			f64x4 rt = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+			for (int kb = 0; kb < 4; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[kb], idop[kb], rt, 0, 0, 0);
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) rt = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], xop[kb], rt, 0, 0, 0);
+#pragma unroll
+			for (int reg = 0; reg < 4; reg++)
+#pragma unroll
+				for (int ti = 0; ti < NT; ti++)
+					acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], rt[reg], acc[ti], 0, 0, 0);
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
+#pragma unroll
+			for (int kb = 0; kb < 4; kb++) bv[kb] = nb[kb];
+		}
+	}
+	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NT * 256, wv, lane);
+}
+
+// ---- the rank-aware least-squares solve: rank and inverse factor of the retained columns from R and jpvt ----------------------------------
+struct LsqRankArgs64 {
+	const double* r; size_t ldr;         // n x n upper triangular (only i <= j is read): qrcp_r_f64_kernel's R, diag(R) >= 0 and non-increasing
+	const int* jpvt;                     // its n pivots, 0-based
+	double rcond;                        // column j is retained when R_jj > rcond R_00
+	double* zeff;                        // NP x NP (ld NP) out, wholly written: Zeff[jpvt[i]][j] = inverse(R11)[i][j] for i <= j < k, zero elsewhere
+	unsigned* status;                    // device word [0] the rank k; null: not wanted
+	unsigned* host_status;               // device-visible alias of a pinned host word receiving k; null: not wanted
+	int n;
+};
+
+// One workgroup, R held in LDS (column-major, ld 64).  The rank k is the number of j with R_jj > rcond R_00, counted by every wave for
+// itself from the same 64 numbers (a NaN on the diagonal is not counted; R_00 == 0 gives k = 0 and Zeff = 0).  R11 = R[:k, :k] is then
+// inverted by column-oriented back substitution, wave w taking columns j = w, w + 16, ... < k and lane i holding row i of the column:
+// from e_j, step l = j .. 0 forms z_l = w_l / R_ll and lanes i < l take w_i <- fma(-R_il, z_l, w_i).  Entry (i, j) is so the terms
+// l = j .. i + 1 in that order, one fused multiply-add each, and one division: a fixed function of R, the same bits on every run.
+// cond(R11) is about 1 / rcond at most, whatever cond(A) is.  The rows go out permuted: row i of the inverse is row jpvt[i] of Zeff (a
+// pivot outside 0 .. n - 1 writes nothing), through an LDS image so that the whole NP x NP block is written once, zeros included.
+// A Zeff = Q1, the orthonormal factor of the retained columns A P1.  jpvt must be a permutation of 0 .. n - 1, as qrcp_r_f64_kernel
+// writes it: with a repeated pivot two lanes write the same word of the LDS image and that row of Zeff is either of the two (nothing
+// outside the image is touched).  No scratch; 64.3 KB of static LDS, like qrcp_r_f64_kernel's 66.4 KB above the 64 KB of older
+// targets: this file is built for gfx950 alone, whose workgroups have 160 KB.
+__global__ __launch_bounds__(1024) void lsq_rank_f64_kernel(const LsqRankArgs64 a) {
+	__shared__ double M[64 * 64], Zl[64 * 64];
+	__shared__ int piv[64];
+	static_assert(sizeof(M) + sizeof(Zl) + sizeof(piv) <= 160 * 1024, "lsq_rank_f64_kernel relies on the 160 KB of LDS of gfx950");
+	const int t = threadIdx.x, lane = t & 63, wv = t >> 6, n = a.n;
+	const int NP = 16 * ((n + 15) / 16);
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		M[e] = (i <= j && j < n) ? a.r[(size_t)j * a.ldr + i] : 0.0;
+		Zl[e] = 0.0;
+	}
+	if (t < 64) piv[t] = t < n ? a.jpvt[t] : -1;
+	__syncthreads();
+	const double dii = M[lane * 64 + lane], d00 = M[0];
+	const bool keep = lane < n && dii > a.rcond * d00;
+	const int k = __popcll(__ballot(keep));
+	for (int j = wv; j < k; j += 16) {
+		double w = lane == j ? 1.0 : 0.0, z = 0.0;
+		for (int l = j; l >= 0; l--) {
+			const double q = w / dii;
+			const double zl = __shfl(q, l, 64);
+			if (lane == l) z = zl;
+			if (lane < l) w = __builtin_fma(-M[l * 64 + lane], zl, w);
+		}
+		const int row = piv[lane];
+		if (lane <= j && row >= 0 && row < n) Zl[j * 64 + row] = z;
+	}
+	__syncthreads();
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		if (i < NP && j < NP) a.zeff[(size_t)j * NP + i] = Zl[e];
+	}
+	if (t == 0) {
+		if (a.status) a.status[0] = (unsigned)k;
+		if (a.host_status) { volatile unsigned* hs = a.host_status; hs[0] = (unsigned)k; }
+	}
+}
+
+}  // namespace tsqrmi
+
+namespace {
+
+// lsq_rank_f64_kernel on stream st: one workgroup
+inline void f64k_rank_launch(hipStream_t st, const tsqrmi::LsqRankArgs64& ka) {
+	hipLaunchKernelGGL(tsqrmi::lsq_rank_f64_kernel, dim3(1), dim3(1024), 0, st, ka);
+}
+// one dense pass on stream st: lsq_dense_f64_kernel<NT, AROW, BROW> (la.z dense) on the grid of f64r_lsq_launch
+inline void f64k_lsq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::LsqArgs64& la, int a_layout = 0, int b_layout = 0) {
+	with_nt(g.NT, [&](auto nt) {
+		with_layout(a_layout, [&](auto ar) {
+			with_layout(b_layout, [&](auto br) {
+				hipLaunchKernelGGL((tsqrmi::lsq_dense_f64_kernel<decltype(nt)::value, decltype(ar)::value, decltype(br)::value>),
+				                   dim3(g.nblocks), dim3(256), 0, st, la);
+			});
+		});
+	});
+}
+
+}  // namespace

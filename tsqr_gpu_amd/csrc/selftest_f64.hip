@@ -206,8 +206,44 @@ int tsqr_selftest_f64_lsq(double* dsum, const double* a, size_t lda, const doubl
 // lsq_update_f64_kernel: xw (NP x 16, ld NP) <- xw + z d (first: xw taken as zero), and x (n x nrhs, ldx) too when last
 int tsqr_selftest_f64_lsq_update(double* xw, double* x, size_t ldx, const double* z, const double* d, int n, int nrhs, int first, int last) {
 	if (n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || ldx < (size_t)n) return -100;
-	hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel, dim3(1), dim3(1024), 0, 0, xw, x, ldx, z, d, n, (int)np_of((size_t)n), nrhs, first, last,
-	                   (double*)nullptr, 0);                  // (no stagnation rule: every update is applied)
+	f64_lsq_update_launch(0, xw, x, ldx, z, d, n, nrhs, first, last, nullptr, 0);   // (no stagnation rule: every update is applied)
+	return f64_sync();
+}
+
+// ---- n <= 64, the passes of a rank-aware least-squares solve (lsq_rank_f64.hip: built into this library only) ------------------------------
+// lsq_dense_f64_kernel + reduction, one pass, with the arguments of tsqr_selftest_f64_lsq_lay: z is a dense NP x NP block (ld NP)
+int tsqr_selftest_f64_lsq_dense_lay(int a_layout, int b_layout, double* dsum, const double* a, size_t lda, const double* b, size_t ldb,
+                                    size_t m, int n, int nrhs, const double* z, const double* x, double* part, size_t part_cap, int nwaves) {
+	if ((a_layout != 0 && a_layout != 1) || (b_layout != 0 && b_layout != 1)) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || lda < (a_layout ? (size_t)n : m) ||
+	    ldb < (b_layout ? (size_t)nrhs : m))
+		return -100;
+	F64Plan g = f64r_plan(m, (size_t)n);
+	if (!f64_override(g, nwaves, g.NT, part_cap)) return -100;
+	const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, n, nrhs, g.nunits, g.nwaves, z, x, part};
+	f64k_lsq_launch(0, g, la, a_layout, b_layout);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, dsum, part, g.nblocks, g.NT * 256, (double)m);
+	return f64_sync();
+}
+
+// lsq_rank_f64_kernel through the product's launcher: r (n x n upper triangular, ldr), jpvt[n] and rcond in; zeff (NP x NP, ld NP) and
+// status[1] (the rank) out
+int tsqr_selftest_f64_lsq_rank(const double* r, size_t ldr, const int* jpvt, double rcond, double* zeff, unsigned* status, int n) {
+	if (n <= 0 || n > (int)PW || ldr < (size_t)n || !r || !jpvt || !zeff || !status) return -100;
+	tsqrmi::LsqRankArgs64 ka{};
+	ka.r = r; ka.ldr = ldr; ka.jpvt = jpvt; ka.rcond = rcond; ka.zeff = zeff; ka.status = status; ka.host_status = nullptr; ka.n = n;
+	f64k_rank_launch(0, ka);
+	return f64_sync();
+}
+
+// lsq_update_f64_kernel<dense> through the product's launcher with the stagnation rule: dprev (16 doubles, or null) and guard as the
+// entries pass them; dense = 0 runs the triangular form on the same arguments
+int tsqr_selftest_f64_lsq_update_rule(int dense, double* xw, double* x, size_t ldx, const double* z, const double* d, int n, int nrhs,
+                                      int first, int last, double* dprev, int guard) {
+	if (n <= 0 || n > (int)PW || nrhs <= 0 || nrhs > (int)F64L_MAX_NRHS || ldx < (size_t)n || (dense != 0 && dense != 1)) return -100;
+	if (dense) f64_lsq_update_launch<true>(0, xw, x, ldx, z, d, n, nrhs, first, last, dprev, guard);
+	else f64_lsq_update_launch<false>(0, xw, x, ldx, z, d, n, nrhs, first, last, dprev, guard);
 	return f64_sync();
 }
 

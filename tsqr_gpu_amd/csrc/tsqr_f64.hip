@@ -451,6 +451,9 @@ __global__ __launch_bounds__(256) void lsq_f64_kernel(const LsqArgs64 a) {
 // X.  D = Q~^T (B - A X) is the correction measured in Q-space: it keeps its bits under a column scaling of A and scales exactly with
 // column j of B, so the verdict is the same for A diag(2^k_c), B diag(2^j_c).  A NaN in D is skipped by the maximum, +Inf compares as
 // not above +Inf: non-finite data are applied as before.
+// ZDENSE (the rank-aware solve, lsq_rank_f64.hip; the library instantiates the flag clear only): Z is dense, zero padded; row i sums k = 0 .. NP - 1, in
+// that order, one fused multiply-add each -- D is zero in rows >= n -- under the same stagnation rule.
+template <bool ZDENSE = false>
 __global__ __launch_bounds__(1024) void lsq_update_f64_kernel(double* xw, double* x, size_t ldx, const double* __restrict__ z,
                                                               const double* __restrict__ d, int n, int NP, int nrhs, int first, int last,
                                                               double* dprev, int guard) {
@@ -470,7 +473,7 @@ __global__ __launch_bounds__(1024) void lsq_update_f64_kernel(double* xw, double
 	if (i < n && j < nrhs) {
 		double s = 0.0;
 		if (apply)
-			for (int k = i; k < n; k++)
+			for (int k = ZDENSE ? 0 : i; k < (ZDENSE ? NP : n); k++)
 				s = __builtin_fma(z[(size_t)k * NP + i], d[((k >> 4) * 4 + ((k & 15) >> 2)) * 64 + (k & 3) * 16 + j], s);
 		v = apply ? (first ? 0.0 : xw[(size_t)j * NP + i]) + s : xw[(size_t)j * NP + i];
 		if (last) x[(size_t)j * ldx + i] = v;

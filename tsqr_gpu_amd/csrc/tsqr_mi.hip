@@ -2668,7 +2668,6 @@ int r_f64_core(int a_layout, int reorth, double* r, size_t ldr, const double* a,
 int lstsq_f64_core(int a_layout, int b_layout, int reorth, int refine, double* x, size_t ldx, double* r, size_t ldr, const double* a, size_t lda,
                    const double* b, size_t ldb, size_t m, size_t n, size_t nrhs, double* wq, double* wr, hipStream_t st) {
 	if (const int rc = r_f64_core(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, st)) return rc;
-	const size_t NP = np_of(n);
 	double *zacc = wq + F64R_ZACC, *xw = wq + F64L_X, *dsum = wq + F64L_D;
 	if (const int rc = f64r_zacc(st, t_sweeps64 % 100, wq, n)) return rc;
 	const F64Plan g = f64r_plan(m, n);
@@ -2679,8 +2678,8 @@ int lstsq_f64_core(int a_layout, int b_layout, int reorth, int refine, double* x
 		HIPCHK(hipGetLastError());
 		launch_reduce1(st, dsum, wr, g.nblocks, g.NT * 256, (double)m);
 		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL(tsqrmi::lsq_update_f64_kernel, dim3(1), dim3(1024), 0, st, xw, x, ldx, (const double*)zacc, (const double*)dsum,
-		                   (int)n, (int)NP, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0, wq + F64L_DPREV, p >= 2 ? 1 : 0);
+		f64_lsq_update_launch(st, xw, x, ldx, zacc, dsum, (int)n, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0, wq + F64L_DPREV,
+		                      p >= 2 ? 1 : 0);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipStreamSynchronize(st));
