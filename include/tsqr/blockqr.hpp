@@ -452,6 +452,35 @@ inline state_t lstsq_fp64(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::lstsq_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
+
+// Not in the reference: the rank of A and the basic solution of min ||A X - B||_F on its numerically independent columns, on the pivoted
+// R-only factorisation (tsqr_mi_lstsq_rank_f64, include/tsqr_mi.h for the contract and the measured accuracy): a and b are read only,
+// no work space of size m.  r and jpvt (n ints on the device) are those of qrcp_fp64 without Q; rank is a host int; rows jpvt[rank:] of
+// x are exact zeros.  rcond: column j is retained when R_jj > rcond R_00; negative: max(m, n) 2^-52.  Returns the states of lstsq_fp64;
+// error_invalid_matrix_size also for a null pointer, error_unsupported_mode also for rcond >= 1 or NaN.
+template <bool Reorthogonalize>
+struct buffer_fp64_lstsq_rank : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n, const std::size_t nrhs) { allocate_doubles(tsqr_mi_working_q_size_f64_lstsq_rank(m, n, nrhs), tsqr_mi_working_r_size_f64_lstsq_rank(m, n, nrhs)); }
+};
+
+template <bool Reorthogonalize>
+inline state_t lstsq_rank_fp64(
+		double* const x_ptr, const std::size_t ldx,
+		double* const r_ptr, const std::size_t ldr,
+		int* const jpvt_ptr, int* const rank,
+		const double* const a_ptr, const std::size_t lda,
+		const double* const b_ptr, const std::size_t ldb,
+		const std::size_t m, const std::size_t n, const std::size_t nrhs,
+		buffer_fp64_lstsq_rank<Reorthogonalize>& bf,
+		const double rcond = -1.0,
+		const int refine = 1,
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major, const layout_t b_layout = col_major) {
+	const int st = tsqr_mi_lstsq_rank_f64(a_layout, b_layout, Reorthogonalize ? 1 : 0, refine, rcond, x_ptr, ldx, r_ptr, ldr, jpvt_ptr, rank,
+	                                      a_ptr, lda, b_ptr, ldb, m, n, nrhs, bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::lstsq_rank_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
 // Not in the reference: double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide, include/tsqr_mi.h for the
 // contract): qr_fp64 itself for n <= 64, whole-matrix CholeskyQR sweeps with the same ladder beyond.  Returns success_factorization,
 // error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.  a_layout, q_layout (tsqr_mi_qr_f64_wide_lay): the

@@ -529,6 +529,59 @@ int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth,
                      void* wq, void* wr, void* stream);
 
 /*
+ * Rank-aware least squares in double precision (not in the reference): the rank of A and the BASIC solution of min ||A X - B||_F on
+ * the numerically independent columns of A; 1 <= n <= 64, n <= m, 1 <= nrhs <= 16.  a (m x n, lda, a_layout) and b (m x nrhs, ldb,
+ * b_layout) as the operands of tsqr_mi_lstsq_f64_lay, read only; x: n x nrhs and r: n x n, column-major (ldx, ldr >= n), jpvt: n int
+ * values, all three on the device; rank: ONE int on the HOST.  Blocking.  Bitwise deterministic from call to call, and the same bits
+ * for either layout of a and of b.  Nothing of size m is stored, nothing is allocated, A and B are never written.
+ * Method.  (1) The ladder of tsqr_mi_r_f64_lay writes R0 into r.  (2) qrcp_r_f64_kernel factors R0 P = H R in place on r without
+ * forming H: r, jpvt and tsqr_mi_last_sweeps_f64 are BITWISE those of tsqr_mi_qrcp_f64 with jobq = 0 on the same a, a_layout and
+ * reorth.  (3) The rank k is the number of j with R_jj > rcond R_00 (diag(R) is non-negative and non-increasing), and
+ * Zeff = P1 inverse(R11), R11 = R[:k, :k], P1 the retained columns jpvt[:k]: cond(R11) is about 1 / rcond at most whatever cond(A) is.
+ * (4) One CholeskyQR step on the retained columns: G1 = (A Zeff)^T (A Zeff) in one pass over A, G1 = Rc^T Rc by plain Cholesky,
+ * Zeff <- Zeff inverse(Rc).  The ladder never stores Q, so on an exactly dependent interior column its R0 is inconsistent in the
+ * columns behind it and A P1 inverse(R11) is orthonormal to about 2e-2 only; after the step it is orthonormal to about
+ * cond(A P1)^2 2^-53.  (5) refine + 1 passes X <- X + Zeff (A Zeff)^T (B - A X), each one pass over A and B, with the stagnation rule of
+ * tsqr_mi_lstsq_f64 (0 <= refine <= 4).  Rows jpvt[rank:] of x are exact zeros, the other rows are the least-squares solution on the
+ * columns jpvt[:rank] -- the basic solution, NOT the minimum-norm one.
+ * Fixed point.  The iteration stops moving when Zeff^T A^T (B - A X) = 0.  Zeff^T = (R11 Rc)^-T P1^T has full row rank for any
+ * non-singular R11 Rc, so that is (A P1)^T (B - A X) = 0, the normal equations of the retained columns: errors in R11 and Rc change
+ * how fast the passes contract, about ||I - (A Zeff)^T (A Zeff)||, never where they stop.
+ * rcond: column j is retained when R_jj > rcond R_00.  rcond < 0 stands for max(m, n) 2^-52.  The pivots of a matrix with dependent
+ * columns are small but carry no bound (tsqr_mi_qrcp_f64): a column is dropped reliably when its pivot is well below rcond R_00 and
+ * kept reliably when well above; on the threshold either may happen.
+ * Accuracy: bounded by what was measured (MI355X, refine = 1, Gaussian and consistent B; profiles/fp64_lstsq_rank_accuracy.md has every
+ * figure next to LAPACK's dgelsd on the retained columns).  The retained columns have cond(A P1) <~ 1 / rcond and each pass contracts
+ * by about cond(A P1)^2 2^-53 after the step.  On the seven cases of tests/pass_refs_f64_lsq_rank.py -- a copied interior column at
+ * 4096 x 16, rank 32 of 51, rank 1 of 33, rank 40 of 64 with singular values down to 1e-4, full rank 300 x 17, three copied tail
+ * columns of 7, one column -- the error ||X[jpvt[:k]] - X*||_F / ||X*||_F against an extended-precision solve stays within
+ * max(2 x LAPACK's, 4 n 2^-53).  Measured / LAPACK's, Gaussian B then consistent B:
+ *   copied column 4096 x 16   2.5e-16 / 1.8e-15    1.6e-17 / 1.2e-15      rank 32 of 51, 1029 rows   8.8e-16 / 3.0e-15    9.2e-17 / 2.9e-15
+ *   rank 1 of 33, 777 rows    2.3e-16 / 1.6e-15    5.3e-17 / 2.0e-16      rank 40 of 64, 4097 rows   1.2e-12 / 1.0e-12    2.3e-14 / 3.8e-14
+ *   full rank 300 x 17        2.9e-16 / 1.7e-15    3.1e-17 / 1.7e-15      3 copied tail columns of 7 1.6e-16 / 7.0e-15    2.9e-17 / 7.9e-15
+ *   one column, 65 rows       1.3e-16 / 2.7e-16    1.0e-17 / 2.8e-16
+ * The hardest of them has cond(A P1) = 1e4 (rank 40 of 64).  Nothing is claimed beyond these cases: in particular not for
+ * cond(A P1) above about 1e6, where the contraction cond(A P1)^2 2^-53 of a pass is no longer small.
+ * Work space: wq of tsqr_mi_working_q_size_f64_lstsq_rank doubles -- tsqr_mi_lstsq_f64's plus Zeff, the step's Gram sum and status
+ * words, independent of m -- and wr of tsqr_mi_working_r_size_f64_lstsq_rank doubles, the R-only entry's.
+ * Returns 0; 1 when ANY of x, r, jpvt, rank, a, b, wq, wr is null (decided first of all), then for the layout, size and leading
+ * dimension rules of tsqr_mi_lstsq_f64_lay (no text); 2 with a text for n > 64, nrhs > 16, refine outside 0 .. 4, rcond >= 1 or NaN,
+ * in that order -- all of 1 and 2 before any HIP call; 3 = TSQR_MI_ERROR_NOT_FINITE from the ladder, unchanged (Inf or NaN in A, a
+ * column norm outside [2^-511, 2^512), and still an exactly ZERO column among non-zero ones: the ladder rejects it before any rank
+ * decision; x, jpvt and *rank are then not written), or 3 with its own text when the Cholesky step on the retained columns meets a
+ * pivot that is not positive or not finite (x is then zero and *rank is written); or -(hipError_t).  Non-null pointers are not
+ * checked further: they must be valid memory of the sizes above.
+ * Not provided: the minimum-norm solution (a complete orthogonal decomposition), n > 64, the row-partitioned and batched forms,
+ * residual norms as an output.
+ */
+size_t tsqr_mi_working_q_size_f64_lstsq_rank(size_t m, size_t n, size_t nrhs);
+size_t tsqr_mi_working_r_size_f64_lstsq_rank(size_t m, size_t n, size_t nrhs);
+int tsqr_mi_lstsq_rank_f64(int a_layout, int b_layout, int reorth, int refine, double rcond,
+                           double* x, size_t ldx, double* r, size_t ldr, int* jpvt, int* rank,
+                           const double* a, size_t lda, const double* b, size_t ldb,
+                           size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
+
+/*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
  * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
  * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column

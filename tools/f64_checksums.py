@@ -1,5 +1,6 @@
 """SHA-256 (first 16 hex digits) of the results of the fp64 entries that take a tensor -- qr_f64_tensor, qr_f64_wide_tensor, lstsq_f64
-(3 right-hand sides), svd_f64_tensor with and without U, qrcp_f64_tensor with and without Q -- at 9211 x 51, 2^20 x 64, 100 x 7 and
+(3 right-hand sides), svd_f64_tensor with and without U, qrcp_f64_tensor with and without Q, lstsq_rank_f64 (x, r, jpvt and the rank, a
+line each; on the same 3 right-hand sides, the default rcond) -- at 9211 x 51, 2^20 x 64, 100 x 7 and
 65536 x 128, torch.randn with seed m + n generated on the device, handed over row-major ("row") and with column-major strides
 ("col"), reorth 0 and 1; at 9211 x 51 also the three entries that can run in place, with overwrite_a=True on a clone.  The entries are
 bitwise deterministic, so two builds of libtsqr_mi.so that are meant to compute the same thing must print the same table:
@@ -47,6 +48,12 @@ def table():
                     out[key + "qrcp1"] = (sha(q), sha(r), sha(p), bq.last_sweeps_f64())
                     r, p = bq.qrcp_f64_tensor(x, reorth=reorth, compute_q=False)
                     out[key + "qrcp0"] = (sha(r), sha(p))
+                    if hasattr(bq.lib(), "tsqr_mi_lstsq_rank_f64"):     # (absent from a --parent-lib older than the entry)
+                        xs, r, p, rank = bq.lstsq_rank_f64(x, b, reorth=reorth)
+                        out[key + "lstsq_rank x"] = (sha(xs), bq.last_sweeps_f64())
+                        out[key + "lstsq_rank r"] = (sha(r),)
+                        out[key + "lstsq_rank jpvt"] = (sha(p),)
+                        out[key + "lstsq_rank rank"] = (rank,)
                     if (m, n) == SHAPES[0]:                 # in place, on a clone (it keeps x's strides); the flag: q IS the clone
                         c = x.clone()
                         q, r = bq.qr_f64_tensor(c, reorth=reorth, overwrite_a=True)
@@ -83,12 +90,15 @@ def main():
     tree = table_in_child("")
     parent = table_in_child(args.parent_lib) if args.parent_lib else None
     for key in sorted(tree):
-        mark = "" if parent is None else (" ==" if parent.get(key) == tree[key] else " != %s" % (parent.get(key),))
+        mark = "" if parent is None else (" new" if key not in parent else " ==" if parent[key] == tree[key] else " != %s" % (parent[key],))
         print(key, tree[key], mark.strip())
     if parent is None:
         return 0
-    print("entries:", len(tree), "all equal:", parent == tree)
-    return 0 if parent == tree else 2
+    # a line the parent library cannot print (an entry it does not have) is marked new and does not count; every line it prints must
+    # be there and equal
+    equal = all(key in tree and tree[key] == parent[key] for key in parent)
+    print("entries:", len(tree), "of the parent:", len(parent), "all of the parent's equal:", equal)
+    return 0 if equal else 2
 
 
 if __name__ == "__main__":

@@ -43,7 +43,13 @@ picks some): six arms interleaved call by call on the same operands in this proc
 tsqr_mi_r_f64_lay, tsqr_mi_svd_f64 with jobu = 0 and with jobu = 1; per arm the median of --calls blocking calls, the ladder sweeps, what
 the pivoting kernel and the dense apply add to the entry under them, and the ratio jobq = 0 / svd jobu = 0: the two answers to "what is
 the numerical rank".  Writes the JSON to --qrcp-out (default profiles/fp64_qrcp_speed.json) and prints it.  --qrcp-arms qrcp_jobq1
-runs that arm alone and writes no file: the run to put under a kernel trace (profiles/fp64_qrcp_kernel_stats_2p20x64.csv)."""
+runs that arm alone and writes no file: the run to put under a kernel trace (profiles/fp64_qrcp_kernel_stats_2p20x64.csv).
+
+--lstsq-rank: instead, the rank-aware least-squares entry (tsqr_mi_lstsq_rank_f64, refine 0 and 1, 3 right-hand sides, the default
+rcond, reorth = 0, column-major Gaussian operands) at the shapes of --svd, next to tsqr_mi_lstsq_f64_lay at refine 1, tsqr_mi_qrcp_f64
+with jobq = 0 and tsqr_mi_r_f64_lay: one process, the five arms interleaved call by call, the median of --calls blocking calls.  Writes
+the JSON to --lstsq-rank-out (default profiles/fp64_lstsq_rank_speed.json) and prints it.  --lstsq-rank-arms lstsq_rank_refine1 runs
+that arm alone and writes no file: the run to put under a kernel trace (profiles/fp64_lstsq_rank_kernel_stats_2p20x64.csv)."""
 import argparse
 import json
 import math
@@ -690,6 +696,66 @@ def qrcp(torch, bq, calls, warmup, only, only_arms=()):
     return out
 
 
+def lstsq_rank(torch, bq, calls, warmup, only, only_arms=()):
+    """--lstsq-rank: tsqr_mi_lstsq_rank_f64 (refine 0 and 1, the default rcond, 3 right-hand sides) next to tsqr_mi_lstsq_f64_lay at
+    refine 1, tsqr_mi_qrcp_f64 at jobq 0 and tsqr_mi_r_f64_lay, column-major Gaussian operands, reorth 0.  No time is set in advance: the
+    expected structure of a call is the jobq 0 call plus one dense Gram pass and refine + 1 dense passes, and the JSON reports the
+    measured sum next to those parts."""
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    nrhs = 3
+    out = {"tool": "f64_speed --lstsq-rank", "calls": calls, "warmup": warmup, "reorth": 0, "layout": "column-major", "nrhs": nrhs,
+           "rcond": "default (max(m, n) 2^-52)", "cases": []}
+    for lg, n in SVD_SHAPES:
+        if only and "2p%dx%d" % (lg, n) not in only:
+            continue
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g).t().contiguous()      # (n, m): column-major m x n
+        b = torch.randn(m, nrhs, dtype=torch.float64, device="cuda", generator=g).t().contiguous()
+        x = [torch.empty(nrhs, n, dtype=torch.float64, device="cuda") for _ in range(3)]
+        r = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(5)]
+        jp = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(3)]
+        rank = [ctypes.c_int(-1) for _ in range(2)]
+        work = job_work_spaces(torch, L, ("qrcp0", "r"), m, n)
+        stream = work["r"][2][2]
+        sized = {}
+        for key, suffix in (("rank", "_lstsq_rank"), ("lstsq", "_lstsq")):
+            wq = torch.empty(getattr(L, "tsqr_mi_working_q_size_f64" + suffix)(m, n, nrhs), dtype=torch.float64, device="cuda")
+            wr = torch.empty(getattr(L, "tsqr_mi_working_r_size_f64" + suffix)(m, n, nrhs), dtype=torch.float64, device="cuda")
+            sized[key] = (wq, wr, (vp(wq.data_ptr()), vp(wr.data_ptr()), stream))
+        ap_, bp_ = vp(a.data_ptr()), vp(b.data_ptr())
+        rank_arm = lambda i, refine: (lambda: L.tsqr_mi_lstsq_rank_f64(0, 0, 0, refine, -1.0, vp(x[i].data_ptr()), n, vp(r[i].data_ptr()), n,
+                                                                     vp(jp[i].data_ptr()), ctypes.byref(rank[i]), ap_, m, bp_, m, m, n, nrhs,
+                                                                     *sized["rank"][2]))
+        arms = [("lstsq_rank_refine0", rank_arm(0, 0)), ("lstsq_rank_refine1", rank_arm(1, 1)),
+                ("lstsq_f64_lay_refine1", lambda: L.tsqr_mi_lstsq_f64_lay(0, 0, 0, 1, vp(x[2].data_ptr()), n, vp(r[2].data_ptr()), n, ap_, m, bp_, m,
+                                                                         m, n, nrhs, *sized["lstsq"][2])),
+                ("qrcp_jobq0", lambda: L.tsqr_mi_qrcp_f64(0, 0, 0, 0, None, m, vp(r[3].data_ptr()), n, vp(jp[2].data_ptr()), ap_, m, m, n,
+                                                          *work["qrcp0"][2])),
+                ("r_f64_lay", lambda: L.tsqr_mi_r_f64_lay(0, 0, vp(r[4].data_ptr()), n, ap_, m, m, n, *work["r"][2]))]
+        arms, med, sweeps = time_arms(bq, arms, calls, warmup, only_arms, L.tsqr_mi_last_sweeps_f64)
+        if only_arms:
+            out["cases"].append({"m": m, "n": n, "median_ms": med})
+            continue
+        case = {"m": m, "n": n}
+        case.update({name + "_median_ms": med[name] for name, _ in arms})
+        # the parts a call is expected to consist of: the jobq 0 call, the dense Gram pass with the step (refine 0 minus jobq 0 minus one
+        # dense pass, itself the difference of the two refine counts)
+        dense_pass = med["lstsq_rank_refine1"] - med["lstsq_rank_refine0"]
+        case.update({"one_dense_pass_ms": dense_pass, "refine0_minus_jobq0_ms": med["lstsq_rank_refine0"] - med["qrcp_jobq0"],
+                     "gram_and_step_ms": med["lstsq_rank_refine0"] - med["qrcp_jobq0"] - dense_pass,
+                     "refine1_over_lstsq_f64_refine1": med["lstsq_rank_refine1"] / med["lstsq_f64_lay_refine1"],
+                     "rank": rank[1].value, "ladder_sweeps": sweeps["lstsq_rank_refine1"],
+                     "r_and_jpvt_bitwise_equal_jobq0": bool(torch.equal(r[1], r[3]) and torch.equal(jp[1], jp[2])),
+                     "x_max_abs_diff_to_lstsq_f64": float((x[1] - x[2]).abs().max().item())})
+        out["cases"].append(case)
+        del a, b, x, r, jp, work, sized
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=None, help="blocking calls per case or arm (default 50; --wide-row-major: 20)")
@@ -710,6 +776,9 @@ def main():
     ap.add_argument("--qrcp", action="store_true", help="time tsqr_mi_qrcp_f64 (jobq 1 and 0) next to tsqr_mi_qr_f64_lay, tsqr_mi_r_f64_lay and tsqr_mi_svd_f64")
     ap.add_argument("--qrcp-arms", default="", help="--qrcp: run only these arms (qrcp_jobq1, qr_f64_lay, qrcp_jobq0, r_f64_lay, svd_jobu0, svd_jobu1) and write no file")
     ap.add_argument("--qrcp-out", default=os.path.join(ROOT, "profiles", "fp64_qrcp_speed.json"), help="--qrcp: the JSON file ('' writes none)")
+    ap.add_argument("--lstsq-rank", action="store_true", help="time tsqr_mi_lstsq_rank_f64 (refine 0 and 1) next to tsqr_mi_lstsq_f64_lay, tsqr_mi_qrcp_f64 (jobq 0) and tsqr_mi_r_f64_lay")
+    ap.add_argument("--lstsq-rank-arms", default="", help="--lstsq-rank: run only these arms (lstsq_rank_refine0, lstsq_rank_refine1, lstsq_f64_lay_refine1, qrcp_jobq0, r_f64_lay) and write no file")
+    ap.add_argument("--lstsq-rank-out", default=os.path.join(ROOT, "profiles", "fp64_lstsq_rank_speed.json"), help="--lstsq-rank: the JSON file ('' writes none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp64_wide_rowmajor_speed.json"), help="--wide-row-major: the JSON file")
     args = ap.parse_args()
     wide_rm = args.wide_row_major or args.wide_col_only
@@ -739,6 +808,14 @@ def main():
         out = qrcp(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], only_arms)
         if args.qrcp_out and not only_arms:
             with open(args.qrcp_out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        print(json.dumps(out))
+        return
+    if args.lstsq_rank:
+        only_arms = [c for c in args.lstsq_rank_arms.split(",") if c]
+        out = lstsq_rank(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], only_arms)
+        if args.lstsq_rank_out and not only_arms:
+            with open(args.lstsq_rank_out, "w") as f:
                 f.write(json.dumps(out, indent=1) + "\n")
         print(json.dumps(out))
         return

@@ -123,6 +123,10 @@ def _c_signatures():
         "tsqr_mi_working_q_size_f64_qrcp": (sz, [sz, sz, ci]), "tsqr_mi_working_r_size_f64_qrcp": (sz, [sz, sz, ci]),
         # (a_layout, q_layout, jobq, reorth, q, ldq, r, ldr, jpvt, a, lda, m, n, wq, wr, stream)
         "tsqr_mi_qrcp_f64": (ci, [ci, ci, ci, ci, vp, sz, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp]),
+        "tsqr_mi_working_q_size_f64_lstsq_rank": (sz, [sz, sz, sz]), "tsqr_mi_working_r_size_f64_lstsq_rank": (sz, [sz, sz, sz]),
+        # (a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs, wq, wr, stream)
+        "tsqr_mi_lstsq_rank_f64": (ci, [ci, ci, ci, ci, ctypes.c_double, vp, sz, vp, sz, vp, ctypes.POINTER(ci), vp, sz, vp, sz, sz, sz, sz,
+                                        vp, vp, vp]),
     }
 
 
@@ -135,7 +139,8 @@ OPTIONAL_SYMBOLS = {
     "tsqr_mi_lstsq_f64", "tsqr_mi_working_q_size_f64_lstsq", "tsqr_mi_working_r_size_f64_lstsq",
     "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay",
     "tsqr_mi_working_q_size_f64_svd", "tsqr_mi_working_r_size_f64_svd", "tsqr_mi_svd_f64", "tsqr_mi_last_jacobi_sweeps_f64",
-    "tsqr_mi_working_q_size_f64_qrcp", "tsqr_mi_working_r_size_f64_qrcp", "tsqr_mi_qrcp_f64"}
+    "tsqr_mi_working_q_size_f64_qrcp", "tsqr_mi_working_r_size_f64_qrcp", "tsqr_mi_qrcp_f64",
+    "tsqr_mi_working_q_size_f64_lstsq_rank", "tsqr_mi_working_r_size_f64_lstsq_rank", "tsqr_mi_lstsq_rank_f64"}
 
 _lib = None
 
@@ -428,6 +433,7 @@ _F64_R = _F64Entry("r_f64", 64, "tsqr_mi_r_f64", "_f64_r")
 _F64_LSTSQ = _F64Entry("lstsq_f64", 64, "tsqr_mi_lstsq_f64", "_f64_lstsq")
 _F64_SVD = _F64Entry("svd_f64", 64, "tsqr_mi_svd_f64", "_f64_svd")       # (its size functions take jobu behind m and n)
 _F64_QRCP = _F64Entry("qrcp_f64", 64, "tsqr_mi_qrcp_f64", "_f64_qrcp")   # (jobq behind m and n)
+_F64_LSTSQ_RANK = _F64Entry("lstsq_rank_f64", 64, "tsqr_mi_lstsq_rank_f64", "_f64_lstsq_rank")   # (nrhs behind m and n; no _lay form)
 
 
 def _null_state(fn, *scalars):
@@ -695,6 +701,60 @@ def lstsq_f64(a, b, reorth=False, refine=1, stream=None):
         raise LstsqError(st, "lstsq_f64: state %d: %s" % (st, last_error()))
     x = x.t()
     return (x[:, 0] if vector else x), r.t()
+
+
+class LstsqRankError(_F64StateError):
+    """lstsq_rank_f64 ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
+
+
+def lstsq_rank_f64(a, b, rcond=None, reorth=False, refine=1, stream=None):
+    """The rank of a and the basic solution of min ||a X - b||_F on its numerically independent columns, in double precision
+    (tsqr_mi_lstsq_rank_f64: include/tsqr_mi.h has the method and the measured accuracy).  a: m x n float64 GPU tensor, 1 <= n <= 64,
+    n <= m; b: m x nrhs (or m) float64 GPU tensor, nrhs <= 16; any strides, read where they lie or copied once under the rule of
+    lstsq_f64; neither is written, and the result has the same bits whichever way an operand is stored.  rcond: column j of the pivoted
+    R is retained when R_jj > rcond R_00; None: max(m, n) 2^-52; must be below 1.  reorth: the R-only ladder's argument; refine:
+    correction passes, 0 .. 4.  Blocking.  Returns (x, r, p, rank): x n x nrhs (n when b is one-dimensional) with exact zeros in the rows
+    p[rank:] and the least-squares solution on the columns p[:rank] in the others -- the basic solution, not the minimum-norm one;
+    r (n x n upper triangular) and p (n int32 pivots, 0-based, a[:, p] = Q r) bitwise qrcp_f64's with compute_q=False on the same a;
+    rank a Python int.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for shapes that do not fit together,
+    LstsqRankError (.state) when the entry does not run the shape or returns a state other than 0: error_not_finite from the ladder (Inf
+    or NaN in a, a column norm outside [2^-511, 2^512), or an exactly zero column among non-zero ones) or from the Cholesky step on the
+    retained columns."""
+    import math
+    import torch
+    entry = _F64_LSTSQ_RANK
+    _check_f64_tensors(entry.name, (("a", a), ("b", b)))
+    if a.dim() != 2 or b.dim() not in (1, 2) or b.shape[0] != a.shape[0]:
+        raise ValueError("lstsq_rank_f64: a must be m x n and b m x nrhs (or m), got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    vector = b.dim() == 1
+    b2 = b.unsqueeze(1) if vector else b
+    m, n = a.shape
+    nrhs = b2.shape[1]
+    rc = -1.0 if rcond is None else float(rcond)
+    # (the C entry rejects a null pointer before it looks at a size, so a shape it does not run is decided here, by its rules and in its
+    # order, without a call)
+    if m == 0 or n == 0 or nrhs == 0 or n > m:
+        raise LstsqRankError(error_invalid_matrix_size, "lstsq_rank_f64: state %d for a %d x %d, nrhs %d" % (error_invalid_matrix_size, m, n, nrhs))
+    for bad, text in ((n > entry.nmax, "n <= 64"), (nrhs > 16, "nrhs <= 16"), (not 0 <= int(refine) <= 4, "0 <= refine <= 4"),
+                      (math.isnan(rc) or rc >= 1.0, "rcond < 1")):
+        if bad:
+            raise LstsqRankError(error_unsupported_mode, "lstsq_rank_f64: state %d for a %d x %d, nrhs %d, refine %d, rcond %r: "
+                                 "tsqr_mi_lstsq_rank_f64 supports %s" % (error_unsupported_mode, m, n, nrhs, int(refine), rcond, text))
+    ac, lda, a_layout = _operand_f64(a)
+    bc, ldb, b_layout = _operand_f64(b2)
+    x = torch.empty((nrhs, n), dtype=torch.float64, device=a.device)
+    r = torch.empty((n, n), dtype=torch.float64, device=a.device)
+    p = torch.empty((n,), dtype=torch.int32, device=a.device)
+    rank = ctypes.c_int(-1)
+    wq, wr = entry.work_space(a.device, m, n, nrhs)
+    with torch.cuda.device(a.device):
+        st = _f64_call(entry.symbol, lib().tsqr_mi_lstsq_rank_f64, stream, a_layout, b_layout, int(bool(reorth)), int(refine), rc,
+                       x.data_ptr(), n, r.data_ptr(), n, p.data_ptr(), ctypes.byref(rank), ac.data_ptr(), lda, bc.data_ptr(), ldb, m, n, nrhs,
+                       wq.data_ptr(), wr.data_ptr())
+    if st:
+        raise LstsqRankError(st, "lstsq_rank_f64: state %d: %s" % (st, last_error()))
+    x = x.t()
+    return (x[:, 0] if vector else x), r.t(), p, int(rank.value)
 
 
 class QrError(_F64StateError):

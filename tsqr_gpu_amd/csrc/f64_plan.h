@@ -142,6 +142,14 @@ inline void f64_lsq_update_launch(hipStream_t st, double* xw, double* x, size_t 
 	                   first, last, dprev, guard);
 }
 
+// ---- tsqr_mi_lstsq_rank_f64 (n <= 64, nrhs <= 16) --------------------------------------------------------------------------------------
+// The ladder is the R-only entry's and the pivoted QR of its R0 is tsqr_mi_qrcp_f64's with jobq = 0; the dense Gram pass of the
+// CholeskyQR step and every least-squares pass behind it run on f64r_plan's grid (lsq_rank_f64.hip has the kernels and their launchers).
+// A partial is never more than the ntri tiles of a Gram partial: wr is the R-only entry's.
+// wq (doubles): [the F64L_WQ layout][Zeff, NP x NP (ld NP): 4096][the step's summed Gram tiles: 10 tiles of 256 + the row-count word of
+// the reduction][status words: [0] the rank, [1] the step's verdict: 8]
+constexpr size_t F64K_ZEFF = F64L_WQ, F64K_G1 = F64K_ZEFF + 4096, F64K_STATUS = F64K_G1 + 10 * 256 + 8, F64K_WQ = F64K_STATUS + 8;
+
 // ---- tsqr_mi_svd_f64 (n <= 64) ------------------------------------------------------------------------------------------------------------
 // jobu = 1 runs the ladder of tsqr_mi_qr_f64_lay on the F64_WQ layout with R in the block behind it, then svd_r_f64_kernel and
 // applyd_f64_kernel.  wq (doubles): [the F64_WQ layout][R, n x n with ld 64: 4096][W, NP x NP with ld NP: 4096][status words: 8]

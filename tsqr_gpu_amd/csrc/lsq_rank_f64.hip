@@ -1,10 +1,12 @@
-// lsq_rank_f64.hip -- the device passes of a rank-aware fp64 least-squares solve (n <= 64, nrhs <= 16) and their launchers: preparatory
-// code that NO entry of libtsqr_mi.so calls yet (DESIGN.md section 9 says what an entry still needs).  Included by selftest.hip alone,
-// behind tsqr_f64.hip and f64_plan.h, so the kernels are built into the test library only and the product library does not carry them:
-//   lsq_rank_f64_kernel  : the rank from the diagonal of a pivoted R and Zeff = P1 inverse(R11), the inverse factor of the retained
-//                          columns, on one workgroup
-//   lsq_dense_f64_kernel : lsq_f64_kernel for a dense Z staged in LDS
-// The third pass, X <- X + Z D for a dense Z, is lsq_update_f64_kernel<true> (tsqr_f64.hip).
+// lsq_rank_f64.hip -- the device passes of the rank-aware fp64 least-squares entry (tsqr_mi_lstsq_rank_f64: n <= 64, nrhs <= 16;
+// include/tsqr_mi.h has the method, DESIGN.md section 9 the figures) and their launchers.  Included by tsqr_mi.hip and selftest.hip behind
+// tsqr_f64.hip and f64_plan.h:
+//   lsq_rank_f64_kernel      : the rank from the diagonal of a pivoted R and Zeff = P1 inverse(R11), the inverse factor of the retained
+//                              columns, on one workgroup
+//   gramq_dense_f64_kernel   : gramq_f64_kernel for a dense Z staged in LDS: per-workgroup partials of (A Zeff)^T (A Zeff)
+//   lsq_rank_step_f64_kernel : the CholeskyQR step on the retained columns, G1 = Rc^T Rc and Zeff <- Zeff inverse(Rc), on one workgroup
+//   lsq_dense_f64_kernel     : lsq_f64_kernel for a dense Z staged in LDS
+// The last pass, X <- X + Z D for a dense Z, is lsq_update_f64_kernel<true> (tsqr_f64.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,6 +97,71 @@ __global__ __launch_bounds__(256) void lsq_dense_f64_kernel(const LsqArgs64 a) {
 	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NT * 256, wv, lane);
 }
 
+// The dense-Z form of gramq_f64_kernel (the CholeskyQR step of the rank-aware solve): what lsq_dense_f64_kernel is to lsq_f64_kernel.
+// Z is a dense NP x NP matrix (ld NP, zero padded), so every output tile of stage 1 sums all 4 NT k-blocks, in the order
+// 0 .. 4 NT - 1, and the 4 NT^2 operands are staged in LDS once per workgroup in operand order: operand (jt, kb) is 64 consecutive
+// doubles, lane l reads element l.  The tile loop, the prefetch, load_rows_rm, the Gram MFMAs and the partials (wg_sum4_store, NTRI
+// tiles) are gramq_f64_kernel's, line for line; a kernel of its own for the reason given above, and kept in step by hand.  On an upper
+// triangular Z it gives gramq_f64_kernel's bits whenever no product of A with a skipped zero is non-finite.
+template <int NT, bool AROW>
+__global__ __launch_bounds__(256) void gramq_dense_f64_kernel(const GramQArgs64 a) {
+	constexpr int NP = 16 * NT, KB = 4 * NT, NTRI = (NT * (NT + 1)) / 2;
+	__shared__ double red[2 * NTRI * 256];
+	__shared__ double zl[NT * KB * 64];
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
+	const int gw = blockIdx.x * 4 + wv;
+	for (int e = threadIdx.x; e < NT * KB * 64; e += 256) {
+		const int l = e & 63, b = e >> 6, jt = b / KB, kb = b % KB;
+		zl[e] = a.z[(size_t)(16 * jt + (l & 15)) * NP + 4 * kb + (l >> 4)];
+	}
+	__syncthreads();                                       // (every wave of the workgroup, idle ones included)
+	f64x4 acc[NTRI];
+#pragma unroll
+	for (int t = 0; t < NTRI; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+	if (gw < a.nwaves) {
+		// a tile beyond the last reads nothing and leaves zeros (gramq_f64_kernel's load_tile)
+		auto load_tile = [&](double (&av)[KB], int tile) {
+			const size_t row = (size_t)tile * 16 + li;
+			const bool live = tile < a.ntiles && row < a.m;
+			if constexpr (AROW) load_rows_rm<KB>(av, a.a, a.lda, row, live, a.n, lq);
+			else {
+#pragma unroll
+				for (int kb = 0; kb < KB; kb++) {
+					const int col = 4 * kb + lq;
+					av[kb] = (live && col < a.n) ? a.a[(size_t)col * a.lda + row] : 0.0;
+				}
+			}
+		};
+		double av[KB], nx[KB];
+		load_tile(av, gw);
+		for (int tile = gw; tile < a.ntiles; tile += a.nwaves) {
+			load_tile(nx, tile + a.nwaves);
+			f64x4 qt[NT];
+#pragma unroll
+			for (int jt = 0; jt < NT; jt++) {
+				qt[jt] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+				for (int kb = 0; kb < KB; kb++)
+					qt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kb], zl[(jt * KB + kb) * 64 + lane], qt[jt], 0, 0, 0);
+			}
+#pragma unroll
+			for (int reg = 0; reg < 4; reg++) {
+				int idx = 0;
+#pragma unroll
+				for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+					for (int tj = ti; tj < NT; tj++) {
+						acc[idx] = __builtin_amdgcn_mfma_f64_16x16x4f64(qt[ti][reg], qt[tj][reg], acc[idx], 0, 0, 0);
+						idx++;
+					}
+			}
+#pragma unroll
+			for (int kb = 0; kb < KB; kb++) av[kb] = nx[kb];
+		}
+	}
+	wg_sum4_store(acc, red, a.part + (size_t)blockIdx.x * NTRI * 256, wv, lane);
+}
+
 // ---- the rank-aware least-squares solve: rank and inverse factor of the retained columns from R and jpvt ----------------------------------
 struct LsqRankArgs64 {
 	const double* r; size_t ldr;         // n x n upper triangular (only i <= j is read): qrcp_r_f64_kernel's R, diag(R) >= 0 and non-increasing
@@ -157,6 +224,94 @@ __global__ __launch_bounds__(1024) void lsq_rank_f64_kernel(const LsqRankArgs64 
 	}
 }
 
+// ---- the CholeskyQR step on the retained columns -----------------------------------------------------------------------------------------
+struct LsqRankStepArgs64 {
+	const double* gsum;                  // the summed tiles of gramq_dense_f64_kernel on Zeff: G1 = (A Zeff)^T (A Zeff), NTRI tiles of 256
+	const unsigned* rank;                // the device word lsq_rank_f64_kernel wrote: k (taken as min(k, n))
+	double* zeff;                        // NP x NP (ld NP), in and out: Zeff <- Zeff inverse(Rc), wholly written
+	unsigned* status;                    // device word [0] the verdict: 0 ok, 1 a pivot of the Cholesky factorisation not positive or not finite
+	unsigned* host_status;               // device-visible alias of a pinned host word receiving the verdict; null: not wanted
+	int n;
+};
+
+// One workgroup, everything in LDS (column-major, ld 64).  Only G1[:k, :k] is read, from the tiles on and above the diagonal (entry
+// (i, j), i <= j, of tile pair (i >> 4, j >> 4): wg_sum4_store's layout).  G1 = I + a perturbation of a few 1e-2 at most, so the
+// factorisation G1[:k, :k] = Rc^T Rc is plain right-looking Cholesky on the upper triangle: no shift, no acceptance ladder.  Step p:
+// every thread reads the pivot g = M_pp; not positive or not finite (a NaN fails g > 0) ends the loop for all threads at once, verdict 1;
+// else row p is divided by sqrt(g) -- one barrier -- and entry (i, j), p < i <= j < k, takes one fused multiply-add, M_ij <-
+// fma(-Rc_pi, Rc_pj, M_ij) -- one barrier.  Entry (i, j) of Rc is so a fixed chain of i fused multiply-adds, a square root and a
+// division.  inverse(Rc) then comes from lsq_rank_f64_kernel's back substitution (wave per column, lane per row, terms l = j .. i + 1
+// in that order), and Zeff <- Zeff inverse(Rc): entry (i, j), j < k, sums l = 0 .. j in that order, one fused multiply-add each; the
+// columns j >= k are written as zeros.  A zero row of Zeff (the rows jpvt[k:] and the padding) sums products of exact zeros with
+// finite numbers and stays an exact zero, and so does an entry (jpvt[i], j) with j < i: the zero structure of lsq_rank_f64_kernel's Zeff
+// is kept.  Every number is a fixed function of the input: the same bits on every run.  k = 0 writes Zeff = 0 and verdict 0; verdict 1
+// writes Zeff = 0 too (the passes behind it then leave X = 0, and the entry reports state 3).  No scratch; 96.5 KB of static LDS:
+// this file is built for gfx950 alone, whose workgroups have 160 KB.
+__global__ __launch_bounds__(1024) void lsq_rank_step_f64_kernel(const LsqRankStepArgs64 a) {
+	__shared__ double M[64 * 64], Zi[64 * 64], Ze[64 * 64];
+	static_assert(sizeof(M) + sizeof(Zi) + sizeof(Ze) <= 160 * 1024, "lsq_rank_step_f64_kernel relies on the 160 KB of LDS of gfx950");
+	const int t = threadIdx.x, lane = t & 63, wv = t >> 6, n = a.n;
+	const int NT = (n + 15) / 16, NP = 16 * NT;
+	const int k = min((int)a.rank[0], n);                  // (uniform: every thread reads the same word)
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		double g = 0.0;
+		if (i <= j && j < k) {
+			const int ti = i >> 4, tj = j >> 4, ri = i & 15;
+			const int idx = ti * NT - (ti * (ti - 1)) / 2 + (tj - ti);
+			g = a.gsum[(size_t)idx * 256 + (ri >> 2) * 64 + (ri & 3) * 16 + (j & 15)];
+		}
+		M[e] = g;
+		Zi[e] = 0.0;
+		Ze[e] = (i < NP && j < NP) ? a.zeff[(size_t)j * NP + i] : 0.0;
+	}
+	__syncthreads();
+	bool bad = false;
+	for (int p = 0; p < k; p++) {
+		const double g = M[p * 64 + p];
+		if (!(g > 0.0) || !(g < __builtin_inf())) { bad = true; break; }     // (uniform: the same LDS word for every thread)
+		const double rpp = sqrt(g);
+		__syncthreads();                                  // every thread has read the pivot
+		if (t < 64 && t >= p && t < k) M[t * 64 + p] = t == p ? rpp : M[t * 64 + p] / rpp;
+		__syncthreads();
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			if (i > p && i <= j && j < k) M[e] = __builtin_fma(-M[i * 64 + p], M[j * 64 + p], M[e]);
+		}
+		__syncthreads();
+	}
+	if (!bad) {
+		const double dii = lane < k ? M[lane * 64 + lane] : 1.0;
+		for (int j = wv; j < k; j += 16) {
+			double w = lane == j ? 1.0 : 0.0, z = 0.0;
+			for (int l = j; l >= 0; l--) {
+				const double q = w / dii;
+				const double zl = __shfl(q, l, 64);
+				if (lane == l) z = zl;
+				if (lane < l) w = __builtin_fma(-M[l * 64 + lane], zl, w);
+			}
+			if (lane <= j) Zi[j * 64 + lane] = z;
+		}
+	}
+	__syncthreads();
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		if (i < NP && j < NP) {
+			double s = 0.0;
+			if (!bad && j < k)
+				for (int l = 0; l <= j; l++) s = __builtin_fma(Ze[l * 64 + i], Zi[j * 64 + l], s);
+			a.zeff[(size_t)j * NP + i] = s;
+		}
+	}
+	if (t == 0) {
+		a.status[0] = bad ? 1u : 0u;
+		if (a.host_status) { volatile unsigned* hs = a.host_status; hs[0] = bad ? 1u : 0u; }
+	}
+}
+
 }  // namespace tsqrmi
 
 namespace {
@@ -164,6 +319,18 @@ namespace {
 // lsq_rank_f64_kernel on stream st: one workgroup
 inline void f64k_rank_launch(hipStream_t st, const tsqrmi::LsqRankArgs64& ka) {
 	hipLaunchKernelGGL(tsqrmi::lsq_rank_f64_kernel, dim3(1), dim3(1024), 0, st, ka);
+}
+// the dense Gram pass on stream st: gramq_dense_f64_kernel<NT, AROW> (ga.z dense) on the grid of f64r_gramq_launch
+inline void f64k_gramq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::GramQArgs64& ga, int a_layout = 0) {
+	with_nt(g.NT, [&](auto nt) {
+		with_layout(a_layout, [&](auto ar) {
+			hipLaunchKernelGGL((tsqrmi::gramq_dense_f64_kernel<decltype(nt)::value, decltype(ar)::value>), dim3(g.nblocks), dim3(256), 0, st, ga);
+		});
+	});
+}
+// lsq_rank_step_f64_kernel on stream st: one workgroup
+inline void f64k_step_launch(hipStream_t st, const tsqrmi::LsqRankStepArgs64& sa) {
+	hipLaunchKernelGGL(tsqrmi::lsq_rank_step_f64_kernel, dim3(1), dim3(1024), 0, st, sa);
 }
 // one dense pass on stream st: lsq_dense_f64_kernel<NT, AROW, BROW> (la.z dense) on the grid of f64r_lsq_launch
 inline void f64k_lsq_launch(hipStream_t st, const F64Plan& g, const tsqrmi::LsqArgs64& la, int a_layout = 0, int b_layout = 0) {

@@ -8,7 +8,7 @@
 #include "tsqr_f64.hip"
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
-#include "lsq_rank_f64.hip"                     // (the test library alone: no entry calls these passes yet)
+#include "lsq_rank_f64.hip"
 #include "f32_plan.h"
 #include "launch_util.h"
 

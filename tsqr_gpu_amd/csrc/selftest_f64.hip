@@ -210,7 +210,7 @@ int tsqr_selftest_f64_lsq_update(double* xw, double* x, size_t ldx, const double
 	return f64_sync();
 }
 
-// ---- n <= 64, the passes of a rank-aware least-squares solve (lsq_rank_f64.hip: built into this library only) ------------------------------
+// ---- n <= 64, the passes of the rank-aware least-squares entry (tsqr_mi_lstsq_rank_f64; lsq_rank_f64.hip) -----------------------------------
 // lsq_dense_f64_kernel + reduction, one pass, with the arguments of tsqr_selftest_f64_lsq_lay: z is a dense NP x NP block (ld NP)
 int tsqr_selftest_f64_lsq_dense_lay(int a_layout, int b_layout, double* dsum, const double* a, size_t lda, const double* b, size_t ldb,
                                     size_t m, int n, int nrhs, const double* z, const double* x, double* part, size_t part_cap, int nwaves) {
@@ -234,6 +234,31 @@ int tsqr_selftest_f64_lsq_rank(const double* r, size_t ldr, const int* jpvt, dou
 	tsqrmi::LsqRankArgs64 ka{};
 	ka.r = r; ka.ldr = ldr; ka.jpvt = jpvt; ka.rcond = rcond; ka.zeff = zeff; ka.status = status; ka.host_status = nullptr; ka.n = n;
 	f64k_rank_launch(0, ka);
+	return f64_sync();
+}
+
+// gramq_dense_f64_kernel + reduction with the arguments of tsqr_selftest_f64_gramq_lay: z is a dense NP x NP block (ld NP).  Every
+// check, the null checks included, stands before any HIP call
+int tsqr_selftest_f64_gramq_dense_lay(int a_layout, double* gsum, const double* a, size_t lda, size_t m, int n, const double* z, double* part,
+                                      size_t part_cap, int nwaves) {
+	if (a_layout != 0 && a_layout != 1) return -100;
+	if (m == 0 || n <= 0 || n > (int)PW || lda < (a_layout ? (size_t)n : m) || !gsum || !a || !z || !part) return -100;
+	F64Plan g = f64r_plan(m, (size_t)n);
+	if (!f64_override(g, nwaves, g.ntri, part_cap)) return -100;
+	const tsqrmi::GramQArgs64 ga{a, lda, m, n, g.nunits, g.nwaves, z, part};
+	f64k_gramq_launch(0, g, ga, a_layout);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, gsum, part, g.nblocks, g.ntri * 256, (double)m);
+	return f64_sync();
+}
+
+// lsq_rank_step_f64_kernel through the product's launcher: gsum (the ntri summed tiles of G1) and rank[1] in; zeff (NP x NP, ld NP) in
+// and out; status[1] (the verdict) out.  Every check stands before any HIP call
+int tsqr_selftest_f64_lsq_rank_step(const double* gsum, const unsigned* rank, double* zeff, unsigned* status, int n) {
+	if (n <= 0 || n > (int)PW || !gsum || !rank || !zeff || !status) return -100;
+	tsqrmi::LsqRankStepArgs64 sa{};
+	sa.gsum = gsum; sa.rank = rank; sa.zeff = zeff; sa.status = status; sa.host_status = nullptr; sa.n = n;
+	f64k_step_launch(0, sa);
 	return f64_sync();
 }
 

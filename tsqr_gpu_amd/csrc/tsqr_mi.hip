@@ -37,6 +37,7 @@
 #include "tsqr_f64.hip"
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
+#include "lsq_rank_f64.hip"
 #include "f32_plan.h"
 #include "launch_util.h"
 #include "validate.hip"
@@ -2918,6 +2919,93 @@ int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth, double* q
 	if (const int rc = f64_job_prologue(jobq, a_layout, q_layout, q, ldq, a, lda, ldr, m, n, "tsqr_mi_qrcp_f64 supports n <= 64")) return rc;
 	return qrcp_f64_core(a_layout, q_layout, jobq, reorth, q, ldq, r, ldr, jpvt, a, lda, m, n, reinterpret_cast<double*>(wq),
 	                     reinterpret_cast<double*>(wr), stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The rank-aware least-squares entry (tsqr_mi_lstsq_rank_f64; n <= 64, nrhs <= 16; kernels: lsq_rank_f64.hip).  The ladder and the
+// pivoted QR of R0 are tsqr_mi_qrcp_f64's with jobq = 0, launch for launch: tsqr_mi_r_f64_lay as it stands with R0 into the caller's r
+// -- it blocks, it reads its verdict words -- then qrcp_r_f64_kernel in place on r with h == null.  Behind it, back to back on the idle
+// stream with one wait at the end: lsq_rank_f64_kernel (the rank into a status word and a pinned word, Zeff into wq[F64K_ZEFF]); the
+// CholeskyQR step on the retained columns -- gramq_dense_f64_kernel on Zeff, the reduction into wq[F64K_G1], lsq_rank_step_f64_kernel
+// (Zeff <- Zeff inverse(Rc), its verdict into a status word and a pinned word); refine + 1 passes, each lsq_dense_f64_kernel
+// (D = (A Zeff)^T (B - A X), X null the first time), the reduction and X <- X + Zeff D (lsq_update_f64_kernel<true>) under the
+// stagnation rule of lstsq_f64_core with its state in wq[F64L_DPREV].  The two pinned words are the thread's verdict words, which the
+// ladder has finished with when it returns (as svd_f64_core keeps its words).
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int lstsq_rank_f64_core(int a_layout, int b_layout, int reorth, int refine, double rcond, double* x, size_t ldx, double* r, size_t ldr,
+                        int* jpvt, int* rank, const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
+                        double* wq, double* wr, void* stream) {
+	const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+	if (const int rc = tsqr_mi_r_f64_lay(a_layout, reorth, r, ldr, a, lda, m, n, wq, wr, stream)) return rc;   // (state 3 included: nothing else ran)
+	tsqrmi::QrcpArgs64 pa{};
+	pa.r0 = r; pa.ldr0 = ldr; pa.r = r; pa.ldr = ldr; pa.jpvt = jpvt; pa.n = (int)n; pa.h = nullptr; pa.status = nullptr;
+	f64_qrcp_r_launch(st, pa);
+	HIPCHK(hipGetLastError());
+	volatile unsigned* words = t_own64.host;             // (the ladder allocated them and has read its verdicts: the stream is idle)
+	words[0] = 0u; words[1] = 1u;                        // (a step kernel that never reported reads as failed)
+	double *zeff = wq + F64K_ZEFF, *xw = wq + F64L_X, *dsum = wq + F64L_D;
+	unsigned* status = reinterpret_cast<unsigned*>(wq + F64K_STATUS);
+	tsqrmi::LsqRankArgs64 ka{};
+	ka.r = r; ka.ldr = ldr; ka.jpvt = jpvt; ka.rcond = rcond; ka.zeff = zeff; ka.status = status; ka.host_status = t_own64.dev; ka.n = (int)n;
+	f64k_rank_launch(st, ka);
+	HIPCHK(hipGetLastError());
+	const F64Plan g = f64r_plan(m, n);
+	if (g.nblocks <= 0) { t_last_error = "fp64 least-squares pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	const tsqrmi::GramQArgs64 ga{a, lda, m, (int)n, g.nunits, g.nwaves, zeff, wr};
+	f64k_gramq_launch(st, g, ga, a_layout);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(st, wq + F64K_G1, wr, g.nblocks, g.ntri * 256, (double)m);
+	HIPCHK(hipGetLastError());
+	tsqrmi::LsqRankStepArgs64 sa{};
+	sa.gsum = wq + F64K_G1; sa.rank = status; sa.zeff = zeff; sa.status = status + 1; sa.host_status = t_own64.dev + 1; sa.n = (int)n;
+	f64k_step_launch(st, sa);
+	HIPCHK(hipGetLastError());
+	for (int p = 0; p <= refine; p++) {
+		const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, (int)n, (int)nrhs, g.nunits, g.nwaves, zeff, p == 0 ? nullptr : xw, wr};
+		f64k_lsq_launch(st, g, la, a_layout, b_layout);
+		HIPCHK(hipGetLastError());
+		launch_reduce1(st, dsum, wr, g.nblocks, g.NT * 256, (double)m);
+		HIPCHK(hipGetLastError());
+		f64_lsq_update_launch<true>(st, xw, x, ldx, zeff, dsum, (int)n, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0, wq + F64L_DPREV,
+		                            p >= 2 ? 1 : 0);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	*rank = (int)words[0];
+	if (words[1] != 0u) {
+		t_last_error = "tsqr_mi_lstsq_rank_f64: the Cholesky step on the retained columns met a pivot that is not positive or not finite";
+		return TSQR_MI_ERROR_NOT_FINITE;
+	}
+	return TSQR_MI_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tsqr_mi_working_q_size_f64_lstsq_rank(size_t m, size_t n, size_t nrhs) { return (m == 0 || n == 0 || nrhs == 0) ? 0 : F64K_WQ; }
+size_t tsqr_mi_working_r_size_f64_lstsq_rank(size_t m, size_t n, size_t nrhs) {
+	return (m == 0 || n == 0 || nrhs == 0) ? 0 : f64r_wr_doubles(m, std::min(n, PW));
+}
+
+int tsqr_mi_lstsq_rank_f64(int a_layout, int b_layout, int reorth, int refine, double rcond, double* x, size_t ldx, double* r, size_t ldr,
+                           int* jpvt, int* rank, const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
+                           void* wq, void* wr, void* stream) {
+	// every state that does not need the device is decided here, before any HIP call; the null checks first of all
+	t_sweeps64 = 0;
+	if (!x || !r || !jpvt || !rank || !a || !b || !wq || !wr) return TSQR_MI_ERROR_INVALID_SIZE;
+	const F64Operand A{a_layout, m, n, lda}, B{b_layout, m, nrhs, ldb}, R{TSQR_MI_COL_MAJOR, n, n, ldr}, X{TSQR_MI_COL_MAJOR, n, nrhs, ldx};
+	if (const int rc = f64_prologue({A, B, R, X}, m, n, PW, "tsqr_mi_lstsq_rank_f64 supports n <= 64")) return rc;
+	if (nrhs > F64L_MAX_NRHS) { t_last_error = "tsqr_mi_lstsq_rank_f64 supports nrhs <= 16"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (refine < 0 || refine > F64L_MAX_REFINE) { t_last_error = "tsqr_mi_lstsq_rank_f64 supports 0 <= refine <= 4"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (!(rcond < 1.0)) { t_last_error = "tsqr_mi_lstsq_rank_f64 supports rcond < 1 (negative: max(m, n) 2^-52)"; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (rcond < 0.0) rcond = (double)std::max(m, n) * 0x1p-52;
+	return lstsq_rank_f64_core(a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs,
+	                           reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr), stream);
 }
 
 }  // extern "C"
