@@ -481,6 +481,33 @@ inline state_t lstsq_rank_fp64(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::lstsq_rank_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
+
+// Not in the reference: lstsq_rank_fp64 with the MINIMUM-NORM solution of the problem truncated at the pivoted-QR rank, LAPACK's dgelsy
+// (tsqr_mi_lstsq_minnorm_f64, include/tsqr_mi.h for the method, the definition and the measured accuracy).  The arguments, states and
+// r, jpvt, rank of lstsq_rank_fp64; every row of x may be non-zero; at full rank x is bitwise lstsq_rank_fp64's.
+template <bool Reorthogonalize>
+struct buffer_fp64_lstsq_minnorm : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t n, const std::size_t nrhs) { allocate_doubles(tsqr_mi_working_q_size_f64_lstsq_minnorm(m, n, nrhs), tsqr_mi_working_r_size_f64_lstsq_minnorm(m, n, nrhs)); }
+};
+
+template <bool Reorthogonalize>
+inline state_t lstsq_minnorm_fp64(
+		double* const x_ptr, const std::size_t ldx,
+		double* const r_ptr, const std::size_t ldr,
+		int* const jpvt_ptr, int* const rank,
+		const double* const a_ptr, const std::size_t lda,
+		const double* const b_ptr, const std::size_t ldb,
+		const std::size_t m, const std::size_t n, const std::size_t nrhs,
+		buffer_fp64_lstsq_minnorm<Reorthogonalize>& bf,
+		const double rcond = -1.0,
+		const int refine = 1,
+		handle_t const stream = nullptr,
+		const layout_t a_layout = col_major, const layout_t b_layout = col_major) {
+	const int st = tsqr_mi_lstsq_minnorm_f64(a_layout, b_layout, Reorthogonalize ? 1 : 0, refine, rcond, x_ptr, ldx, r_ptr, ldr, jpvt_ptr, rank,
+	                                         a_ptr, lda, b_ptr, ldb, m, n, nrhs, bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::lstsq_minnorm_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
 // Not in the reference: double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide, include/tsqr_mi.h for the
 // contract): qr_fp64 itself for n <= 64, whole-matrix CholeskyQR sweeps with the same ladder beyond.  Returns success_factorization,
 // error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.  a_layout, q_layout (tsqr_mi_qr_f64_wide_lay): the

@@ -543,7 +543,7 @@ int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth,
  * columns behind it and A P1 inverse(R11) is orthonormal to about 2e-2 only; after the step it is orthonormal to about
  * cond(A P1)^2 2^-53.  (5) refine + 1 passes X <- X + Zeff (A Zeff)^T (B - A X), each one pass over A and B, with the stagnation rule of
  * tsqr_mi_lstsq_f64 (0 <= refine <= 4).  Rows jpvt[rank:] of x are exact zeros, the other rows are the least-squares solution on the
- * columns jpvt[:rank] -- the basic solution, NOT the minimum-norm one.
+ * columns jpvt[:rank] -- the basic solution, NOT the minimum-norm one (tsqr_mi_lstsq_minnorm_f64 below).
  * Fixed point.  The iteration stops moving when Zeff^T A^T (B - A X) = 0.  Zeff^T = (R11 Rc)^-T P1^T has full row rank for any
  * non-singular R11 Rc, so that is (A P1)^T (B - A X) = 0, the normal equations of the retained columns: errors in R11 and Rc change
  * how fast the passes contract, about ||I - (A Zeff)^T (A Zeff)||, never where they stop.
@@ -571,8 +571,7 @@ int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth,
  * decision; x, jpvt and *rank are then not written), or 3 with its own text when the Cholesky step on the retained columns meets a
  * pivot that is not positive or not finite (x is then zero and *rank is written); or -(hipError_t).  Non-null pointers are not
  * checked further: they must be valid memory of the sizes above.
- * Not provided: the minimum-norm solution (a complete orthogonal decomposition), n > 64, the row-partitioned and batched forms,
- * residual norms as an output.
+ * Not provided: n > 64, the row-partitioned and batched forms, residual norms as an output.
  */
 size_t tsqr_mi_working_q_size_f64_lstsq_rank(size_t m, size_t n, size_t nrhs);
 size_t tsqr_mi_working_r_size_f64_lstsq_rank(size_t m, size_t n, size_t nrhs);
@@ -580,6 +579,56 @@ int tsqr_mi_lstsq_rank_f64(int a_layout, int b_layout, int reorth, int refine, d
                            double* x, size_t ldx, double* r, size_t ldr, int* jpvt, int* rank,
                            const double* a, size_t lda, const double* b, size_t ldb,
                            size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
+
+/*
+ * Minimum-norm rank-aware least squares in double precision (not in the reference): the arguments, operand rules, limits and states of
+ * tsqr_mi_lstsq_rank_f64, and its r, jpvt, *rank and tsqr_mi_last_sweeps_f64 BITWISE on the same operands; x is the MINIMUM-NORM solution
+ * of the problem truncated at the rank k of the pivoted QR: among all X that minimise ||Q1 Q1^T A X - B||_F, Q1 an orthonormal basis of
+ * the retained columns A P1, the one of least ||X||_F.  That is LAPACK's dgelsy (and scipy.linalg.lstsq with lapack_driver="gelsy") at
+ * the same rank.  dgelsd, numpy.linalg.lstsq and torch.linalg.lstsq truncate by SINGULAR VALUES instead: they agree with this entry
+ * when A has exact rank k, and differ by about (what the truncation discards) x cond(A P1) otherwise.  Every row of x may be non-zero.
+ * At full rank (k = n) x is BITWISE tsqr_mi_lstsq_rank_f64's.  Blocking, bitwise deterministic from call to call, the same bits for
+ * either layout of a and of b; nothing of size m is stored, A and B are never written, and A is read exactly as often as by the basic
+ * entry.
+ * Method, with P = [P1 P2] the pivoting and k the rank.  (1) - (3) as tsqr_mi_lstsq_rank_f64.  (4) The dense Gram pass of the CholeskyQR
+ * step runs on Zg: Zeff with column j = k .. n - 1 set to the unit vector e_jpvt[j].  The same tiles then hold G11 = (A Zeff)^T (A Zeff),
+ * bit for bit as before, and G12 = (A Zeff)^T A P2, taken from A itself and not from r: the ladder's R0 is inconsistent behind an exactly
+ * copied column, which is why the step exists.  The step runs unchanged: G11 = Rc^T Rc, Zeff <- Zeff inverse(Rc), A Zeff = Q1.
+ * (5) One workgroup (lsq_minnorm_f64_kernel) repeats that factorisation with G12 carried along, S12 = Rc^-T G12 = Q1^T A P2, and forms
+ * M = inverse(R11') S12 with inverse(R11') = P1^T Zeff upper triangular, so that S = Q1^T A P = R11' [I M]; C = I + M M^T and its plain
+ * Cholesky factor (C is SPD, cond(C) <= 1 + ||M||^2); and Zmn = P pinv(S): rows jpvt[:k] are inverse(C) inverse(R11'), rows jpvt[k:] are
+ * M^T inverse(C) inverse(R11'), columns >= k are zero.  (6) refine + 1 passes X <- X + Zmn (A Zeff)^T (B - A X): the passes of the basic
+ * entry with Zmn in place of Zeff as the factor of the update, under the same stagnation rule.
+ * Fixed point.  D = Q1^T (B - A X) = Q1^T B - S P^T X holds for the true S, because the part of A outside range(Q1) is orthogonal to
+ * Q1.  Every update lies in range(Zmn) = range(P [I; M^T]), so the iteration stops at S P^T X = Q1^T B with X in range(P [I; M^T]) =
+ * range((S P^T)^T): the minimum-norm solution of the truncated problem.  Errors in inverse(C) and inverse(R11') change how fast the
+ * passes contract, not where they stop; errors in M change where they stop, at about cond(A P1) 2^-53.
+ * Accuracy: bounded by what was measured (MI355X, refine = 1; profiles/fp64_lstsq_minnorm_accuracy.md has every figure).  On the seven
+ * cases of tests/pass_refs_f64_lsq_rank.py the error ||X - X*||_F / ||X*||_F against an extended-precision minimum-norm solution of the
+ * truncated problem stays within max(2 x LAPACK's, 4 n 2^-53), LAPACK's being numpy.linalg.lstsq on the same projected problem
+ * (Q1^T A, Q1^T B).  Measured / LAPACK's, Gaussian B then consistent B:
+ *   copied column 4096 x 16   2.5e-16 / 4.2e-15    5.3e-17 / 3.2e-15      rank 32 of 51, 1029 rows   8.1e-16 / 2.3e-15    3.7e-16 / 2.2e-15
+ *   rank 1 of 33, 777 rows    7.0e-16 / 7.9e-16    1.5e-16 / 5.5e-16      rank 40 of 64, 4097 rows   9.3e-13 / 8.4e-13    1.8e-14 / 7.1e-14
+ *   full rank 300 x 17        3.0e-16 / 1.1e-15    2.9e-17 / 1.3e-15      3 copied tail columns of 7 2.7e-16 / 7.5e-16    3.9e-17 / 7.7e-16
+ *   one column, 65 rows       1.4e-16 / 2.5e-16    0       / 2.0e-16
+ * On the copied column rows 4 and 11 of x agree to 9.6e-16 relative and ||X||_F is 0.148.  Cost over tsqr_mi_lstsq_rank_f64 (medians of
+ * 50 blocking calls, arms interleaved): 0.21 ms at n = 64 and 0.02 ms at n = 16, independent of m.
+ * Nothing is claimed beyond these seven cases, where cond(A P1) <= 1e4.  refine = 0 is not held to that bound (a model of the method
+ * has 4.0e-10 on rank 40 of 64 with a consistent B).
+ * Work space: wq of tsqr_mi_working_q_size_f64_lstsq_minnorm doubles -- the basic entry's plus Zmn, independent of m -- and wr of
+ * tsqr_mi_working_r_size_f64_lstsq_minnorm doubles, the basic entry's.
+ * Returns the states of tsqr_mi_lstsq_rank_f64 in its order, every text naming this entry, all of 1 and 2 before any HIP call; 3 from
+ * the ladder or from the Cholesky step as there, and 3 with its own text when the Cholesky factorisation of C meets a pivot that is not
+ * positive or not finite (x is then zero and *rank is written); or -(hipError_t).
+ * Not provided: truncation by singular values (dgelsd's definition), n > 64, the row-partitioned and batched forms, residual norms as an
+ * output.
+ */
+size_t tsqr_mi_working_q_size_f64_lstsq_minnorm(size_t m, size_t n, size_t nrhs);
+size_t tsqr_mi_working_r_size_f64_lstsq_minnorm(size_t m, size_t n, size_t nrhs);
+int tsqr_mi_lstsq_minnorm_f64(int a_layout, int b_layout, int reorth, int refine, double rcond,
+                              double* x, size_t ldx, double* r, size_t ldr, int* jpvt, int* rank,
+                              const double* a, size_t lda, const double* b, size_t ldb,
+                              size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
 
 /*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,

@@ -1,6 +1,6 @@
 """SHA-256 (first 16 hex digits) of the results of the fp64 entries that take a tensor -- qr_f64_tensor, qr_f64_wide_tensor, lstsq_f64
-(3 right-hand sides), svd_f64_tensor with and without U, qrcp_f64_tensor with and without Q, lstsq_rank_f64 (x, r, jpvt and the rank, a
-line each; on the same 3 right-hand sides, the default rcond) -- at 9211 x 51, 2^20 x 64, 100 x 7 and
+(3 right-hand sides), svd_f64_tensor with and without U, qrcp_f64_tensor with and without Q, lstsq_rank_f64 and the same with minimum_norm=True
+(x, r, jpvt and the rank, a line each; on the same 3 right-hand sides, the default rcond) -- at 9211 x 51, 2^20 x 64, 100 x 7 and
 65536 x 128, torch.randn with seed m + n generated on the device, handed over row-major ("row") and with column-major strides
 ("col"), reorth 0 and 1; at 9211 x 51 also the three entries that can run in place, with overwrite_a=True on a clone.  The entries are
 bitwise deterministic, so two builds of libtsqr_mi.so that are meant to compute the same thing must print the same table:
@@ -54,6 +54,12 @@ def table():
                         out[key + "lstsq_rank r"] = (sha(r),)
                         out[key + "lstsq_rank jpvt"] = (sha(p),)
                         out[key + "lstsq_rank rank"] = (rank,)
+                    if hasattr(bq.lib(), "tsqr_mi_lstsq_minnorm_f64"):  # (absent from a --parent-lib older than the entry)
+                        xs, r, p, rank = bq.lstsq_rank_f64(x, b, reorth=reorth, minimum_norm=True)
+                        out[key + "lstsq_minnorm x"] = (sha(xs), bq.last_sweeps_f64())
+                        out[key + "lstsq_minnorm r"] = (sha(r),)
+                        out[key + "lstsq_minnorm jpvt"] = (sha(p),)
+                        out[key + "lstsq_minnorm rank"] = (rank,)
                     if (m, n) == SHAPES[0]:                 # in place, on a clone (it keeps x's strides); the flag: q IS the clone
                         c = x.clone()
                         q, r = bq.qr_f64_tensor(c, reorth=reorth, overwrite_a=True)

@@ -49,7 +49,10 @@ runs that arm alone and writes no file: the run to put under a kernel trace (pro
 rcond, reorth = 0, column-major Gaussian operands) at the shapes of --svd, next to tsqr_mi_lstsq_f64_lay at refine 1, tsqr_mi_qrcp_f64
 with jobq = 0 and tsqr_mi_r_f64_lay: one process, the five arms interleaved call by call, the median of --calls blocking calls.  Writes
 the JSON to --lstsq-rank-out (default profiles/fp64_lstsq_rank_speed.json) and prints it.  --lstsq-rank-arms lstsq_rank_refine1 runs
-that arm alone and writes no file: the run to put under a kernel trace (profiles/fp64_lstsq_rank_kernel_stats_2p20x64.csv)."""
+that arm alone and writes no file: the run to put under a kernel trace (profiles/fp64_lstsq_rank_kernel_stats_2p20x64.csv).
+--lstsq-minnorm: instead, the minimum-norm entry (tsqr_mi_lstsq_minnorm_f64, refine 1, 3 right-hand sides, the default rcond) next to
+tsqr_mi_lstsq_rank_f64 on the same operands, in one process with the arms interleaved, on the same four shapes; writes the JSON to
+--lstsq-minnorm-out (default profiles/fp64_lstsq_minnorm_speed.json) and prints it."""
 import argparse
 import json
 import math
@@ -756,6 +759,59 @@ def lstsq_rank(torch, bq, calls, warmup, only, only_arms=()):
     return out
 
 
+def lstsq_minnorm(torch, bq, calls, warmup, only):
+    """--lstsq-minnorm: tsqr_mi_lstsq_minnorm_f64 next to tsqr_mi_lstsq_rank_f64, both at refine 1 with the default rcond and 3
+    right-hand sides, column-major Gaussian operands, reorth 0, and on the same A with its last column a copy of its first (rank n - 1:
+    M is not empty).  No time is set in advance: the expected difference is the two single-workgroup kernels the entry adds."""
+    import ctypes
+    L = bq.lib()
+    vp = ctypes.c_void_p
+    nrhs = 3
+    out = {"tool": "f64_speed --lstsq-minnorm", "calls": calls, "warmup": warmup, "reorth": 0, "layout": "column-major", "nrhs": nrhs,
+           "refine": 1, "rcond": "default (max(m, n) 2^-52)", "cases": []}
+    for lg, n in SVD_SHAPES:
+        if only and "2p%dx%d" % (lg, n) not in only:
+            continue
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + n)
+        a = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g).t().contiguous()      # (n, m): column-major m x n
+        b = torch.randn(m, nrhs, dtype=torch.float64, device="cuda", generator=g).t().contiguous()
+        ac = a.clone()
+        ac[n - 1] = ac[0]                                      # the copied column
+        x = [torch.empty(nrhs, n, dtype=torch.float64, device="cuda") for _ in range(4)]
+        r = [torch.empty(n, n, dtype=torch.float64, device="cuda") for _ in range(4)]
+        jp = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(4)]
+        rank = [ctypes.c_int(-1) for _ in range(4)]
+        stream = job_work_spaces(torch, L, ("r",), m, n)["r"][2][2]
+        sized = {}
+        for key in ("rank", "minnorm"):
+            wq = torch.empty(getattr(L, "tsqr_mi_working_q_size_f64_lstsq_" + key)(m, n, nrhs), dtype=torch.float64, device="cuda")
+            wr = torch.empty(getattr(L, "tsqr_mi_working_r_size_f64_lstsq_" + key)(m, n, nrhs), dtype=torch.float64, device="cuda")
+            sized[key] = (wq, wr, (vp(wq.data_ptr()), vp(wr.data_ptr()), stream))
+        bp_ = vp(b.data_ptr())
+        arm = lambda i, key, mat, rcond=-1.0: (lambda: getattr(L, "tsqr_mi_lstsq_%s_f64" % key)(
+            0, 0, 0, 1, rcond, vp(x[i].data_ptr()), n, vp(r[i].data_ptr()), n, vp(jp[i].data_ptr()), ctypes.byref(rank[i]), vp(mat.data_ptr()),
+            m, bp_, m, m, n, nrhs, *sized[key][2]))
+        arms = [("basic", arm(0, "rank", a)), ("minnorm", arm(1, "minnorm", a))]
+        copied = [("basic_copied", arm(2, "rank", ac, 1e-8)), ("minnorm_copied", arm(3, "minnorm", ac, 1e-8))]      # (rcond 1e-8 there)
+        copied_states = [fn() for _, fn in copied]              # (a state other than 0 is reported, and the pair is not timed)
+        arms, med, sweeps = time_arms(bq, arms + (copied if not any(copied_states) else []), calls, warmup, (), L.tsqr_mi_last_sweeps_f64)
+        case = {"m": m, "n": n, "copied_states": copied_states}
+        case.update({name + "_median_ms": med[name] for name, _ in arms})
+        if not any(copied_states):
+            case["minnorm_minus_basic_copied_ms"] = med["minnorm_copied"] - med["basic_copied"]
+        case.update({"minnorm_minus_basic_ms": med["minnorm"] - med["basic"],
+                     "ranks": [v.value for v in rank], "ladder_sweeps": sweeps["minnorm"],
+                     "full_rank_x_bitwise_equal": bool(torch.equal(x[0], x[1])),
+                     "r_and_jpvt_bitwise_equal": bool(torch.equal(r[0], r[1]) and torch.equal(jp[0], jp[1]) and torch.equal(r[2], r[3])
+                                                      and torch.equal(jp[2], jp[3])),
+                     "copied_norm_x_basic": float(x[2].norm().item()), "copied_norm_x_minnorm": float(x[3].norm().item())})
+        out["cases"].append(case)
+        del a, ac, b, x, r, jp, sized
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=None, help="blocking calls per case or arm (default 50; --wide-row-major: 20)")
@@ -779,6 +835,8 @@ def main():
     ap.add_argument("--lstsq-rank", action="store_true", help="time tsqr_mi_lstsq_rank_f64 (refine 0 and 1) next to tsqr_mi_lstsq_f64_lay, tsqr_mi_qrcp_f64 (jobq 0) and tsqr_mi_r_f64_lay")
     ap.add_argument("--lstsq-rank-arms", default="", help="--lstsq-rank: run only these arms (lstsq_rank_refine0, lstsq_rank_refine1, lstsq_f64_lay_refine1, qrcp_jobq0, r_f64_lay) and write no file")
     ap.add_argument("--lstsq-rank-out", default=os.path.join(ROOT, "profiles", "fp64_lstsq_rank_speed.json"), help="--lstsq-rank: the JSON file ('' writes none)")
+    ap.add_argument("--lstsq-minnorm", action="store_true", help="time tsqr_mi_lstsq_minnorm_f64 next to tsqr_mi_lstsq_rank_f64 (refine 1), arms interleaved")
+    ap.add_argument("--lstsq-minnorm-out", default=os.path.join(ROOT, "profiles", "fp64_lstsq_minnorm_speed.json"), help="--lstsq-minnorm: the JSON file ('' writes none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp64_wide_rowmajor_speed.json"), help="--wide-row-major: the JSON file")
     args = ap.parse_args()
     wide_rm = args.wide_row_major or args.wide_col_only
@@ -816,6 +874,13 @@ def main():
         out = lstsq_rank(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], only_arms)
         if args.lstsq_rank_out and not only_arms:
             with open(args.lstsq_rank_out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        print(json.dumps(out))
+        return
+    if args.lstsq_minnorm:
+        out = lstsq_minnorm(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c])
+        if args.lstsq_minnorm_out:
+            with open(args.lstsq_minnorm_out, "w") as f:
                 f.write(json.dumps(out, indent=1) + "\n")
         print(json.dumps(out))
         return

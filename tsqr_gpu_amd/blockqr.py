@@ -127,6 +127,10 @@ def _c_signatures():
         # (a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs, wq, wr, stream)
         "tsqr_mi_lstsq_rank_f64": (ci, [ci, ci, ci, ci, ctypes.c_double, vp, sz, vp, sz, vp, ctypes.POINTER(ci), vp, sz, vp, sz, sz, sz, sz,
                                         vp, vp, vp]),
+        "tsqr_mi_working_q_size_f64_lstsq_minnorm": (sz, [sz, sz, sz]), "tsqr_mi_working_r_size_f64_lstsq_minnorm": (sz, [sz, sz, sz]),
+        # (the arguments of tsqr_mi_lstsq_rank_f64)
+        "tsqr_mi_lstsq_minnorm_f64": (ci, [ci, ci, ci, ci, ctypes.c_double, vp, sz, vp, sz, vp, ctypes.POINTER(ci), vp, sz, vp, sz, sz, sz, sz,
+                                           vp, vp, vp]),
     }
 
 
@@ -140,7 +144,8 @@ OPTIONAL_SYMBOLS = {
     "tsqr_mi_r_f64_lay", "tsqr_mi_lstsq_f64_lay", "tsqr_mi_qr_f64_lay", "tsqr_mi_qr_f64_wide_lay",
     "tsqr_mi_working_q_size_f64_svd", "tsqr_mi_working_r_size_f64_svd", "tsqr_mi_svd_f64", "tsqr_mi_last_jacobi_sweeps_f64",
     "tsqr_mi_working_q_size_f64_qrcp", "tsqr_mi_working_r_size_f64_qrcp", "tsqr_mi_qrcp_f64",
-    "tsqr_mi_working_q_size_f64_lstsq_rank", "tsqr_mi_working_r_size_f64_lstsq_rank", "tsqr_mi_lstsq_rank_f64"}
+    "tsqr_mi_working_q_size_f64_lstsq_rank", "tsqr_mi_working_r_size_f64_lstsq_rank", "tsqr_mi_lstsq_rank_f64",
+    "tsqr_mi_working_q_size_f64_lstsq_minnorm", "tsqr_mi_working_r_size_f64_lstsq_minnorm", "tsqr_mi_lstsq_minnorm_f64"}
 
 _lib = None
 
@@ -434,6 +439,7 @@ _F64_LSTSQ = _F64Entry("lstsq_f64", 64, "tsqr_mi_lstsq_f64", "_f64_lstsq")
 _F64_SVD = _F64Entry("svd_f64", 64, "tsqr_mi_svd_f64", "_f64_svd")       # (its size functions take jobu behind m and n)
 _F64_QRCP = _F64Entry("qrcp_f64", 64, "tsqr_mi_qrcp_f64", "_f64_qrcp")   # (jobq behind m and n)
 _F64_LSTSQ_RANK = _F64Entry("lstsq_rank_f64", 64, "tsqr_mi_lstsq_rank_f64", "_f64_lstsq_rank")   # (nrhs behind m and n; no _lay form)
+_F64_LSTSQ_MINNORM = _F64Entry("lstsq_rank_f64", 64, "tsqr_mi_lstsq_minnorm_f64", "_f64_lstsq_minnorm")   # (lstsq_rank_f64 with minimum_norm=True)
 
 
 def _null_state(fn, *scalars):
@@ -707,7 +713,7 @@ class LstsqRankError(_F64StateError):
     """lstsq_rank_f64 ended with a non-zero state (.state: error_invalid_matrix_size, error_unsupported_mode or error_not_finite)"""
 
 
-def lstsq_rank_f64(a, b, rcond=None, reorth=False, refine=1, stream=None):
+def lstsq_rank_f64(a, b, rcond=None, reorth=False, refine=1, stream=None, *, minimum_norm=False):
     """The rank of a and the basic solution of min ||a X - b||_F on its numerically independent columns, in double precision
     (tsqr_mi_lstsq_rank_f64: include/tsqr_mi.h has the method and the measured accuracy).  a: m x n float64 GPU tensor, 1 <= n <= 64,
     n <= m; b: m x nrhs (or m) float64 GPU tensor, nrhs <= 16; any strides, read where they lie or copied once under the rule of
@@ -719,10 +725,15 @@ def lstsq_rank_f64(a, b, rcond=None, reorth=False, refine=1, stream=None):
     rank a Python int.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for shapes that do not fit together,
     LstsqRankError (.state) when the entry does not run the shape or returns a state other than 0: error_not_finite from the ladder (Inf
     or NaN in a, a column norm outside [2^-511, 2^512), or an exactly zero column among non-zero ones) or from the Cholesky step on the
-    retained columns."""
+    retained columns.
+    minimum_norm=True (keyword only; tsqr_mi_lstsq_minnorm_f64): x is the minimum-norm solution of the problem truncated at that rank,
+    what LAPACK's dgelsy and scipy.linalg.lstsq(lapack_driver="gelsy") return at the same rank (numpy.linalg.lstsq and torch.linalg.lstsq
+    truncate by singular values instead and agree when a has exact rank).  Every row of x may then be non-zero; r, p and rank are bitwise
+    those of the default, and at full rank so is x.  The same arguments, checks and errors; error_not_finite also from the Cholesky
+    factorisation of C = I + M M^T."""
     import math
     import torch
-    entry = _F64_LSTSQ_RANK
+    entry = _F64_LSTSQ_MINNORM if minimum_norm else _F64_LSTSQ_RANK
     _check_f64_tensors(entry.name, (("a", a), ("b", b)))
     if a.dim() != 2 or b.dim() not in (1, 2) or b.shape[0] != a.shape[0]:
         raise ValueError("lstsq_rank_f64: a must be m x n and b m x nrhs (or m), got %s and %s" % (tuple(a.shape), tuple(b.shape)))
@@ -739,7 +750,7 @@ def lstsq_rank_f64(a, b, rcond=None, reorth=False, refine=1, stream=None):
                       (math.isnan(rc) or rc >= 1.0, "rcond < 1")):
         if bad:
             raise LstsqRankError(error_unsupported_mode, "lstsq_rank_f64: state %d for a %d x %d, nrhs %d, refine %d, rcond %r: "
-                                 "tsqr_mi_lstsq_rank_f64 supports %s" % (error_unsupported_mode, m, n, nrhs, int(refine), rcond, text))
+                                 "%s supports %s" % (error_unsupported_mode, m, n, nrhs, int(refine), rcond, entry.symbol, text))
     ac, lda, a_layout = _operand_f64(a)
     bc, ldb, b_layout = _operand_f64(b2)
     x = torch.empty((nrhs, n), dtype=torch.float64, device=a.device)
@@ -748,7 +759,7 @@ def lstsq_rank_f64(a, b, rcond=None, reorth=False, refine=1, stream=None):
     rank = ctypes.c_int(-1)
     wq, wr = entry.work_space(a.device, m, n, nrhs)
     with torch.cuda.device(a.device):
-        st = _f64_call(entry.symbol, lib().tsqr_mi_lstsq_rank_f64, stream, a_layout, b_layout, int(bool(reorth)), int(refine), rc,
+        st = _f64_call(entry.symbol, getattr(lib(), entry.symbol), stream, a_layout, b_layout, int(bool(reorth)), int(refine), rc,
                        x.data_ptr(), n, r.data_ptr(), n, p.data_ptr(), ctypes.byref(rank), ac.data_ptr(), lda, bc.data_ptr(), ldb, m, n, nrhs,
                        wq.data_ptr(), wr.data_ptr())
     if st:

@@ -149,6 +149,9 @@ inline void f64_lsq_update_launch(hipStream_t st, double* xw, double* x, size_t 
 // wq (doubles): [the F64L_WQ layout][Zeff, NP x NP (ld NP): 4096][the step's summed Gram tiles: 10 tiles of 256 + the row-count word of
 // the reduction][status words: [0] the rank, [1] the step's verdict: 8]
 constexpr size_t F64K_ZEFF = F64L_WQ, F64K_G1 = F64K_ZEFF + 4096, F64K_STATUS = F64K_G1 + 10 * 256 + 8, F64K_WQ = F64K_STATUS + 8;
+// tsqr_mi_lstsq_minnorm_f64: the same layout, status word [2] the verdict of lsq_minnorm_f64_kernel, and behind it
+// [Zmn, NP x NP (ld NP): 4096].  Rc is not stored: that kernel repeats the step's factorisation on the same G11.
+constexpr size_t F64M_ZMN = F64K_WQ, F64M_WQ = F64M_ZMN + 4096;
 
 // ---- tsqr_mi_svd_f64 (n <= 64) ------------------------------------------------------------------------------------------------------------
 // jobu = 1 runs the ladder of tsqr_mi_qr_f64_lay on the F64_WQ layout with R in the block behind it, then svd_r_f64_kernel and

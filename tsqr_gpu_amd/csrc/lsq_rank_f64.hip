@@ -6,6 +6,8 @@
 //   gramq_dense_f64_kernel   : gramq_f64_kernel for a dense Z staged in LDS: per-workgroup partials of (A Zeff)^T (A Zeff)
 //   lsq_rank_step_f64_kernel : the CholeskyQR step on the retained columns, G1 = Rc^T Rc and Zeff <- Zeff inverse(Rc), on one workgroup
 //   lsq_dense_f64_kernel     : lsq_f64_kernel for a dense Z staged in LDS
+//   lsq_zg_f64_kernel        : (tsqr_mi_lstsq_minnorm_f64) unit vectors into the dropped columns of Zeff, so that the Gram pass also gives G12
+//   lsq_minnorm_f64_kernel   : (tsqr_mi_lstsq_minnorm_f64) the update factor Zmn = P pinv(Q1^T A P) of the minimum-norm form, on one workgroup
 // The last pass, X <- X + Z D for a dense Z, is lsq_update_f64_kernel<true> (tsqr_f64.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -312,10 +314,208 @@ __global__ __launch_bounds__(1024) void lsq_rank_step_f64_kernel(const LsqRankSt
 	}
 }
 
+// ---- the minimum-norm form (tsqr_mi_lstsq_minnorm_f64): Zg, and the update factor Zmn = P pinv(S) -----------------------------------------
+struct LsqZgArgs64 {
+	const int* jpvt;                     // the n pivots, 0-based
+	const unsigned* rank;                // the device word lsq_rank_f64_kernel wrote: k (taken as min(k, n))
+	double* zeff;                        // NP x NP (ld NP), in and out: column j, k <= j < n, of lsq_rank_f64_kernel's Zeff is zero; entry (jpvt[j], j) <- 1
+	int n;
+};
+
+// Zeff -> Zg in place: column j = k .. n - 1 becomes the unit vector e_jpvt[j], one thread per column, one store each (a pivot outside
+// 0 .. n - 1 stores nothing); nothing else is touched.  The dense Gram pass on Zg then holds G12 = (A Zeff)^T A P2 in the columns
+// k .. n - 1 of the rows 0 .. k - 1 next to G11 = (A Zeff)^T (A Zeff), whose entries keep their bits: an MFMA output entry depends on its
+// own two columns of A Z alone.  lsq_rank_step_f64_kernel reads the columns below k of Zeff only and writes the others as zeros.
+__global__ __launch_bounds__(64) void lsq_zg_f64_kernel(const LsqZgArgs64 a) {
+	const int j = threadIdx.x, n = a.n;
+	const int NP = 16 * ((n + 15) / 16);
+	const int k = min((int)a.rank[0], n);
+	if (j < k || j >= n) return;
+	const int row = a.jpvt[j];
+	if (row >= 0 && row < n) a.zeff[(size_t)j * NP + row] = 1.0;
+}
+
+struct LsqMinnormArgs64 {
+	const double* gsum;                  // the summed tiles of gramq_dense_f64_kernel on Zg: G11 in [:k, :k], G12 in [:k, k:n], NTRI tiles of 256
+	const unsigned* rank;                // the device word lsq_rank_f64_kernel wrote: k (taken as min(k, n))
+	const int* jpvt;                     // the n pivots, 0-based
+	const double* zeff;                  // NP x NP (ld NP): Zeff behind lsq_rank_step_f64_kernel on the same G11, A Zeff = Q1
+	double* zmn;                         // NP x NP (ld NP) out, wholly written: Zmn = P pinv(S), S = Q1^T A P = R11' [I M]; columns >= k zero
+	unsigned* status;                    // device word [0] the verdict: 0 ok, 1 a pivot of G11 (the step's verdict), 2 a pivot of C not positive or not finite
+	unsigned* host_status;               // device-visible alias of a pinned host word receiving the verdict; null: not wanted
+	int n;
+};
+
+// One workgroup, four 64 x 64 blocks in LDS (column-major, ld 64), each used twice.  With R11' = inverse(P1^T Zeff) (k x k, upper
+// triangular; never formed) the retained columns are A P1 = Q1 R11', and S = Q1^T A P = R11' [I M].
+//   W0 <- [Rc | S12]: lsq_rank_step_f64_kernel's right-looking Cholesky of G11 = Rc^T Rc, operation for operation (the same bits), with
+//         the columns k .. n - 1 of G12 carried along as further columns of the rows 0 .. k - 1: row p divided by Rc_pp, entry (i, j),
+//         p < i < k <= j < n, one fused multiply-add.  That is the forward substitution S12 = Rc^-T G12 = Q1^T A P2.
+//   W1 <- T = P1^T Zeff = inverse(R11'), read from zeff (rows jpvt[:k], upper triangle)
+//   W2 <- M = T S12 (k x (n - k), kept in the columns k .. n - 1): entry (i, j) sums l = i .. k - 1 in that order
+//   W3 <- C = I + M M^T, upper triangle: entry (i, j) starts from 1 or 0 and sums the columns k .. n - 1 in that order; then C = Uc^T Uc by
+//         the same Cholesky.  C is SPD with cond(C) <= 1 + ||M||^2: no shift.  A bad pivot: verdict 2.
+//   W0 <- Ui = inverse(Uc): lsq_rank_f64_kernel's back substitution
+//   W3 <- Y = Ui^T T: entry (i, j) sums l = 0 .. i;   W1 <- V = Ui Y = inverse(C) T: entry (i, j) sums l = i .. k - 1
+//   W0 <- the image of Zmn: row jpvt[i], i < k, is row i of V; row jpvt[i], k <= i < n, is row i - k of M^T V, entry (i, j) summing
+//         l = 0 .. k - 1; the columns >= k, the padding and every row no pivot names stay zero.  (A pivot outside 0 .. n - 1 is skipped.)
+// Every sum is a fixed chain of one fused multiply-add per term from +0 (or 1): the same bits on every run.  At k = n there is no M:
+// C = I exactly, Uc = Ui = I exactly, Y = V = T exactly (products with exact ones, sums of exact zeros), and Zmn is BITWISE the Zeff that
+// came in.  k = 0 writes Zmn = 0 and verdict 0; verdicts 1 and 2 write Zmn = 0.  No scratch; 128.3 KB of static LDS: this file is built
+// for gfx950 alone, whose workgroups have 160 KB.
+__global__ __launch_bounds__(1024) void lsq_minnorm_f64_kernel(const LsqMinnormArgs64 a) {
+	__shared__ double W0[64 * 64], W1[64 * 64], W2[64 * 64], W3[64 * 64];
+	__shared__ int piv[64];
+	static_assert(sizeof(W0) + sizeof(W1) + sizeof(W2) + sizeof(W3) + sizeof(piv) <= 160 * 1024,
+	              "lsq_minnorm_f64_kernel relies on the 160 KB of LDS of gfx950");
+	const int t = threadIdx.x, lane = t & 63, wv = t >> 6, n = a.n;
+	const int NT = (n + 15) / 16, NP = 16 * NT;
+	const int k = min((int)a.rank[0], n);                  // (uniform: every thread reads the same word)
+	if (t < 64) {
+		const int row = t < n ? a.jpvt[t] : -1;
+		piv[t] = (row >= 0 && row < n) ? row : -1;
+	}
+	__syncthreads();
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		double g = 0.0, z = 0.0;
+		if (i <= j && i < k && j < n) {
+			const int ti = i >> 4, tj = j >> 4, ri = i & 15;
+			const int idx = ti * NT - (ti * (ti - 1)) / 2 + (tj - ti);
+			g = a.gsum[(size_t)idx * 256 + (ri >> 2) * 64 + (ri & 3) * 16 + (j & 15)];
+		}
+		if (i <= j && j < k && piv[i] >= 0) z = a.zeff[(size_t)j * NP + piv[i]];
+		W0[e] = g;
+		W1[e] = z;
+	}
+	__syncthreads();
+	// the Cholesky factorisation of the leading k x k block of W (upper triangle), the columns k .. nc - 1 of its rows carried along
+	auto chol = [&](double* W, int nc) -> bool {
+		for (int p = 0; p < k; p++) {
+			const double g = W[p * 64 + p];
+			if (!(g > 0.0) || !(g < __builtin_inf())) return true;            // (uniform: the same LDS word for every thread)
+			const double rpp = sqrt(g);
+			__syncthreads();                                  // every thread has read the pivot
+			if (t < 64 && t >= p && t < nc) W[t * 64 + p] = t == p ? rpp : W[t * 64 + p] / rpp;
+			__syncthreads();
+#pragma unroll
+			for (int u = 0; u < 4; u++) {
+				const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+				if (i > p && i <= j && i < k && j < nc) W[e] = __builtin_fma(-W[i * 64 + p], W[j * 64 + p], W[e]);
+			}
+			__syncthreads();
+		}
+		return false;
+	};
+	unsigned verdict = chol(W0, n) ? 1u : 0u;
+	if (verdict == 0u) {
+		// M = T S12
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			double s = 0.0;
+			if (i < k && j >= k && j < n)
+				for (int l = i; l < k; l++) s = __builtin_fma(W1[l * 64 + i], W0[j * 64 + l], s);
+			W2[e] = s;
+		}
+		__syncthreads();
+		// C = I + M M^T; W0 is free: cleared for Ui
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			double s = 0.0;
+			if (i <= j && j < k) {
+				s = i == j ? 1.0 : 0.0;
+				for (int c = k; c < n; c++) s = __builtin_fma(W2[c * 64 + i], W2[c * 64 + j], s);
+			}
+			W3[e] = s;
+			W0[e] = 0.0;
+		}
+		__syncthreads();
+		if (chol(W3, k)) verdict = 2u;
+	}
+	if (verdict == 0u) {
+		// Ui = inverse(Uc)
+		const double dii = lane < k ? W3[lane * 64 + lane] : 1.0;
+		for (int j = wv; j < k; j += 16) {
+			double w = lane == j ? 1.0 : 0.0, z = 0.0;
+			for (int l = j; l >= 0; l--) {
+				const double q = w / dii;
+				const double zl = __shfl(q, l, 64);
+				if (lane == l) z = zl;
+				if (lane < l) w = __builtin_fma(-W3[l * 64 + lane], zl, w);
+			}
+			if (lane <= j) W0[j * 64 + lane] = z;
+		}
+		__syncthreads();
+		// Y = Ui^T T
+		double y[4];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			double s = 0.0;
+			if (i < k && j < k)
+				for (int l = 0; l <= i; l++) s = __builtin_fma(W0[i * 64 + l], W1[j * 64 + l], s);
+			y[u] = s;
+		}
+#pragma unroll
+		for (int u = 0; u < 4; u++) W3[t + 1024 * u] = y[u];                  // (W3 held Uc: only its own thread reads or writes a word here)
+		__syncthreads();
+		// V = Ui Y
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			double s = 0.0;
+			if (i < k && j < k)
+				for (int l = i; l < k; l++) s = __builtin_fma(W0[l * 64 + i], W3[j * 64 + l], s);
+			y[u] = s;
+		}
+		__syncthreads();                                      // every thread has read T (W1) and Ui (W0)
+#pragma unroll
+		for (int u = 0; u < 4; u++) { W1[t + 1024 * u] = y[u]; W0[t + 1024 * u] = 0.0; }
+		__syncthreads();
+		// the image of Zmn: rows jpvt[:k] take V, rows jpvt[k:n] take M^T V
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+			if (i < n && j < k && piv[i] >= 0) {
+				double s = 0.0;
+				if (i < k) s = W1[e];
+				else
+					for (int l = 0; l < k; l++) s = __builtin_fma(W2[i * 64 + l], W1[j * 64 + l], s);
+				W0[j * 64 + piv[i]] = s;
+			}
+		}
+	} else {
+		__syncthreads();                                      // (uniform branch: every thread is here) the last reads of W0 are done
+#pragma unroll
+		for (int u = 0; u < 4; u++) W0[t + 1024 * u] = 0.0;
+	}
+	__syncthreads();
+#pragma unroll
+	for (int u = 0; u < 4; u++) {
+		const int e = t + 1024 * u, i = e & 63, j = e >> 6;
+		if (i < NP && j < NP) a.zmn[(size_t)j * NP + i] = W0[e];
+	}
+	if (t == 0) {
+		a.status[0] = verdict;
+		if (a.host_status) { volatile unsigned* hs = a.host_status; hs[0] = verdict; }
+	}
+}
+
 }  // namespace tsqrmi
 
 namespace {
 
+// lsq_zg_f64_kernel on stream st: one wave
+inline void f64k_zg_launch(hipStream_t st, const tsqrmi::LsqZgArgs64& za) {
+	hipLaunchKernelGGL(tsqrmi::lsq_zg_f64_kernel, dim3(1), dim3(64), 0, st, za);
+}
+// lsq_minnorm_f64_kernel on stream st: one workgroup
+inline void f64k_minnorm_launch(hipStream_t st, const tsqrmi::LsqMinnormArgs64& ma) {
+	hipLaunchKernelGGL(tsqrmi::lsq_minnorm_f64_kernel, dim3(1), dim3(1024), 0, st, ma);
+}
 // lsq_rank_f64_kernel on stream st: one workgroup
 inline void f64k_rank_launch(hipStream_t st, const tsqrmi::LsqRankArgs64& ka) {
 	hipLaunchKernelGGL(tsqrmi::lsq_rank_f64_kernel, dim3(1), dim3(1024), 0, st, ka);

@@ -262,6 +262,28 @@ int tsqr_selftest_f64_lsq_rank_step(const double* gsum, const unsigned* rank, do
 	return f64_sync();
 }
 
+// ---- the passes the minimum-norm entry adds (tsqr_mi_lstsq_minnorm_f64; lsq_rank_f64.hip) --------------------------------------------------
+// lsq_zg_f64_kernel through the product's launcher: jpvt (n ints) and rank[1] in; zeff (NP x NP, ld NP) in and out.  Every check stands
+// before any HIP call
+int tsqr_selftest_f64_lsq_zg(const int* jpvt, const unsigned* rank, double* zeff, int n) {
+	if (n <= 0 || n > (int)PW || !jpvt || !rank || !zeff) return -100;
+	tsqrmi::LsqZgArgs64 za{};
+	za.jpvt = jpvt; za.rank = rank; za.zeff = zeff; za.n = n;
+	f64k_zg_launch(0, za);
+	return f64_sync();
+}
+
+// lsq_minnorm_f64_kernel through the product's launcher: gsum (the ntri summed tiles of the Gram matrix on Zg), rank[1], jpvt (n ints)
+// and zeff (NP x NP, ld NP) in; zmn (NP x NP, ld NP) and status[1] (the verdict) out.  Every check stands before any HIP call
+int tsqr_selftest_f64_lsq_minnorm(const double* gsum, const unsigned* rank, const int* jpvt, const double* zeff, double* zmn, unsigned* status,
+                                  int n) {
+	if (n <= 0 || n > (int)PW || !gsum || !rank || !jpvt || !zeff || !zmn || !status) return -100;
+	tsqrmi::LsqMinnormArgs64 ma{};
+	ma.gsum = gsum; ma.rank = rank; ma.jpvt = jpvt; ma.zeff = zeff; ma.zmn = zmn; ma.status = status; ma.host_status = nullptr; ma.n = n;
+	f64k_minnorm_launch(0, ma);
+	return f64_sync();
+}
+
 // lsq_update_f64_kernel<dense> through the product's launcher with the stagnation rule: dprev (16 doubles, or null) and guard as the
 // entries pass them; dense = 0 runs the triangular form on the same arguments
 int tsqr_selftest_f64_lsq_update_rule(int dense, double* xw, double* x, size_t ldx, const double* z, const double* d, int n, int nrhs,

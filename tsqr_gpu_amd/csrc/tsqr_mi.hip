@@ -2933,9 +2933,27 @@ int tsqr_mi_qrcp_f64(int a_layout, int q_layout, int jobq, int reorth, double* q
 // (D = (A Zeff)^T (B - A X), X null the first time), the reduction and X <- X + Zeff D (lsq_update_f64_kernel<true>) under the
 // stagnation rule of lstsq_f64_core with its state in wq[F64L_DPREV].  The two pinned words are the thread's verdict words, which the
 // ladder has finished with when it returns (as svd_f64_core keeps its words).
+// The minimum-norm entry (tsqr_mi_lstsq_minnorm_f64) is the same sequence with three changes: lsq_zg_f64_kernel in front of the Gram
+// pass (Zeff -> Zg, so that the same tiles also hold G12), lsq_minnorm_f64_kernel behind the step (Zmn into wq[F64M_ZMN], its verdict
+// into status word [2] and a third pinned word), and Zmn in place of Zeff as the factor of the update.  Every other launch, and every
+// launch of the basic entry, is unchanged.
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
+// the texts of an entry of this family: the basic one and the minimum-norm one differ in their names alone
+struct LstsqRankTexts {
+	const char *n_max, *nrhs_max, *refine_range, *rcond_range, *step_pivot;
+};
+const LstsqRankTexts LSTSQ_RANK_TEXTS{
+	"tsqr_mi_lstsq_rank_f64 supports n <= 64", "tsqr_mi_lstsq_rank_f64 supports nrhs <= 16", "tsqr_mi_lstsq_rank_f64 supports 0 <= refine <= 4",
+	"tsqr_mi_lstsq_rank_f64 supports rcond < 1 (negative: max(m, n) 2^-52)",
+	"tsqr_mi_lstsq_rank_f64: the Cholesky step on the retained columns met a pivot that is not positive or not finite"};
+const LstsqRankTexts LSTSQ_MINNORM_TEXTS{
+	"tsqr_mi_lstsq_minnorm_f64 supports n <= 64", "tsqr_mi_lstsq_minnorm_f64 supports nrhs <= 16",
+	"tsqr_mi_lstsq_minnorm_f64 supports 0 <= refine <= 4", "tsqr_mi_lstsq_minnorm_f64 supports rcond < 1 (negative: max(m, n) 2^-52)",
+	"tsqr_mi_lstsq_minnorm_f64: the Cholesky step on the retained columns met a pivot that is not positive or not finite"};
+
+template <bool MINNORM>
 int lstsq_rank_f64_core(int a_layout, int b_layout, int reorth, int refine, double rcond, double* x, size_t ldx, double* r, size_t ldr,
                         int* jpvt, int* rank, const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
                         double* wq, double* wr, void* stream) {
@@ -2947,7 +2965,9 @@ int lstsq_rank_f64_core(int a_layout, int b_layout, int reorth, int refine, doub
 	HIPCHK(hipGetLastError());
 	volatile unsigned* words = t_own64.host;             // (the ladder allocated them and has read its verdicts: the stream is idle)
 	words[0] = 0u; words[1] = 1u;                        // (a step kernel that never reported reads as failed)
+	if constexpr (MINNORM) words[2] = 2u;                // (and so does lsq_minnorm_f64_kernel)
 	double *zeff = wq + F64K_ZEFF, *xw = wq + F64L_X, *dsum = wq + F64L_D;
+	const double* zupd = MINNORM ? wq + F64M_ZMN : zeff;     // the factor of the update X <- X + zupd D
 	unsigned* status = reinterpret_cast<unsigned*>(wq + F64K_STATUS);
 	tsqrmi::LsqRankArgs64 ka{};
 	ka.r = r; ka.ldr = ldr; ka.jpvt = jpvt; ka.rcond = rcond; ka.zeff = zeff; ka.status = status; ka.host_status = t_own64.dev; ka.n = (int)n;
@@ -2955,6 +2975,12 @@ int lstsq_rank_f64_core(int a_layout, int b_layout, int reorth, int refine, doub
 	HIPCHK(hipGetLastError());
 	const F64Plan g = f64r_plan(m, n);
 	if (g.nblocks <= 0) { t_last_error = "fp64 least-squares pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	if constexpr (MINNORM) {
+		tsqrmi::LsqZgArgs64 za{};
+		za.jpvt = jpvt; za.rank = status; za.zeff = zeff; za.n = (int)n;
+		f64k_zg_launch(st, za);
+		HIPCHK(hipGetLastError());
+	}
 	const tsqrmi::GramQArgs64 ga{a, lda, m, (int)n, g.nunits, g.nwaves, zeff, wr};
 	f64k_gramq_launch(st, g, ga, a_layout);
 	HIPCHK(hipGetLastError());
@@ -2964,23 +2990,54 @@ int lstsq_rank_f64_core(int a_layout, int b_layout, int reorth, int refine, doub
 	sa.gsum = wq + F64K_G1; sa.rank = status; sa.zeff = zeff; sa.status = status + 1; sa.host_status = t_own64.dev + 1; sa.n = (int)n;
 	f64k_step_launch(st, sa);
 	HIPCHK(hipGetLastError());
+	if constexpr (MINNORM) {
+		tsqrmi::LsqMinnormArgs64 ma{};
+		ma.gsum = wq + F64K_G1; ma.rank = status; ma.jpvt = jpvt; ma.zeff = zeff; ma.zmn = wq + F64M_ZMN; ma.status = status + 2;
+		ma.host_status = t_own64.dev + 2; ma.n = (int)n;
+		f64k_minnorm_launch(st, ma);
+		HIPCHK(hipGetLastError());
+	}
 	for (int p = 0; p <= refine; p++) {
 		const tsqrmi::LsqArgs64 la{a, lda, b, ldb, m, (int)n, (int)nrhs, g.nunits, g.nwaves, zeff, p == 0 ? nullptr : xw, wr};
 		f64k_lsq_launch(st, g, la, a_layout, b_layout);
 		HIPCHK(hipGetLastError());
 		launch_reduce1(st, dsum, wr, g.nblocks, g.NT * 256, (double)m);
 		HIPCHK(hipGetLastError());
-		f64_lsq_update_launch<true>(st, xw, x, ldx, zeff, dsum, (int)n, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0, wq + F64L_DPREV,
+		f64_lsq_update_launch<true>(st, xw, x, ldx, zupd, dsum, (int)n, (int)nrhs, p == 0 ? 1 : 0, p == refine ? 1 : 0, wq + F64L_DPREV,
 		                            p >= 2 ? 1 : 0);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipStreamSynchronize(st));
 	*rank = (int)words[0];
 	if (words[1] != 0u) {
-		t_last_error = "tsqr_mi_lstsq_rank_f64: the Cholesky step on the retained columns met a pivot that is not positive or not finite";
+		t_last_error = (MINNORM ? LSTSQ_MINNORM_TEXTS : LSTSQ_RANK_TEXTS).step_pivot;
 		return TSQR_MI_ERROR_NOT_FINITE;
 	}
+	if constexpr (MINNORM) {
+		if (words[2] != 0u) {
+			t_last_error = "tsqr_mi_lstsq_minnorm_f64: the Cholesky factorisation of C = I + M M^T met a pivot that is not positive or not finite";
+			return TSQR_MI_ERROR_NOT_FINITE;
+		}
+	}
 	return TSQR_MI_SUCCESS;
+}
+
+// the entry of either form: every state that does not need the device is decided here, before any HIP call; the null checks first of all
+template <bool MINNORM>
+int lstsq_rank_f64_entry(int a_layout, int b_layout, int reorth, int refine, double rcond, double* x, size_t ldx, double* r, size_t ldr,
+                         int* jpvt, int* rank, const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
+                         void* wq, void* wr, void* stream) {
+	const LstsqRankTexts& tx = MINNORM ? LSTSQ_MINNORM_TEXTS : LSTSQ_RANK_TEXTS;
+	t_sweeps64 = 0;
+	if (!x || !r || !jpvt || !rank || !a || !b || !wq || !wr) return TSQR_MI_ERROR_INVALID_SIZE;
+	const F64Operand A{a_layout, m, n, lda}, B{b_layout, m, nrhs, ldb}, R{TSQR_MI_COL_MAJOR, n, n, ldr}, X{TSQR_MI_COL_MAJOR, n, nrhs, ldx};
+	if (const int rc = f64_prologue({A, B, R, X}, m, n, PW, tx.n_max)) return rc;
+	if (nrhs > F64L_MAX_NRHS) { t_last_error = tx.nrhs_max; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (refine < 0 || refine > F64L_MAX_REFINE) { t_last_error = tx.refine_range; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (!(rcond < 1.0)) { t_last_error = tx.rcond_range; return TSQR_MI_ERROR_UNSUPPORTED; }
+	if (rcond < 0.0) rcond = (double)std::max(m, n) * 0x1p-52;
+	return lstsq_rank_f64_core<MINNORM>(a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs,
+	                                    reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr), stream);
 }
 
 }  // namespace
@@ -2995,17 +3052,18 @@ size_t tsqr_mi_working_r_size_f64_lstsq_rank(size_t m, size_t n, size_t nrhs) {
 int tsqr_mi_lstsq_rank_f64(int a_layout, int b_layout, int reorth, int refine, double rcond, double* x, size_t ldx, double* r, size_t ldr,
                            int* jpvt, int* rank, const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
                            void* wq, void* wr, void* stream) {
-	// every state that does not need the device is decided here, before any HIP call; the null checks first of all
-	t_sweeps64 = 0;
-	if (!x || !r || !jpvt || !rank || !a || !b || !wq || !wr) return TSQR_MI_ERROR_INVALID_SIZE;
-	const F64Operand A{a_layout, m, n, lda}, B{b_layout, m, nrhs, ldb}, R{TSQR_MI_COL_MAJOR, n, n, ldr}, X{TSQR_MI_COL_MAJOR, n, nrhs, ldx};
-	if (const int rc = f64_prologue({A, B, R, X}, m, n, PW, "tsqr_mi_lstsq_rank_f64 supports n <= 64")) return rc;
-	if (nrhs > F64L_MAX_NRHS) { t_last_error = "tsqr_mi_lstsq_rank_f64 supports nrhs <= 16"; return TSQR_MI_ERROR_UNSUPPORTED; }
-	if (refine < 0 || refine > F64L_MAX_REFINE) { t_last_error = "tsqr_mi_lstsq_rank_f64 supports 0 <= refine <= 4"; return TSQR_MI_ERROR_UNSUPPORTED; }
-	if (!(rcond < 1.0)) { t_last_error = "tsqr_mi_lstsq_rank_f64 supports rcond < 1 (negative: max(m, n) 2^-52)"; return TSQR_MI_ERROR_UNSUPPORTED; }
-	if (rcond < 0.0) rcond = (double)std::max(m, n) * 0x1p-52;
-	return lstsq_rank_f64_core(a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs,
-	                           reinterpret_cast<double*>(wq), reinterpret_cast<double*>(wr), stream);
+	return lstsq_rank_f64_entry<false>(a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs, wq, wr,
+	                                   stream);
+}
+
+size_t tsqr_mi_working_q_size_f64_lstsq_minnorm(size_t m, size_t n, size_t nrhs) { return (m == 0 || n == 0 || nrhs == 0) ? 0 : F64M_WQ; }
+size_t tsqr_mi_working_r_size_f64_lstsq_minnorm(size_t m, size_t n, size_t nrhs) { return tsqr_mi_working_r_size_f64_lstsq_rank(m, n, nrhs); }
+
+int tsqr_mi_lstsq_minnorm_f64(int a_layout, int b_layout, int reorth, int refine, double rcond, double* x, size_t ldx, double* r, size_t ldr,
+                              int* jpvt, int* rank, const double* a, size_t lda, const double* b, size_t ldb, size_t m, size_t n, size_t nrhs,
+                              void* wq, void* wr, void* stream) {
+	return lstsq_rank_f64_entry<true>(a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs, wq, wr,
+	                                  stream);
 }
 
 }  // extern "C"
