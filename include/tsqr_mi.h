@@ -500,7 +500,9 @@ int tsqr_mi_last_jacobi_sweeps_f64(void);
  * Method: QR, a small pivoted QR of R, then a product.  A = Q0 R0 by the ladder, R0 into r; R0 P = H R on one workgroup in place on r
  * (qrcp_r_f64_kernel, tsqr_f64.hip: Householder reflectors built as dlarfg builds them on R0 scaled by a power of two to
  * max |r_ij| in [1, 2); at every step the squared norms of the remaining part of every remaining column are summed afresh, never
- * downdated; the pivot is the largest, the lowest index on a tie; a column that is exactly zero gives H_k = I and R_kk = 0 without a
+ * downdated; the pivot is the largest, on a tie the one at the lowest POSITION among the remaining columns as the swaps of the steps
+ * before have left them -- step k exchanges the columns at positions k and p, so among equal columns that is not always the lowest
+ * column of A: norms (1, 1, 2) give jpvt = (2, 1, 0); a column that is exactly zero gives H_k = I and R_kk = 0 without a
  * division; a negative R_kk is made positive by negating row k of R and column k of H, which is exact).  n steps, no iteration, no
  * state of its own.
  *   jobq = 1  the ladder of tsqr_mi_qr_f64_lay, called as it stands (reorth as there), writes Q0 into q; then Q = Q0 H in place on

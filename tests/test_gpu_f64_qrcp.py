@@ -302,8 +302,11 @@ def test_qrcp_numerical_rank(bq):
 
 
 def test_qrcp_copied_column_is_recorded(bq):
-    """outside the band: the ladder accepts an exactly copied column on its shifted path -- recorded in profiles/fp64_qrcp_accuracy.md,
-    nothing is asserted beyond the call returning"""
+    """outside the band: the ladder accepts an exactly copied column on its shifted path -- recorded in profiles/fp64_qrcp_accuracy.md.
+    The bands are not asserted; when the state is 0, what holds whatever the ladder did is (check_structure: a permutation, R exactly
+    upper triangular, diag(R) >= 0 and non-increasing, the pivot property).  This is the input the rank-aware least-squares entry
+    exists for: on the same A with rcond = 1e-8 it returns rank 15, and the column it drops is one of the two copies."""
+    torch = _torch()
     a = np.array(matrix(4096, 16, None))
     a[:, 11] = a[:, 4]
     for jobq in (0, 1):
@@ -312,6 +315,12 @@ def test_qrcp_copied_column_is_recorded(bq):
         print("qrcp copied column: jobq %d state %d sweeps %d jpvt %s diag(R) %s"
               % (jobq, state, sweeps, jp.tolist() if state == 0 else None, None if d is None else np.array2string(d, precision=3)))
         assert state in (0, bq.error_not_finite)
+        if state == 0:
+            check_structure(r, jp, "copied column jobq %d" % jobq)
+    b = np.random.default_rng(5).standard_normal((4096, 3))
+    x, r, p, rank = bq.lstsq_rank_f64(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), rcond=1e-8)
+    print("qrcp copied column: lstsq_rank_f64 rank %d jpvt %s" % (rank, p.tolist()))
+    assert rank == 15 and int(p[15]) in (4, 11) and not bool(x[int(p[15])].any())
 
 
 def test_qrcp_f64_tensor(bq):
