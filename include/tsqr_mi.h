@@ -748,6 +748,16 @@ void tsqr_mi_set_tuning(int level0_waves, int tree_chunks_per_wave);
 /* waves of the Gram kernel / of the apply kernel (apply: persistent grid of apply_waves/4 workgroups; default = all that are resident
  * at once).  Work-buffer sizes follow the Gram setting: set it before allocating. */
 void tsqr_mi_set_tuning2(int gram_waves, int apply_waves);
+/* Load policy of A in the two streaming passes of a full 64-column call (m a multiple of 128, at most 2^20 rows, 16-byte aligned
+ * columns: the Gram block kernel and the 64-row apply kernel).  0 auto, 1 cache-allocating loads, 2 streamed: nontemporal loads in both
+ * passes, for devices whose nontemporal Q stores allocate in the memory-side cache and displace A between calls.  Auto measures the two
+ * once per process and device on the first blocking fp32_tc_cor call of at least 128 MiB that is out of place (a few call times, on
+ * the caller's operands), takes the streamed loads only when they are clearly faster, and uses the cache-allocating loads everywhere
+ * else; calls in flight (submit, and the loop and batch entries beyond loop depth 1) never measure.  The policy changes no bit of Q, R or the verdicts.  Process-wide; the
+ * environment variable TSQR_MI_LOAD_POLICY sets the initial value. */
+void tsqr_mi_set_load_policy(int p);
+/* the policy the last such call used (1 or 2); 0 before the first one */
+int tsqr_mi_get_load_policy(void);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,7 @@ def _c_signatures():
         # (the arguments of tsqr_mi_lstsq_rank_f64)
         "tsqr_mi_lstsq_minnorm_f64": (ci, [ci, ci, ci, ci, ctypes.c_double, vp, sz, vp, sz, vp, ctypes.POINTER(ci), vp, sz, vp, sz, sz, sz, sz,
                                            vp, vp, vp]),
+        "tsqr_mi_set_load_policy": (None, [ci]), "tsqr_mi_get_load_policy": (ci, []),
     }
 
 
@@ -145,7 +146,8 @@ OPTIONAL_SYMBOLS = {
     "tsqr_mi_working_q_size_f64_svd", "tsqr_mi_working_r_size_f64_svd", "tsqr_mi_svd_f64", "tsqr_mi_last_jacobi_sweeps_f64",
     "tsqr_mi_working_q_size_f64_qrcp", "tsqr_mi_working_r_size_f64_qrcp", "tsqr_mi_qrcp_f64",
     "tsqr_mi_working_q_size_f64_lstsq_rank", "tsqr_mi_working_r_size_f64_lstsq_rank", "tsqr_mi_lstsq_rank_f64",
-    "tsqr_mi_working_q_size_f64_lstsq_minnorm", "tsqr_mi_working_r_size_f64_lstsq_minnorm", "tsqr_mi_lstsq_minnorm_f64"}
+    "tsqr_mi_working_q_size_f64_lstsq_minnorm", "tsqr_mi_working_r_size_f64_lstsq_minnorm", "tsqr_mi_lstsq_minnorm_f64",
+    "tsqr_mi_set_load_policy", "tsqr_mi_get_load_policy"}
 
 _lib = None
 

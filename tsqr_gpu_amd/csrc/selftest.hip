@@ -105,7 +105,7 @@ extern "C" int tsqr_selftest_chain(const float* a, size_t lda, size_t m, int npa
 	double* gsum1 = partB + (size_t)nparts * nelem; double* gsum2 = gsum1 + 2568;
 	unsigned* ticket = reinterpret_cast<unsigned*>(gsum2 + 2568);
 	(void)hipMemset(ticket, 0, 8);
-	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES);
+	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES);
 	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES);
 	tsqrmi::GramArgs ga{};
 	ga.a = a; ga.lda = lda; ga.m = m; ga.n = 64; ga.nchunks = (int)(m / 128); ga.part = partA;
@@ -115,7 +115,7 @@ extern "C" int tsqr_selftest_chain(const float* a, size_t lda, size_t m, int npa
 		c.scond_floor = 4.0f;
 		return c;
 	};
-	hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, 0, ga);
+	hipLaunchKernelGGL(tsqrmi::gram_blk_kernel<false>, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, 0, ga);
 	launch_reduce1(0, gsum1, partA, nparts, nelem, (double)m);
 	hipLaunchKernelGGL(tsqrmi::chol16_kernel, dim3(1), dim3(1024), 0, 0, chol(0, gsum1));
 	tsqrmi::ChainArgs ch{};
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void gram_blk_stamp_kernel(const tsqrmi::Gr
 	extern __shared__ __attribute__((aligned(16))) float gb_as_st[];
 	unsigned long long t0 = 0;
 	if (threadIdx.x == 0) t0 = __builtin_amdgcn_s_memrealtime();
-	tsqrmi::gram_blk_body(a, gb_as_st, blockIdx.x, gridDim.x);
+	tsqrmi::gram_blk_body<false>(a, gb_as_st, blockIdx.x, gridDim.x);
 	if (threadIdx.x == 0) {
 		unsigned xcc, hw;
 		asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));

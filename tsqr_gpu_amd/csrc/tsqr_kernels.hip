@@ -1018,6 +1018,9 @@ constexpr int GB_OLD_SHARE = 20;                       // of 32: the share of a 
 constexpr int GB_LDS_BYTES = 2 * 64 * GB_RS * 4;
 // (the body takes its workgroup number and the number of Gram workgroups as arguments: gram_blk_chain_kernel below runs it on a part of
 // its grid)
+// NT_A: the block loads of A are nontemporal (the streamed load policy, tsqr_mi_set_load_policy) -- the cache-policy bits are an immediate
+// of the buffer load, so the policy is a template flag of the one loop: same instructions, same waits, same partials.
+template <bool NT_A>
 __device__ __forceinline__ void gram_blk_body(const GramArgs& a, float* gb_as, const int wg, const int nwg) {
 	constexpr int NTRI = 10;
 	static_assert(GB_LDS_BYTES >= (int)sizeof(double) * 2 * NTRI * 256, "the final workgroup reduction aliases the block buffers");
@@ -1056,7 +1059,7 @@ __device__ __forceinline__ void gram_blk_body(const GramArgs& a, float* gb_as, c
 		// (no branch at all: past the end the last block is simply loaded again and never used)
 		const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.a + (size_t)min(b, blast) * GB_ROWS), 0, -1, 0x00020000);
 #pragma unroll
-		for (int k = 0; k < 8; k++) v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff0 + k * soffk, 0));
+		for (int k = 0; k < 8; k++) v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff0 + k * soffk, NT_A ? 2 : 0));
 	};
 	auto stage = [&](const f32x4 (&v)[8], float* buf) {
 #pragma unroll
@@ -1121,10 +1124,11 @@ __device__ __forceinline__ void gram_blk_body(const GramArgs& a, float* gb_as, c
 	__syncthreads();                                     // the workgroup sum aliases the block buffers
 	wg_sum4_store(tot, reinterpret_cast<double*>(gb_as), a.part + (size_t)wg * NTRI * 256, wv, lane);
 }
+template <bool NT_A = false>
 __global__ __launch_bounds__(256, 2) void gram_blk_kernel(const GramArgs a) {
 	extern __shared__ __attribute__((aligned(16))) float gb_as[];        // [buffer][column][GB_RS]
 	announce_previous_call(a.announce, a.announce_seq);
-	gram_blk_body(a, gb_as, blockIdx.x, gridDim.x);
+	gram_blk_body<NT_A>(a, gb_as, blockIdx.x, gridDim.x);
 }
 
 // gram_reduce1_kernel: partials -> G in ONE launch (deterministic: fixed partition, fixed tree).  A workgroup owns 16
@@ -1794,7 +1798,7 @@ __global__ __launch_bounds__(256, 2) void gram_blk_chain_kernel(const GramArgs a
 	announce_previous_call(a.announce, a.announce_seq);
 	const int nchain = ch.direct ? 1 : ch.nred;
 	if ((int)blockIdx.x >= nchain) {
-		gram_blk_body(a, gb_as, (int)blockIdx.x - nchain, (int)gridDim.x - nchain);
+		gram_blk_body<false>(a, gb_as, (int)blockIdx.x - nchain, (int)gridDim.x - nchain);   // (plain loads: the chained stream on one A lives off its residency)
 		return;
 	}
 	const CholArgs& c = ch.chol;
@@ -2144,9 +2148,13 @@ __device__ __forceinline__ void gramq_accumulate(f64x4 (&gtot)[G::NTRI], const f
 // partial format as gram_bf16_kernel) -- the second sweep of a reorthogonalisation then needs no Gram pass of its own.
 // IO = _Float16 (fp16 I/O modes): a.a and a.q hold halves (8-byte aligned rows of four: the host checks lda, ldq % 4 == 0 and the
 // bases); a block is widened on its way into As and the result narrowed on its way out -- the products run on the same engines.
-template <int ENGINE, int NT, bool UPD, int ROWS, bool GRAMQ, int NW = 4, class IO = float>
+// NT_A (the plain 64-row fp32 kernels only): the block loads of A are nontemporal -- the streamed load policy (tsqr_mi_set_load_policy);
+// a compile-time choice of the one load group, so the loop, its prefetch depth and its waits are those of the plain instance.  The Z
+// staging loads and the Q stores are the same in both.
+template <int ENGINE, int NT, bool UPD, int ROWS, bool GRAMQ, int NW = 4, class IO = float, bool NT_A = false>
 __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 	static_assert(!GRAMQ || NW == 4, "the fused Gram accumulation is written for four waves");
+	static_assert(!NT_A || (!UPD && !GRAMQ && ROWS == 64 && NW == 4 && sizeof(IO) == 4), "streamed A: the plain 64-row fp32 kernels only");
 	static_assert(sizeof(IO) == 4 || (!UPD && !GRAMQ), "fp16 I/O: the plain product only");
 	using G = ApplyGeom<ENGINE, NT, UPD, ROWS, NW>;
 	constexpr int NP = G::NP, RS = G::RS, CPI = G::CPI, NI = G::NI, SL = G::SL, ZS = G::ZS, KT = G::KT, NB = G::NB, NTRI = G::NTRI;
@@ -2174,6 +2182,8 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 					if constexpr (sizeof(T) == 2) {
 						const f16x4 h = *reinterpret_cast<const f16x4*>(src);
 						v[k] = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+					} else if constexpr (NT_A) {
+						v[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(src));
 					} else {
 						v[k] = *reinterpret_cast<const f32x4u*>(src);
 					}
@@ -2512,7 +2522,7 @@ __device__ __forceinline__ void apply_wg_body(const ApplyArgs& a) {
 	}
 }
 
-template <int ENGINE, int NT, bool UPD, int ROWS, bool GRAMQ = false>
+template <int ENGINE, int NT, bool UPD, int ROWS, bool GRAMQ = false, bool NT_A = false>
 __global__ __launch_bounds__(256) void apply_wg_kernel(const ApplyArgs a) {
 	if constexpr (UPD) {
 		ApplyArgs b = a;                                 // (uniform: the slice's own arguments, in scalar registers)
@@ -2522,7 +2532,7 @@ __global__ __launch_bounds__(256) void apply_wg_kernel(const ApplyArgs a) {
 		}
 		apply_wg_body<ENGINE, NT, UPD, ROWS, false>(b);
 	} else {
-		apply_wg_body<ENGINE, NT, UPD, ROWS, false>(a);
+		apply_wg_body<ENGINE, NT, UPD, ROWS, false, 4, float, NT_A>(a);
 	}
 }
 // the variant that also accumulates Q^T Q: two waves per SIMD (the register allocator is told to stay within 256 registers)

@@ -48,6 +48,7 @@ namespace {
 // process-wide settings (atomics: written by the tsqr_mi_set_* calls, snapshotted once per call) and per-thread diagnostics
 // ---------------------------------------------------------------------------------------------------------------------------
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+int clamp_load_policy(int p) { return (p == 1 || p == 2) ? p : 0; }
 
 struct Settings {
 	std::atomic<int> policy{0};          // 0 auto, 1 Householder, 2 Gram without check/fallback
@@ -56,6 +57,8 @@ struct Settings {
 	std::atomic<int> wide{1};            // 64 < n <= 128: one Cholesky-QR panel of up to 128 columns first (policy 5 turns it off)
 	std::atomic<int> apply_wgs{0};       // workgroups of the apply pass; 0: as many as are resident at once (tsqr_mi_set_tuning2)
 	std::atomic<int> loop_depth{3};      // *_loop entries: 1 blocking calls, 2 two calls in flight, 3 also the chained schedule (tsqr_mi_set_loop_depth)
+	std::atomic<int> load_policy{clamp_load_policy(env_int("TSQR_MI_LOAD_POLICY", 0))};   // loads of A in gram_blk_kernel and the plain 64-row apply kernel:
+	                                     // 0 auto (measured once, measure_load_policy), 1 cache-allocating, 2 streamed (tsqr_mi_set_load_policy)
 	// the two environment switches that are left (read once at load): the floor of the bf16-split level's bound on the scaled
 	// conditioning S, and a diagnostic print of every Cholesky verdict
 	const float bf16_scond_floor = (float)env_int("TSQR_MI_BF16_MAX_SCOND", BF16_SCOND_FLOOR_DEFAULT);
@@ -67,6 +70,7 @@ struct Settings {
 	const int debug = env_int("TSQR_MI_DEBUG", 0);
 };
 Settings g_set;
+std::atomic<int> g_load_policy_used{0};                // what the last call that took gram_blk_kernel used (1 / 2; 0: no such call yet)
 std::atomic<unsigned> g_seq{0};                        // sequence numbers of the completion flags (any thread)
 
 thread_local std::string t_last_error;
@@ -130,7 +134,8 @@ struct DevOnce {
 int blk_kernel_attrs(int dev) {
 	static DevOnce attr;
 	if (attr.need(dev)) {
-		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
 		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tsqrmi::gram_blk_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tsqrmi::GB_LDS_BYTES));
 		attr.done(dev);
 	}
@@ -284,6 +289,7 @@ struct SweepOpts {
 	int relax = 0;                                       // bf16-level Cholesky launches use the relaxed rule (CholArgs::relax: another sweep follows)
 	int retry_shift = 0;                                 // ... and factor a rejected matrix again at once, shifted (CholArgs::retry_shift)
 	bool q_read_back = false;                            // Q is read back at once by the next sweep: plain stores, ascending block order (ApplyArgs::plain_q / forward)
+	int load_policy = 0;                                 // loads of A in the panel's two passes: 1 cache-allocating, 2 streamed, 0: panel_qr resolves it (resolve_load_policy)
 };
 struct Ctx {
 	hipStream_t st = nullptr;
@@ -527,6 +533,18 @@ inline bool blk_gram_ok(const float* a, size_t lda, size_t m, size_t n) {
 	return n == PW && m % 128 == 0 && m <= ((size_t)1 << 20) && lda % 4 == 0 && lda <= ((size_t)1 << 24) && (reinterpret_cast<uintptr_t>(a) & 15) == 0;
 }
 
+// The load policy of A for one panel whose Gram pass takes gram_blk_kernel (tsqr_mi_set_load_policy).  A pinned setting holds for every
+// such panel; under the auto setting the streamed policy is taken only where it was measured faster (measure_load_policy: once per
+// process and device, by the first eligible blocking call) and only for what it was measured on: operands of at least 128 MiB, out of
+// place, no profiling.  Everything else -- and every call before the measurement -- loads as it always did.
+constexpr double LOAD_POLICY_MIN_BYTES = 128.0 * 1048576.0;
+std::atomic<int> g_load_policy_chosen[MAX_DEV];        // 0 not measured yet, 1 cache-allocating, 2 streamed
+int resolve_load_policy(int dev, double bytes, bool as_measured) {   // as_measured: out of place, and the apply pass is the plain 64-row kernel (both passes follow the policy)
+	const int pinned = g_set.load_policy.load();
+	if (pinned) return pinned;
+	return (bytes >= LOAD_POLICY_MIN_BYTES && as_measured && !t_prof.on && g_load_policy_chosen[dev].load() == 2) ? 2 : 1;
+}
+
 // Gram matrix of src (m x n) in MFMA-accumulator order -> c.gsum() (ntri*256 doubles + the local row count behind them), summed
 // over the ranks of a row-partitioned call.  bf16 = true: bf16x3-split MFMA (memory-bound, f32 C/D layout), false: fp64 MFMA.
 // io_half: src holds halves (fp16 I/O modes, bf16 level only): gram_h_kernel takes them as MFMA operands directly.
@@ -554,7 +572,9 @@ int gram_g(Ctx& c, const SweepOpts& o, const float* src, size_t ld, size_t m, si
 		a.nchunks = (int)(m / 128);
 		nparts = std::min(a.nchunks, g.nblocks);
 		ProfScope ps(KC_GRAM, c.st);
-		hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, a);
+		if (o.load_policy == 2) hipLaunchKernelGGL(tsqrmi::gram_blk_kernel<true>, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, a);
+		else hipLaunchKernelGGL(tsqrmi::gram_blk_kernel<false>, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, a);
+		g_load_policy_used.store(o.load_policy == 2 ? 2 : 1);
 	} else {
 		ProfScope ps(KC_GRAM, c.st);
 		with_nt(NT, [&](auto nt) { launch_gram<decltype(nt)::value>(a, g.nblocks, bf16, c.st); });
@@ -635,10 +655,16 @@ inline bool apply_no_pre(tsqrmi::ApplyArgs&, int, size_t, unsigned) { return fal
 // same whoever computes a block: the last run leaves the result), ~0.7 ms once; the uneven shares are taken only when they are 1 %
 // faster.  TSQR_MI_APPLY_SHARES=0 / 1 / 2 pins equal / both / by round only.
 // Sets a's shares; true: this was the measurement, the pass has run.
-template <auto KERNEL> bool choose_block_shares(Ctx& c, tsqrmi::ApplyArgs& a, int per_cu, size_t lds, unsigned gy) {
+// KEY: the instance whose choice this one shares (the streamed-load instance of a kernel takes the shares of the plain one, whichever of the
+// two measured them).
+template <auto KEY> std::atomic<int> (&block_shares_chosen())[MAX_DEV][2] {
+	static std::atomic<int> chosen[MAX_DEV][2];      // 0 not measured yet, 1 both, 2 rounds only, 3 equal; [1]: a matrix beyond the Infinity Cache
+	return chosen;
+}
+template <auto KERNEL, auto KEY = KERNEL> bool choose_block_shares(Ctx& c, tsqrmi::ApplyArgs& a, int per_cu, size_t lds, unsigned gy) {
 	if (a.nwaves != 1024 || per_cu != 4) return false;
 	static const int pinned = env_int("TSQR_MI_APPLY_SHARES", -1);
-	static std::atomic<int> chosen[MAX_DEV][2];      // 0 not measured yet, 1 both, 2 rounds only, 3 equal; [1]: a matrix beyond the Infinity Cache
+	auto& chosen = block_shares_chosen<KEY>();
 	auto set_mode = [](tsqrmi::ApplyArgs& x, int mode) {
 		x.share[0] = x.share[1] = x.share[2] = x.share[3] = 0; x.even_share = 0;
 		if (mode == 1 || mode == 2) { x.share[0] = 18; x.share[1] = 17; x.share[2] = 15; x.share[3] = 14; x.even_share = (mode == 1) ? 69 : 64; }
@@ -689,6 +715,15 @@ template <int E, int NT, bool UPD, int ROWS, bool GRAMQ = false> int launch_appl
 	grid.wgs = g_set.apply_wgs.load();
 	if (UPD) grid.gy = UpdApply<E>::gy(a.multi_cols);
 	if (GRAMQ) grid.max_wgs = o.gramq_cap;               // one partial per workgroup: never more than the buffer holds
+	if constexpr (!UPD && !GRAMQ && ROWS == 64 && NT == 4) {
+		// the streamed load policy: the same kernel with nontemporal loads of A (an instance of its own: its own attributes, the same grid and shares)
+		if (o.load_policy == 2) {
+			constexpr auto streamed = &tsqrmi::apply_wg_kernel<E, NT, UPD, ROWS, false, true>;
+			return launch_apply<streamed, tsqrmi::ApplyGeom<E, NT, UPD, ROWS>, GRAMQ, CAP, true>(c, a, grid, [&](tsqrmi::ApplyArgs& x, int per_cu, size_t lds, unsigned gy) {
+				return choose_block_shares<streamed, kernel>(c, x, per_cu, lds, gy);
+			});
+		}
+	}
 	return launch_apply<kernel, tsqrmi::ApplyGeom<E, NT, UPD, ROWS>, GRAMQ, CAP, true>(c, a, grid, [&](tsqrmi::ApplyArgs& x, int per_cu, size_t lds, unsigned gy) {
 		if constexpr (GRAMQ) {
 			x.gpart = o.gramq_part;
@@ -816,7 +851,12 @@ int panel_qr(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, int r_en
 	for (int e = r_engine; e >= 1; e--) {                // 2: bf16-split Gram, 1: fp64 Gram; with check_now a rejected level escalates
 		// (o.gramq_ready: only the bf16-level request, e == 2, takes ready partials, and this loop makes one such request at the most.  Sweeps
 		// are fused for n <= 64 alone -- one panel, one call of this function -- so the sweep's value can be forwarded as it is.)
-		rc = gram_g(c, o, ap, lda, m, cc, e == 2);
+		// (the load policy is a matter of the panels gram_blk_kernel takes -- gram_g sends the same ones there; every other panel's two passes
+		// are the kernels and loads they always were)
+		SweepOpts po = o;
+		if (!(e == 2 && blk_gram_ok(ap, lda, m, cc))) po.load_policy = 1;
+		else if (po.load_policy == 0) po.load_policy = resolve_load_policy(c.dev, (double)m * (double)cc * sizeof(float), qp != ap && engine == 1);
+		rc = gram_g(c, po, ap, lda, m, cc, e == 2);
 		if (rc) return rc;
 		rc = chol_from_g(c, o, rpp, ldr, cc, e);
 		if (rc) return rc;
@@ -831,7 +871,7 @@ int panel_qr(Ctx& c, const SweepOpts& o, int* gramq_nparts, int engine, int r_en
 			c.min_level = std::min(c.min_level, e);
 			// speculative (unchecked) launch under the auto policy: the kernel itself skips the pass when the level was rejected
 			const unsigned* skip = (!check_now && c.policy == 0) ? c.status_dev(o.slot) : nullptr;
-			return apply_rinv(c, o, gramq_nparts, engine, qp, ldq, ap, lda, rpp, ldr, m, cc, /*z_ready=*/true, skip);
+			return apply_rinv(c, po, gramq_nparts, engine, qp, ldq, ap, lda, rpp, ldr, m, cc, /*z_ready=*/true, skip);
 		}
 	}
 	if ((direct_shift || (r_engine >= 1 && check_now)) && c.policy == 0) {
@@ -1197,6 +1237,51 @@ int qr_two_sweeps(Ctx& c, int engine, int level, int first_level, bool check_now
 	return wait_done(c);                                 // completion flag in the pinned words, or a plain stream sync
 }
 
+// The auto load policy (tsqr_mi_set_load_policy, resolve_load_policy), measured once per process and device by the first blocking call
+// that is eligible: a full 64-column fp32_tc_cor call of at least 128 MiB, out of place, accepted at the bf16-split level, no profiling.
+// What a policy changes is what one call's passes leave in the Infinity Cache for the NEXT call's Gram pass, so the unit timed is the call
+// sequence -- Gram pass, reduction, Cholesky, apply pass on the caller's operands, with the block shares already chosen -- and never a
+// single pass: the two arms take turns in runs of two sequences (1 1 2 2 1 1 2 2 ...) and only the second sequence of a run counts, the
+// first inherits the other arm's cache state.  The streamed policy is taken when its mean is below the cache-allocating arm's by more
+// than the larger of 3 % and that arm's own max - min.  Every sequence writes the same Q, R and verdict (the policy does not touch the
+// arithmetic): the last one leaves the result.  ~2.3 ms once.  Leaves the stream idle.
+void measure_load_policy(Ctx& c, int engine, float* q, size_t ldq, float* r, size_t ldr, float* a, size_t lda, size_t m, size_t n) {
+	constexpr int RUNS = 3, NSEQ = 4 * RUNS;
+	hipEvent_t ev[NSEQ + 1];
+	bool ok = true;
+	for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+	int choice = 1;
+	if (ok) {
+		for (int i = 0; i < NSEQ && ok; i++) {
+			SweepOpts o{};
+			o.load_policy = ((i >> 1) & 1) ? 2 : 1;
+			(void)hipEventRecord(ev[i], c.st);
+			ok = sweep(c, o, nullptr, engine, 2, /*check_now=*/false, q, ldq, r, ldr, a, lda, m, n) == 0;
+		}
+		(void)hipEventRecord(ev[NSEQ], c.st);
+		ok = (hipEventSynchronize(ev[NSEQ]) == hipSuccess) && ok;
+		float sum[2] = {0.f, 0.f}, lo = 1e30f, hi = 0.f;
+		for (int i = 1; i < NSEQ && ok; i += 2) {
+			float ms = 0.f;
+			ok = hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess;
+			const int arm = (i >> 1) & 1;
+			sum[arm] += ms;
+			if (arm == 0) { lo = std::min(lo, ms); hi = std::max(hi, ms); }
+			if (g_set.debug) fprintf(stderr, "[tsqr_mi] load policy %d: sequence %.4f ms\n", arm + 1, ms);
+		}
+		if (ok) {
+			const float mean1 = sum[0] / RUNS, mean2 = sum[1] / RUNS;
+			if (mean2 < mean1 - std::max(0.03f * mean1, hi - lo)) choice = 2;
+			if (g_set.debug) fprintf(stderr, "[tsqr_mi] load policy: cache-allocating %.4f ms (spread %.4f), streamed %.4f ms -> %d\n", mean1, hi - lo, mean2, choice);
+		}
+	} else {
+		(void)hipStreamSynchronize(c.st);
+	}
+	for (auto& e : ev) (void)hipEventDestroy(e);
+	(void)hipGetLastError();
+	g_load_policy_chosen[c.dev].store(choice);           // (a measurement that failed is not asked for again: the policy stays what it was)
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // the whole factorisation (single GPU: comm inactive; row-partitioned: this rank's block)
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1269,6 +1354,11 @@ int qr_core(Ctx& c, int engine, int reorth, float* q, size_t ldq, float* r, size
 			rc = read_status(c, 0, &status, &scond1);
 			if (rc) return rc;
 			if (status != 0) { c.min_level = 2; continue; }       // rejected: step down and redo
+			// the accepted first large blocking call of the process on this device measures the load policy (the share measurement of its
+			// apply pass has run by now); submit / batch entries never come here: they use what was chosen, or the cache-allocating loads
+			if (level == 2 && engine == 1 && q != a && !t_prof.on && !c.comm.active() && g_set.load_policy.load() == 0 &&
+			    g_load_policy_chosen[c.dev].load() == 0 && (double)m * (double)n * sizeof(float) >= LOAD_POLICY_MIN_BYTES && blk_gram_ok(a, lda, m, n))
+				measure_load_policy(c, engine, q, ldq, r, ldr, a, lda, m, n);
 		} else {
 			rc = wait_done(c);                           // completion flag in the pinned words, or a plain stream sync
 			if (rc) return rc;
@@ -1401,6 +1491,8 @@ void tsqr_mi_set_tuning(int level0_waves, int tree_chunks_per_wave) {
 	if (level0_waves > 0) g_set.level0_waves = level0_waves;
 	if (tree_chunks_per_wave > 1) g_set.tree_cpw = tree_chunks_per_wave;
 }
+void tsqr_mi_set_load_policy(int p) { g_set.load_policy = clamp_load_policy(p); }
+int tsqr_mi_get_load_policy(void) { return g_load_policy_used.load(); }
 void tsqr_mi_set_tuning2(int gram_waves, int apply_waves) {
 	if (gram_waves > 0) g_set.gram_waves = gram_waves;
 	if (apply_waves > 0) g_set.apply_wgs = std::max(1, apply_waves / 4);   // the apply kernel is launched as a persistent grid of workgroups (4 waves each)
@@ -1773,7 +1865,7 @@ static int chained64(const Mats& mt, int count, const Call& cl, int* done) {
 	};
 	{
 		ProfScope ps(KC_GRAM, c.st);
-		hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args_64(c, mt.a(0), cl, nchunks, g, part[0]));
+		hipLaunchKernelGGL(tsqrmi::gram_blk_kernel<false>, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args_64(c, mt.a(0), cl, nchunks, g, part[0]));
 	}
 	HIPCHK(hipGetLastError());
 	return run_chained(comp, mt, count, 3, step, [&](int i) { return rejected_tail(CallEnv{}, mt, count, cl, i, comp, done); }, done);
@@ -1873,7 +1965,7 @@ static int chained_dist(const CallEnv& env, const Mats& mt, int count, const Cal
 	if (mine) {
 		{
 			ProfScope ps(KC_GRAM, c.st);
-			hipLaunchKernelGGL(tsqrmi::gram_blk_kernel, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args_64(c, mt.a(0), cl, nchunks, g, part));
+			hipLaunchKernelGGL(tsqrmi::gram_blk_kernel<false>, dim3(nparts), dim3(256), tsqrmi::GB_LDS_BYTES, c.st, gram_args_64(c, mt.a(0), cl, nchunks, g, part));
 		}
 		HIPCHK(hipGetLastError());
 		rc = reduce_allreduce(1);
