@@ -508,6 +508,33 @@ inline state_t lstsq_minnorm_fp64(
 	if (st < 0) throw std::runtime_error(std::string("mtk::qr::lstsq_minnorm_fp64: ") + tsqr_mi_last_error());
 	return st;
 }
+// Not in the reference: a block w (m x n) orthogonalised against an orthonormal basis v (m x k, read only), the step of block Arnoldi,
+// block Lanczos, LOBPCG and randomised range finders (tsqr_mi_orth_f64, include/tsqr_mi.h for the method and the contract): w is
+// overwritten by q with v^T q = 0, q^T q = I and w_in = v s + q r; s (k x n, lds) and r (n x n upper triangular, ldr) are column-major.
+// 1 <= n <= 64, 1 <= k <= 1024, k + n <= m.  passes: 2 (BCGS2, the default) or 1.  Returns success_factorization,
+// error_invalid_matrix_size (every size, layout or passes error: this entry has no error_unsupported_mode) or error_not_finite, after
+// which w, s and r are undefined.  State 0 is no test that w was independent of v: compare diag(r) with w's column norms.
+template <bool Reorthogonalize>
+struct buffer_fp64_orth : detail::buffer_fp64_base {
+	void allocate(const std::size_t m, const std::size_t k, const std::size_t n) { allocate_doubles(tsqr_mi_working_q_size_f64_orth(m, k, n), tsqr_mi_working_r_size_f64_orth(m, k, n)); }
+};
+
+template <bool Reorthogonalize>
+inline state_t orth_fp64(
+		double* const w_ptr, const std::size_t ldw,
+		double* const s_ptr, const std::size_t lds,
+		double* const r_ptr, const std::size_t ldr,
+		const double* const v_ptr, const std::size_t ldv,
+		const std::size_t m, const std::size_t k, const std::size_t n,
+		buffer_fp64_orth<Reorthogonalize>& bf,
+		handle_t const stream = nullptr,
+		const layout_t v_layout = col_major, const layout_t w_layout = col_major,
+		const int passes = 2) {
+	const int st = tsqr_mi_orth_f64(v_layout, w_layout, passes, Reorthogonalize ? 1 : 0, w_ptr, ldw, s_ptr, lds, r_ptr, ldr, v_ptr, ldv, m, k, n,
+	                                bf.dwq, bf.dwr, stream);
+	if (st < 0) throw std::runtime_error(std::string("mtk::qr::orth_fp64: ") + tsqr_mi_last_error());
+	return st;
+}
 // Not in the reference: double-precision tall-skinny QR for 1 <= n <= 1024, n <= m (tsqr_mi_qr_f64_wide, include/tsqr_mi.h for the
 // contract): qr_fp64 itself for n <= 64, whole-matrix CholeskyQR sweeps with the same ladder beyond.  Returns success_factorization,
 // error_invalid_matrix_size, error_unsupported_mode (n > 1024) or error_not_finite.  a_layout, q_layout (tsqr_mi_qr_f64_wide_lay): the

@@ -633,6 +633,46 @@ int tsqr_mi_lstsq_minnorm_f64(int a_layout, int b_layout, int reorth, int refine
                               size_t m, size_t n, size_t nrhs, void* wq, void* wr, void* stream);
 
 /*
+ * Block orthogonalisation against an existing basis in double precision (not in the reference): the step of block Arnoldi, block
+ * Lanczos, LOBPCG, randomised range finders and s-step Krylov methods.  V (m x k, read only) holds an orthonormal basis -- the caller
+ * promises that, the call does not test it -- and W (m x n) a new block.  On return W holds Q with V^T Q = 0, Q^T Q = I and
+ * W_in = V S + Q R; S is k x n and R n x n upper triangular with diag(R) >= 0 like tsqr_mi_qr_f64's, both column-major.
+ * 1 <= n <= 64, 1 <= k <= 1024, k + n <= m.  v_layout, w_layout: TSQR_MI_COL_MAJOR or TSQR_MI_ROW_MAJOR for V and for W, as in
+ * tsqr_mi_qr_f64_lay (ldv >= m or >= k, ldw >= m or >= n); lds >= k, ldr >= n.  W must not overlap V, S or R, nor S R.
+ * Method: BCGS2 (block classical Gram-Schmidt with reorthogonalisation) with the n <= 64 ladder as the inner QR.  A round is
+ * (1) Si = V^T X, the cross-Gram pass (orth_gram_f64_kernel: one wave per 64-column block of V and row slice on
+ * v_mfma_f64_16x16x4_f64, the slices summed in a fixed tree); (2) X <- X - V Si in place in W (orth_update_f64_kernel, Si staged in
+ * LDS in 64-row blocks); (3) X = Qi Ri by the ladder of tsqr_mi_qr_f64_lay in place, with its device passes, acceptance rule and
+ * `reorth`.  passes = 1 runs one round: S = S1, R = R1.  passes = 2 runs two: S = S1 + S2 R1, R = R2 R1.  One round is NOT enough when
+ * the projected block is ill conditioned or W lies close to span(V): with W = V C + 1e-6 G, cond(G) = 1e8 (1003 x 130 basis, 17 columns)
+ * a model of one round leaves ||V^T Q||_F = 4.7e-9 where two leave 1.3e-15.  Use passes = 1 only where that loss is known not to matter.
+ * Nothing of size m x k or m x n is allocated or stored besides W itself; the call allocates nothing.  Blocking, bitwise
+ * deterministic from call to call, and Q, S, R, the state and the sweep count are BITWISE the same for all four layout pairs (a
+ * row-major instance puts the same value into the register the column-major one holds it in, or swaps the MFMA operands).  Nothing at a
+ * row >= m, or between the column count and the leading dimension of an operand, is read or written.
+ * Accuracy (passes = 2, reorth = 0, the cases of tests/pass_refs_f64_orth.py): ||Q^T Q - I||_F <= 1e-11 and
+ * ||W - V S - Q R||_F / ||W||_F <= 1e-13, the QR entry's claims restated, and ||V^T Q||_F <= max(2 x a NumPy model's on the same data,
+ * 4 max(k, n) 2^-53); profiles/fp64_orth_accuracy.md has the table.
+ * Work space: wq of tsqr_mi_working_q_size_f64_orth(m, k, n) doubles (the QR entry's plus R of round 2 and the work copy of S: it grows
+ * with k, not with m) and wr of tsqr_mi_working_r_size_f64_orth(m, k, n) doubles (partials of the Gram passes, at most 4 Mi doubles).
+ * Both are monotone in m, k and n.
+ * Returns 0; 1 = TSQR_MI_ERROR_INVALID_SIZE for a null pointer, passes outside {1, 2}, a size outside the ranges above (n > 64 and
+ * k > 1024 included: this entry has no state 2), a layout other than the two, or a leading dimension below its operand's extent -- all
+ * before any HIP call, and no operand is touched; 3 = TSQR_MI_ERROR_NOT_FINITE, the ladder's state 3 on the projected block (this
+ * includes Inf or NaN in V or W, which reach it through S); or -(hipError_t).  After state 3, W, S and R are UNDEFINED.
+ * tsqr_mi_last_sweeps_f64 reports the SUM of the ladder's sweeps over the rounds, plus 100 when either took the shifted path.
+ * State 0 is no test that W was independent of V: a W inside span(V) gives an orthonormal Q of rounding noise and a tiny R.  Compare
+ * diag(R) with the column norms of W before using Q as a new direction.
+ * Not provided: breakdown detection, k > 1024, n > 64, the row-partitioned and batched forms.
+ */
+size_t tsqr_mi_working_q_size_f64_orth(size_t m, size_t k, size_t n);
+size_t tsqr_mi_working_r_size_f64_orth(size_t m, size_t k, size_t n);
+int tsqr_mi_orth_f64(int v_layout, int w_layout, int passes, int reorth,
+                     double* w, size_t ldw, double* s, size_t lds, double* r, size_t ldr,
+                     const double* v, size_t ldv, size_t m, size_t k, size_t n,
+                     void* wq, void* wr, void* stream);
+
+/*
  * Wide double-precision tall-skinny QR (not in the reference): tsqr_mi_qr_f64's arguments, operand rules and states for 1 <= n <= 1024,
  * n <= m.  n <= 64 IS tsqr_mi_qr_f64 (bitwise the same results, its work-space sizes).  64 < n <= 1024: the same ladder of CholeskyQR
  * sweeps and the same acceptance rule (CholArgs64 in tsqr_f64.hip), each sweep over all n columns at once: the Gram matrix on 64-column

@@ -1,6 +1,7 @@
 """SHA-256 (first 16 hex digits) of the results of the fp64 entries that take a tensor -- qr_f64_tensor, qr_f64_wide_tensor, lstsq_f64
 (3 right-hand sides), svd_f64_tensor with and without U, qrcp_f64_tensor with and without Q, lstsq_rank_f64 and the same with minimum_norm=True
-(x, r, jpvt and the rank, a line each; on the same 3 right-hand sides, the default rcond) -- at 9211 x 51, 2^20 x 64, 100 x 7 and
+(x, r, jpvt and the rank, a line each; on the same 3 right-hand sides, the default rcond), orth_f64_tensor with passes 1 and 2 (the
+matrix as w against the Q of a Gaussian m x 2 n matrix as v) -- at 9211 x 51, 2^20 x 64, 100 x 7 and
 65536 x 128, torch.randn with seed m + n generated on the device, handed over row-major ("row") and with column-major strides
 ("col"), reorth 0 and 1; at 9211 x 51 also the three entries that can run in place, with overwrite_a=True on a clone.  The entries are
 bitwise deterministic, so two builds of libtsqr_mi.so that are meant to compute the same thing must print the same table:
@@ -60,6 +61,14 @@ def table():
                         out[key + "lstsq_minnorm r"] = (sha(r),)
                         out[key + "lstsq_minnorm jpvt"] = (sha(p),)
                         out[key + "lstsq_minnorm rank"] = (rank,)
+                    if hasattr(bq.lib(), "tsqr_mi_orth_f64") and m >= 4 * n:   # (absent from a --parent-lib older than the entry)
+                        # w = the matrix of the line; v: the Q of another Gaussian matrix of 2 n columns in the same layout
+                        gv = torch.Generator(device="cuda").manual_seed(m + 3 * n)
+                        vq = bq.qr_f64_wide_tensor(torch.randn(m, 2 * n, dtype=torch.float64, device="cuda", generator=gv), reorth=True)[0]
+                        vq = vq if name == "row" else vq.t().contiguous().t()
+                        for passes in (1, 2):
+                            q, s_, r = bq.orth_f64_tensor(vq, x, passes=passes, reorth=reorth)
+                            out[key + "orth p%d" % passes] = (sha(q), sha(s_), sha(r), bq.last_sweeps_f64())
                     if (m, n) == SHAPES[0]:                 # in place, on a clone (it keeps x's strides); the flag: q IS the clone
                         c = x.clone()
                         q, r = bq.qr_f64_tensor(c, reorth=reorth, overwrite_a=True)

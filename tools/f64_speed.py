@@ -52,7 +52,10 @@ the JSON to --lstsq-rank-out (default profiles/fp64_lstsq_rank_speed.json) and p
 that arm alone and writes no file: the run to put under a kernel trace (profiles/fp64_lstsq_rank_kernel_stats_2p20x64.csv).
 --lstsq-minnorm: instead, the minimum-norm entry (tsqr_mi_lstsq_minnorm_f64, refine 1, 3 right-hand sides, the default rcond) next to
 tsqr_mi_lstsq_rank_f64 on the same operands, in one process with the arms interleaved, on the same four shapes; writes the JSON to
---lstsq-minnorm-out (default profiles/fp64_lstsq_minnorm_speed.json) and prints it."""
+--lstsq-minnorm-out (default profiles/fp64_lstsq_minnorm_speed.json) and prints it.
+--orth: instead, the block orthogonalisation entry (tsqr_mi_orth_f64) next to the composed form and to qr_f64_wide_tensor on [V W]
+(orth() below has the arms and shapes); writes the JSON to --orth-out (default profiles/fp64_orth_speed.json) and prints it;
+--orth-arms runs the named arms alone, for a kernel trace."""
 import argparse
 import json
 import math
@@ -812,6 +815,89 @@ def lstsq_minnorm(torch, bq, calls, warmup, only):
     return out
 
 
+ORTH_SHAPES = ((20, 64, 64), (20, 256, 64), (20, 1024, 64), (16, 256, 16))
+
+
+def orth(torch, bq, calls, warmup, only, only_arms=()):
+    """--orth: tsqr_mi_orth_f64 (arm a) next to the composition available without it (arm b: w -= v @ (v.T @ w), then qr_f64_tensor in
+    place; with passes = 2 both steps twice and the small products S = S1 + S2 R1, R = R2 R1 in torch) and to qr_f64_wide_tensor on
+    [V W] (arm c, where k + n <= 1024), at 2^20 x (k = 64, 256, 1024) x 64 and 2^16 x 256 x 16, both layouts, passes 1 and 2, reorth 0.
+    V: the Q of a Gaussian matrix (qr_f64_wide_tensor, reorth); W Gaussian.  One process, the arms interleaved call by call, medians of
+    --calls blocking calls.  Arms a and b work in place, so each of their calls first copies W into its work tensor; that copy alone is
+    the arm copy_w.  No time is set in advance."""
+    out = {"tool": "f64_speed --orth", "calls": calls, "warmup": warmup, "reorth": 0, "cases": []}
+    for lg, k, n in ORTH_SHAPES:
+        tag = "2p%dx%dx%d" % (lg, k, n)
+        if only and tag not in only:
+            continue
+        m = 1 << lg
+        g = torch.Generator(device="cuda").manual_seed(lg + k + n)
+        v_rm = bq.qr_f64_wide_tensor(torch.randn(m, k, dtype=torch.float64, device="cuda", generator=g), reorth=True, overwrite_a=True)[0]
+        w_rm = torch.randn(m, n, dtype=torch.float64, device="cuda", generator=g)
+        case = {"m": m, "k": k, "n": n}
+        for layout in ("row", "col"):
+            row = layout == "row"
+            as_layout = (lambda t: t) if row else (lambda t: t.t().contiguous().t())
+            v, w0 = as_layout(v_rm), as_layout(w_rm)
+            wk = torch.empty_strided(w0.shape, w0.stride(), dtype=torch.float64, device="cuda")
+            vw = as_layout(torch.cat([v_rm, w_rm], dim=1)) if k + n <= 1024 else None
+            s = torch.empty(n, k, dtype=torch.float64, device="cuda")
+            r = torch.empty(n, n, dtype=torch.float64, device="cuda")
+            bf = bq.buffer_f64_orth()
+            bf.allocate(m, k, n)
+            ldv, ldw = (k, n) if row else (m, m)
+
+            def arm_a(passes):
+                def call():
+                    wk.copy_(w0)
+                    return bq.orth_f64(wk, ldw, s, k, r, n, v, ldv, m, k, n, bf, passes=passes, v_row_major=row, w_row_major=row)
+                return call
+
+            def arm_b(passes):
+                def call():
+                    wk.copy_(w0)
+                    s_acc = r_acc = None
+                    x = wk
+                    for _ in range(passes):
+                        si = v.t() @ x
+                        x -= v @ si
+                        x, ri = bq.qr_f64_tensor(x, overwrite_a=True)
+                        s_acc, r_acc = (si, ri) if s_acc is None else (s_acc + si @ r_acc, ri @ r_acc)
+                    torch.cuda.synchronize()
+                    return 0
+                return call
+
+            def arm_c():
+                bq.qr_f64_wide_tensor(vw)
+                return 0
+
+            def copy_w():
+                wk.copy_(w0)
+                torch.cuda.synchronize()
+                return 0
+
+            arms = [("copy_w_" + layout, copy_w)]
+            for passes in (1, 2):
+                arms += [("a_orth_p%d_%s" % (passes, layout), arm_a(passes)), ("b_composed_p%d_%s" % (passes, layout), arm_b(passes))]
+            if vw is not None:
+                arms.append(("c_qr_wide_%s" % layout, arm_c))
+            arms, med, sweeps = time_arms(bq, arms, calls, warmup, only_arms, bq.last_sweeps_f64)
+            case.update({name + "_median_ms": med[name] for name, _ in arms})
+            if sweeps is not None:
+                case.update({name + "_sweeps": sweeps[name] for name, _ in arms if name.startswith("a_")})
+                for passes in (1, 2):
+                    a, b = med["a_orth_p%d_%s" % (passes, layout)], med["b_composed_p%d_%s" % (passes, layout)]
+                    case["a_over_b_p%d_%s" % (passes, layout)] = a / b
+                    if vw is not None:
+                        case["a_over_c_p%d_%s" % (passes, layout)] = a / med["c_qr_wide_%s" % layout]
+            del v, w0, wk, vw, bf
+            torch.cuda.empty_cache()
+        out["cases"].append(case)
+        del v_rm, w_rm
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=None, help="blocking calls per case or arm (default 50; --wide-row-major: 20)")
@@ -837,6 +923,9 @@ def main():
     ap.add_argument("--lstsq-rank-out", default=os.path.join(ROOT, "profiles", "fp64_lstsq_rank_speed.json"), help="--lstsq-rank: the JSON file ('' writes none)")
     ap.add_argument("--lstsq-minnorm", action="store_true", help="time tsqr_mi_lstsq_minnorm_f64 next to tsqr_mi_lstsq_rank_f64 (refine 1), arms interleaved")
     ap.add_argument("--lstsq-minnorm-out", default=os.path.join(ROOT, "profiles", "fp64_lstsq_minnorm_speed.json"), help="--lstsq-minnorm: the JSON file ('' writes none)")
+    ap.add_argument("--orth", action="store_true", help="time tsqr_mi_orth_f64 next to the composed form (torch.matmul + qr_f64_tensor) and qr_f64_wide_tensor on [V W]")
+    ap.add_argument("--orth-arms", default="", help="--orth: run only these arms (e.g. a_orth_p2_col) and write no file: for a kernel trace")
+    ap.add_argument("--orth-out", default=os.path.join(ROOT, "profiles", "fp64_orth_speed.json"), help="--orth: the JSON file ('' writes none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp64_wide_rowmajor_speed.json"), help="--wide-row-major: the JSON file")
     args = ap.parse_args()
     wide_rm = args.wide_row_major or args.wide_col_only
@@ -874,6 +963,14 @@ def main():
         out = lstsq_rank(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], only_arms)
         if args.lstsq_rank_out and not only_arms:
             with open(args.lstsq_rank_out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        print(json.dumps(out))
+        return
+    if args.orth:
+        only_arms = [c for c in args.orth_arms.split(",") if c]
+        out = orth(torch, bq, args.calls, args.warmup, [c for c in args.cases.split(",") if c], only_arms)
+        if args.orth_out and not only_arms:
+            with open(args.orth_out, "w") as f:
                 f.write(json.dumps(out, indent=1) + "\n")
         print(json.dumps(out))
         return

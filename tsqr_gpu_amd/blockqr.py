@@ -132,6 +132,9 @@ def _c_signatures():
         "tsqr_mi_lstsq_minnorm_f64": (ci, [ci, ci, ci, ci, ctypes.c_double, vp, sz, vp, sz, vp, ctypes.POINTER(ci), vp, sz, vp, sz, sz, sz, sz,
                                            vp, vp, vp]),
         "tsqr_mi_set_load_policy": (None, [ci]), "tsqr_mi_get_load_policy": (ci, []),
+        "tsqr_mi_working_q_size_f64_orth": (sz, [sz, sz, sz]), "tsqr_mi_working_r_size_f64_orth": (sz, [sz, sz, sz]),
+        # (v_layout, w_layout, passes, reorth, w, ldw, s, lds, r, ldr, v, ldv, m, k, n, wq, wr, stream)
+        "tsqr_mi_orth_f64": (ci, [ci, ci, ci, ci, vp, sz, vp, sz, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
     }
 
 
@@ -147,7 +150,8 @@ OPTIONAL_SYMBOLS = {
     "tsqr_mi_working_q_size_f64_qrcp", "tsqr_mi_working_r_size_f64_qrcp", "tsqr_mi_qrcp_f64",
     "tsqr_mi_working_q_size_f64_lstsq_rank", "tsqr_mi_working_r_size_f64_lstsq_rank", "tsqr_mi_lstsq_rank_f64",
     "tsqr_mi_working_q_size_f64_lstsq_minnorm", "tsqr_mi_working_r_size_f64_lstsq_minnorm", "tsqr_mi_lstsq_minnorm_f64",
-    "tsqr_mi_set_load_policy", "tsqr_mi_get_load_policy"}
+    "tsqr_mi_set_load_policy", "tsqr_mi_get_load_policy",
+    "tsqr_mi_working_q_size_f64_orth", "tsqr_mi_working_r_size_f64_orth", "tsqr_mi_orth_f64"}
 
 _lib = None
 
@@ -441,6 +445,7 @@ _F64_LSTSQ = _F64Entry("lstsq_f64", 64, "tsqr_mi_lstsq_f64", "_f64_lstsq")
 _F64_SVD = _F64Entry("svd_f64", 64, "tsqr_mi_svd_f64", "_f64_svd")       # (its size functions take jobu behind m and n)
 _F64_QRCP = _F64Entry("qrcp_f64", 64, "tsqr_mi_qrcp_f64", "_f64_qrcp")   # (jobq behind m and n)
 _F64_LSTSQ_RANK = _F64Entry("lstsq_rank_f64", 64, "tsqr_mi_lstsq_rank_f64", "_f64_lstsq_rank")   # (nrhs behind m and n; no _lay form)
+_F64_ORTH = _F64Entry("orth_f64", 64, "tsqr_mi_orth_f64", "_f64_orth")   # (its size functions take m, k, n; no _lay form; k <= 1024)
 _F64_LSTSQ_MINNORM = _F64Entry("lstsq_rank_f64", 64, "tsqr_mi_lstsq_minnorm_f64", "_f64_lstsq_minnorm")   # (lstsq_rank_f64 with minimum_norm=True)
 
 
@@ -1031,6 +1036,98 @@ def qrcp_f64_tensor(a, reorth=False, compute_q=True, overwrite_a=False, stream=N
                      wq.data_ptr(), wr.data_ptr())
     p = jpvt.to(torch.int64)
     return (q, r.t(), p) if jobq else (r.t(), p)
+
+
+class OrthError(_F64StateError):
+    """orth_f64_tensor ended with a non-zero state (.state: error_invalid_matrix_size or error_not_finite)"""
+
+
+class buffer_f64_orth(buffer_f64):
+    """Work space of orth_f64 (tsqr_mi_working_{q,r}_size_f64_orth doubles on the GPU); allocate(m, k, n).  reorthogonalize: the reorth
+    argument of the inner ladder, as in buffer_f64."""
+    _entry = _F64_ORTH
+
+    def allocate(self, m, k, n):
+        import torch
+        if self.dwq is not None or self.dwr is not None:
+            raise RuntimeError("The buffer has been already allocated")
+        self.dwq, self.dwr = (torch.empty(max(size, 1), dtype=torch.float64, device=self.device) for size in self._entry.sizes(m, k, n))
+
+
+def check_f64_orth_operands(m, k, n, ldw, lds, ldr, ldv, w, s, r, v, v_row_major=False, w_row_major=False):
+    """The size and overlap rules of orth_f64 on (address, elements) pairs: every leading dimension at least its operand's extent along
+    it (the rows; the columns of a row-major v or w), room for the whole operand, w apart from v, s and r, and s apart from r (v is
+    read only: it may share memory with s or r only at the caller's risk, and that is rejected too).  Raises ValueError."""
+    ops = (("w", w, ldw, m, n, w_row_major), ("v", v, ldv, m, k, v_row_major), ("s", s, lds, k, n, False), ("r", r, ldr, n, n, False))
+    span = dict(zip((o[0] for o in ops), _f64_spans("orth_f64", ops)))
+    _f64_apart("orth_f64", span, set(), False, "")
+
+
+def _orth_size_ok(m, k, n, passes):
+    return passes in (1, 2) and 1 <= n <= 64 and 1 <= k <= 1024 and k + n <= m
+
+
+def orth_f64(w, ldw, s, lds, r, ldr, v, ldv, m, k, n, bf, passes=2, stream=None, reorthogonalize=None, v_row_major=False,
+             w_row_major=False):
+    """Block orthogonalisation against an existing basis (tsqr_mi_orth_f64: include/tsqr_mi.h has the method and the contract):
+    v (m x k, orthonormal columns, read only) and w (m x n) are float64 GPU tensors holding column-major data, or ROW-major data with
+    v_row_major / w_row_major (element (i, j) at i * ld + j); only data_ptr and numel are used.  1 <= n <= 64, 1 <= k <= 1024,
+    k + n <= m, passes 1 or 2.  w is overwritten by q with v^T q = 0, q^T q = I and w_in = v s + q r; s (k x n, lds) and r (n x n upper
+    triangular, ldr) are column-major.  bf is a buffer_f64_orth.  Blocking; returns the state: 0, error_invalid_matrix_size (a size or
+    passes outside the ranges: this entry has no error_unsupported_mode) or error_not_finite (w, s and r are then undefined).  Operands are
+    checked before anything is launched: TypeError for a wrong dtype or a CPU tensor, ValueError for a short tensor, a short leading
+    dimension or overlapping operands.  last_sweeps_f64() tells the sum of the ladder's sweeps over the rounds.  State 0 is no test that w
+    was independent of v: compare diag(r) with w's column norms."""
+    entry = _F64_ORTH
+    reorth = bf.reorthogonalize if reorthogonalize is None else bool(reorthogonalize)
+    _check_f64_tensors(entry.name, (("w", w), ("s", s), ("r", r), ("v", v)))
+    if not _orth_size_ok(m, k, n, passes):
+        return error_invalid_matrix_size
+    pair = lambda t: (t.data_ptr(), t.numel())
+    check_f64_orth_operands(m, k, n, ldw, lds, ldr, ldv, pair(w), pair(s), pair(r), pair(v), bool(v_row_major), bool(w_row_major))
+    entry.check_buffer(bf, m, k, n)
+    return _f64_call(entry.symbol, lib().tsqr_mi_orth_f64, stream, ROW_MAJOR if v_row_major else COL_MAJOR,
+                     ROW_MAJOR if w_row_major else COL_MAJOR, int(passes), int(reorth), w.data_ptr(), ldw, s.data_ptr(), lds, r.data_ptr(), ldr,
+                     v.data_ptr(), ldv, m, k, n, bf.dwq.data_ptr(), bf.dwr.data_ptr())
+
+
+def orth_f64_tensor(v, w, passes=2, reorth=False, overwrite_w=False, stream=None):
+    """(q, s, r) of the block orthogonalisation of w against the orthonormal basis v (tsqr_mi_orth_f64: include/tsqr_mi.h has the method):
+    v m x k and w m x n two-dimensional float64 GPU tensors, 1 <= n <= 64, 1 <= k <= 1024, k + n <= m, any strides; v^T q = 0,
+    q^T q = I, w = v s + q r with s k x n and r n x n upper triangular, diag(r) >= 0.  Each operand is used where it lies when its columns
+    or its rows are contiguous (_operand_f64's rule, as for qr_f64_tensor), each with its own layout, and copied once into column-major
+    storage otherwise; q has w's shape and layout, and q, s and r have the same bits whichever way v and w are stored.
+    overwrite_w=True: when w is used where it lies, q IS w; otherwise w is never written (the call then works on a copy of w: the only
+    m x n allocation).  passes: 2 (BCGS2) or 1 (one round; not enough when w lies close to span(v)).  reorth: the inner ladder's argument.
+    The work space is allocated per call.  Blocking.  Raises TypeError for a wrong dtype or a CPU tensor, ValueError for tensors that are
+    not two-dimensional or whose row counts differ, OrthError (.state) for a state other than 0: error_invalid_matrix_size for sizes or
+    passes outside the ranges, error_not_finite from the ladder on the projected block (Inf or NaN in v or w included).  State 0 is no
+    test that w was independent of v: compare diag(r) with w's column norms."""
+    import torch
+    entry = _F64_ORTH
+    _check_f64_tensors("orth_f64_tensor", (("v", v), ("w", w)))
+    if v.dim() != 2 or w.dim() != 2 or v.shape[0] != w.shape[0]:
+        raise ValueError("orth_f64_tensor: v must be m x k and w m x n, got %s and %s" % (tuple(v.shape), tuple(w.shape)))
+    (m, k), n = v.shape, w.shape[1]
+    if not _orth_size_ok(m, k, n, passes):
+        raise OrthError(error_invalid_matrix_size, "orth_f64_tensor: state %d for v %d x %d, w %d x %d, passes %r"
+                        % (error_invalid_matrix_size, m, k, m, n, passes))
+    vc, ldv, v_layout = _operand_f64(v)
+    wc, ldw, w_layout = _operand_f64(w)
+    if wc.data_ptr() == w.data_ptr() and not overwrite_w:  # (used where it lies but not to be written: q starts as a copy in w's layout)
+        if w_layout == ROW_MAJOR:
+            wc, ldw = w.clone(memory_format=torch.contiguous_format), n
+        else:
+            wc, ldw = w.t().clone(memory_format=torch.contiguous_format).t(), m
+    s = torch.empty((n, k), dtype=torch.float64, device=w.device)
+    r = torch.empty((n, n), dtype=torch.float64, device=w.device)
+    wq, wr = entry.work_space(w.device, m, k, n)
+    with torch.cuda.device(w.device):
+        st = _f64_call(entry.symbol, lib().tsqr_mi_orth_f64, stream, v_layout, w_layout, int(passes), int(bool(reorth)), wc.data_ptr(), ldw,
+                       s.data_ptr(), k, r.data_ptr(), n, vc.data_ptr(), ldv, m, k, n, wq.data_ptr(), wr.data_ptr())
+    if st:
+        raise OrthError(st, "orth_f64_tensor: state %d: %s" % (st, last_error()))
+    return wc, s.t(), r.t()
 
 
 def get_working_q_size_f64_dist(m_local, n, nranks):

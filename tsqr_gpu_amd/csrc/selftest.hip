@@ -9,6 +9,7 @@
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
 #include "lsq_rank_f64.hip"
+#include "orth_f64.hip"
 #include "f32_plan.h"
 #include "launch_util.h"
 

@@ -420,4 +420,57 @@ int tsqr_selftest_f64w_rmul(double* r, size_t ldr, const double* rw, double* rc,
 	return f64_sync();
 }
 
+// ---- tsqr_mi_orth_f64 (orth_f64.hip): each pass alone, on the product's plan (f64o_plan) and launchers -----------------------------------
+// out[0..5]: NT, kblocks, nslices, cps, nch, doubles of the partials.  Host only.
+int tsqr_selftest_f64_orth_plan(size_t m, size_t k, size_t n, long long* out) {
+	if (!out || n == 0 || n > PW || k == 0 || k > F64O_MAX_K || m < k || m - k < n) return -100;
+	const F64OPlan g = f64o_plan(m, k, n);
+	out[0] = g.NT; out[1] = g.kblocks; out[2] = g.nslices; out[3] = (long long)g.cps; out[4] = (long long)g.nch;
+	out[5] = (long long)g.nslices * g.kblocks * 64 * 16 * g.NT;
+	return 0;
+}
+
+namespace {
+inline bool f64o_bad(int v_layout, int x_layout, const void* v, size_t ldv, const void* x, size_t ldx, size_t m, int k, int n) {
+	if ((v_layout != 0 && v_layout != 1) || (x_layout != 0 && x_layout != 1) || !v || !x) return true;
+	if (n <= 0 || n > (int)PW || k <= 0 || k > (int)F64O_MAX_K || m < (size_t)k || m - (size_t)k < (size_t)n) return true;
+	return ldv < (v_layout ? (size_t)k : m) || ldx < (x_layout ? (size_t)n : m);
+}
+}  // namespace
+
+// orth_gram_f64_kernel + the reduction: sw[kblocks * 64 * NP + 1] = V^T X in the work layout (S[64 b + r][c] at b * 64 * NP + 64 c + r),
+// the row count behind it; part: part_cap doubles for the partials
+int tsqr_selftest_f64_orth_gram(int v_layout, int x_layout, double* sw, const double* v, size_t ldv, const double* x, size_t ldx, size_t m,
+                                int k, int n, double* part, size_t part_cap) {
+	if (!sw || !part || f64o_bad(v_layout, x_layout, v, ldv, x, ldx, m, k, n)) return -100;
+	const F64OPlan g = f64o_plan(m, (size_t)k, (size_t)n);
+	const size_t blk = (size_t)64 * 16 * g.NT;
+	if ((size_t)g.nslices * g.kblocks * blk > part_cap) return -100;
+	const tsqrmi::OrthGramArgs64 ga{v, ldv, x, ldx, m, k, n, g.kblocks, g.nslices, g.cps, g.nch, part};
+	f64o_gram_launch(0, g, ga, v_layout, x_layout);
+	HIPCHK(hipGetLastError());
+	launch_reduce1(0, sw, part, g.nslices, (int)(g.kblocks * blk), (double)m);
+	return f64_sync();
+}
+
+// orth_update_f64_kernel: x <- x - v S in place, S given in the work layout (sw: kblocks * 64 * NP doubles)
+int tsqr_selftest_f64_orth_update(int v_layout, int x_layout, double* x, size_t ldx, const double* v, size_t ldv, const double* sw, size_t m,
+                                  int k, int n) {
+	if (!sw || f64o_bad(v_layout, x_layout, v, ldv, x, ldx, m, k, n)) return -100;
+	const F64OPlan g = f64o_plan(m, (size_t)k, (size_t)n);
+	const tsqrmi::OrthUpdateArgs64 ua{x, ldx, v, ldv, m, k, n, g.kblocks, sw};
+	f64o_update_launch(0, g, ua, v_layout, x_layout);
+	return f64_sync();
+}
+
+// orth_s_f64_kernel: s (k x n, lds) = Sw (second = 0) or s += Sw r1 (second = 1; r1 n x n upper triangular, ldr)
+int tsqr_selftest_f64_orth_s(double* s, size_t lds, const double* sw, const double* r1, size_t ldr, int k, int n, int second) {
+	if (!s || !sw || n <= 0 || n > (int)PW || k <= 0 || k > (int)F64O_MAX_K || lds < (size_t)k) return -100;
+	if (second != 0 && second != 1) return -100;
+	if (second && (!r1 || ldr < (size_t)n)) return -100;
+	const tsqrmi::OrthSArgs64 sa{s, lds, sw, r1, ldr, k, n, (int)np_of((size_t)n), second};
+	f64o_s_launch(0, sa);
+	return f64_sync();
+}
+
 }  // extern "C"

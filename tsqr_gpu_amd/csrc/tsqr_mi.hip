@@ -38,6 +38,7 @@
 #include "tsqr_f64_wide.hip"
 #include "f64_plan.h"
 #include "lsq_rank_f64.hip"
+#include "orth_f64.hip"
 #include "f32_plan.h"
 #include "launch_util.h"
 #include "validate.hip"
@@ -3156,6 +3157,76 @@ int tsqr_mi_lstsq_minnorm_f64(int a_layout, int b_layout, int reorth, int refine
                               void* wq, void* wr, void* stream) {
 	return lstsq_rank_f64_entry<true>(a_layout, b_layout, reorth, refine, rcond, x, ldx, r, ldr, jpvt, rank, a, lda, b, ldb, m, n, nrhs, wq, wr,
 	                                  stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Block orthogonalisation against an existing basis (tsqr_mi_orth_f64; n <= 64, k <= 1024; kernels: orth_f64.hip): BCGS2 with the
+// n <= 64 ladder as the inner QR.  Round i of `passes`: the cross-Gram pass and its reduction (Si = V^T X into wq[F64O_SW]), the
+// projection update X <- X - V Si in place in w, the caller's S (round 1: S = S1; round 2: S += S2 R1, with R1 still in the caller's r),
+// all enqueued back to back, then the ladder of tsqr_mi_qr_f64_lay in place on w (qr_f64_core as that entry calls it; it blocks, it
+// reads its verdict words) with R into the caller's r (round 1) or into wq[F64O_RW] (round 2), and behind round 2 r <- R2 r
+// (trimul_f64_kernel) with one more wait.  The sweep count is the sum over the rounds, plus 100 when either took the shifted path.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int orth_f64_core(int v_layout, int w_layout, int passes, int reorth, double* w, size_t ldw, double* s, size_t lds, double* r, size_t ldr,
+                  const double* v, size_t ldv, size_t m, size_t k, size_t n, double* wq, double* wr, void* stream) {
+	const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+	const F64OPlan g = f64o_plan(m, k, n);
+	if (g.nslices <= 0 || g.kblocks <= 0) { t_last_error = "fp64 cross-Gram pass without partials"; return TSQR_MI_ERROR_INVALID_SIZE; }
+	double *sw = wq + F64O_SW, *rw = wq + F64O_RW;
+	const int NP = 16 * g.NT;
+	int sweeps = 0;
+	bool shifted = false;
+	for (int round = 0; round < passes; round++) {
+		const tsqrmi::OrthGramArgs64 ga{v, ldv, w, ldw, m, (int)k, (int)n, g.kblocks, g.nslices, g.cps, g.nch, wr};
+		f64o_gram_launch(st, g, ga, v_layout, w_layout);
+		HIPCHK(hipGetLastError());
+		launch_reduce1(st, sw, wr, g.nslices, g.kblocks * 64 * NP, (double)m);
+		HIPCHK(hipGetLastError());
+		const tsqrmi::OrthUpdateArgs64 ua{w, ldw, v, ldv, m, (int)k, (int)n, g.kblocks, sw};
+		f64o_update_launch(st, g, ua, v_layout, w_layout);
+		HIPCHK(hipGetLastError());
+		const tsqrmi::OrthSArgs64 sa{s, lds, sw, r, ldr, (int)k, (int)n, NP, round};
+		f64o_s_launch(st, sa);
+		HIPCHK(hipGetLastError());
+		const int rc = qr_f64_core(reorth, w, ldw, round ? rw : r, round ? 64 : ldr, w, ldw, m, n, wq, wr, stream, nullptr, w_layout, w_layout);
+		sweeps += t_sweeps64 % 100;
+		shifted = shifted || t_sweeps64 >= 100;
+		t_sweeps64 = sweeps + (shifted ? 100 : 0);
+		if (rc) return rc;                                   // (state 3 included: w, s and r are undefined)
+	}
+	if (passes == 2) {
+		f64_rmul_launch(st, r, ldr, rw, (int)n);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	return TSQR_MI_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tsqr_mi_working_q_size_f64_orth(size_t m, size_t k, size_t n) { return (m == 0 || k == 0 || n == 0) ? 0 : f64o_wq_doubles(k); }
+size_t tsqr_mi_working_r_size_f64_orth(size_t m, size_t k, size_t n) {
+	return (m == 0 || k == 0 || n == 0) ? 0 : f64o_wr_doubles(m, k, std::min(n, PW));
+}
+
+// every state 1 is decided here, before any HIP call; the null checks first of all
+int tsqr_mi_orth_f64(int v_layout, int w_layout, int passes, int reorth, double* w, size_t ldw, double* s, size_t lds, double* r, size_t ldr,
+                     const double* v, size_t ldv, size_t m, size_t k, size_t n, void* wq, void* wr, void* stream) {
+	t_sweeps64 = 0;
+	if (!w || !s || !r || !v || !wq || !wr) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (passes != 1 && passes != 2) return TSQR_MI_ERROR_INVALID_SIZE;
+	if (n == 0 || n > PW || k == 0 || k > F64O_MAX_K || m < k || m - k < n) return TSQR_MI_ERROR_INVALID_SIZE;
+	const F64Operand V{v_layout, m, k, ldv}, W{w_layout, m, n, ldw}, S{TSQR_MI_COL_MAJOR, k, n, lds}, R{TSQR_MI_COL_MAJOR, n, n, ldr};
+	if (const int rc = f64_prologue({V, W, S, R}, m, n, PW, "tsqr_mi_orth_f64 supports n <= 64")) return rc;
+	if (const int rc = latch_all()) return rc;           // (tickets of tsqr_mi_qr_f32_submit in flight: their verdicts first)
+	return orth_f64_core(v_layout, w_layout, passes, reorth, w, ldw, s, lds, r, ldr, v, ldv, m, k, n, reinterpret_cast<double*>(wq),
+	                     reinterpret_cast<double*>(wr), stream);
 }
 
 }  // extern "C"
